@@ -10,6 +10,10 @@ preconditioner apply, 2 dots + 1 norm, vector updates).  Inputs are resident in 
 timed region; setup (assembly, ILU(0), coarse basis, R A R^T) is reported separately.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  `--full` adds what the headline figure does not
+need: the full solve to 1e-10, the host check of the GenEO eigenpairs, the CPU baseline (oracle) with its parity checks and
+the second workload (`secondary`).  `--dump-outputs DIR` writes what the timed steps computed (see write_outputs).
 """
 from __future__ import annotations
 
@@ -79,6 +83,26 @@ def init_distributed(gpus):
     return rank, world, device, comm, backend, shared, ndev, dist
 
 
+DUMP_SAMPLE = 1 << 20      # entries kept of a longer vector: 8 MB in float64, so the three files stay far below 64 MB
+DUMP_SEED = 20240531
+
+
+def write_outputs(path, x, r, defect):
+    """What a caller of the timed CG steps holds after the last one: the iterate x and the residual r = b - A x (the caller's b,
+    updated in place) in the rank's non-overlapping layout, and the defect ||r||.  Vectors longer than DUMP_SAMPLE are written at
+    the same DUMP_SEED-drawn sorted positions in every run of the same size, so two builds compare entry for entry."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = x.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    for name, v in (("x", x), ("residual", r)):
+        a = v.detach().cpu().numpy().astype(np.float64, copy=False)
+        np.save(os.path.join(path, f"{name}.npy"), a if idx is None else a[idx])
+    np.save(os.path.join(path, "defect.npy"), np.array([defect], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,7 +127,17 @@ def main():
                     help="time the RANK-LOCAL workload of an N-GPU run on this one GPU: the first 8 / N subdomains of the decomposition, every phase, "
                          "exchanges with the absent ranks cut (problem.restrict_decomposition); no solve, no CPU leg; not a benchmark of the metric")
     ap.add_argument("--no-secondary", action="store_true", help="skip the second workload (configs[3], bench_convdiff.py --problem dg) appended as `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the full solve, the GenEO host check, the CPU baseline and the second workload (each can still be skipped by its "
+                         "--no-* / --cpu-iters 0 option); without it those are skipped")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the iterate x, the residual b - A x (fixed seeded sample of 2^20 entries each when longer) "
+                         "and ||r|| of the last step as DIR/<name>.npy (float64; rank 0's part)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_solve, args.cpu_iters, args.no_secondary, args.no_geneo_check = True, 0, True, True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver may call it: this process becomes the launcher.  It starts the N workers (one
@@ -226,6 +260,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert np.isfinite(deff), "defect became non-finite inside the timed region"
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, x, b, deff)
 
     its_per_s = args.steps / elapsed
     ndof = grid.nglobal

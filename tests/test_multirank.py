@@ -109,7 +109,7 @@ def test_bench_gpus_2_bare_command_rehearsal():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    args = ["--grid", "48", "--steps", "5", "--warmup", "2", "--cpu-iters", "0"]
+    args = ["--grid", "48", "--steps", "5", "--warmup", "2", "--full", "--cpu-iters", "0"]
     p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p2.returncode == 0, p2.stdout[-2000:] + p2.stderr[-4000:]
     lines = [ln for ln in p2.stdout.splitlines() if ln.startswith("{")]
