@@ -782,7 +782,7 @@ static int geneo_run(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, i
     info->setup_s = t_setup;
     info->iterate_s = t_loop;
     info->nev = nev;
-    info->direct_flops = direct ? own.T->direct_flops : 0.0;
+    info->direct_flops = direct ? ilu0_direct_flops(own.T) : 0.0;
   }
   return DDM_OK;
 }

@@ -140,7 +140,8 @@ int ddm_ilu0_status(ddm_ctx *ctx, const ddm_ilu0 *F, int *status);
  * Every spin is bounded (it ends with the status word set, never in a hang); DDM_TRSV_MODE=levels (one launch per dependency
  * level, no spinning) is the engine for a GPU that is shared with other processes. */
 int ddm_ilu0_peek_status(const ddm_ilu0 *F);
-/* engine the next ddm_ilu0_solve uses: 8 = pipe, 4 = xcd2 (also when pipe declined the matrix), 0 = one launch per level */
+/* engine the next ddm_ilu0_solve uses: 8 = pipe, 4 = xcd2 (also when pipe declined the matrix), 0 = one launch per level (also the
+ * host sparse direct factor), 16 = device supernodal factor, 32 = box (DDM_TRSV_MODE=box; pipe when box declined the matrix) */
 int ddm_ilu0_engine(const ddm_ilu0 *F);
 /* ddm_ilu0_create returns while the schedule of the single-launch engine is still being built on host threads (2.6 s at 216^3; the
  * first ddm_ilu0_solve waits for it, so does ddm_ilu0_engine).  ddm_ilu0_wait joins that work now and returns its error, so that a
