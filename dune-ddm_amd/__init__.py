@@ -88,6 +88,7 @@ SYMBOLS = {
     "ddm_ilu0_debug_stamps": (_I32, [_P, _P, _P, _P, _P]),
     "ddm_ilu0_status": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_int)]),
     "ddm_ilu0_peek_status": (_I32, [_P]),
+    "ddm_ilu0_set_status": (_I32, [_P, _I32]),
     "ddm_halo_exchange_to": (_I32, [_P, _P, _P, _P]),
     "ddm_schwarz_local_solver": (_P, [_P]),
     "ddm_ilu0_pipe_trace": (_I32, [_P, _P, _P, _P, _P, _P, _I64, ctypes.POINTER(ctypes.c_int64)]),
@@ -154,6 +155,13 @@ SYMBOLS = {
     "ddm_cg_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_gmres_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_bicgstab_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(SolveResult)]),
+    "ddm_op_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
+    "ddm_op_applyscaleadd_multi": (_I32, [_P, _P, _I32, _D, _P, _P]),
+    "ddm_dot_multi": (_I32, [_P, _P, _I32, _P, _P, _P]),
+    "ddm_schwarz_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
+    "ddm_galerkin_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
+    "ddm_combined_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
+    "ddm_cg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
     "ddm_cg_defect": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_double)]),
@@ -285,6 +293,17 @@ def torch_context(device=0):
     ctx = Context(device, s.cuda_stream)
     ctx._torch_stream = s
     return ctx
+
+
+def _ncols(X, Y=None):
+    """columns m of an (n, m) row-major block (n-vectors count as m = 1); both blocks must have the same shape and be contiguous"""
+    shape = tuple(X.shape)
+    if Y is not None and tuple(Y.shape) != shape:
+        raise ValueError(f"block shapes differ: {shape} and {tuple(Y.shape)}")
+    for t in (X, Y):
+        if t is not None and hasattr(t, "is_contiguous") and not t.is_contiguous():
+            raise ValueError("block vectors must be row-major contiguous (n, m) tensors")
+    return 1 if len(shape) == 1 else int(shape[1])
 
 
 def _ptr(t):
@@ -527,6 +546,20 @@ class NonOverlappingOperator:
         self.ctx.check(self.ctx.lib.ddm_norm(self.ctx.h, self.h, _ptr(x), ctypes.byref(r)))
         return r.value
 
+    def apply_multi(self, X, Y):
+        """Y = A X for (n, m) row-major device blocks (ddm_op_apply_multi)"""
+        self.ctx.check(self.ctx.lib.ddm_op_apply_multi(self.ctx.h, self.h, _ncols(X, Y), _ptr(X), _ptr(Y)))
+
+    def applyscaleadd_multi(self, alpha, X, Y):
+        self.ctx.check(self.ctx.lib.ddm_op_applyscaleadd_multi(self.ctx.h, self.h, _ncols(X, Y), float(alpha), _ptr(X), _ptr(Y)))
+
+    def dot_multi(self, X, Y):
+        """the m owner-masked dots <X_c, Y_c> as a numpy array (ddm_dot_multi)"""
+        m = _ncols(X, Y)
+        r = np.zeros(max(m, 1), dtype=np.float64)
+        self.ctx.check(self.ctx.lib.ddm_dot_multi(self.ctx.h, self.h, m, _ptr(X), _ptr(Y), _hp(r)))
+        return r[:m]
+
 
 class SchwarzPreconditioner:
     """dune/ddm/schwarz.hh:54-220 with the ILU(0) local solver on the device."""
@@ -549,6 +582,13 @@ class SchwarzPreconditioner:
 
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_schwarz_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))
+
+    def apply_multi(self, X, D):
+        self.ctx.check(self.ctx.lib.ddm_schwarz_apply_multi(self.ctx.h, self.h, _ncols(X, D), _ptr(X), _ptr(D)))
+
+    def local_solver(self):
+        """the local solver object (ddm_ilu0 *, borrowed) as a raw pointer"""
+        return self.ctx.lib.ddm_schwarz_local_solver(self.h)
 
     def num_levels(self):
         return (int(self.ctx.lib.ddm_schwarz_num_levels(self.h, 0)), int(self.ctx.lib.ddm_schwarz_num_levels(self.h, 1)))
@@ -601,6 +641,9 @@ class GalerkinPreconditioner:
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_galerkin_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))
 
+    def apply_multi(self, X, D):
+        self.ctx.check(self.ctx.lib.ddm_galerkin_apply_multi(self.ctx.h, self.h, _ncols(X, D), _ptr(X), _ptr(D)))
+
 
 def galerkin_products(ctx: Context, A_dir: CsrMatrix, left, right, row0, row1):
     """out[i, j] = <left_i, A_dir right_j> over rows [row0, row1); left/right: torch (k x n) device tensors."""
@@ -627,6 +670,9 @@ class CombinedPreconditioner:
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_combined_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))
 
+    def apply_multi(self, X, D):
+        self.ctx.check(self.ctx.lib.ddm_combined_apply_multi(self.ctx.h, self.h, _ncols(X, D), _ptr(X), _ptr(D)))
+
     def check_status(self):
         self.ctx.check(self.ctx.lib.ddm_combined_status(self.ctx.h, self.h))
 
@@ -640,6 +686,21 @@ def cg_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditio
     ctx.check(ctx.lib.ddm_cg_solve(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(fixed_iterations),
                                    _hp(hist), ctypes.byref(res)))
     return res, (hist[:res.iterations + 1] if history else None)
+
+
+def cg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, history=True):
+    """m independent CGSolver::apply recurrences at once (ddm_cg_solve_multi).  X, B: (n, m) row-major device tensors (B is overwritten by
+    the defects).  Returns (list of m SolveResult, history): history is (iters + 1) x m with iters the largest iteration count; the
+    entries of a column after it converged are NaN (its history stops there)."""
+    m = _ncols(X, B)
+    res = (SolveResult * max(m, 1))()
+    hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
+    ctx.check(ctx.lib.ddm_cg_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), _hp(hist), res))
+    out = [res[c] for c in range(m)]
+    if not history:
+        return out, None
+    iters = max([r.iterations for r in out] + [0])
+    return out, hist[:iters + 1, :m]
 
 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,

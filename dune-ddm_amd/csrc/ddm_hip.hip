@@ -76,6 +76,9 @@ struct ddm_ctx {
   std::map<std::string, TimerEntry> timers;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_fence = nullptr; // ddm_ctx_fence
+  // multi-RHS scratch (csrc/multi_rhs.hpp), allocated on first use: dot partials, per-column CG scalars, active-column mask
+  double *mpartial = nullptr, *mscal = nullptr;
+  int32_t *mactive = nullptr;
 };
 
 static std::mutex g_err_mutex;
@@ -252,6 +255,9 @@ extern "C" void ddm_ctx_destroy(ddm_ctx *ctx)
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(ctx->partial);
   (void)hipFree(ctx->scal);
+  (void)hipFree(ctx->mpartial);
+  (void)hipFree(ctx->mscal);
+  (void)hipFree(ctx->mactive);
   if (ctx->ev_fence) (void)hipEventDestroy(ctx->ev_fence);
   (void)hipEventDestroy(ctx->ev0);
   (void)hipEventDestroy(ctx->ev1);
@@ -786,6 +792,8 @@ struct ddm_halo {
   double *sendbuf = nullptr, *recvbuf = nullptr;
   bool remote = false; // any traffic to/from other ranks
   std::vector<int64_t> send_counts, recv_counts; // per peer (the layout of sendbuf / recvbuf)
+  double *msend = nullptr, *mrecv = nullptr; // multi-RHS buffers (m x the single-vector layout), mcols columns
+  int mcols = 0;
 };
 
 extern "C" int ddm_halo_create(ddm_ctx *ctx, int tag, int mode, int64_t nsend, const int64_t *send_idx,
@@ -848,6 +856,8 @@ extern "C" void ddm_halo_destroy(ddm_halo *H)
   (void)hipFree(H->src_pos);
   (void)hipFree(H->sendbuf);
   (void)hipFree(H->recvbuf);
+  (void)hipFree(H->msend);
+  (void)hipFree(H->mrecv);
   delete H;
 }
 extern "C" double *ddm_halo_sendbuf(ddm_halo *H) { return H->sendbuf; }
@@ -920,6 +930,8 @@ struct ddm_op {
   uint8_t *owner = nullptr;
   int64_t n = 0;
   double *tmp = nullptr;
+  double *mtmp = nullptr; // multi-RHS block (mcols columns)
+  int mcols = 0;
 };
 extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out)
 {
@@ -944,6 +956,7 @@ extern "C" void ddm_op_destroy(ddm_op *op)
   if (!op) return;
   (void)hipFree(op->owner);
   (void)hipFree(op->tmp);
+  (void)hipFree(op->mtmp);
   delete op;
 }
 extern "C" int ddm_op_apply(ddm_ctx *ctx, ddm_op *op, const double *x, double *y)
@@ -983,6 +996,8 @@ struct ddm_schwarz {
   double *pou = nullptr;
   double *d_ovlp = nullptr, *x_ovlp = nullptr;
   ddm_halo *copy = nullptr, *add = nullptr;
+  double *md_ovlp = nullptr, *mx_ovlp = nullptr; // multi-RHS blocks (mcols columns)
+  int mcols = 0;
 };
 extern "C" int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
                                   const int32_t *ext_map_host, const double *pou_host, int type, ddm_halo *ovlp_copy,
@@ -1048,6 +1063,8 @@ extern "C" void ddm_schwarz_destroy(ddm_schwarz *S)
   (void)hipFree(S->pou);
   (void)hipFree(S->d_ovlp);
   (void)hipFree(S->x_ovlp);
+  (void)hipFree(S->md_ovlp);
+  (void)hipFree(S->mx_ovlp);
   delete S;
 }
 extern "C" int64_t ddm_schwarz_num_levels(const ddm_schwarz *S, int upper) { return ddm_ilu0_num_levels(S->solver, upper); }
@@ -1111,6 +1128,8 @@ struct ddm_galerkin {
   double *partial = nullptr, *d0 = nullptr, *x0 = nullptr;
   double *d_ovlp = nullptr, *x_ovlp = nullptr;
   ddm_halo *copy = nullptr, *add = nullptr;
+  double *mpartial = nullptr, *md0 = nullptr, *mx0 = nullptr, *md_ovlp = nullptr, *mx_ovlp = nullptr; // multi-RHS blocks (mcols columns)
+  int mcols = 0;
 };
 static constexpr int64_t COARSE_CHUNK_ROWS = 8192;
 
@@ -1182,6 +1201,11 @@ extern "C" void ddm_galerkin_destroy(ddm_galerkin *G)
   (void)hipFree(G->x0);
   (void)hipFree(G->d_ovlp);
   (void)hipFree(G->x_ovlp);
+  (void)hipFree(G->mpartial);
+  (void)hipFree(G->md0);
+  (void)hipFree(G->mx0);
+  (void)hipFree(G->md_ovlp);
+  (void)hipFree(G->mx_ovlp);
   delete G;
 }
 // d_ovlp_ready: the overlapping defect (extended + owner values copied to all holders) if the caller already has it -- in the
@@ -1274,6 +1298,8 @@ struct ddm_combined {
   int64_t n = 0;
   bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
   bool overlap = false; // ... and the coarse chain runs on a side stream beside the local solve (measured slower: off by default)
+  double *mdnext = nullptr, *mp = nullptr, *mq = nullptr; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
+  int mcols = 0, mcg_cols = 0;
 };
 extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)
 {
@@ -1308,6 +1334,9 @@ extern "C" void ddm_combined_destroy(ddm_combined *C)
 {
   if (!C) return;
   (void)hipFree(C->dnext);
+  (void)hipFree(C->mdnext);
+  (void)hipFree(C->mp);
+  (void)hipFree(C->mq);
   delete C;
 }
 // Additive combination, fused: both levels start from the same extended defect and add over the same interface, so their
@@ -1830,3 +1859,5 @@ extern "C" int ddm_synth_q1_matrix(int dim, const int64_t *bshape, const double 
     synth::q1_rows(A, indptr, indices, data, nthreads);
     return DDM_OK;
 }
+
+#include "multi_rhs.hpp"

@@ -1,0 +1,271 @@
+// Device kernels of the multi-right-hand-side path (ddm_*_multi, csrc/multi_rhs.hpp): m independent columns stored as a row-major
+// n x m block (entry (i, c) at i * m + c, the layout of ddm_csr_mm and ddm_ilu0_solve_multi), 1 <= m <= MULTI_MAX.
+// Element-wise kernels run one thread per block entry (consecutive threads = consecutive addresses).  Reductions keep the tree of
+// the single-vector kernels where that costs nothing: the owner-masked dots and the fused CG update use the grid, the thread-to-row
+// mapping and block_sum of k_dot_partial / k_cg_update_norm, so every column's sum is bit-identical to the single-vector one.
+#pragma once
+#include "kernels.hpp"
+
+namespace ddm {
+
+constexpr int MULTI_MAX = 32; // columns of one block (ddm_cg_solve_multi)
+
+// ---- halo: pack / deterministic unpack of m columns (one message of m x count doubles per peer) ----------------------------------
+__global__ void k_pack_multi(int64_t nsend, int m, const int64_t *__restrict__ idx, const double *__restrict__ v, double *__restrict__ buf)
+{
+  const int64_t total = nsend * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t k = t / m;
+    buf[t] = v[idx[k] * m + (t - k * m)];
+  }
+}
+// contributions in list order, as k_unpack: bit-identical per column
+template <bool ADD>
+__global__ void k_unpack_multi(int64_t ndst, int m, const int64_t *__restrict__ dst_idx, const int64_t *__restrict__ dst_ptr,
+                               const int64_t *__restrict__ src_pos, const double *__restrict__ buf, double *__restrict__ v)
+{
+  const int64_t total = ndst * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t k = t / m;
+    const int c = (int)(t - k * m);
+    const int64_t i = dst_idx[k] * m + c;
+    double s = ADD ? v[i] : 0.0;
+    for (int64_t q = dst_ptr[k]; q < dst_ptr[k + 1]; ++q) s = ADD ? s + buf[src_pos[q] * m + c] : buf[src_pos[q] * m + c];
+    v[i] = s;
+  }
+}
+// column c of an n x m block <-> a contiguous vector (the column-by-column exchange through the fixed-layout alltoall callback)
+template <bool TO_BLOCK>
+__global__ void k_column_copy(int64_t n, int m, int c, const double *__restrict__ src, double *__restrict__ dst)
+{
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    if (TO_BLOCK) dst[i * m + c] = src[i];
+    else dst[i] = src[i * m + c];
+  }
+}
+
+// ---- Schwarz level: extend / restrict / partition of unity --------------------------------------------------------------------------
+__global__ void k_extend_multi(int64_t n, int m, const int32_t *__restrict__ ext_map, const double *__restrict__ d, double *__restrict__ dov)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t i = t / m;
+    const int32_t e = ext_map[i];
+    dov[t] = e >= 0 ? d[(int64_t)e * m + (t - i * m)] : 0.0;
+  }
+}
+template <bool ACC>
+__global__ void k_restrict_multi(int64_t n, int m, const int32_t *__restrict__ ext_map, const double *__restrict__ xov, double *__restrict__ x)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t i = t / m;
+    const int32_t e = ext_map[i];
+    if (e >= 0) {
+      const int64_t o = (int64_t)e * m + (t - i * m);
+      x[o] = ACC ? x[o] + xov[t] : xov[t];
+    }
+  }
+}
+// x = x * w (w may be NULL), then x += add (may be NULL): the tail of the Schwarz level in the fused additive combination, in the
+// order of the single-vector epilogue (k_scale, then k_axpy with 1.0)
+__global__ void k_scale_add_multi(int64_t n, int m, const double *__restrict__ w, const double *__restrict__ add, double *__restrict__ x)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    double v = x[t];
+    if (w) v *= w[t / m];
+    if (add) v += add[t];
+    x[t] = v;
+  }
+}
+
+// ---- coarse level ------------------------------------------------------------------------------------------------------------------
+// partial[(ch * kmax + j) * m + c] = <r_j, d_c> over the rows of chunk ch.  One wave per (chunk, basis vector): its lanes cover
+// R = 64 / m consecutive rows x m columns of the block (lane = row offset * m + column), so each basis entry is read once for all
+// m columns and the block rows are read contiguously; the R lanes of one column are summed at the end.
+__global__ __launch_bounds__(WG) void k_coarse_restrict_partial_multi(int kmax, int64_t ld, const double *__restrict__ basis, int m,
+                                                                       const double *__restrict__ d, const RowChunk *__restrict__ chunks,
+                                                                       double *__restrict__ partial, int nchunk)
+{
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int R = 64 / m, rr = lane / m, c = lane - rr * m;
+  const bool on = rr < R;
+  for (int ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const RowChunk cu = chunks[ch];
+    for (int j = w; j < kmax; j += 4) {
+      const double *bj = basis + (int64_t)j * ld;
+      double s = 0.0;
+      if (on) {
+        int64_t r = cu.r0 + rr;
+        for (; r + 3 * R < cu.r1; r += 4 * R) { // four rows of each stream in flight per lane
+          double bv[4], dv[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) bv[u] = __builtin_nontemporal_load(bj + r + u * R);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) dv[u] = d[(r + u * R) * m + c];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) s += bv[u] * dv[u];
+        }
+        for (; r < cu.r1; r += R) s += bj[r] * d[r * m + c];
+      }
+      double acc = s;
+      for (int q = 1; q < R; ++q) { // lanes c, c + m, c + 2m, ... hold the partial sums of column c
+        const double o = __shfl(s, lane + q * m, 64);
+        acc += o;
+      }
+      if (lane < m) partial[((int64_t)ch * kmax + j) * m + lane] = acc;
+    }
+  }
+}
+// one workgroup: chunk partials of every (subdomain, vector, column) summed in chunk order, scattered to the K x m coarse defect
+__global__ __launch_bounds__(WG) void k_coarse_restrict_final_multi(int nsub, int kmax, int m, const int32_t *__restrict__ sub_chunk_ptr,
+                                                                     const double *__restrict__ partial, const int64_t *__restrict__ coarse_index,
+                                                                     int64_t K, double *__restrict__ d0)
+{
+  for (int64_t i = threadIdx.x; i < K * m; i += WG) d0[i] = 0.0;
+  __syncthreads();
+  const int total = nsub * kmax * m;
+  for (int t = threadIdx.x; t < total; t += WG) {
+    const int sj = t / m, c = t - sj * m;
+    const int s = sj / kmax, j = sj - s * kmax;
+    const int64_t gi = coarse_index[sj];
+    if (gi < 0) continue;
+    double acc = 0.0;
+    for (int q = sub_chunk_ptr[s]; q < sub_chunk_ptr[s + 1]; ++q) acc += partial[((int64_t)q * kmax + j) * m + c];
+    d0[gi * m + c] = acc;
+  }
+}
+// X0 = A0^-1 D0 with the replicated K x K inverse and K x m blocks: one thread per entry of X0 (the row of A0^-1 is shared by the
+// m threads of one row; D0 is read along its rows)
+__global__ __launch_bounds__(WG) void k_dense_mm(int64_t K, int m, const double *__restrict__ M, const double *__restrict__ D0, double *__restrict__ X0)
+{
+  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= K * m) return;
+  const int64_t row = t / m;
+  const int c = (int)(t - row * m);
+  const double *mr = M + row * K;
+  double s = 0.0;
+  for (int64_t k = 0; k < K; ++k) s += mr[k] * D0[k * m + c];
+  X0[t] = s;
+}
+// x_ovlp[r, c] = sum_j x0[(s, j), c] r_j[r]: one thread per block entry, the basis vectors added in the order of k_coarse_prolong
+// (the same products and sums per entry)
+__global__ __launch_bounds__(WG) void k_coarse_prolong_multi(int kmax, int64_t ld, const double *__restrict__ basis, int m, const double *__restrict__ x0,
+                                                              const int64_t *__restrict__ coarse_index, const RowChunk *__restrict__ chunks,
+                                                              double *__restrict__ xov, int nchunk)
+{
+  __shared__ int64_t gidx[COARSE_KMAX];
+  for (int ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const RowChunk cu = chunks[ch];
+    __syncthreads(); // gidx of the previous chunk is no longer read
+    if (threadIdx.x < kmax) gidx[threadIdx.x] = coarse_index[(int64_t)cu.sub * kmax + threadIdx.x];
+    __syncthreads();
+    const int64_t e1 = cu.r1 * m;
+    for (int64_t e = cu.r0 * m + threadIdx.x; e < e1; e += WG) {
+      const int64_t r = e / m;
+      const int c = (int)(e - r * m);
+      double s = 0.0;
+      for (int j = 0; j < kmax; ++j) {
+        const int64_t gi = gidx[j];
+        const double cj = gi >= 0 ? x0[gi * m + c] : 0.0;
+        s += cj * __builtin_nontemporal_load(basis + (int64_t)j * ld + r);
+      }
+      xov[e] = s;
+    }
+  }
+}
+
+// ---- CG vector work ----------------------------------------------------------------------------------------------------------------
+// owner-masked dots of columns [c0, c0 + CB): the grid, rows per thread and block_sum of k_dot_partial; partial[c * gridDim.x + b]
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_dot_partial_multi(int64_t n, int m, int c0, const uint8_t *__restrict__ mask, const double *__restrict__ x,
+                                                          const double *__restrict__ y, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double s[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) s[u] = 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const double *xi = x + i * m + c0, *yi = y + i * m + c0;
+#pragma unroll
+      for (int u = 0; u < CB; ++u) s[u] += xi[u] * yi[u];
+    }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double t = block_sum(s[u], red);
+    if (threadIdx.x == 0) partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = t;
+  }
+}
+// one workgroup per column: the partials summed as k_reduce_final does
+__global__ __launch_bounds__(WG) void k_reduce_final_multi(int nb, const double *__restrict__ partial, double *__restrict__ out)
+{
+  __shared__ double red[4];
+  const double *p = partial + (int64_t)blockIdx.x * nb;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += WG) s += p[i];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+// per-column CG scalars of the ACTIVE columns (a converged column keeps its values; nothing is multiplied by a zero step).
+// scal: [0..M) rholast, [M..2M) alpha = <p, q>, [2M..3M) lambda, [3M..4M) rho, [4M..5M) beta, [5M..6M) <b, b>; M = MULTI_MAX
+__global__ void k_cg_beta_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) {
+    scal[4 * MULTI_MAX + c] = scal[3 * MULTI_MAX + c] / scal[c];
+    scal[c] = scal[3 * MULTI_MAX + c];
+  }
+}
+__global__ void k_cg_lambda_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) scal[2 * MULTI_MAX + c] = scal[c] / scal[MULTI_MAX + c];
+}
+// p = beta p + q in the active columns
+__global__ void k_cg_direction_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ scal, const double *__restrict__ q,
+                                     double *__restrict__ p)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) p[t] = scal[4 * MULTI_MAX + c] * p[t] + q[t];
+  }
+}
+// x += lambda p; b -= lambda q; partial sums of <b, b> for columns [c0, c0 + CB) -- k_cg_update_norm per column (same grid, rows per
+// thread and block_sum).  Columns that are not active are neither read nor written (their partials are 0).
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
+                                                             const uint8_t *__restrict__ mask, const double *__restrict__ p, const double *__restrict__ q,
+                                                             double *__restrict__ x, double *__restrict__ b, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double lam[CB], s[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    lam[u] = scal[2 * MULTI_MAX + c0 + u];
+    s[u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    const int64_t o = i * m + c0;
+    const bool own = !MASKED || mask[i];
+#pragma unroll
+    for (int u = 0; u < CB; ++u)
+      if (on[u]) {
+        x[o + u] += lam[u] * p[o + u];
+        const double bi = b[o + u] - lam[u] * q[o + u];
+        b[o + u] = bi;
+        if (own) s[u] += bi * bi;
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double t = block_sum(s[u], red);
+    if (threadIdx.x == 0) partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+} // namespace ddm

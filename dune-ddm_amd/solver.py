@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, cg_solve, galerkin_products)
+               SchwarzPreconditioner, cg_solve, cg_solve_multi, galerkin_products)
 from .problem import Decomposition, RankLocal
 
 
@@ -287,6 +287,28 @@ class TwoLevelSchwarz:
             raise NotImplementedError("solver type '" + str(solver) + "' (cgsolver, restartedgmressolver and bicgstabsolver are available on the device)")
         res, hist = cg_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, fixed_iterations, history)
         return res, hist, x
+
+    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None):
+        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi), each column as ``solve`` would run it.
+        B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
+        (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
+        torch = self.torch
+        n_o = self.rl.n_o
+        if B is None:
+            B = np.asarray(self.rl.b, dtype=np.float64).reshape(n_o, 1)
+
+        def block(a):
+            t = a.to(self.dev, torch.float64) if isinstance(a, torch.Tensor) else self.to_device(np.asarray(a, dtype=np.float64))
+            t = t.reshape(n_o, 1) if t.dim() == 1 else t
+            if t.dim() != 2 or t.shape[0] != n_o:
+                raise ValueError(f"expected an (n_o, m) block with n_o = {n_o}, got {tuple(t.shape)}")
+            return t.contiguous().clone()
+        Bd = block(B)
+        X = torch.zeros_like(Bd) if X0 is None else block(X0)
+        if X.shape != Bd.shape:
+            raise ValueError(f"X0 {tuple(X.shape)} and B {tuple(Bd.shape)} differ")
+        res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
+        return res, hist, X
 
 
 class TwoLevelSchwarzSolver:

@@ -140,6 +140,8 @@ int ddm_ilu0_status(ddm_ctx *ctx, const ddm_ilu0 *F, int *status);
  * Every spin is bounded (it ends with the status word set, never in a hang); DDM_TRSV_MODE=levels (one launch per dependency
  * level, no spinning) is the engine for a GPU that is shared with other processes. */
 int ddm_ilu0_peek_status(const ddm_ilu0 *F);
+/* diagnostic: overwrite that status word (0 clears it), so that a caller can exercise the fail-fast path of the applies */
+int ddm_ilu0_set_status(ddm_ilu0 *F, int status);
 /* engine the next ddm_ilu0_solve uses: 8 = pipe, 4 = xcd2 (also when pipe declined the matrix), 0 = one launch per level (also the
  * host sparse direct factor), 16 = device supernodal factor, 32 = box (DDM_TRSV_MODE=box; pipe when box declined the matrix) */
 int ddm_ilu0_engine(const ddm_ilu0 *F);
@@ -431,6 +433,29 @@ int ddm_cg_steps(ddm_ctx *ctx, ddm_cg *cg, int k);
 int ddm_cg_defect(ddm_ctx *ctx, ddm_cg *cg, double *def_host);
 double ddm_cg_def0(const ddm_cg *cg);
 void ddm_cg_end(ddm_ctx *ctx, ddm_cg *cg);
+
+/* ---- several right-hand sides at once --------------------------------------------------------------------------------------
+ * Block vectors are DEVICE pointers to row-major n x nrhs blocks (entry (i, c) at i * nrhs + c: the layout of ddm_csr_mm and
+ * ddm_ilu0_solve_multi), 1 <= nrhs <= 32 (DDM_EINVAL outside).  Every column is what the single-vector entry point computes on it;
+ * summation orders are kept where that costs nothing (halo exchanges, dots, prolongation: bit-identical per column), elsewhere the
+ * columns differ from the single-vector results by rounding only.  Each object allocates its block scratch on first use for the widest
+ * nrhs seen and reuses it.  With the alltoall callback (ddm_ctx_set_comm) a halo block is exchanged column by column through the
+ * unchanged callback; in-library (RCCL) and single-rank exchanges send one message of nrhs x count doubles per peer. */
+int ddm_op_apply_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X, double *Y);                       /* nonoverlapping_operator.hh:34-39 */
+int ddm_op_applyscaleadd_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, double alpha, const double *X, double *Y); /* :41-50 */
+/* result_host[c] = <X_c, Y_c> (owner-masked, :76-81): one reduction kernel, one all-reduce of nrhs doubles; synchronous */
+int ddm_dot_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X, const double *Y, double *result_host);
+int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, double *X, const double *D);   /* schwarz.hh:115-149 */
+int ddm_galerkin_apply_multi(ddm_ctx *ctx, ddm_galerkin *G, int nrhs, double *X, const double *D); /* galerkin_preconditioner.hh:151-194 */
+int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X, const double *D); /* combined_preconditioner.hh:127-163 */
+/* nrhs INDEPENDENT dune-istl CGSolver::apply recurrences (the loop of ddm_cg_solve per column; not a block-Krylov method).  X: initial
+ * guesses / solutions, B: right-hand sides, overwritten by the defects.  Column c stops on its own test (def < reduction def0 or
+ * def < 1e-30; def0 < 1e-30: converged at once) and is then frozen -- its x, defect and history stop changing -- while the others go on;
+ * the loop ends when every column has converged or after maxit iterations.  hist_host (may be NULL): (maxit + 1) x nrhs row-major, entry
+ * (i, c) = ||r_i|| of column c for i <= res[c].iterations (later entries are not written).  res: nrhs entries.  DDM_ENUMERIC on a NaN
+ * defect and when a local solve gave up (ddm_ilu0_peek_status), as ddm_cg_solve. */
+int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                       double *hist_host, ddm_solve_result *res);
 
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,
