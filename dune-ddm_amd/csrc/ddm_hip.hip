@@ -2,6 +2,7 @@
 // HIP graphs, the CG driver) around the kernels in kernels.hpp.  gfx950 only, no fallback path.
 #include "../../include/ddm_hip.h"
 #include "host_vec.hpp"
+#include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "trsv_pipe.hpp"
 #include "trsv_box.hpp"
@@ -25,6 +26,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace ddm;
@@ -69,16 +71,16 @@ struct ddm_ctx {
   // side stream of the additive combination: the coarse level's restrict / solve / prolong run beside the latency-bound local solve
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  double *partial = nullptr; // RED_MAX_BLOCKS doubles
-  double *scal = nullptr;    // 16 device scalars
+  dbuf<double> partial; // RED_MAX_BLOCKS doubles
+  dbuf<double> scal;    // 16 device scalars
   int num_cu = 256;           // compute units of the device: persistent kernels launch at most this many workgroups
   bool timing = false;
   std::map<std::string, TimerEntry> timers;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_fence = nullptr; // ddm_ctx_fence
   // multi-RHS scratch (csrc/multi_rhs.hpp), allocated on first use: dot partials, per-column CG scalars, active-column mask
-  double *mpartial = nullptr, *mscal = nullptr;
-  int32_t *mactive = nullptr;
+  dbuf<double> mpartial, mscal;
+  dbuf<int32_t> mactive;
 };
 
 static std::mutex g_err_mutex;
@@ -135,19 +137,16 @@ struct BackgroundTransfers {
   }
 };
 template <class T>
-static int upload(ddm_ctx *ctx, const T *host, int64_t n, T **dev)
+static int upload(ddm_ctx *ctx, const T *host, int64_t n, dbuf<T> &dev)
 {
-  *dev = nullptr;
-  if (n <= 0) {
-    HIPCHECK(ctx, hipMalloc((void **)dev, sizeof(T)));
-    return DDM_OK;
-  }
-  HIPCHECK(ctx, hipMalloc((void **)dev, sizeof(T) * (size_t)n));
+  static_assert(std::is_trivially_copyable_v<T>, "uploaded byte by byte: descriptor structs hold views (raw pointers), never owners");
+  HIPCHECK(ctx, dev.alloc(n));
+  if (n <= 0) return DDM_OK;
   if (t_transfer_stream) { // background setup thread: its own non-blocking stream (see BackgroundTransfers)
-    HIPCHECK(ctx, hipMemcpyAsync(*dev, host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, t_transfer_stream));
+    HIPCHECK(ctx, hipMemcpyAsync(dev, host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, t_transfer_stream));
     HIPCHECK(ctx, hipStreamSynchronize(t_transfer_stream));
   } else
-    HIPCHECK(ctx, hipMemcpy(*dev, host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(ctx, hipMemcpy(dev, host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
   return DDM_OK;
 }
 // hipMemset that a background setup thread may call (same reason)
@@ -222,8 +221,7 @@ extern "C" int ddm_ctx_create(int device, void *hip_stream, ddm_ctx **out)
     }
     ctx->own_stream = true;
   }
-  if (hipMalloc((void **)&ctx->partial, sizeof(double) * RED_MAX_BLOCKS) != hipSuccess ||
-      hipMalloc((void **)&ctx->scal, sizeof(double) * 16) != hipSuccess ||
+  if (ctx->partial.alloc(RED_MAX_BLOCKS) != hipSuccess || ctx->scal.alloc(16) != hipSuccess ||
       hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
     delete ctx;
     return DDM_EHIP;
@@ -252,12 +250,7 @@ extern "C" void ddm_ctx_destroy(ddm_ctx *ctx)
     ctx->rccl_comm = nullptr;
   }
   if (!ctx) return;
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(ctx->partial);
-  (void)hipFree(ctx->scal);
-  (void)hipFree(ctx->mpartial);
-  (void)hipFree(ctx->mscal);
-  (void)hipFree(ctx->mactive);
+  (void)hipStreamSynchronize(ctx->stream); // (before the buffers go: `delete` below releases them)
   if (ctx->ev_fence) (void)hipEventDestroy(ctx->ev_fence);
   (void)hipEventDestroy(ctx->ev0);
   (void)hipEventDestroy(ctx->ev1);
@@ -406,12 +399,14 @@ extern "C" int ddm_ctx_comm_counts(ddm_ctx *ctx, int64_t *counts)
 
 extern "C" int ddm_malloc(ddm_ctx *ctx, int64_t bytes, void **dptr)
 {
-  HIPCHECK(ctx, hipMalloc(dptr, (size_t)std::max<int64_t>(bytes, 8)));
+  dbuf<unsigned char> b;
+  HIPCHECK(ctx, b.alloc(std::max<int64_t>(bytes, 8)));
+  *dptr = b.release(); // the caller owns it: ddm_free
   return DDM_OK;
 }
 extern "C" int ddm_free(ddm_ctx *ctx, void *dptr)
 {
-  HIPCHECK(ctx, hipFree(dptr));
+  HIPCHECK(ctx, dbuf<unsigned char>((unsigned char *)dptr).reset());
   return DDM_OK;
 }
 extern "C" int ddm_memset_zero(ddm_ctx *ctx, void *dptr, int64_t bytes)
@@ -496,17 +491,21 @@ struct ddm_csr {
   hvec<int64_t> h_rp; // host copies are kept for the ILU(0) factorisation / analysis
   hvec<int32_t> h_ci;
   hvec<double> h_va;
+  // Device arrays.  The pattern is read through the views rp / ci / blk_row: they point at this matrix's own arrays (own_*) or, for
+  // a values-only companion on another matrix's pattern (csr_adopt), at that matrix's, which has to outlive the companion.
+  dbuf<int64_t> own_rp;
+  dbuf<int32_t> own_ci, own_blk_row;
   int64_t *rp = nullptr;
   int32_t *ci = nullptr;
-  double *va = nullptr;
+  dbuf<double> va;
   int32_t *blk_row = nullptr;
   int nblk = 0;
-  bool borrowed_pattern = false; // rp / ci / blk_row belong to another ddm_csr (values-only companion on the same pattern)
-  bool host_only = false;        // created by ddm_csr_create_host: no device arrays
-  int32_t *row_order = nullptr;  // cache-blocked processing order of the rows for the block products (csr_row_order_tiled), or null
+  bool host_only = false;       // created by ddm_csr_create_host: no device arrays
+  dbuf<int32_t> row_order;      // cache-blocked processing order of the rows for the block products (csr_row_order_tiled), or empty
   std::thread uploader;          // device copies still in flight (csr_adopt): csr_wait_upload joins it
   int upload_rc = 0;
   std::string upload_err;
+  void view_pattern_of(const ddm_csr &P) { rp = P.own_rp, ci = P.own_ci, blk_row = P.own_blk_row, nblk = P.nblk; }
 };
 
 static std::vector<int32_t> csr_row_blocks(int64_t nrows, const int64_t *rowptr);
@@ -519,7 +518,7 @@ static int csr_create_impl(ddm_ctx *ctx, int64_t nrows, int64_t ncols, const int
     if (rowptr[i + 1] < rowptr[i]) return fail(ctx, DDM_EINVAL, "row pointers not monotone at row %lld", (long long)i);
   for (int64_t k = 0; k < nnz; ++k)
     if (col[k] < 0 || col[k] >= ncols) return fail(ctx, DDM_EINVAL, "column index out of range at entry %lld", (long long)k);
-  ddm_csr *A = new ddm_csr;
+  auto A = std::make_unique<ddm_csr>();
   A->nrows = nrows;
   A->ncols = ncols;
   A->nnz = nnz;
@@ -531,18 +530,15 @@ static int csr_create_impl(ddm_ctx *ctx, int64_t nrows, int64_t ncols, const int
   if (host_only) { // analysis / assembly input only (the GenEO pencil is built from the host arrays): no device copy
     A->host_only = true;
     A->nblk = 0;
-    *out = A;
+    *out = A.release();
     return DDM_OK;
   }
-  int rc = upload(ctx, rowptr, nrows + 1, &A->rp);
-  if (!rc) rc = upload(ctx, col, nnz, &A->ci);
-  if (!rc) rc = upload(ctx, val, nnz, &A->va);
-  if (!rc) rc = upload(ctx, blk.data(), (int64_t)blk.size(), &A->blk_row);
-  if (rc) {
-    ddm_csr_destroy(A);
-    return rc;
-  }
-  *out = A;
+  DDMCHECK(upload(ctx, rowptr, nrows + 1, A->own_rp));
+  DDMCHECK(upload(ctx, col, nnz, A->own_ci));
+  DDMCHECK(upload(ctx, val, nnz, A->va));
+  DDMCHECK(upload(ctx, blk.data(), (int64_t)blk.size(), A->own_blk_row));
+  A->view_pattern_of(*A);
+  *out = A.release();
   return DDM_OK;
 }
 extern "C" int ddm_csr_create(ddm_ctx *ctx, int64_t nrows, int64_t ncols, const int64_t *rowptr, const int32_t *col, const double *val, ddm_csr **out)
@@ -558,14 +554,7 @@ extern "C" int ddm_csr_create_host(ddm_ctx *ctx, int64_t nrows, int64_t ncols, c
 extern "C" void ddm_csr_destroy(ddm_csr *A)
 {
   if (!A) return;
-  if (A->uploader.joinable()) A->uploader.join();
-  (void)hipFree(A->row_order);
-  if (!A->borrowed_pattern) {
-    (void)hipFree(A->rp);
-    (void)hipFree(A->ci);
-    (void)hipFree(A->blk_row);
-  }
-  (void)hipFree(A->va);
+  if (A->uploader.joinable()) A->uploader.join(); // (it writes the members)
   delete A;
 }
 // row-block schedule of the CSR-stream kernel: <= SPMV_NNZ non-zeros and <= WG rows per block, a row longer than SPMV_NNZ gets a
@@ -679,16 +668,15 @@ static ddm_csr *csr_adopt(ddm_ctx *ctx, int64_t n, hvec<int64_t> &&rp, hvec<int3
   A->h_rp = std::move(rp);
   A->h_ci = std::move(ci);
   A->h_va = std::move(va);
-  C->borrowed_pattern = true;
-  *companion = C;
+  *companion = C; // values only: views A's pattern
   const int device = ctx->device;
   auto cv = std::make_shared<hvec<double>>(std::move(companion_values));
   std::vector<int64_t> bp(block_ptr ? block_ptr : nullptr, block_ptr ? block_ptr + nblocks + 1 : nullptr);
   A->uploader = std::thread([A, C, cv, device, bp]() {
-    auto up = [&](const void *src, size_t bytes, void **dst) {
+    auto up = [&](const auto &src, auto &dst) {
       if (A->upload_rc) return;
-      hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 8));
-      if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+      hipError_t e = dst.alloc((int64_t)src.size());
+      if (e == hipSuccess && src.size()) e = hipMemcpy(dst, src.data(), sizeof(src[0]) * src.size(), hipMemcpyHostToDevice);
       if (e != hipSuccess) {
         A->upload_rc = DDM_EHIP;
         A->upload_err = std::string("matrix upload failed: ") + hipGetErrorString(e);
@@ -697,19 +685,17 @@ static ddm_csr *csr_adopt(ddm_ctx *ctx, int64_t n, hvec<int64_t> &&rp, hvec<int3
     (void)hipSetDevice(device);
     const std::vector<int32_t> blk = csr_row_blocks(A->nrows, A->h_rp.data());
     A->nblk = (int)blk.size() - 1;
-    up(A->h_rp.data(), sizeof(int64_t) * A->h_rp.size(), (void **)&A->rp);
-    up(A->h_ci.data(), sizeof(int32_t) * A->h_ci.size(), (void **)&A->ci);
-    up(A->h_va.data(), sizeof(double) * A->h_va.size(), (void **)&A->va);
-    up(blk.data(), sizeof(int32_t) * blk.size(), (void **)&A->blk_row);
-    up(cv->data(), sizeof(double) * cv->size(), (void **)&C->va);
+    up(A->h_rp, A->own_rp);
+    up(A->h_ci, A->own_ci);
+    up(A->h_va, A->va);
+    up(blk, A->own_blk_row);
+    up(*cv, C->va);
     if (bp.size() >= 2 && !std::getenv("DDM_SPMM_NATURAL_ORDER")) {
       std::vector<int32_t> order;
-      if (csr_row_order_tiled((int64_t)bp.size() - 1, bp.data(), A->h_rp.data(), A->h_ci.data(), order)) up(order.data(), sizeof(int32_t) * order.size(), (void **)&A->row_order);
+      if (csr_row_order_tiled((int64_t)bp.size() - 1, bp.data(), A->h_rp.data(), A->h_ci.data(), order)) up(order, A->row_order);
     }
-    C->rp = A->rp;
-    C->ci = A->ci;
-    C->blk_row = A->blk_row;
-    C->nblk = A->nblk;
+    A->view_pattern_of(*A);
+    C->view_pattern_of(*A);
   });
   return A;
 }
@@ -788,11 +774,11 @@ extern "C" int ddm_csr_mm(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double
 struct ddm_halo {
   int tag = 0, mode = 0;
   int64_t nsend = 0, nrecv = 0, ndst = 0, self_off_send = 0, self_off_recv = 0, self_count = 0;
-  int64_t *send_idx = nullptr, *dst_idx = nullptr, *dst_ptr = nullptr, *src_pos = nullptr;
-  double *sendbuf = nullptr, *recvbuf = nullptr;
+  dbuf<int64_t> send_idx, dst_idx, dst_ptr, src_pos;
+  dbuf<double> sendbuf, recvbuf;
   bool remote = false; // any traffic to/from other ranks
   std::vector<int64_t> send_counts, recv_counts; // per peer (the layout of sendbuf / recvbuf)
-  double *msend = nullptr, *mrecv = nullptr; // multi-RHS buffers (m x the single-vector layout), mcols columns
+  dbuf<double> msend, mrecv; // multi-RHS buffers (m x the single-vector layout), mcols columns
   int mcols = 0;
 };
 
@@ -801,7 +787,7 @@ extern "C" int ddm_halo_create(ddm_ctx *ctx, int tag, int mode, int64_t nsend, c
                                const int64_t *dst_ptr, const int64_t *src_pos, ddm_halo **out)
 {
   if (!ctx || !out || (mode != 0 && mode != 1)) return fail(ctx, DDM_EINVAL, "ddm_halo_create: bad arguments");
-  ddm_halo *H = new ddm_halo;
+  auto H = std::make_unique<ddm_halo>();
   H->tag = tag;
   H->mode = mode;
   H->nsend = nsend;
@@ -814,52 +800,28 @@ extern "C" int ddm_halo_create(ddm_ctx *ctx, int tag, int mode, int64_t nsend, c
       H->self_off_send = ssum;
       H->self_off_recv = rsum;
       H->self_count = send_counts[r];
-      if (send_counts[r] != recv_counts[r]) {
-        delete H;
-        return fail(ctx, DDM_EINVAL, "halo: self send/recv counts differ");
-      }
+      if (send_counts[r] != recv_counts[r]) return fail(ctx, DDM_EINVAL, "halo: self send/recv counts differ");
     } else if (send_counts[r] || recv_counts[r])
       H->remote = true;
     ssum += send_counts[r];
     rsum += recv_counts[r];
   }
-  if (ssum != nsend) {
-    delete H;
-    return fail(ctx, DDM_EINVAL, "halo: send_counts do not sum to nsend");
-  }
+  if (ssum != nsend) return fail(ctx, DDM_EINVAL, "halo: send_counts do not sum to nsend");
   H->nrecv = rsum;
   const int64_t nsrc = ndst > 0 ? dst_ptr[ndst] : 0;
   for (int64_t k = 0; k < nsrc; ++k)
-    if (src_pos[k] < 0 || src_pos[k] >= rsum) {
-      delete H;
-      return fail(ctx, DDM_EINVAL, "halo: src_pos out of range");
-    }
-  int rc = upload(ctx, send_idx, nsend, &H->send_idx);
-  if (!rc) rc = upload(ctx, dst_idx, ndst, &H->dst_idx);
-  if (!rc) rc = upload(ctx, dst_ptr, ndst + 1, &H->dst_ptr);
-  if (!rc) rc = upload(ctx, src_pos, nsrc, &H->src_pos);
-  if (!rc && hipMalloc((void **)&H->sendbuf, sizeof(double) * (size_t)std::max<int64_t>(nsend, 1)) != hipSuccess) rc = DDM_EHIP;
-  if (!rc && hipMalloc((void **)&H->recvbuf, sizeof(double) * (size_t)std::max<int64_t>(rsum, 1)) != hipSuccess) rc = DDM_EHIP;
-  if (rc) {
-    ddm_halo_destroy(H);
-    return fail(ctx, rc, "halo: device allocation failed");
-  }
-  *out = H;
+    if (src_pos[k] < 0 || src_pos[k] >= rsum) return fail(ctx, DDM_EINVAL, "halo: src_pos out of range");
+  int rc = upload(ctx, send_idx, nsend, H->send_idx);
+  if (!rc) rc = upload(ctx, dst_idx, ndst, H->dst_idx);
+  if (!rc) rc = upload(ctx, dst_ptr, ndst + 1, H->dst_ptr);
+  if (!rc) rc = upload(ctx, src_pos, nsrc, H->src_pos);
+  if (!rc && H->sendbuf.alloc(nsend) != hipSuccess) rc = DDM_EHIP;
+  if (!rc && H->recvbuf.alloc(rsum) != hipSuccess) rc = DDM_EHIP;
+  if (rc) return fail(ctx, rc, "halo: device allocation failed");
+  *out = H.release();
   return DDM_OK;
 }
-extern "C" void ddm_halo_destroy(ddm_halo *H)
-{
-  if (!H) return;
-  (void)hipFree(H->send_idx);
-  (void)hipFree(H->dst_idx);
-  (void)hipFree(H->dst_ptr);
-  (void)hipFree(H->src_pos);
-  (void)hipFree(H->sendbuf);
-  (void)hipFree(H->recvbuf);
-  (void)hipFree(H->msend);
-  (void)hipFree(H->mrecv);
-  delete H;
-}
+extern "C" void ddm_halo_destroy(ddm_halo *H) { delete H; }
 extern "C" double *ddm_halo_sendbuf(ddm_halo *H) { return H->sendbuf; }
 extern "C" double *ddm_halo_recvbuf(ddm_halo *H) { return H->recvbuf; }
 
@@ -927,10 +889,10 @@ static int dot_device(ddm_ctx *ctx, int64_t n, const uint8_t *mask, const double
 struct ddm_op {
   const ddm_csr *A = nullptr;
   ddm_halo *halo = nullptr;
-  uint8_t *owner = nullptr;
+  dbuf<uint8_t> owner;
   int64_t n = 0;
-  double *tmp = nullptr;
-  double *mtmp = nullptr; // multi-RHS block (mcols columns)
+  dbuf<double> tmp;
+  dbuf<double> mtmp; // multi-RHS block (mcols columns)
   int mcols = 0;
 };
 extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out)
@@ -938,27 +900,17 @@ extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add
   if (!ctx || !A || !out || !owner_mask_host) return fail(ctx, DDM_EINVAL, "ddm_op_create: bad arguments");
   if (A->nrows != A->ncols) return fail(ctx, DDM_EINVAL, "operator matrix must be square");
   if (novlp_add && novlp_add->mode != 1) return fail(ctx, DDM_EINVAL, "operator halo must be an 'add' halo");
-  ddm_op *op = new ddm_op;
+  auto op = std::make_unique<ddm_op>();
   op->A = A;
   op->halo = novlp_add;
   op->n = A->nrows;
-  int rc = upload(ctx, owner_mask_host, op->n, &op->owner);
-  if (!rc && hipMalloc((void **)&op->tmp, sizeof(double) * (size_t)std::max<int64_t>(op->n, 1)) != hipSuccess) rc = DDM_EHIP;
-  if (rc) {
-    ddm_op_destroy(op);
-    return fail(ctx, rc, "ddm_op_create: allocation failed");
-  }
-  *out = op;
+  int rc = upload(ctx, owner_mask_host, op->n, op->owner);
+  if (!rc && op->tmp.alloc(op->n) != hipSuccess) rc = DDM_EHIP;
+  if (rc) return fail(ctx, rc, "ddm_op_create: allocation failed");
+  *out = op.release();
   return DDM_OK;
 }
-extern "C" void ddm_op_destroy(ddm_op *op)
-{
-  if (!op) return;
-  (void)hipFree(op->owner);
-  (void)hipFree(op->tmp);
-  (void)hipFree(op->mtmp);
-  delete op;
-}
+extern "C" void ddm_op_destroy(ddm_op *op) { delete op; }
 extern "C" int ddm_op_apply(ddm_ctx *ctx, ddm_op *op, const double *x, double *y)
 {
   ScopedTimer t(ctx, "Operator/apply");
@@ -991,13 +943,14 @@ extern "C" int ddm_norm(ddm_ctx *ctx, ddm_op *op, const double *x, double *resul
 struct ddm_schwarz {
   int64_t n = 0, n_novlp = 0;
   int type = 1;
-  ddm_ilu0 *solver = nullptr;
-  int32_t *ext_map = nullptr;
-  double *pou = nullptr;
-  double *d_ovlp = nullptr, *x_ovlp = nullptr;
+  ddm_ilu0 *solver = nullptr; // owned
+  dbuf<int32_t> ext_map;
+  dbuf<double> pou;
+  dbuf<double> d_ovlp, x_ovlp;
   ddm_halo *copy = nullptr, *add = nullptr;
-  double *md_ovlp = nullptr, *mx_ovlp = nullptr; // multi-RHS blocks (mcols columns)
+  dbuf<double> md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
   int mcols = 0;
+  ~ddm_schwarz() { ddm_ilu0_destroy(solver); }
 };
 extern "C" int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
                                   const int32_t *ext_map_host, const double *pou_host, int type, ddm_halo *ovlp_copy,
@@ -1036,37 +989,21 @@ extern "C" int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
   const int64_t n = A_dir->nrows;
   for (int64_t i = 0; i < n; ++i)
     if (ext_map_host[i] >= n_novlp) return fail(ctx, DDM_EINVAL, "ext_map entry out of range"); // size checks, schwarz.hh:186-193
-  ddm_schwarz *S = new ddm_schwarz;
+  auto S = std::make_unique<ddm_schwarz>();
   S->n = n;
   S->n_novlp = n_novlp;
   S->type = type;
   S->copy = ovlp_copy;
   S->add = ovlp_add;
-  int rc = direct ? ddm_direct_create(ctx, A_dir, nblocks, block_ptr, general ? 1 : 0, 0.0, &S->solver)
-                  : ddm_ilu0_create(ctx, A_dir, nblocks, block_ptr, &S->solver); // factorisation happens in the ctor (:92)
-  if (!rc) rc = upload(ctx, ext_map_host, n, &S->ext_map);
-  if (!rc && pou_host) rc = upload(ctx, pou_host, n, &S->pou);
-  if (!rc && hipMalloc((void **)&S->d_ovlp, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess) rc = fail(ctx, DDM_EHIP, "alloc");
-  if (!rc && hipMalloc((void **)&S->x_ovlp, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess) rc = fail(ctx, DDM_EHIP, "alloc");
-  if (rc) {
-    ddm_schwarz_destroy(S);
-    return rc;
-  }
-  *out = S;
+  DDMCHECK(direct ? ddm_direct_create(ctx, A_dir, nblocks, block_ptr, general ? 1 : 0, 0.0, &S->solver)
+                  : ddm_ilu0_create(ctx, A_dir, nblocks, block_ptr, &S->solver)); // factorisation happens in the ctor (:92)
+  DDMCHECK(upload(ctx, ext_map_host, n, S->ext_map));
+  if (pou_host) DDMCHECK(upload(ctx, pou_host, n, S->pou));
+  if (S->d_ovlp.alloc(n) != hipSuccess || S->x_ovlp.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "alloc");
+  *out = S.release();
   return DDM_OK;
 }
-extern "C" void ddm_schwarz_destroy(ddm_schwarz *S)
-{
-  if (!S) return;
-  ddm_ilu0_destroy(S->solver);
-  (void)hipFree(S->ext_map);
-  (void)hipFree(S->pou);
-  (void)hipFree(S->d_ovlp);
-  (void)hipFree(S->x_ovlp);
-  (void)hipFree(S->md_ovlp);
-  (void)hipFree(S->mx_ovlp);
-  delete S;
-}
+extern "C" void ddm_schwarz_destroy(ddm_schwarz *S) { delete S; }
 extern "C" int64_t ddm_schwarz_num_levels(const ddm_schwarz *S, int upper) { return ddm_ilu0_num_levels(S->solver, upper); }
 extern "C" int64_t ddm_schwarz_factor_nnz(const ddm_schwarz *S) { return (S && S->solver) ? S->solver->nnz : 0; } // stored entries of L + U (+ diagonal)
 extern "C" int ddm_schwarz_engine(const ddm_schwarz *S) { return S ? ddm_ilu0_engine(S->solver) : -1; }
@@ -1118,17 +1055,17 @@ extern "C" int ddm_schwarz_apply(ddm_ctx *ctx, ddm_schwarz *S, double *x, const 
 // ---- GalerkinPreconditioner --------------------------------------------------------------------
 struct ddm_galerkin {
   int64_t n = 0, n_novlp = 0, nsub = 0, kmax = 0, K = 0, ld = 0;
-  int32_t *ext_map = nullptr;
-  double *basis = nullptr;       // kmax x ld
-  int64_t *coarse_index = nullptr;
-  double *a0inv = nullptr;
-  RowChunk *chunks = nullptr;
-  int32_t *sub_chunk_ptr = nullptr;
+  dbuf<int32_t> ext_map;
+  dbuf<double> basis;       // kmax x ld
+  dbuf<int64_t> coarse_index;
+  dbuf<double> a0inv;
+  dbuf<RowChunk> chunks;
+  dbuf<int32_t> sub_chunk_ptr;
   int nchunk = 0;
-  double *partial = nullptr, *d0 = nullptr, *x0 = nullptr;
-  double *d_ovlp = nullptr, *x_ovlp = nullptr;
+  dbuf<double> partial, d0, x0;
+  dbuf<double> d_ovlp, x_ovlp;
   ddm_halo *copy = nullptr, *add = nullptr;
-  double *mpartial = nullptr, *md0 = nullptr, *mx0 = nullptr, *md_ovlp = nullptr, *mx_ovlp = nullptr; // multi-RHS blocks (mcols columns)
+  dbuf<double> mpartial, md0, mx0, md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
   int mcols = 0;
 };
 static constexpr int64_t COARSE_CHUNK_ROWS = 8192;
@@ -1145,7 +1082,7 @@ extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, con
   if (sub_ptr[0] != 0 || sub_ptr[nsub] != n) return fail(ctx, DDM_EINVAL, "Template vectors must match size of matrix"); // :131
   for (int64_t t = 0; t < nsub * kmax; ++t)
     if (coarse_index[t] >= K) return fail(ctx, DDM_EINVAL, "coarse_index out of range");
-  ddm_galerkin *G = new ddm_galerkin;
+  auto G = std::make_unique<ddm_galerkin>();
   G->n = n;
   G->n_novlp = n_novlp;
   G->nsub = nsub;
@@ -1162,52 +1099,23 @@ extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, con
     scp[s + 1] = (int32_t)chunks.size();
   }
   G->nchunk = (int)chunks.size();
-  int rc = upload(ctx, ext_map_host, n, &G->ext_map);
-  if (!rc) rc = upload(ctx, coarse_index, nsub * kmax, &G->coarse_index);
-  if (!rc) rc = upload(ctx, a0inv_host, K * K, &G->a0inv);
-  if (!rc) rc = upload(ctx, chunks.data(), (int64_t)chunks.size(), &G->chunks);
-  if (!rc) rc = upload(ctx, scp.data(), nsub + 1, &G->sub_chunk_ptr);
-  auto dalloc = [&](double **p, int64_t cnt) {
-    if (!rc && hipMalloc((void **)p, sizeof(double) * (size_t)std::max<int64_t>(cnt, 1)) != hipSuccess) rc = fail(ctx, DDM_EHIP, "galerkin: allocation failed");
-  };
-  dalloc(&G->basis, kmax * G->ld);
-  dalloc(&G->partial, (int64_t)G->nchunk * kmax);
-  dalloc(&G->d0, K + 1); // (+ 1: a scalar may ride on the all-reduce, coarse_allreduce)
-  dalloc(&G->x0, K);
-  dalloc(&G->d_ovlp, n);
-  dalloc(&G->x_ovlp, n);
-  if (!rc && hipMemset(G->basis, 0, sizeof(double) * (size_t)(kmax * G->ld)) != hipSuccess) rc = DDM_EHIP;
-  if (!rc && hipMemcpy2D(G->basis, sizeof(double) * (size_t)G->ld, basis_host, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n,
-                         (size_t)kmax, hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(ctx, DDM_EHIP, "galerkin: basis upload failed");
-  if (rc) {
-    ddm_galerkin_destroy(G);
-    return rc;
-  }
-  *out = G;
+  DDMCHECK(upload(ctx, ext_map_host, n, G->ext_map));
+  DDMCHECK(upload(ctx, coarse_index, nsub * kmax, G->coarse_index));
+  DDMCHECK(upload(ctx, a0inv_host, K * K, G->a0inv));
+  DDMCHECK(upload(ctx, chunks.data(), (int64_t)chunks.size(), G->chunks));
+  DDMCHECK(upload(ctx, scp.data(), nsub + 1, G->sub_chunk_ptr));
+  if (G->basis.alloc(kmax * G->ld) != hipSuccess || G->partial.alloc((int64_t)G->nchunk * kmax) != hipSuccess ||
+      G->d0.alloc(K + 1) != hipSuccess || // (+ 1: a scalar may ride on the all-reduce, coarse_allreduce)
+      G->x0.alloc(K) != hipSuccess || G->d_ovlp.alloc(n) != hipSuccess || G->x_ovlp.alloc(n) != hipSuccess)
+    return fail(ctx, DDM_EHIP, "galerkin: allocation failed");
+  if (hipMemset(G->basis, 0, sizeof(double) * (size_t)(kmax * G->ld)) != hipSuccess) return DDM_EHIP;
+  if (hipMemcpy2D(G->basis, sizeof(double) * (size_t)G->ld, basis_host, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n,
+                  (size_t)kmax, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ctx, DDM_EHIP, "galerkin: basis upload failed");
+  *out = G.release();
   return DDM_OK;
 }
-extern "C" void ddm_galerkin_destroy(ddm_galerkin *G)
-{
-  if (!G) return;
-  (void)hipFree(G->ext_map);
-  (void)hipFree(G->basis);
-  (void)hipFree(G->coarse_index);
-  (void)hipFree(G->a0inv);
-  (void)hipFree(G->chunks);
-  (void)hipFree(G->sub_chunk_ptr);
-  (void)hipFree(G->partial);
-  (void)hipFree(G->d0);
-  (void)hipFree(G->x0);
-  (void)hipFree(G->d_ovlp);
-  (void)hipFree(G->x_ovlp);
-  (void)hipFree(G->mpartial);
-  (void)hipFree(G->md0);
-  (void)hipFree(G->mx0);
-  (void)hipFree(G->md_ovlp);
-  (void)hipFree(G->mx_ovlp);
-  delete G;
-}
+extern "C" void ddm_galerkin_destroy(ddm_galerkin *G) { delete G; }
 // d_ovlp_ready: the overlapping defect (extended + owner values copied to all holders) if the caller already has it -- in the
 // additive combination both levels start from the same defect (schwarz.hh:121-125 and galerkin_preconditioner.hh:159-162)
 static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d, bool acc, const double *d_ovlp_ready = nullptr)
@@ -1250,20 +1158,20 @@ extern "C" int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
     return fail(ctx, DDM_EINVAL, "ddm_galerkin_products: bad arguments");
   if (A_dir->host_only) return fail(ctx, DDM_EINVAL, "the matrix was created without device arrays (ddm_csr_create_host)");
   const int64_t n = A_dir->nrows;
-  double *y = nullptr, *partial = nullptr, *outd = nullptr;
-  RowChunk *chunks = nullptr;
+  dbuf<double> y, partial, outd;
+  dbuf<RowChunk> chunks;
   std::vector<RowChunk> hc;
   for (int64_t r = row0; r < row1; r += COARSE_CHUNK_ROWS) hc.push_back(RowChunk{r, std::min(r + COARSE_CHUNK_ROWS, row1), 0, 0});
   const int nchunk = (int)hc.size();
-  HIPCHECK(ctx, hipMalloc((void **)&y, sizeof(double) * (size_t)n));
-  HIPCHECK(ctx, hipMalloc((void **)&partial, sizeof(double) * (size_t)std::max<int64_t>((int64_t)nchunk * nleft, 1)));
-  HIPCHECK(ctx, hipMalloc((void **)&outd, sizeof(double) * (size_t)(nleft * nright)));
-  int rc = upload(ctx, hc.data(), (int64_t)hc.size(), &chunks);
+  HIPCHECK(ctx, y.alloc(n));
+  HIPCHECK(ctx, partial.alloc((int64_t)nchunk * nleft));
+  HIPCHECK(ctx, outd.alloc(nleft * nright));
+  int rc = upload(ctx, hc.data(), (int64_t)hc.size(), chunks);
   std::vector<int32_t> scp = {0, nchunk};
   std::vector<int64_t> cidx(nleft);
-  int32_t *d_scp = nullptr;
-  int64_t *d_cidx = nullptr;
-  if (!rc) rc = upload(ctx, scp.data(), 2, &d_scp);
+  dbuf<int32_t> d_scp;
+  dbuf<int64_t> d_cidx;
+  if (!rc) rc = upload(ctx, scp.data(), 2, d_scp);
   for (int64_t j = 0; j < nright && !rc; ++j) {
     // y[row0:row1) = (A_dir right_j)[row0:row1): only the rows the products below read (a whole-matrix product per vector and call
     // was 1 s of the headline setup: 1 280 passes over 3.5 GB); same row sums in the same order as ddm_csr_mv
@@ -1272,19 +1180,13 @@ extern "C" int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
                          right + j * n, (int64_t)1, y + row0, (int64_t)1);
     if (hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "ddm_galerkin_products: kernel launch failed");
     for (int64_t i = 0; i < nleft; ++i) cidx[i] = i;
-    if (!d_cidx) rc = upload(ctx, cidx.data(), nleft, &d_cidx);
+    if (!d_cidx) rc = upload(ctx, cidx.data(), nleft, d_cidx);
     if (rc) break;
     if (nchunk > 0)
       hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(nchunk), dim3(WG), 0, ctx->stream, (int)nleft, n, left, y, chunks, partial, nchunk);
     hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, ctx->stream, 1, (int)nleft, d_scp, partial, d_cidx, nleft, outd + j * nleft);
   }
   if (!rc) rc = ddm_memcpy_d2h(ctx, out_host, outd, sizeof(double) * (size_t)(nleft * nright));
-  (void)hipFree(y);
-  (void)hipFree(partial);
-  (void)hipFree(outd);
-  (void)hipFree(chunks);
-  (void)hipFree(d_scp);
-  (void)hipFree(d_cidx);
   return rc;
 }
 
@@ -1294,11 +1196,11 @@ struct ddm_combined {
   ddm_op *op = nullptr;
   ddm_schwarz *schwarz = nullptr;
   ddm_galerkin *galerkin = nullptr;
-  double *dnext = nullptr;
+  dbuf<double> dnext;
   int64_t n = 0;
   bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
   bool overlap = false; // ... and the coarse chain runs on a side stream beside the local solve (measured slower: off by default)
-  double *mdnext = nullptr, *mp = nullptr, *mq = nullptr; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
+  dbuf<double> mdnext, mp, mq; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
   int mcols = 0, mcg_cols = 0;
 };
 extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)
@@ -1306,7 +1208,7 @@ extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwa
   if (!ctx || !out || !schwarz) return fail(ctx, DDM_EINVAL, "ERROR: No preconditioners added yet"); // combined_preconditioner.hh:77
   if (mode != 0 && mode != 1) return fail(ctx, DDM_ENOTIMPL, "Unknown apply mode in CombinedPreconditioner, use either additive or multiplicative"); // :68
   if (mode == 1 && galerkin && !op) return fail(ctx, DDM_EINVAL, "ERROR: ApplyMode is multiplicative but operator A is not provided. Set with `set_op`"); // :146
-  ddm_combined *C = new ddm_combined;
+  auto C = std::make_unique<ddm_combined>();
   C->mode = mode;
   C->op = op;
   C->schwarz = schwarz;
@@ -1318,11 +1220,8 @@ extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwa
     C->fused = !(f && f[0] == '0') && galerkin->copy == schwarz->copy && galerkin->add == schwarz->add && galerkin->n == schwarz->n && galerkin->n_novlp == schwarz->n_novlp;
     C->overlap = C->fused && e && e[0] == '1' && (ctx->nranks == 1 || ctx->rccl);
   }
-  if (hipMalloc((void **)&C->dnext, sizeof(double) * (size_t)std::max<int64_t>(C->n, 1)) != hipSuccess) {
-    delete C;
-    return fail(ctx, DDM_EHIP, "combined: allocation failed");
-  }
-  *out = C;
+  if (C->dnext.alloc(C->n) != hipSuccess) return fail(ctx, DDM_EHIP, "combined: allocation failed");
+  *out = C.release();
   return DDM_OK;
 }
 extern "C" int ddm_combined_status(ddm_ctx *ctx, const ddm_combined *C)
@@ -1330,15 +1229,7 @@ extern "C" int ddm_combined_status(ddm_ctx *ctx, const ddm_combined *C)
   if (!C) return fail(ctx, DDM_EINVAL, "ddm_combined_status: bad arguments");
   return C->schwarz ? ddm_schwarz_status(ctx, C->schwarz) : DDM_OK;
 }
-extern "C" void ddm_combined_destroy(ddm_combined *C)
-{
-  if (!C) return;
-  (void)hipFree(C->dnext);
-  (void)hipFree(C->mdnext);
-  (void)hipFree(C->mp);
-  (void)hipFree(C->mq);
-  delete C;
-}
+extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
 // Additive combination, fused: both levels start from the same extended defect and add over the same interface, so their
 // overlapping results are summed BEFORE the exchange (linearity of addOwnerCopyToAll; schwarz.hh:138-146 +
 // galerkin_preconditioner.hh:190-193 + combined_preconditioner.hh:136-142) -- one extend, one copy-halo, one halo add and one restrict
@@ -1435,7 +1326,8 @@ extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, cons
 struct ddm_cg {
   ddm_op *op = nullptr;
   ddm_combined *prec = nullptr;
-  double *x = nullptr, *b = nullptr, *p = nullptr, *q = nullptr;
+  double *x = nullptr, *b = nullptr; // the caller's
+  dbuf<double> p, q;
   int64_t n = 0;
   int it = 0;
   double def0 = 0.0;
@@ -1443,38 +1335,25 @@ struct ddm_cg {
 extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, ddm_cg **out)
 {
   if (!ctx || !op || !prec || !x || !b || !out) return fail(ctx, DDM_EINVAL, "ddm_cg_begin: bad arguments");
-  ddm_cg *S = new ddm_cg;
+  auto S = std::make_unique<ddm_cg>();
   S->op = op;
   S->prec = prec;
   S->x = x;
   S->b = b;
   S->n = op->n;
-  if (hipMalloc((void **)&S->p, sizeof(double) * (size_t)std::max<int64_t>(S->n, 1)) != hipSuccess ||
-      hipMalloc((void **)&S->q, sizeof(double) * (size_t)std::max<int64_t>(S->n, 1)) != hipSuccess) {
-    (void)hipFree(S->p);
-    delete S;
-    return fail(ctx, DDM_EHIP, "ddm_cg_begin: allocation failed");
-  }
-  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // prec.pre(x,b); b -= A x
+  if (S->p.alloc(S->n) != hipSuccess || S->q.alloc(S->n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_cg_begin: allocation failed");
+  DDMCHECK(ddm_op_applyscaleadd(ctx, op, -1.0, x, b)); // prec.pre(x,b); b -= A x
   double bb = 0.0;
-  if (!rc) rc = dot_device(ctx, S->n, op->owner, b, b, ctx->scal + 5);
-  if (!rc) rc = ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double));
-  if (rc) {
-    (void)hipFree(S->p);
-    (void)hipFree(S->q);
-    delete S;
-    return rc;
-  }
+  DDMCHECK(dot_device(ctx, S->n, op->owner, b, b, ctx->scal + 5));
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double)));
   S->def0 = std::sqrt(bb);
-  *out = S;
+  *out = S.release();
   return DDM_OK;
 }
 extern "C" void ddm_cg_end(ddm_ctx *ctx, ddm_cg *S)
 {
   if (!S) return;
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(S->p);
-  (void)hipFree(S->q);
   delete S;
 }
 extern "C" double ddm_cg_def0(const ddm_cg *S) { return S->def0; }
@@ -1586,6 +1465,13 @@ extern "C" int ddm_cg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double
   return rc;
 }
 
+// synchronises the context's stream when it goes out of scope: the Krylov drivers declare it AFTER their work arrays, so that an
+// early return waits for the enqueued kernels before the arrays are released
+struct StreamDrain {
+  ddm_ctx *ctx;
+  ~StreamDrain() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
 // ---- restarted GMRES -----------------------------------------------------------------------------
 // dune-istl RestartedGMResSolver::apply (DUNE 2.10 solvers.hh; not in the snapshot, restated from the
 // published implementation): left preconditioning, modified Gram-Schmidt, Givens rotations; the
@@ -1630,18 +1516,12 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
   const int64_t n = op->n;
   const int m = restart;
   const int G = grid_for(n);
-  double *V = nullptr, *w = nullptr, *hdev = nullptr;
-  HIPCHECK(ctx, hipMalloc((void **)&V, sizeof(double) * (size_t)std::max<int64_t>(n, 1) * (size_t)(m + 1)));
-  HIPCHECK(ctx, hipMalloc((void **)&w, sizeof(double) * (size_t)std::max<int64_t>(n, 1)));
-  HIPCHECK(ctx, hipMalloc((void **)&hdev, sizeof(double) * (size_t)(m + 2)));
+  dbuf<double> V, w, hdev;
+  HIPCHECK(ctx, V.alloc(std::max<int64_t>(n, 1) * (m + 1)));
+  HIPCHECK(ctx, w.alloc(n));
+  HIPCHECK(ctx, hdev.alloc(m + 2));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
   auto v = [&](int k) { return V + (size_t)k * (size_t)n; };
-  auto cleanup = [&](int rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(V);
-    (void)hipFree(w);
-    (void)hipFree(hdev);
-    return rc;
-  };
   std::vector<double> s(m + 1), cs(m), sn(m), hcol(m + 2), y(m);
   std::vector<std::vector<double>> H(m + 1, std::vector<double>(m, 0.0));
   int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
@@ -1649,7 +1529,7 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
   double nn = 0.0;
   if (!rc) rc = dot_device(ctx, n, op->owner, v(0), v(0), hdev);
   if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
-  if (rc) return cleanup(rc);
+  if (rc) return rc;
   double norm = std::sqrt(nn);
   const double def0 = norm;
   res->def0 = def0;
@@ -1658,10 +1538,10 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
   res->reduction = 1.0;
   res->elapsed_s = 0.0;
   if (hist_host) hist_host[0] = def0;
-  if (!(def0 == def0)) return cleanup(fail(ctx, DDM_ENUMERIC, "initial defect is NaN"));
+  if (!(def0 == def0)) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
   if (def0 < 1e-30) {
     res->converged = 1;
-    return cleanup(DDM_OK);
+    return DDM_OK;
   }
   const auto t0 = std::chrono::steady_clock::now();
   int j = 0;
@@ -1730,7 +1610,7 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
     rc = ddm_ilu0_status(ctx, prec->schwarz->solver, &st);
     if (!rc && st) rc = fail(ctx, DDM_ENUMERIC, "persistent triangular solve timed out waiting for a level (results invalid)");
   }
-  return cleanup(rc);
+  return rc;
 }
 
 // ---- BiCGSTAB ------------------------------------------------------------------------------------
@@ -1744,22 +1624,18 @@ extern "C" int ddm_bicgstab_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   const int64_t n = op->n;
   const int G = grid_for(n);
   const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
-  double *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // rt, p, v, y, t
-  auto cleanup = [&](int rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (double *q : buf) (void)hipFree(q);
-    return rc;
-  };
+  dbuf<double> buf[5]; // rt, p, v, y, t
+  StreamDrain drain{ctx}; // (declared after the buffers: every return waits for the stream before they are released)
   for (auto &q : buf)
-    if (hipMalloc((void **)&q, bytes) != hipSuccess) return cleanup(fail(ctx, DDM_EHIP, "ddm_bicgstab_solve: allocation failed"));
+    if (q.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_bicgstab_solve: allocation failed");
   double *rt = buf[0], *p = buf[1], *v = buf[2], *y = buf[3], *t = buf[4], *r = b;
   const double EPS = 1e-80;
   const bool verbose = std::getenv("DDM_KRYLOV_VERBOSE") != nullptr;
   int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, r); // r = b - A x (b is overwritten by the defect, as in dune-istl)
-  if (rc) return cleanup(rc);
+  if (rc) return rc;
   HIPCHECK(ctx, hipMemcpyAsync(rt, r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   double norm = 0.0;
-  if ((rc = ddm_norm(ctx, op, r, &norm))) return cleanup(rc);
+  if ((rc = ddm_norm(ctx, op, r, &norm))) return rc;
   const double def0 = norm;
   res->def0 = def0;
   res->iterations = 0;
@@ -1769,11 +1645,11 @@ extern "C" int ddm_bicgstab_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   int nh = 0;
   if (hist_host) hist_host[nh] = def0;
   ++nh;
-  if (!(def0 == def0)) return cleanup(fail(ctx, DDM_ENUMERIC, "initial defect is NaN"));
+  if (!(def0 == def0)) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
   if (def0 < 1e-30) {
     res->converged = 1;
     if (nhist) *nhist = nh;
-    return cleanup(DDM_OK);
+    return DDM_OK;
   }
   HIPCHECK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
   HIPCHECK(ctx, hipMemsetAsync(v, 0, bytes, ctx->stream));
@@ -1822,15 +1698,15 @@ extern "C" int ddm_bicgstab_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
     if ((rc = ddm_norm(ctx, op, r, &norm))) break;
     if (record(norm)) { conv = true; break; }
   }
-  if (rc) return cleanup(rc);
+  if (rc) return rc;
   (void)hipStreamSynchronize(ctx->stream);
   res->elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   res->iterations = (int32_t)std::ceil(std::min(it, (double)maxit));
   res->converged = conv ? 1 : 0;
   if (nhist) *nhist = nh;
   int st = 0;
-  if (prec->schwarz && !ddm_ilu0_status(ctx, prec->schwarz->solver, &st) && st) return cleanup(fail(ctx, DDM_ENUMERIC, "local triangular solve timed out (code %d)", st));
-  return cleanup(DDM_OK);
+  if (prec->schwarz && !ddm_ilu0_status(ctx, prec->schwarz->solver, &st) && st) return fail(ctx, DDM_ENUMERIC, "local triangular solve timed out (code %d)", st);
+  return DDM_OK;
 }
 
 #include "geneo.hpp"

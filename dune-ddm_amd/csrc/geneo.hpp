@@ -80,20 +80,13 @@ struct GeneoWork {
   ddm_ctx *ctx = nullptr;
   int64_t n = 0;
   int nsub = 0, m = 0, p = 0, nchunk = 0;
-  std::vector<void *> allocs;
-  GChunk *chunks = nullptr;
-  int32_t *sub_chunk_ptr = nullptr, *sub_of_row = nullptr;
-  double *partial = nullptr;
-  ~GeneoWork()
-  {
-    for (void *q : allocs) (void)hipFree(q);
-  }
+  dbuf<GChunk> chunks;
+  dbuf<int32_t> sub_chunk_ptr, sub_of_row;
+  dbuf<double> partial;
   template <class T>
-  int alloc(T **ptr, size_t count)
+  int alloc(dbuf<T> &buf, size_t count)
   {
-    *ptr = nullptr;
-    if (hipMalloc((void **)ptr, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) return fail(ctx, DDM_EHIP, "GenEO: device allocation of %zu bytes failed", sizeof(T) * count);
-    allocs.push_back(*ptr);
+    if (buf.alloc((int64_t)count) != hipSuccess) return fail(ctx, DDM_EHIP, "GenEO: device allocation of %zu bytes failed", sizeof(T) * count);
     return DDM_OK;
   }
   // G[sub] = U^T V per subdomain (pu x pv row-major, nsub matrices).  Blocks wider than the register tiles of the kernel (128 x 80)
@@ -294,28 +287,22 @@ static bool csr_values_symmetric(const ddm_csr *A)
 // (MsGFEMCoarseSpace): P X = keep_b .* X - A^^-1 G_ib X,  P^T R = keep_b .* R - G_bi A^^-T (interior .* R).
 struct ddm_harmonic {
   int64_t n = 0;
-  ddm_csr *Gib = nullptr, *Gbi = nullptr;
-  ddm_ilu0 *F = nullptr;
-  double *keep = nullptr;   // 1 outside the interior (rows the extension leaves alone)
-  double *keep_b = nullptr; // 1 on boundary rows only (projection: rows that are neither interior nor boundary are zeroed)
-  double *isint = nullptr;  // 1 on interior rows
-  double *t1 = nullptr, *t2 = nullptr;
+  ddm_csr *Gib = nullptr, *Gbi = nullptr; // owned
+  ddm_ilu0 *F = nullptr;                  // owned
+  dbuf<double> keep;   // 1 outside the interior (rows the extension leaves alone)
+  dbuf<double> keep_b; // 1 on boundary rows only (projection: rows that are neither interior nor boundary are zeroed)
+  dbuf<double> isint;  // 1 on interior rows
+  dbuf<double> t1, t2; // work blocks (n x tcols)
   int tcols = 0;
   bool symmetric = true;
+  ~ddm_harmonic()
+  {
+    ddm_csr_destroy(Gib);
+    ddm_csr_destroy(Gbi);
+    ddm_ilu0_destroy(F);
+  }
 };
-extern "C" void ddm_harmonic_destroy(ddm_harmonic *H)
-{
-  if (!H) return;
-  ddm_csr_destroy(H->Gib);
-  ddm_csr_destroy(H->Gbi);
-  ddm_ilu0_destroy(H->F);
-  (void)hipFree(H->keep);
-  (void)hipFree(H->keep_b);
-  (void)hipFree(H->isint);
-  (void)hipFree(H->t1);
-  (void)hipFree(H->t2);
-  delete H;
-}
+extern "C" void ddm_harmonic_destroy(ddm_harmonic *H) { delete H; }
 // cls[i]: 0 = interior, 1 = boundary, anything else = neither (its values count as zero in the right-hand side, :109-118)
 static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, const uint8_t *cls, bool want_transpose, ddm_harmonic **out)
 {
@@ -378,9 +365,9 @@ static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks,
       k1[(size_t)i] = cls[i] == 1 ? 1.0 : 0.0;
       k2[(size_t)i] = cls[i] == 0 ? 1.0 : 0.0;
     }
-    rc = upload(ctx, k0.data(), n, &H->keep);
-    if (!rc) rc = upload(ctx, k1.data(), n, &H->keep_b);
-    if (!rc) rc = upload(ctx, k2.data(), n, &H->isint);
+    rc = upload(ctx, k0.data(), n, H->keep);
+    if (!rc) rc = upload(ctx, k1.data(), n, H->keep_b);
+    if (!rc) rc = upload(ctx, k2.data(), n, H->isint);
   }
   if (rc) {
     ddm_harmonic_destroy(H);
@@ -389,22 +376,10 @@ static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks,
   *out = H;
   return DDM_OK;
 }
-static int harmonic_reserve(ddm_ctx *ctx, ddm_harmonic *H, int m)
-{
-  if (m <= H->tcols) return DDM_OK;
-  (void)hipFree(H->t1);
-  (void)hipFree(H->t2);
-  H->t1 = H->t2 = nullptr;
-  H->tcols = 0;
-  HIPCHECK(ctx, hipMalloc((void **)&H->t1, sizeof(double) * (size_t)std::max<int64_t>(H->n, 1) * m));
-  HIPCHECK(ctx, hipMalloc((void **)&H->t2, sizeof(double) * (size_t)std::max<int64_t>(H->n, 1) * m));
-  H->tcols = m;
-  return DDM_OK;
-}
 // X <- keep .* X - A^^-1 G_ib X  (keep = rows outside the interior, or boundary rows only)
 static int harmonic_apply(ddm_ctx *ctx, ddm_harmonic *H, int m, double *X, int64_t ldx, bool boundary_only)
 {
-  DDMCHECK(harmonic_reserve(ctx, H, m));
+  HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
   DDMCHECK(csr_mm_ld(ctx, H->Gib, m, X, ldx, H->t1, m));
   DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));
   hipLaunchKernelGGL(k_geneo_project, dim3((unsigned)((H->n * (int64_t)m + 255) / 256)), dim3(256), 0, ctx->stream, H->n, m, boundary_only ? H->keep_b : H->keep,
@@ -415,7 +390,7 @@ static int harmonic_apply(ddm_ctx *ctx, ddm_harmonic *H, int m, double *X, int64
 // R <- keep_b .* R - G_bi A^^-1 (interior .* R)   (transpose of the projection; symmetric A only)
 static int harmonic_apply_transposed(ddm_ctx *ctx, ddm_harmonic *H, int m, double *R, int64_t ldr)
 {
-  DDMCHECK(harmonic_reserve(ctx, H, m));
+  HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
   const unsigned g = (unsigned)((H->n * (int64_t)m + 255) / 256);
   hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(g), dim3(256), 0, ctx->stream, H->n, m, H->isint, (const double *)R, ldr, H->t1, (int64_t)m);
   DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));
@@ -577,39 +552,39 @@ static int geneo_run(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, i
     for (int64_t r = sub_ptr[s]; r < sub_ptr[s + 1]; ++r) sor[(size_t)r] = (int32_t)s;
   }
   W.nchunk = (int)chunks.size();
-  DDMCHECK(W.alloc(&W.chunks, chunks.size()));
-  DDMCHECK(W.alloc(&W.sub_chunk_ptr, scp.size()));
-  DDMCHECK(W.alloc(&W.sub_of_row, (size_t)n));
-  DDMCHECK(W.alloc(&W.partial, (size_t)W.nchunk * p * p * 2)); // (two products per chunk: gram2_sym)
+  DDMCHECK(W.alloc(W.chunks, chunks.size()));
+  DDMCHECK(W.alloc(W.sub_chunk_ptr, scp.size()));
+  DDMCHECK(W.alloc(W.sub_of_row, (size_t)n));
+  DDMCHECK(W.alloc(W.partial, (size_t)W.nchunk * p * p * 2)); // (two products per chunk: gram2_sym)
   HIPCHECK(ctx, hipMemcpy(W.chunks, chunks.data(), sizeof(GChunk) * chunks.size(), hipMemcpyHostToDevice));
   HIPCHECK(ctx, hipMemcpy(W.sub_chunk_ptr, scp.data(), sizeof(int32_t) * scp.size(), hipMemcpyHostToDevice));
   HIPCHECK(ctx, hipMemcpy(W.sub_of_row, sor.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  double *S[2], *AS[2], *CS[2], *R = nullptr, *maskd = nullptr, *poud = nullptr;
+  dbuf<double> S[2], AS[2], CS[2], R, maskd, poud;
   for (int b = 0; b < 2; ++b) {
-    DDMCHECK(W.alloc(&S[b], (size_t)n * p));
-    DDMCHECK(W.alloc(&AS[b], (size_t)n * p));
-    DDMCHECK(W.alloc(&CS[b], (size_t)n * p));
+    DDMCHECK(W.alloc(S[b], (size_t)n * p));
+    DDMCHECK(W.alloc(AS[b], (size_t)n * p));
+    DDMCHECK(W.alloc(CS[b], (size_t)n * p));
     HIPCHECK(ctx, hipMemsetAsync(S[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(AS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(CS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
   }
-  DDMCHECK(W.alloc(&R, (size_t)n * m));
-  DDMCHECK(W.alloc(&maskd, (size_t)n));
-  DDMCHECK(W.alloc(&poud, (size_t)n));
+  DDMCHECK(W.alloc(R, (size_t)n * m));
+  DDMCHECK(W.alloc(maskd, (size_t)n));
+  DDMCHECK(W.alloc(poud, (size_t)n));
   {
     std::vector<double> mk((size_t)n);
     for (int64_t i = 0; i < n; ++i) mk[(size_t)i] = (dirichlet_host && dirichlet_host[i]) ? 0.0 : 1.0;
     HIPCHECK(ctx, hipMemcpy(maskd, mk.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     HIPCHECK(ctx, hipMemcpy(poud, pou_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   }
-  double *gA, *gC, *gmm[5], *svec[2], *Yd, *mud;
-  DDMCHECK(W.alloc(&gA, (size_t)nsub * p * p));
-  DDMCHECK(W.alloc(&gC, (size_t)nsub * p * p));
-  for (int k = 0; k < 5; ++k) DDMCHECK(W.alloc(&gmm[k], (size_t)nsub * m * m));
-  for (int k = 0; k < 2; ++k) DDMCHECK(W.alloc(&svec[k], (size_t)nsub * m));
+  dbuf<double> gA, gC, gmm[5], svec[2], Yd, mud;
+  DDMCHECK(W.alloc(gA, (size_t)nsub * p * p));
+  DDMCHECK(W.alloc(gC, (size_t)nsub * p * p));
+  for (int k = 0; k < 5; ++k) DDMCHECK(W.alloc(gmm[k], (size_t)nsub * m * m));
+  for (int k = 0; k < 2; ++k) DDMCHECK(W.alloc(svec[k], (size_t)nsub * m));
   const int q2 = 2 * m; // fused rotation: [X_new | P_new]
-  DDMCHECK(W.alloc(&Yd, (size_t)nsub * p * q2));
-  DDMCHECK(W.alloc(&mud, (size_t)nsub * m));
+  DDMCHECK(W.alloc(Yd, (size_t)nsub * p * q2));
+  DDMCHECK(W.alloc(mud, (size_t)nsub * m));
   std::vector<double> hA((size_t)nsub * p * p), hC((size_t)nsub * p * p), hY((size_t)nsub * p * q2), hmu((size_t)nsub * m);
   std::vector<double> h_rr((size_t)nsub * m * m), h_rw((size_t)nsub * m * m), h_aa((size_t)nsub * m * m);
   std::vector<double> dscale((size_t)nsub * p, 1.0); // column scaling of S = [X | W | P] folded into the projected problem
@@ -805,12 +780,11 @@ static int geneo_basis_impl(ddm_ctx *ctx, const char *who, const ddm_csr *A_neu,
   // one), double nev until the largest computed one exceeds it or nev >= nev_max
   for (;;) {
     if (nev > kmax) return fail(ctx, DDM_EINVAL, "%s: kmax = %lld is smaller than nev = %d", who, (long long)kmax, nev);
-    double *basis_dev = nullptr;
-    HIPCHECK(ctx, hipMalloc((void **)&basis_dev, sizeof(double) * (size_t)nev * (size_t)std::max<int64_t>(n, 1)));
+    dbuf<double> basis_dev;
+    HIPCHECK(ctx, basis_dev.alloc(nev * std::max<int64_t>(n, 1)));
     std::vector<double> eig((size_t)nsub * nev);
     int rc = geneo_run(ctx, A_neu, B_neu, nsub, sub_ptr, pou_host, dirichlet_host, P, nev, basis_dev, eig.data(), info, con, pou_pencil_host, op_C);
     if (!rc && hipMemcpy(basis_host, basis_dev, sizeof(double) * (size_t)nev * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, DDM_EHIP, "%s: basis download failed", who);
-    (void)hipFree(basis_dev);
     if (rc) return rc;
     bool done = true;
     if (P.threshold > 0.0) {
@@ -902,12 +876,11 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   struct Guard {
     ddm_harmonic *H;
     ddm_csr *I = nullptr;
-    double *d = nullptr;
+    dbuf<double> d;
     ~Guard()
     {
       ddm_harmonic_destroy(H);
       ddm_csr_destroy(I);
-      (void)hipFree(d);
     }
   } g{H};
   if (!H->symmetric) return fail(ctx, DDM_ENOTIMPL, "ddm_svd_basis: the interior block of A_dir is not symmetric");
@@ -916,9 +889,9 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   for (int64_t i = 0; i <= n; ++i) rp[(size_t)i] = i;
   for (int64_t i = 0; i < n; ++i) ci[(size_t)i] = (int32_t)i;
   DDMCHECK(ddm_csr_create(ctx, n, n, rp.data(), ci.data(), ones.data(), &g.I));
-  DDMCHECK(upload(ctx, pou_int.data(), n, &g.d));
+  DDMCHECK(upload(ctx, pou_int.data(), n, g.d));
   const std::function<int(int, const double *, int64_t, double *, int64_t)> op = [&](int m, const double *X, int64_t ldx, double *Y, int64_t ldy) -> int {
-    DDMCHECK(harmonic_reserve(ctx, H, m));
+    HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
     const unsigned gr = (unsigned)((n * (int64_t)m + 255) / 256);
     hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)g.d, X, ldx, H->t1, (int64_t)m); // D x
     DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));                                                                 // A_ii^-T
@@ -960,9 +933,9 @@ static int blockvec_setup(ddm_ctx *ctx, GeneoWork &W, int64_t nsub, const int64_
     scp[(size_t)s + 1] = (int32_t)chunks.size();
   }
   W.nchunk = (int)chunks.size();
-  DDMCHECK(W.alloc(&W.chunks, chunks.size()));
-  DDMCHECK(W.alloc(&W.sub_chunk_ptr, scp.size()));
-  DDMCHECK(W.alloc(&W.partial, (size_t)std::max(W.nchunk, 1) * (size_t)pmax_sq));
+  DDMCHECK(W.alloc(W.chunks, chunks.size()));
+  DDMCHECK(W.alloc(W.sub_chunk_ptr, scp.size()));
+  DDMCHECK(W.alloc(W.partial, (size_t)std::max(W.nchunk, 1) * (size_t)pmax_sq));
   HIPCHECK(ctx, hipMemcpy(W.chunks, chunks.data(), sizeof(GChunk) * chunks.size(), hipMemcpyHostToDevice));
   HIPCHECK(ctx, hipMemcpy(W.sub_chunk_ptr, scp.data(), sizeof(int32_t) * scp.size(), hipMemcpyHostToDevice));
   return DDM_OK;
@@ -973,8 +946,8 @@ extern "C" int ddm_blockvec_gram(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_
   if (!ctx || !sub_ptr || !U || !V || !G_host || nsub < 1 || pu < 1 || pv < 1 || ldu < pu || ldv < pv) return fail(ctx, DDM_EINVAL, "ddm_blockvec_gram: bad arguments");
   GeneoWork W;
   DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, pu * pv));
-  double *G = nullptr;
-  DDMCHECK(W.alloc(&G, (size_t)nsub * pu * pv));
+  dbuf<double> G;
+  DDMCHECK(W.alloc(G, (size_t)nsub * pu * pv));
   DDMCHECK(W.gram(U, ldu, pu, V, ldv, pv, G));
   return ddm_memcpy_d2h(ctx, G_host, G, (int64_t)sizeof(double) * nsub * pu * pv);
 }
@@ -984,8 +957,8 @@ extern "C" int ddm_blockvec_gram2_sym(ddm_ctx *ctx, int64_t nsub, const int64_t 
   if (!ctx || !sub_ptr || !U || !V1 || !V2 || !G1_host || !G2_host || nsub < 1 || p < 1 || ldu < p || ldv < p) return fail(ctx, DDM_EINVAL, "ddm_blockvec_gram2_sym: bad arguments");
   GeneoWork W;
   DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, 2 * p * p));
-  double *G = nullptr;
-  DDMCHECK(W.alloc(&G, (size_t)nsub * p * p * 2));
+  dbuf<double> G;
+  DDMCHECK(W.alloc(G, (size_t)nsub * p * p * 2));
   const bool upper_only = W.gram2_sym(U, ldu, V1, V2, ldv, p, G, G + (size_t)nsub * p * p);
   HIPCHECK(ctx, hipGetLastError());
   DDMCHECK(ddm_memcpy_d2h(ctx, G1_host, G, (int64_t)sizeof(double) * nsub * p * p));
@@ -1004,8 +977,8 @@ extern "C" int ddm_blockvec_rotate(ddm_ctx *ctx, int64_t nsub, const int64_t *su
     return fail(ctx, DDM_EINVAL, "ddm_blockvec_rotate: bad arguments");
   GeneoWork W;
   DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, 1));
-  double *Y = nullptr;
-  DDMCHECK(W.alloc(&Y, (size_t)nsub * p * q));
+  dbuf<double> Y;
+  DDMCHECK(W.alloc(Y, (size_t)nsub * p * q));
   DDMCHECK(ddm_memcpy_h2d(ctx, Y, Y_host, (int64_t)sizeof(double) * nsub * p * q));
   const double *Ux[1] = {U};
   double *Ox[1] = {Out};

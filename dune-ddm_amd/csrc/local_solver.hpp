@@ -45,12 +45,12 @@ static int ilu0_factor_block(const int64_t *rp, const int32_t *ci, double *lu, i
 struct TriSchedule { // one triangular factor, level by level in sliced ELL
   int64_t nlev = 0;
   std::vector<LevelDesc> desc;        // per level
-  int32_t *rows = nullptr;            // [n] rows sorted by level
-  int32_t *cols = nullptr;            // sliced ELL columns
-  double *vals = nullptr;             // sliced ELL values
-  double *dinv = nullptr;             // upper only: inverse pivots in level order
-  float *vals_f32 = nullptr, *dinv_f32 = nullptr; // single-precision copies for the preconditioner sweeps (made on first use)
-  LevelDesc *d_desc = nullptr;        // device copy (for the small-level kernel)
+  dbuf<int32_t> rows;                 // [n] rows sorted by level
+  dbuf<int32_t> cols;                 // sliced ELL columns
+  dbuf<double> vals;                  // sliced ELL values
+  dbuf<double> dinv;                  // upper only: inverse pivots in level order
+  dbuf<float> vals_f32, dinv_f32;     // single-precision copies for the preconditioner sweeps (made on first use)
+  dbuf<LevelDesc> d_desc;             // device copy (for the small-level kernel)
   struct Launch {                     // execution plan
     int first, count;                 // levels [first, first+count)
     bool small;                       // one workgroup loops over the levels
@@ -63,13 +63,13 @@ struct TriCsr { // one triangular factor of the sparse direct solver: rows in le
   int64_t nlev = 0;
   std::vector<CsrLevel> desc;
   int64_t nrows = 0, entries = 0; // transformed rows (real + virtual unknowns of the supernodes), stored entries
-  int32_t *rows = nullptr;        // destination unknown of a row
-  int32_t *rhs = nullptr;         // index of its right-hand side (lower: in d, upper: in x) or -1 (none)
-  int64_t *lrp = nullptr;
-  int32_t *cols = nullptr;
-  double *vals = nullptr;
-  double *dinv = nullptr; // upper only
-  CsrLevel *d_desc = nullptr;
+  dbuf<int32_t> rows;             // destination unknown of a row
+  dbuf<int32_t> rhs;              // index of its right-hand side (lower: in d, upper: in x) or -1 (none)
+  dbuf<int64_t> lrp;
+  dbuf<int32_t> cols;
+  dbuf<double> vals;
+  dbuf<double> dinv; // upper only
+  dbuf<CsrLevel> d_desc;
   struct Launch {
     int first, count;
     bool fused;
@@ -77,7 +77,7 @@ struct TriCsr { // one triangular factor of the sparse direct solver: rows in le
   std::vector<Launch> plan;
   // block-wise variant (rows ordered by (block, level)): one workgroup per block runs the block's whole solve
   int nblocks = 0;
-  int32_t *blk_lev_ptr = nullptr;
+  dbuf<int32_t> blk_lev_ptr;
 };
 
 static constexpr int SMALL_LEVEL_ROWS = 2048;
@@ -183,11 +183,11 @@ static int build_schedule(ddm_ctx *ctx, const ddm_csr *A, const hvec<double> &lu
       l += 1;
     }
   }
-  DDMCHECK(upload(ctx, rows.data(), n, &S.rows));
-  DDMCHECK(upload(ctx, cols.data(), ent, &S.cols));
-  DDMCHECK(upload(ctx, vals.data(), ent, &S.vals));
-  if (upper) DDMCHECK(upload(ctx, dinv.data(), n, &S.dinv));
-  DDMCHECK(upload(ctx, S.desc.data(), nlev, &S.d_desc));
+  DDMCHECK(upload(ctx, rows.data(), n, S.rows));
+  DDMCHECK(upload(ctx, cols.data(), ent, S.cols));
+  DDMCHECK(upload(ctx, vals.data(), ent, S.vals));
+  if (upper) DDMCHECK(upload(ctx, dinv.data(), n, S.dinv));
+  DDMCHECK(upload(ctx, S.desc.data(), nlev, S.d_desc));
   return DDM_OK;
 }
 
@@ -437,26 +437,15 @@ static int build_csr_schedule(ddm_ctx *ctx, const ddm_csr *A, const hvec<double>
   }
   S.nrows = nr;
   S.entries = (int64_t)rcol.size();
-  DDMCHECK(upload(ctx, rows.data(), nr, &S.rows));
-  DDMCHECK(upload(ctx, rhs.data(), nr, &S.rhs));
-  DDMCHECK(upload(ctx, lrp.data(), nr + 1, &S.lrp));
-  DDMCHECK(upload(ctx, cols.data(), (int64_t)rcol.size(), &S.cols));
-  DDMCHECK(upload(ctx, vals.data(), (int64_t)rval.size(), &S.vals));
-  if (upper) DDMCHECK(upload(ctx, dinv.data(), nr, &S.dinv));
-  DDMCHECK(upload(ctx, S.desc.data(), nlev, &S.d_desc));
-  if (block_ptr) DDMCHECK(upload(ctx, blp.data(), (int64_t)blp.size(), &S.blk_lev_ptr));
+  DDMCHECK(upload(ctx, rows.data(), nr, S.rows));
+  DDMCHECK(upload(ctx, rhs.data(), nr, S.rhs));
+  DDMCHECK(upload(ctx, lrp.data(), nr + 1, S.lrp));
+  DDMCHECK(upload(ctx, cols.data(), (int64_t)rcol.size(), S.cols));
+  DDMCHECK(upload(ctx, vals.data(), (int64_t)rval.size(), S.vals));
+  if (upper) DDMCHECK(upload(ctx, dinv.data(), nr, S.dinv));
+  DDMCHECK(upload(ctx, S.desc.data(), nlev, S.d_desc));
+  if (block_ptr) DDMCHECK(upload(ctx, blp.data(), (int64_t)blp.size(), S.blk_lev_ptr));
   return DDM_OK;
-}
-static void free_csr_schedule(TriCsr &S)
-{
-  (void)hipFree(S.blk_lev_ptr);
-  (void)hipFree(S.rhs);
-  (void)hipFree(S.rows);
-  (void)hipFree(S.lrp);
-  (void)hipFree(S.cols);
-  (void)hipFree(S.vals);
-  (void)hipFree(S.dinv);
-  (void)hipFree(S.d_desc);
 }
 static int enqueue_tri_csr(ddm_ctx *ctx, const TriCsr &S, bool upper, const double *d, double *x)
 {
@@ -494,103 +483,83 @@ static void enqueue_multi_levels_csr(ddm_ctx *ctx, const TriCsr &S, bool upper, 
                        S.dinv, D, ldd, X, ldx);
   }
 }
-static void free_schedule(TriSchedule &S)
-{
-  (void)hipFree(S.rows);
-  (void)hipFree(S.cols);
-  (void)hipFree(S.vals);
-  (void)hipFree(S.dinv);
-  (void)hipFree(S.vals_f32);
-  (void)hipFree(S.dinv_f32);
-  (void)hipFree(S.d_desc);
-}
 
 // ---- the parts of a factor ----------------------------------------------------------------------
-template <class... P>
-static void dev_free(P *...p) { ((void)hipFree((void *)p), ...); }
+// Device arrays are dbuf members (device_buffer.hpp), so a part's destructor only says what is NOT memory, or an order that matters.
 
 // Engine of the single-vector solve; the values are the codes ddm_ilu0_engine reports.
 enum class Engine : int { Levels = 0, Xcd2 = 4, Pipe = 8, Supernodal = 16, Box = 32 };
 
 struct LevelEngine { // one launch per level (runs of small levels in one workgroup); also the multi-RHS solves of every ILU(0) factor
   TriSchedule L, U;
-  float *xf = nullptr; // n x xf_nrhs work block of the single-precision multi-RHS sweeps
+  dbuf<float> xf; // n x xf_nrhs work block of the single-precision multi-RHS sweeps
   int xf_nrhs = 0;
-  ~LevelEngine() { free_schedule(L); free_schedule(U); (void)hipFree(xf); }
 };
 
 struct XcdEngine { // xcd2 (XCD-local + loader waves): per-block (subdomain) level schedules, built on first use (build_xcd_schedule)
   int ngroups = 0;
-  GroupDesc *groups = nullptr;
-  LevelDesc *desc = nullptr;
-  int64_t *flag_off = nullptr;
-  int32_t *rows = nullptr, *cols = nullptr;
-  double *vals = nullptr, *dinv = nullptr;
-  unsigned *flags = nullptr;
-  double *dperm = nullptr; // right-hand side permuted into level order (loader engine)
-  int64_t *lpos = nullptr; // positions of the L parts (only those need the permuted right-hand side)
-  ~XcdEngine() { dev_free(groups, desc, flag_off, rows, cols, vals, dinv, flags, dperm, lpos); }
+  dbuf<GroupDesc> groups;
+  dbuf<LevelDesc> desc;
+  dbuf<int64_t> flag_off;
+  dbuf<int32_t> rows, cols;
+  dbuf<double> vals, dinv;
+  dbuf<unsigned> flags;
+  dbuf<double> dperm; // right-hand side permuted into level order (loader engine)
+  dbuf<int64_t> lpos; // positions of the L parts (only those need the permuted right-hand side)
 };
 
 struct PipeEngine { // pipe: chains x tasks, see trsv_pipe_host.hpp
   int ngroups = 0;
-  pipe::Group *groups = nullptr;
-  pipe::Task *tasks = nullptr;
-  unsigned char *stream = nullptr;
-  int32_t *koff = nullptr, *posU = nullptr, *rowU = nullptr; // rowU: natural row of every U position (-1: padding)
-  double *ypos = nullptr, *xpos = nullptr;
-  unsigned long long *progress = nullptr;
-  unsigned *queue = nullptr;
+  dbuf<pipe::Group> groups;
+  dbuf<pipe::Task> tasks;
+  dbuf<unsigned char> stream;
+  dbuf<int32_t> koff, posU, rowU; // rowU: natural row of every U position (-1: padding)
+  dbuf<double> ypos, xpos;
+  dbuf<unsigned long long> progress;
+  dbuf<unsigned> queue;
   int64_t nposU = 0;
   int spread = 0; // placement-independent mode (set when a subdomain has more work per level than one XCD's workgroups take)
   int grid = 0;
   pipe::Stats stats;
-  ~PipeEngine() { dev_free(groups, tasks, stream, koff, posU, rowU, ypos, xpos, progress, queue); }
 };
 
 struct BoxEngine { // box (trsv_box_host.hpp): structured leading box of every block + a nested factor for the rows behind it
   int nblocks = 0;
   int64_t nshell = 0, nprod = 0;
-  box::Block *blocks = nullptr;
-  box::StepTab *steps = nullptr;
-  double *stream = nullptr;
-  unsigned long long *einfo = nullptr;
-  double *E = nullptr, *ext_val = nullptr;
-  int32_t *ext_col = nullptr;
-  double *xs = nullptr;
-  unsigned long long *prog = nullptr;
-  unsigned *queue = nullptr;
-  unsigned long long *dbg = nullptr;    // DDM_BOX_CHECK: pinned host words of the kernels' address check
+  dbuf<box::Block> blocks;
+  dbuf<box::StepTab> steps;
+  dbuf<double> stream;
+  dbuf<unsigned long long> einfo;
+  dbuf<double> E, ext_val;
+  dbuf<int32_t> ext_col;
+  dbuf<double> xs;
+  dbuf<unsigned long long> prog;
+  dbuf<unsigned> queue;
+  unsigned long long *dbg = nullptr;    // DDM_BOX_CHECK: pinned host words of the kernels' address check (hipHostMalloc)
   int64_t n = 0, stream_len = 0, xs_len = 0, prog_len = 0, einfo_len = 0;
   // shell system
-  int64_t *srp = nullptr;
-  int32_t *sci = nullptr, *srow = nullptr;
-  double *sva = nullptr, *ds = nullptr, *xsol = nullptr;
+  dbuf<int64_t> srp;
+  dbuf<int32_t> sci, srow;
+  dbuf<double> sva, ds, xsol;
   ddm_csr *shell_csr = nullptr;
   ddm_ilu0 *shell = nullptr;
   int grid = 0;
   box::Stats stats;
-  ~BoxEngine()
+  ~BoxEngine() // the body runs before the members go: the nested factor (it reads shell_csr), then its matrix, then the arrays above
   {
     ddm_ilu0_destroy(shell);
     ddm_csr_destroy(shell_csr);
-    dev_free(blocks, steps, stream, einfo, E, ext_val, ext_col, xs, prog, queue, srp, sci, srow, sva, ds, xsol);
     if (dbg) (void)hipHostFree(dbg);
   }
 };
 
 struct CsrDirect { // host sparse direct factor (ddm_chol_create): lives in a fill-reducing order, d / x are permuted around the solve
   ddm_csr *pattern = nullptr; // host-only CSR pattern of L + D + L^T in the permuted order (owned)
-  int32_t *perm = nullptr;    // device: perm[new] = old
+  dbuf<int32_t> perm;         // device: perm[new] = old
   int64_t nvirt = 0;          // virtual unknowns of the supernodal transformation: the permuted solution holds n + nvirt entries
   TriCsr Lc, Uc;              // global levels: multi-RHS solves, one launch per level
   TriCsr Lb, Ub;              // the same factors ordered by (block, level): single right-hand side, one workgroup per block
-  ~CsrDirect()
-  {
-    delete pattern;
-    (void)hipFree(perm);
-    for (TriCsr *S : {&Lc, &Uc, &Lb, &Ub}) free_csr_schedule(*S);
-  }
+  ~CsrDirect() { delete pattern; }
 };
 
 struct SnDirect { // supernodal factor computed ON THE DEVICE (sn_chol.hpp); solves run on its panels, in place in pd / pD
@@ -600,11 +569,10 @@ struct SnDirect { // supernodal factor computed ON THE DEVICE (sn_chol.hpp); sol
   // captured HIP graphs; the matrix is kept as device copies of its three arrays
   int refine_steps = 0;
   double refine_omega[5] = {0, 0, 0, 0, 0}; // backward error of the probe after 0, 1, .. steps
-  int64_t *ref_rp = nullptr;
-  int32_t *ref_ci = nullptr;
-  double *ref_va = nullptr, *pr = nullptr; // pr: residual block (n x pr_cols)
+  dbuf<int64_t> ref_rp;
+  dbuf<int32_t> ref_ci;
+  dbuf<double> ref_va, pr; // pr: residual block (n x pr_cols)
   int pr_cols = 0;
-  ~SnDirect() { dev_free(ref_rp, ref_ci, ref_va, pr); }
 };
 
 struct GraphCache { // one captured, instantiated solve (capture_and_launch)
@@ -623,10 +591,10 @@ struct ddm_ilu0 {
   // straight into it, so the host can look at it without synchronising the stream (ilu0_peek_status: every apply checks the
   // applies before it -- fail fast instead of returning stale results until somebody calls ddm_ilu0_status)
   unsigned *err = nullptr;
-  XcdState *xstate = nullptr; // tickets and epoch of the persistent kernels (pipe, xcd2, box)
+  dbuf<XcdState> xstate; // tickets and epoch of the persistent kernels (pipe, xcd2, box)
   // direct factors: right-hand side / solution permuted into the factor's order (n, n + nvirt doubles), the same for row-major blocks
-  double *pd = nullptr, *px = nullptr;
-  double *pD = nullptr, *pX = nullptr;
+  dbuf<double> pd, px;
+  dbuf<double> pD, pX;
   int pm_nrhs = 0;
   double direct_flops = 0.0;
   // the pipe / box part is built in the background (its own host threads + uploads; 2.6 s at 216^3, nothing of it is needed before
@@ -649,29 +617,16 @@ struct ddm_ilu0 {
   int mg_nrhs = 0;
   int64_t mg_ldd = 0, mg_ldx = 0;
   bool mg_f32 = false; // the cached graph runs the single-precision sweeps
-  ~ddm_ilu0()
+  ~ddm_ilu0() // the body runs before any member goes: the builder thread writes the parts, the graph execs point into the arrays
   {
     if (builder.joinable()) builder.join();
     graph.reset();
     mgraph.reset();
     if (err) (void)hipHostFree(err);
-    dev_free(xstate, pd, px, pD, pX);
-  } // (the engine parts free themselves)
+  }
 };
 static inline double ilu0_direct_flops(const ddm_ilu0 *F) { return F->direct_flops; }
 
-// (re)allocates a device work block of n x cols entries when it has fewer than `cols` columns (contents are not kept)
-template <class T>
-static int grow(ddm_ctx *ctx, T *&p, int &have, int cols, int64_t n)
-{
-  if (have >= cols) return DDM_OK;
-  (void)hipFree(p);
-  p = nullptr;
-  have = 0;
-  HIPCHECK(ctx, hipMalloc((void **)&p, sizeof(T) * (size_t)n * (size_t)cols));
-  have = cols;
-  return DDM_OK;
-}
 static int ilu0_alloc_status(ddm_ctx *ctx, ddm_ilu0 *F)
 {
   if (hipHostMalloc((void **)&F->err, 128, hipHostMallocMapped) != hipSuccess) return fail(ctx, DDM_EHIP, "local solver: allocation failed");
@@ -682,7 +637,7 @@ static int ilu0_alloc_status(ddm_ctx *ctx, ddm_ilu0 *F)
 static int ilu0_alloc_xstate(ddm_ctx *ctx, ddm_ilu0 *F)
 {
   if (F->xstate) return DDM_OK;
-  HIPCHECK(ctx, hipMalloc((void **)&F->xstate, sizeof(XcdState)));
+  HIPCHECK(ctx, F->xstate.alloc(1));
   HIPCHECK(ctx, dev_memset(F->xstate, 0, sizeof(XcdState)));
   return DDM_OK;
 }
@@ -1019,12 +974,9 @@ static int sn_probe_refinement(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, doub
     b[(size_t)i] = (double)(int64_t)(lcg >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
     bn2 += b[(size_t)i] * b[(size_t)i];
   }
-  double *db = nullptr, *dx = nullptr;
-  HIPCHECK(ctx, hipMalloc((void **)&db, sizeof(double) * (size_t)n));
-  if (hipMalloc((void **)&dx, sizeof(double) * (size_t)n) != hipSuccess) {
-    (void)hipFree(db);
-    return fail(ctx, DDM_EHIP, "sparse direct solver: allocation failed");
-  }
+  dbuf<double> db, dx;
+  HIPCHECK(ctx, db.alloc(n));
+  if (dx.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "sparse direct solver: allocation failed");
   int rc = ddm_memcpy_h2d(ctx, db, b.data(), sizeof(double) * (size_t)n);
   auto omega_now = [&](double &om) -> int {
     int r = ddm_memcpy_d2h(ctx, x.data(), dx, sizeof(double) * (size_t)n); // (synchronises the stream)
@@ -1055,10 +1007,10 @@ static int sn_probe_refinement(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, doub
   };
   auto solve_with = [&](int steps) -> int {
     if (steps > 0 && !R.ref_rp) { // device copies of the matrix for the residuals
-      HIPCHECK(ctx, hipMalloc((void **)&R.ref_rp, sizeof(int64_t) * (size_t)(n + 1)));
-      HIPCHECK(ctx, hipMalloc((void **)&R.ref_ci, sizeof(int32_t) * (size_t)std::max<int64_t>(A->nnz, 1)));
-      HIPCHECK(ctx, hipMalloc((void **)&R.ref_va, sizeof(double) * (size_t)std::max<int64_t>(A->nnz, 1)));
-      HIPCHECK(ctx, hipMalloc((void **)&R.pr, sizeof(double) * (size_t)n));
+      HIPCHECK(ctx, R.ref_rp.alloc(n + 1));
+      HIPCHECK(ctx, R.ref_ci.alloc(A->nnz));
+      HIPCHECK(ctx, R.ref_va.alloc(A->nnz));
+      HIPCHECK(ctx, R.pr.alloc(n));
       R.pr_cols = 1;
       HIPCHECK(ctx, hipMemcpyAsync(R.ref_rp, A->rp, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHECK(ctx, hipMemcpyAsync(R.ref_ci, A->ci, sizeof(int32_t) * (size_t)A->nnz, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1087,11 +1039,9 @@ static int sn_probe_refinement(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, doub
   R.refine_steps = steps;
   F->graph.reset(); // (bound to the probe vectors)
   if (steps == 0) { // (no residuals needed)
-    dev_free(R.ref_rp, R.ref_ci, R.ref_va, R.pr);
-    R.ref_rp = nullptr, R.ref_ci = nullptr, R.ref_va = R.pr = nullptr, R.pr_cols = 0;
+    (void)R.ref_rp.reset(), (void)R.ref_ci.reset(), (void)R.ref_va.reset(), (void)R.pr.reset();
+    R.pr_cols = 0;
   }
-  (void)hipFree(db);
-  (void)hipFree(dx);
   *omega_out = om;
   return rc;
 }
@@ -1191,8 +1141,7 @@ static int sn_direct_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, con
   F->sn = std::make_unique<SnDirect>();
   F->sn->f.reset(S);
   int rc = ilu0_alloc_status(ctx, F);
-  if (!rc && (hipMalloc((void **)&F->pd, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess ||
-              hipMalloc((void **)&F->px, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess))
+  if (!rc && (F->pd.alloc(n) != hipSuccess || F->px.alloc(n) != hipSuccess))
     rc = fail(ctx, DDM_EHIP, "sparse direct solver: allocation failed");
   double omega = 0.0;
   if (!rc) rc = sn_probe_refinement(ctx, F, A, &omega);
@@ -1326,9 +1275,8 @@ static int direct_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, c
     std::fprintf(stderr, "[ddm] direct factor: %lld rows, %lld stored entries; %zu supernodes (>= %d rows) with %lld rows; levels L/U %lld/%lld (transformed rows %lld)\n",
                  (long long)F->n, (long long)F->nnz, SN.j0.size(), min_sn, (long long)SN.nvirt, (long long)C.Lc.nlev, (long long)C.Uc.nlev, (long long)C.Lc.nrows);
   if (!rc) rc = ilu0_alloc_status(ctx, F);
-  if (!rc) rc = upload(ctx, R.perm.data(), A->nrows, &C.perm);
-  if (!rc && (hipMalloc((void **)&F->pd, sizeof(double) * (size_t)std::max<int64_t>(F->n, 1)) != hipSuccess ||
-              hipMalloc((void **)&F->px, sizeof(double) * (size_t)std::max<int64_t>(F->n + C.nvirt, 1)) != hipSuccess))
+  if (!rc) rc = upload(ctx, R.perm.data(), A->nrows, C.perm);
+  if (!rc && (F->pd.alloc(F->n) != hipSuccess || F->px.alloc(F->n + C.nvirt) != hipSuccess))
     rc = fail(ctx, DDM_EHIP, "ddm_chol_create: allocation failed");
   if (rc) {
     ddm_ilu0_destroy(F);
@@ -1464,14 +1412,14 @@ static int build_xcd_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   }
   auto X = std::make_unique<XcdEngine>();
   X->ngroups = nb;
-  DDMCHECK(upload(ctx, groups.data(), (int64_t)groups.size(), &X->groups));
-  DDMCHECK(upload(ctx, desc.data(), (int64_t)desc.size(), &X->desc));
-  DDMCHECK(upload(ctx, flag_off.data(), (int64_t)flag_off.size(), &X->flag_off));
-  DDMCHECK(upload(ctx, rows.data(), (int64_t)rows.size(), &X->rows));
-  DDMCHECK(upload(ctx, cols.data(), (int64_t)cols.size(), &X->cols));
-  DDMCHECK(upload(ctx, vals.data(), (int64_t)vals.size(), &X->vals));
-  DDMCHECK(upload(ctx, dinv.data(), (int64_t)dinv.size(), &X->dinv));
-  HIPCHECK(ctx, hipMalloc((void **)&X->flags, sizeof(unsigned) * (size_t)std::max<int64_t>(nflag, 1)));
+  DDMCHECK(upload(ctx, groups.data(), (int64_t)groups.size(), X->groups));
+  DDMCHECK(upload(ctx, desc.data(), (int64_t)desc.size(), X->desc));
+  DDMCHECK(upload(ctx, flag_off.data(), (int64_t)flag_off.size(), X->flag_off));
+  DDMCHECK(upload(ctx, rows.data(), (int64_t)rows.size(), X->rows));
+  DDMCHECK(upload(ctx, cols.data(), (int64_t)cols.size(), X->cols));
+  DDMCHECK(upload(ctx, vals.data(), (int64_t)vals.size(), X->vals));
+  DDMCHECK(upload(ctx, dinv.data(), (int64_t)dinv.size(), X->dinv));
+  HIPCHECK(ctx, X->flags.alloc(nflag));
   HIPCHECK(ctx, dev_memset(X->flags, 0, sizeof(unsigned) * (size_t)std::max<int64_t>(nflag, 1)));
   DDMCHECK(ilu0_alloc_xstate(ctx, F));
   {
@@ -1483,9 +1431,9 @@ static int build_xcd_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
       for (int64_t p = 0; p < nbk; ++p) lpos.push_back(base + p);
       base += 2 * nbk;
     }
-    DDMCHECK(upload(ctx, lpos.data(), (int64_t)lpos.size(), &X->lpos));
+    DDMCHECK(upload(ctx, lpos.data(), (int64_t)lpos.size(), X->lpos));
   }
-  HIPCHECK(ctx, hipMalloc((void **)&X->dperm, sizeof(double) * (size_t)std::max<int64_t>((int64_t)rows.size(), 1)));
+  HIPCHECK(ctx, X->dperm.alloc((int64_t)rows.size()));
   HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_xcd2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(TrsvLds)));
   F->xcd = std::move(X);
   return DDM_OK;
@@ -1515,24 +1463,24 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   // all XCDs (write-through hand-overs); measured at 216^3: 1 subdomain 6.9 vs 9.2 ms, 2 subdomains 7.6 vs 8.3 ms
   E->spread = spread_env >= 0 ? spread_env : (nb < 8 && S.stats.max_rows_per_level > 48.0 * 64.0 ? 1 : 0);
   E->nposU = S.nposU;
-  DDMCHECK(upload(ctx, S.groups.data(), (int64_t)S.groups.size(), &E->groups));
-  DDMCHECK(upload(ctx, S.tasks.data(), (int64_t)S.tasks.size(), &E->tasks));
-  DDMCHECK(upload(ctx, S.stream.data(), (int64_t)S.stream.size(), &E->stream));
-  DDMCHECK(upload(ctx, S.koff.data(), (int64_t)S.koff.size(), &E->koff));
-  DDMCHECK(upload(ctx, S.posU.data(), (int64_t)S.posU.size(), &E->posU));
+  DDMCHECK(upload(ctx, S.groups.data(), (int64_t)S.groups.size(), E->groups));
+  DDMCHECK(upload(ctx, S.tasks.data(), (int64_t)S.tasks.size(), E->tasks));
+  DDMCHECK(upload(ctx, S.stream.data(), (int64_t)S.stream.size(), E->stream));
+  DDMCHECK(upload(ctx, S.koff.data(), (int64_t)S.koff.size(), E->koff));
+  DDMCHECK(upload(ctx, S.posU.data(), (int64_t)S.posU.size(), E->posU));
   {
     std::vector<int32_t> rowU((size_t)std::max<int64_t>(S.nposU, 1), -1);
     for (size_t i = 0; i < S.posU.size(); ++i) rowU[(size_t)S.posU[i]] = (int32_t)i;
-    DDMCHECK(upload(ctx, rowU.data(), (int64_t)rowU.size(), &E->rowU));
+    DDMCHECK(upload(ctx, rowU.data(), (int64_t)rowU.size(), E->rowU));
   }
-  HIPCHECK(ctx, hipMalloc((void **)&E->ypos, sizeof(double) * (size_t)std::max<int64_t>(S.nposL, 1)));
-  HIPCHECK(ctx, hipMalloc((void **)&E->xpos, sizeof(double) * (size_t)std::max<int64_t>(S.nposU, 1)));
+  HIPCHECK(ctx, E->ypos.alloc(S.nposL));
+  HIPCHECK(ctx, E->xpos.alloc(S.nposU));
   HIPCHECK(ctx, dev_memset(E->ypos, 0, sizeof(double) * (size_t)std::max<int64_t>(S.nposL, 1)));
   HIPCHECK(ctx, dev_memset(E->xpos, 0, sizeof(double) * (size_t)std::max<int64_t>(S.nposU, 1)));
   const size_t pbytes = sizeof(unsigned long long) * 16 * std::max<size_t>(S.tasks.size(), 1);
-  HIPCHECK(ctx, hipMalloc((void **)&E->progress, pbytes));
+  HIPCHECK(ctx, E->progress.alloc((int64_t)(pbytes / sizeof(unsigned long long))));
   HIPCHECK(ctx, dev_memset(E->progress, 0, pbytes));
-  HIPCHECK(ctx, hipMalloc((void **)&E->queue, sizeof(unsigned) * 32 * 4 * (size_t)nb));
+  HIPCHECK(ctx, E->queue.alloc(32 * 4 * (int64_t)nb));
   HIPCHECK(ctx, dev_memset(E->queue, 0, sizeof(unsigned) * 32 * 4 * (size_t)nb));
   DDMCHECK(ilu0_alloc_xstate(ctx, F));
   HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
@@ -1600,29 +1548,29 @@ static int build_box_engine(ddm_ctx *ctx, ddm_ilu0 *F)
   X->nshell = (int64_t)S.srow.size();
   X->nprod = (int64_t)S.ext_val.size();
   X->stats = S.stats;
-  int rc = upload(ctx, S.blocks.data(), (int64_t)S.blocks.size(), &X->blocks);
-  if (!rc) rc = upload(ctx, S.steps.data(), (int64_t)S.steps.size(), &X->steps);
-  if (!rc) rc = upload(ctx, S.stream.data(), (int64_t)S.stream.size(), &X->stream);
-  if (!rc) rc = upload(ctx, (const unsigned long long *)S.einfo.data(), (int64_t)S.einfo.size(), &X->einfo);
-  if (!rc) rc = upload(ctx, S.ext_val.data(), X->nprod, &X->ext_val);
-  if (!rc) rc = upload(ctx, S.ext_col.data(), X->nprod, &X->ext_col);
-  if (!rc) rc = upload(ctx, S.srp.data(), (int64_t)S.srp.size(), &X->srp);
-  if (!rc) rc = upload(ctx, S.sci.data(), (int64_t)S.sci.size(), &X->sci);
-  if (!rc) rc = upload(ctx, S.sva.data(), (int64_t)S.sva.size(), &X->sva);
-  if (!rc) rc = upload(ctx, S.srow.data(), X->nshell, &X->srow);
+  int rc = upload(ctx, S.blocks.data(), (int64_t)S.blocks.size(), X->blocks);
+  if (!rc) rc = upload(ctx, S.steps.data(), (int64_t)S.steps.size(), X->steps);
+  if (!rc) rc = upload(ctx, S.stream.data(), (int64_t)S.stream.size(), X->stream);
+  if (!rc) rc = upload(ctx, (const unsigned long long *)S.einfo.data(), (int64_t)S.einfo.size(), X->einfo);
+  if (!rc) rc = upload(ctx, S.ext_val.data(), X->nprod, X->ext_val);
+  if (!rc) rc = upload(ctx, S.ext_col.data(), X->nprod, X->ext_col);
+  if (!rc) rc = upload(ctx, S.srp.data(), (int64_t)S.srp.size(), X->srp);
+  if (!rc) rc = upload(ctx, S.sci.data(), (int64_t)S.sci.size(), X->sci);
+  if (!rc) rc = upload(ctx, S.sva.data(), (int64_t)S.sva.size(), X->sva);
+  if (!rc) rc = upload(ctx, S.srow.data(), X->nshell, X->srow);
   if (rc) return rc;
-  auto zalloc = [&](void **p, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 8);
-    if (hipMalloc(p, bytes) != hipSuccess) return fail(ctx, DDM_EHIP, "box engine: allocation failed");
-    if (dev_memset(*p, 0, bytes) != hipSuccess) return fail(ctx, DDM_EHIP, "box engine: memset failed");
+  auto zalloc = [&](auto &buf, int64_t count) {
+    count = std::max<int64_t>(count, 1);
+    if (buf.alloc(count) != hipSuccess) return fail(ctx, DDM_EHIP, "box engine: allocation failed");
+    if (dev_memset(buf, 0, sizeof(*buf.get()) * (size_t)count) != hipSuccess) return fail(ctx, DDM_EHIP, "box engine: memset failed");
     return DDM_OK;
   };
-  rc = zalloc((void **)&X->E, sizeof(double) * (size_t)X->nprod);
-  if (!rc) rc = zalloc((void **)&X->xs, sizeof(double) * (size_t)S.xs_len);
-  if (!rc) rc = zalloc((void **)&X->prog, sizeof(unsigned long long) * (size_t)S.prog_len);
-  if (!rc) rc = zalloc((void **)&X->queue, sizeof(unsigned) * 32 * 2 * (size_t)nb);
-  if (!rc) rc = zalloc((void **)&X->ds, sizeof(double) * (size_t)X->nshell);
-  if (!rc) rc = zalloc((void **)&X->xsol, sizeof(double) * (size_t)X->nshell);
+  rc = zalloc(X->E, X->nprod);
+  if (!rc) rc = zalloc(X->xs, S.xs_len);
+  if (!rc) rc = zalloc(X->prog, S.prog_len);
+  if (!rc) rc = zalloc(X->queue, 32 * 2 * (int64_t)nb);
+  if (!rc) rc = zalloc(X->ds, X->nshell);
+  if (!rc) rc = zalloc(X->xsol, X->nshell);
   if (!rc) rc = ilu0_alloc_xstate(ctx, F);
   if (rc) return rc;
   if (X->nshell > 0) { // the rows behind the boxes: a factor object of their own with the general engines
@@ -1711,7 +1659,7 @@ static int enqueue_box(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, co
   int dbg = 0;   // diagnostic: DDM_BOX_DEBUG bit mask switches phases off (1 forward boxes, 2 nested solve, 4 products, 8 backward boxes, 16 shell rhs / out)
   if (const char *e = std::getenv("DDM_BOX_DEBUG")) dbg = std::atoi(e);
   hipLaunchKernelGGL(k_pipe_prologue, dim3(1), dim3(64), 0, ctx->stream, F->xstate, X->queue, X->nblocks * 2);
-  hipLaunchKernelGGL(k_box_fill, dim3(grid_for(X->xs_len, WG, 4096)), dim3(WG), 0, ctx->stream, X->xs_len, (unsigned long long *)X->xs);   // "not written yet"
+  hipLaunchKernelGGL(k_box_fill, dim3(grid_for(X->xs_len, WG, 4096)), dim3(WG), 0, ctx->stream, X->xs_len, (unsigned long long *)X->xs.get());   // "not written yet"
   if (!(dbg & 1)) hipLaunchKernelGGL((k_box_sweep<false>), dim3(X->grid), dim3(BOX_WG), 0, ctx->stream, P);
   if (X->nshell > 0 && !(dbg & 2)) {
     if (!(dbg & 16))
@@ -1727,7 +1675,7 @@ static int enqueue_box(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, co
   P.scale = scale;
   P.add = add;
   hipLaunchKernelGGL(k_pipe_prologue, dim3(1), dim3(64), 0, ctx->stream, F->xstate, X->queue, X->nblocks * 2);
-  hipLaunchKernelGGL(k_box_fill, dim3(grid_for(X->xs_len, WG, 4096)), dim3(WG), 0, ctx->stream, X->xs_len, (unsigned long long *)X->xs);
+  hipLaunchKernelGGL(k_box_fill, dim3(grid_for(X->xs_len, WG, 4096)), dim3(WG), 0, ctx->stream, X->xs_len, (unsigned long long *)X->xs.get());
   if (!(dbg & 8)) hipLaunchKernelGGL((k_box_sweep<true>), dim3(X->grid), dim3(BOX_WG), 0, ctx->stream, P);
   if (X->nshell > 0 && !(dbg & 16))
     hipLaunchKernelGGL(k_box_shell_out, dim3(grid_for(X->nshell)), dim3(WG), 0, ctx->stream, X->nshell, (const int32_t *)X->srow, (const double *)X->xsol, x, scale, add);
@@ -1828,15 +1776,13 @@ static int capture_and_launch(ddm_ctx *ctx, GraphCache &cache, Enqueue &&enqueue
 // store drain + flag; work items; total cycles (s_memtime ticks, 100 MHz constant clock on gfx9).
 extern "C" int ddm_ilu0_debug_stamps(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned long long *out_host)
 {
-  unsigned long long *st = nullptr;
-  HIPCHECK(ctx, hipMalloc((void **)&st, 64));
+  dbuf<unsigned long long> st;
+  HIPCHECK(ctx, st.alloc(8));
   HIPCHECK(ctx, hipMemset(st, 0, 64));
   DDMCHECK(ilu0_join(ctx, F));
   if (!F->xcd) DDMCHECK(build_xcd_schedule(ctx, F));
   enqueue_xcd2(ctx, F, d, x, F->err, st);
-  int rc = ddm_memcpy_d2h(ctx, out_host, st, 48);
-  (void)hipFree(st);
-  return rc;
+  return ddm_memcpy_d2h(ctx, out_host, st, 48);
 }
 
 // Diagnostic (not part of the product path): one solve with the stamped build of the pipe kernel.  Per task 8 words
@@ -1853,8 +1799,8 @@ extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, d
   *ntasks = nt;
   if (!out_host) return DDM_OK;
   if (capacity_tasks < nt || !d || !x || d == x) return fail(ctx, DDM_EINVAL, "ddm_ilu0_pipe_trace: bad arguments");
-  unsigned long long *st = nullptr;
-  HIPCHECK(ctx, hipMalloc((void **)&st, sizeof(unsigned long long) * PIPE_STAMP_WORDS * (size_t)(nt + 1)));
+  dbuf<unsigned long long> st;
+  HIPCHECK(ctx, st.alloc(PIPE_STAMP_WORDS * (nt + 1)));
   HIPCHECK(ctx, hipMemsetAsync(st, 0, sizeof(unsigned long long) * PIPE_STAMP_WORDS * (size_t)(nt + 1), ctx->stream));
   enqueue_pipe(ctx, F, d, x, F->err, st);
   int rc = ddm_memcpy_d2h(ctx, out_host, st, (int64_t)sizeof(unsigned long long) * PIPE_STAMP_WORDS * nt);
@@ -1866,7 +1812,6 @@ extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, d
       meta_host[2 * t + 1] = tasks[(size_t)t].sweep;
     }
   }
-  (void)hipFree(st);
   return rc;
 }
 
@@ -1957,15 +1902,15 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
     LevelEngine &E = *F->lev;
     for (TriSchedule *S : {&E.L, &E.U}) {
       if (!S->vals_f32 && S->ell_entries > 0) {
-        HIPCHECK(ctx, hipMalloc((void **)&S->vals_f32, sizeof(float) * (size_t)S->ell_entries));
+        HIPCHECK(ctx, S->vals_f32.alloc(S->ell_entries));
         hipLaunchKernelGGL(k_to_float, dim3((unsigned)((S->ell_entries + 255) / 256)), dim3(256), 0, ctx->stream, S->ell_entries, (const double *)S->vals, S->vals_f32);
       }
       if (S == &E.U && !S->dinv_f32) {
-        HIPCHECK(ctx, hipMalloc((void **)&S->dinv_f32, sizeof(float) * (size_t)std::max<int64_t>(F->n, 1)));
+        HIPCHECK(ctx, S->dinv_f32.alloc(F->n));
         hipLaunchKernelGGL(k_to_float, dim3((unsigned)((F->n + 255) / 256)), dim3(256), 0, ctx->stream, F->n, (const double *)S->dinv, S->dinv_f32);
       }
     }
-    DDMCHECK(grow(ctx, E.xf, E.xf_nrhs, nrhs, F->n));
+    HIPCHECK(ctx, reserve_cols(E.xf_nrhs, nrhs, E.xf, F->n));
     HIPCHECK(ctx, hipGetLastError());
   }
   F->mgraph.reset();
@@ -1975,17 +1920,13 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
     const double *partial_before = S.f->d_partial, *contrib_before = S.f->d_contrib;
     if (!sn::reserve(*S.f, w)) return fail(ctx, DDM_EHIP, "sparse direct solver: allocation failed");
     if (S.f->d_partial != partial_before || S.f->d_contrib != contrib_before) F->graph.reset(); // the single-vector graph's nodes hold the old scratch pointers
-    DDMCHECK(grow(ctx, F->pD, F->pm_nrhs, w, F->n));
+    HIPCHECK(ctx, reserve_cols(F->pm_nrhs, w, F->pD, F->n));
     if (S.refine_steps > 0 && S.pr_cols < w) {
-      DDMCHECK(grow(ctx, S.pr, S.pr_cols, w, F->n));
+      HIPCHECK(ctx, reserve_cols(S.pr_cols, w, S.pr, F->n));
       F->graph.reset(); // (the single-vector graph holds the old residual buffer)
     }
   }
-  if (F->csr && F->pm_nrhs < nrhs) {
-    int have = 0;
-    DDMCHECK(grow(ctx, F->pX, have, nrhs, F->n + F->csr->nvirt));
-    DDMCHECK(grow(ctx, F->pD, F->pm_nrhs, nrhs, F->n));
-  }
+  if (F->csr) HIPCHECK(ctx, reserve_cols<double>(F->pm_nrhs, nrhs, {{F->pX, F->n + F->csr->nvirt}, {F->pD, F->n}}));
   F->mg_D = D;
   F->mg_X = X;
   F->mg_nrhs = nrhs;

@@ -6,14 +6,6 @@
 // its per-level latency once for all of them.
 #include "multi_kernels.hpp"
 
-// (re)allocates a rows x m block; contents are not kept
-static int multi_block(ddm_ctx *ctx, double *&p, int64_t rows, int m)
-{
-  (void)hipFree(p);
-  p = nullptr;
-  HIPCHECK(ctx, hipMalloc((void **)&p, sizeof(double) * (size_t)std::max<int64_t>(rows * m, 1)));
-  return DDM_OK;
-}
 static int multi_check(ddm_ctx *ctx, int m, const char *what)
 {
   if (m < 1 || m > MULTI_MAX) return fail(ctx, DDM_EINVAL, "%s: nrhs = %d outside [1, %d]", what, m, MULTI_MAX);
@@ -22,9 +14,9 @@ static int multi_check(ddm_ctx *ctx, int m, const char *what)
 static int ctx_multi_scratch(ddm_ctx *ctx)
 {
   if (ctx->mscal) return DDM_OK;
-  HIPCHECK(ctx, hipMalloc((void **)&ctx->mpartial, sizeof(double) * (size_t)RED_MAX_BLOCKS * MULTI_MAX));
-  HIPCHECK(ctx, hipMalloc((void **)&ctx->mactive, sizeof(int32_t) * MULTI_MAX));
-  HIPCHECK(ctx, hipMalloc((void **)&ctx->mscal, sizeof(double) * 8 * MULTI_MAX));
+  HIPCHECK(ctx, ctx->mpartial.alloc((int64_t)RED_MAX_BLOCKS * MULTI_MAX));
+  HIPCHECK(ctx, ctx->mactive.alloc(MULTI_MAX));
+  HIPCHECK(ctx, ctx->mscal.alloc(8 * MULTI_MAX));
   return DDM_OK;
 }
 
@@ -35,12 +27,7 @@ static int halo_exchange_multi(ddm_ctx *ctx, ddm_halo *H, int m, double *v)
 {
   if (!H) return DDM_OK;
   if (H->nsend == 0 && H->ndst == 0 && !H->remote) return DDM_OK;
-  if (H->mcols < m) {
-    H->mcols = 0;
-    DDMCHECK(multi_block(ctx, H->msend, H->nsend, m));
-    DDMCHECK(multi_block(ctx, H->mrecv, H->nrecv, m));
-    H->mcols = m;
-  }
+  HIPCHECK(ctx, reserve_cols<double>(H->mcols, m, {{H->msend, H->nsend}, {H->mrecv, H->nrecv}}));
   if (H->nsend > 0) hipLaunchKernelGGL(k_pack_multi, dim3(grid_for(H->nsend * m)), dim3(WG), 0, ctx->stream, H->nsend, m, H->send_idx, (const double *)v, H->msend);
   const double *rbuf = H->mrecv;
   if (ctx->rccl && (ctx->nranks > 1 || ctx->rccl_self)) {
@@ -133,11 +120,7 @@ static int op_apply_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *X, doub
 static int op_applyscaleadd_multi(ddm_ctx *ctx, ddm_op *op, int m, double alpha, const double *X, double *Y)
 {
   ScopedTimer t(ctx, "Operator/applyscaleadd");
-  if (op->mcols < m) {
-    op->mcols = 0;
-    DDMCHECK(multi_block(ctx, op->mtmp, op->n, m));
-    op->mcols = m;
-  }
+  HIPCHECK(ctx, reserve_cols(op->mcols, m, op->mtmp, op->n));
   DDMCHECK(csr_mm_ld(ctx, op->A, m, X, m, op->mtmp, m));
   DDMCHECK(halo_exchange_multi(ctx, op->halo, m, op->mtmp));
   hipLaunchKernelGGL(k_axpy, dim3(grid_for(op->n * m)), dim3(WG), 0, ctx->stream, op->n * m, alpha, (const double *)op->mtmp, Y); // element-wise: y += alpha t
@@ -169,11 +152,7 @@ extern "C" int ddm_dot_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X
 // ---- SchwarzPreconditioner -----------------------------------------------------------------------------------------------------------
 static int schwarz_multi_scratch(ddm_ctx *ctx, ddm_schwarz *S, int m)
 {
-  if (S->mcols >= m) return DDM_OK;
-  S->mcols = 0;
-  DDMCHECK(multi_block(ctx, S->md_ovlp, S->n, m));
-  DDMCHECK(multi_block(ctx, S->mx_ovlp, S->n, m));
-  S->mcols = m;
+  HIPCHECK(ctx, reserve_cols<double>(S->mcols, m, {{S->md_ovlp, S->n}, {S->mx_ovlp, S->n}}));
   return DDM_OK;
 }
 static int local_status_check(ddm_ctx *ctx, const ddm_schwarz *S)
@@ -218,14 +197,7 @@ extern "C" int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, d
 // ---- GalerkinPreconditioner ----------------------------------------------------------------------------------------------------------
 static int galerkin_multi_scratch(ddm_ctx *ctx, ddm_galerkin *G, int m)
 {
-  if (G->mcols >= m) return DDM_OK;
-  G->mcols = 0;
-  DDMCHECK(multi_block(ctx, G->mpartial, (int64_t)G->nchunk * G->kmax, m));
-  DDMCHECK(multi_block(ctx, G->md0, G->K, m));
-  DDMCHECK(multi_block(ctx, G->mx0, G->K, m));
-  DDMCHECK(multi_block(ctx, G->md_ovlp, G->n, m));
-  DDMCHECK(multi_block(ctx, G->mx_ovlp, G->n, m));
-  G->mcols = m;
+  HIPCHECK(ctx, reserve_cols<double>(G->mcols, m, {{G->mpartial, (int64_t)G->nchunk * G->kmax}, {G->md0, G->K}, {G->mx0, G->K}, {G->md_ovlp, G->n}, {G->mx_ovlp, G->n}}));
   return DDM_OK;
 }
 // restrict (one pass over the basis for all columns) -> one all-reduce of K x m doubles -> A0^-1 D0 -> prolong into G->mx_ovlp
@@ -307,11 +279,7 @@ static int combined_apply_multi_impl(ddm_ctx *ctx, ddm_combined *C, int m, doubl
     return galerkin_apply_multi_impl(ctx, G, m, X, D, true, share ? S->md_ovlp : nullptr);
   }
   // multiplicative: dnext = d - A x; x += P1 dnext (:149-158)
-  if (C->mcols < m) {
-    C->mcols = 0;
-    DDMCHECK(multi_block(ctx, C->mdnext, C->n, m));
-    C->mcols = m;
-  }
+  HIPCHECK(ctx, reserve_cols(C->mcols, m, C->mdnext, C->n));
   HIPCHECK(ctx, hipMemcpyAsync(C->mdnext, D, sizeof(double) * (size_t)(C->n * m), hipMemcpyDeviceToDevice, ctx->stream));
   DDMCHECK(op_applyscaleadd_multi(ctx, C->op, m, -1.0, X, C->mdnext));
   return galerkin_apply_multi_impl(ctx, G, m, X, C->mdnext, true);
@@ -360,12 +328,7 @@ extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   const int64_t n = op->n;
   for (int c = 0; c < m; ++c) res[c] = ddm_solve_result{0, 0, 0.0, 1.0, 0.0};
   DDMCHECK(ctx_multi_scratch(ctx));
-  if (prec->mcg_cols < m) { // search directions p, q: block scratch of the preconditioner object
-    prec->mcg_cols = 0;
-    DDMCHECK(multi_block(ctx, prec->mp, n, m));
-    DDMCHECK(multi_block(ctx, prec->mq, n, m));
-    prec->mcg_cols = m;
-  }
+  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // search directions p, q: block scratch of the preconditioner object
   double *P = prec->mp, *Q = prec->mq;
   double bb[MULTI_MAX], def0[MULTI_MAX], def[MULTI_MAX];
   int32_t active[MULTI_MAX];

@@ -34,6 +34,7 @@
 #include <mutex>
 #include <vector>
 
+#include "device_buffer.hpp"
 #include "sn_chol_host.hpp"
 
 namespace sn {
@@ -977,32 +978,32 @@ struct Factor {
   std::vector<int32_t> h_colour;         // colour of every supernode
   std::vector<int32_t> h_first;          // host copy of `first`
   // device
-  int32_t *d_first = nullptr, *d_nrow = nullptr, *d_rows = nullptr, *d_sn_of_col = nullptr, *d_iperm = nullptr, *d_perm = nullptr;
-  int64_t *d_rptr = nullptr, *d_pptr = nullptr;
-  double *d_panels = nullptr;
-  int32_t *d_lev_sn = nullptr;   // supernodes sorted by level
-  int32_t *d_preT = nullptr;     // per level: exclusive prefix of the row-tile counts (lev_ptr[l] + l .. : cnt + 1 entries)
-  int32_t *d_preU = nullptr;     // the same for the update tiles T (T + 1) / 2
-  int32_t *d_big_sn = nullptr, *d_big_index = nullptr, *d_preB = nullptr; // supernodes with more than BWD_SMALL row tiles, per level
+  dbuf<int32_t> d_first, d_nrow, d_rows, d_sn_of_col, d_iperm, d_perm;
+  dbuf<int64_t> d_rptr, d_pptr;
+  dbuf<double> d_panels;
+  dbuf<int32_t> d_lev_sn;   // supernodes sorted by level
+  dbuf<int32_t> d_preT;     // per level: exclusive prefix of the row-tile counts (lev_ptr[l] + l .. : cnt + 1 entries)
+  dbuf<int32_t> d_preU;     // the same for the update tiles T (T + 1) / 2
+  dbuf<int32_t> d_big_sn, d_big_index, d_preB; // supernodes with more than BWD_SMALL row tiles, per level
   std::vector<int32_t> h_tilesT, h_tilesU, h_tilesB; // totals per level
-  unsigned *d_err = nullptr;
+  dbuf<unsigned> d_err;
   bool lu = false;               // L U variant
-  double *d_upanels = nullptr;
-  int64_t *d_uptr = nullptr;
-  int32_t *d_piv = nullptr;
+  dbuf<double> d_upanels;
+  dbuf<int64_t> d_uptr;
+  dbuf<int32_t> d_piv;
   int64_t uentries = 0;
   std::vector<int32_t> h_tilesUF; // L U: all T x T update tiles per level
-  int32_t *d_preUF = nullptr;
-  double *d_partial = nullptr;
+  dbuf<int32_t> d_preUF;
+  dbuf<double> d_partial;
   int64_t partial_cap = 0; // doubles
   // single-vector solves: the persistent kernel for the top levels (sn_solve1.hpp)
   std::vector<int32_t> sn_block;  // block of every supernode
   int32_t ltop = 0, ntop = 0;     // tree levels ltop .. nlev - 1 are walked by k_sn_top1 (ntop = 0: level kernels only)
   TopPlan top{};
-  int32_t *d_top_ints = nullptr;  // all integer arrays of the plan in one allocation
-  double *d_top_partial = nullptr;
-  TopSync *d_top_sync = nullptr;
-  unsigned long long *d_top_flags = nullptr, *d_top_stamps = nullptr; // stamps: diagnostics (DDM_SN_TOP_STAMPS)
+  dbuf<int32_t> d_top_ints;  // all integer arrays of the plan in one allocation
+  dbuf<double> d_top_partial;
+  dbuf<TopSync> d_top_sync;
+  dbuf<unsigned long long> d_top_flags, d_top_stamps; // stamps: diagnostics (DDM_SN_TOP_STAMPS)
   int top_grid = 0, top_spread = 0, chain_grid = 0;
   // CHAINS of the top levels (sn_solve1.hpp): a separator wider than SN_MAX_COLS is a chain of links s -> s + 1 = parent(s), each the
   // only child of the next.  For the single-vector solves a chain is ONE dense unit with an explicitly inverted triangle.
@@ -1010,16 +1011,16 @@ struct Factor {
   ChainDev chd{};
   ChainPlan chp{};
   const int32_t *ch_link_sn = nullptr, *ch_link_chain = nullptr, *ch_link_pre = nullptr, *ch_inv_chain = nullptr, *ch_inv_i = nullptr;
-  int32_t *d_chain_ints = nullptr;
-  int64_t *d_chain_offs = nullptr;
-  double *d_chain_w = nullptr, *d_chain_e = nullptr, *d_chain_v = nullptr, *d_chain_u = nullptr; // inverse triangles / blocks of the external rows (L; L U: also U^T)
+  dbuf<int32_t> d_chain_ints;
+  dbuf<int64_t> d_chain_offs;
+  dbuf<double> d_chain_w, d_chain_e, d_chain_v, d_chain_u; // inverse triangles / blocks of the external rows (L; L U: also U^T)
   bool chains_ready = false;
-  int64_t *d_tptr = nullptr, *d_tmid = nullptr;  // transposed row lists (Meta::tptr / tmid / tidx)
-  int32_t *d_tidx = nullptr, *d_tpos = nullptr;
-  double *d_contrib = nullptr; // slots of the forward sweep: one per entry of `rows` and right-hand side
+  dbuf<int64_t> d_tptr, d_tmid;  // transposed row lists (Meta::tptr / tmid / tidx)
+  dbuf<int32_t> d_tidx, d_tpos;
+  dbuf<double> d_contrib; // slots of the forward sweep: one per entry of `rows` and right-hand side
   int64_t contrib_cap = 0, nrows_total = 0;
   int64_t max_big_tiles = 0;
-  void release()
+  ~Factor()
   {
     if (d_top_stamps) { // diagnostics: barrier log of the LAST launch of the persistent kernel
       std::vector<unsigned long long> h(4000);
@@ -1030,40 +1031,15 @@ struct Factor {
           std::fprintf(stderr, "  barrier %3d: arrive %8.2f release %8.2f  work %6.2f wait %6.2f\n", c, (double)(h[2 * c] - t0) / 100.0, (double)(h[2 * c + 1] - t0) / 100.0,
                        c > 1 ? (double)(h[2 * c] - h[2 * c - 1]) / 100.0 : 0.0, (double)(h[2 * c + 1] - h[2 * c]) / 100.0);
       }
-      (void)hipFree(d_top_stamps);
-      d_top_stamps = nullptr;
     }
-    for (void *p : {(void *)d_first, (void *)d_nrow, (void *)d_rows, (void *)d_sn_of_col, (void *)d_iperm, (void *)d_perm, (void *)d_rptr, (void *)d_pptr, (void *)d_panels,
-                    (void *)d_lev_sn, (void *)d_preT, (void *)d_preU, (void *)d_big_sn, (void *)d_big_index, (void *)d_preB, (void *)d_err, (void *)d_partial,
-                    (void *)d_upanels, (void *)d_uptr, (void *)d_piv, (void *)d_preUF, (void *)d_tptr, (void *)d_tmid, (void *)d_tidx, (void *)d_tpos, (void *)d_chain_ints, (void *)d_chain_offs, (void *)d_chain_w, (void *)d_chain_e, (void *)d_chain_v, (void *)d_chain_u, (void *)d_contrib, (void *)d_top_ints, (void *)d_top_partial, (void *)d_top_sync, (void *)d_top_flags})
-      if (p) (void)hipFree(p);
-    d_first = d_nrow = d_rows = d_sn_of_col = d_iperm = d_perm = d_lev_sn = d_preT = d_preU = d_big_sn = d_big_index = d_preB = nullptr;
-    d_rptr = d_pptr = nullptr;
-    d_panels = d_partial = d_upanels = d_contrib = nullptr;
-    d_tptr = d_tmid = nullptr;
-    d_tidx = d_tpos = nullptr;
-    d_chain_ints = nullptr;
-    d_chain_offs = nullptr;
-    d_chain_w = d_chain_e = d_chain_v = d_chain_u = nullptr;
-    chains_ready = false;
-    d_top_ints = nullptr;
-    d_top_partial = nullptr;
-    d_top_sync = nullptr;
-    d_top_flags = nullptr;
-    top = TopPlan{};
-    ntop = 0;
-    d_uptr = nullptr;
-    d_piv = d_preUF = nullptr;
-    d_err = nullptr;
   }
-  ~Factor() { release(); }
 };
 
 template <class T>
-static inline bool up(const std::vector<T> &h, T **d)
+static inline bool up(const std::vector<T> &h, dbuf<T> &d)
 {
-  if (hipMalloc((void **)d, sizeof(T) * std::max<size_t>(h.size(), 1)) != hipSuccess) return false;
-  return h.empty() || hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (d.alloc((int64_t)h.size()) != hipSuccess) return false;
+  return h.empty() || hipMemcpy(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // Top levels of the single-vector solve (sn_solve1.hpp): those from the first level on which every later level has at most
@@ -1150,13 +1126,13 @@ static inline bool build_top_plan(Factor &F, const std::vector<int32_t> &lev_sn,
   };
   const size_t o_ap = put(a_ptr), o_as = put(a_sn), o_fh = put(fph), o_fp = put(f_ptr), o_fi = put(f_items), o_pp = put(p_ptr), o_pi = put(p_items), o_pf = put(p_first),
                o_gp = put(g_ptr), o_gi = put(g_items);
-  if (!up(all, &F.d_top_ints)) return false;
-  if (hipMalloc((void **)&F.d_top_partial, sizeof(double) * std::max<size_t>(p_items.size() / 2, 1) * SN_MAX_COLS) != hipSuccess) return false;
-  if (hipMalloc((void **)&F.d_top_sync, sizeof(TopSync)) != hipSuccess || hipMemset(F.d_top_sync, 0, sizeof(TopSync)) != hipSuccess) return false;
-  const size_t fbytes = sizeof(unsigned long long) * 9 * TOP_MAX_WG * TOP_FLAG_STRIDE;
-  if (hipMalloc((void **)&F.d_top_flags, fbytes) != hipSuccess || hipMemset(F.d_top_flags, 0, fbytes) != hipSuccess) return false;
+  if (!up(all, F.d_top_ints)) return false;
+  if (F.d_top_partial.alloc((int64_t)std::max<size_t>(p_items.size() / 2, 1) * SN_MAX_COLS) != hipSuccess) return false;
+  if (F.d_top_sync.alloc(1) != hipSuccess || hipMemset(F.d_top_sync, 0, sizeof(TopSync)) != hipSuccess) return false;
+  const int64_t fwords = (int64_t)9 * TOP_MAX_WG * TOP_FLAG_STRIDE;
+  if (F.d_top_flags.alloc(fwords) != hipSuccess || hipMemset(F.d_top_flags, 0, sizeof(unsigned long long) * (size_t)fwords) != hipSuccess) return false;
   if (std::getenv("DDM_SN_TOP_STAMPS")) {
-    if (hipMalloc((void **)&F.d_top_stamps, 8 * 4000) != hipSuccess || hipMemset(F.d_top_stamps, 0, 8 * 4000) != hipSuccess) return false;
+    if (F.d_top_stamps.alloc(4000) != hipSuccess || hipMemset(F.d_top_stamps, 0, 8 * 4000) != hipSuccess) return false;
   }
   F.top.ntop = ntop;
   F.top.nph = nph;
@@ -1342,13 +1318,12 @@ static inline bool upload_chains(Factor &F)
   const size_t o_c0 = put(H.col0), o_nc = put(H.ncol), o_fs = put(H.first_sn), o_nl = put(H.nlinks), o_ls = put(H.last_sn), o_ne = put(H.nE), o_yp = put(y_ptr), o_yi = put(y_items),
                o_eh = put(eph), o_ep = put(e_ptr), o_ei = put(e_items), o_tp = put(t_ptr), o_ti = put(t_items), o_xp = put(x_ptr), o_xi = put(x_items), o_lsn = put(H.link_sn),
                o_lch = put(H.link_chain), o_lpre = put(H.link_pre), o_ic = put(H.inv_chain), o_ii = put(H.inv_i);
-  if (!up(all, &F.d_chain_ints)) return false;
+  if (!up(all, F.d_chain_ints)) return false;
   std::vector<int64_t> offs(H.woff);
   offs.insert(offs.end(), H.eoff.begin(), H.eoff.end());
-  if (!up(offs, &F.d_chain_offs)) return false;
-  auto dalloc = [](double **p, int64_t cnt) { return hipMalloc((void **)p, sizeof(double) * (size_t)std::max<int64_t>(cnt, 1)) == hipSuccess; };
-  if (!dalloc(&F.d_chain_w, H.wtot) || !dalloc(&F.d_chain_e, H.etot)) return false;
-  if (F.lu && (!dalloc(&F.d_chain_v, H.wtot) || !dalloc(&F.d_chain_u, H.etot))) return false;
+  if (!up(offs, F.d_chain_offs)) return false;
+  if (F.d_chain_w.alloc(H.wtot) != hipSuccess || F.d_chain_e.alloc(H.etot) != hipSuccess) return false;
+  if (F.lu && (F.d_chain_v.alloc(H.wtot) != hipSuccess || F.d_chain_u.alloc(H.etot) != hipSuccess)) return false;
   const int32_t *I = F.d_chain_ints;
   F.chd.nchain = nch;
   F.chd.col0 = I + o_c0;
@@ -1405,12 +1380,9 @@ static inline hipError_t chain_setup(Factor &F, hipStream_t st)
   const ChainHost &H = F.ch;
   if (H.nchain() == 0) return hipSuccess;
   hipError_t e;
-  double *Ltmp = nullptr, *Utmp = nullptr;
-  if ((e = hipMalloc((void **)&Ltmp, sizeof(double) * (size_t)std::max<int64_t>(H.wtot, 1))) != hipSuccess) return e;
-  if (F.lu && (e = hipMalloc((void **)&Utmp, sizeof(double) * (size_t)std::max<int64_t>(H.wtot, 1))) != hipSuccess) {
-    (void)hipFree(Ltmp);
-    return e;
-  }
+  dbuf<double> Ltmp, Utmp; // (released when the function returns: after the synchronisation below)
+  if ((e = Ltmp.alloc(H.wtot)) != hipSuccess) return e;
+  if (F.lu && (e = Utmp.alloc(H.wtot)) != hipSuccess) return e;
   (void)hipMemsetAsync(Ltmp, 0, sizeof(double) * (size_t)H.wtot, st);
   (void)hipMemsetAsync(F.d_chain_w, 0, sizeof(double) * (size_t)H.wtot, st);
   (void)hipMemsetAsync(F.d_chain_e, 0, sizeof(double) * (size_t)std::max<int64_t>(H.etot, 1), st);
@@ -1437,8 +1409,6 @@ static inline hipError_t chain_setup(Factor &F, hipStream_t st)
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(Ltmp);
-  if (Utmp) (void)hipFree(Utmp);
   if (e == hipSuccess) F.chains_ready = true;
   return e;
 }
@@ -1605,18 +1575,18 @@ static inline bool build(Factor &F, int64_t n, int64_t nblocks, const int64_t *b
       }
     std::vector<int32_t> tpos(rows.size());
     for (size_t k = 0; k < tidx.size(); ++k) tpos[(size_t)tidx[k]] = (int32_t)k;
-    if (!up(tptr, &F.d_tptr) || !up(tmid, &F.d_tmid) || !up(tidx, &F.d_tidx) || !up(tpos, &F.d_tpos)) return false;
+    if (!up(tptr, F.d_tptr) || !up(tmid, F.d_tmid) || !up(tidx, F.d_tidx) || !up(tpos, F.d_tpos)) return false;
   }
-  bool ok = up(first, &F.d_first) && up(nrow, &F.d_nrow) && up(rows, &F.d_rows) && up(sn_of_col, &F.d_sn_of_col) && up(iperm, &F.d_iperm) && up(F.h_perm, &F.d_perm) &&
-            up(rptr, &F.d_rptr) && up(pptr, &F.d_pptr) && up(lev_sn, &F.d_lev_sn) && up(preT, &F.d_preT) && up(preU, &F.d_preU) && up(big_sn, &F.d_big_sn) &&
-            up(big_index, &F.d_big_index) && up(preB, &F.d_preB);
+  bool ok = up(first, F.d_first) && up(nrow, F.d_nrow) && up(rows, F.d_rows) && up(sn_of_col, F.d_sn_of_col) && up(iperm, F.d_iperm) && up(F.h_perm, F.d_perm) &&
+            up(rptr, F.d_rptr) && up(pptr, F.d_pptr) && up(lev_sn, F.d_lev_sn) && up(preT, F.d_preT) && up(preU, F.d_preU) && up(big_sn, F.d_big_sn) &&
+            up(big_index, F.d_big_index) && up(preB, F.d_preB);
   if (!ok) return false;
-  if (hipMalloc((void **)&F.d_err, 128) != hipSuccess || hipMemset(F.d_err, 0, 128) != hipSuccess) return false;
-  if (hipMalloc((void **)&F.d_panels, sizeof(double) * (size_t)std::max<int64_t>(F.entries, 1)) != hipSuccess) return false;
+  if (F.d_err.alloc(32) != hipSuccess || hipMemset(F.d_err, 0, 128) != hipSuccess) return false;
+  if (F.d_panels.alloc(F.entries) != hipSuccess) return false;
   if (lu) {
-    if (!up(uptr, &F.d_uptr) || !up(preUF, &F.d_preUF)) return false;
-    if (hipMalloc((void **)&F.d_upanels, sizeof(double) * (size_t)std::max<int64_t>(F.uentries, 1)) != hipSuccess) return false;
-    if (hipMalloc((void **)&F.d_piv, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess) return false;
+    if (!up(uptr, F.d_uptr) || !up(preUF, F.d_preUF)) return false;
+    if (F.d_upanels.alloc(F.uentries) != hipSuccess) return false;
+    if (F.d_piv.alloc(n) != hipSuccess) return false;
   }
   if (!build_top_plan(F, lev_sn, nrow, first)) return false;
   F.h_first = first;
@@ -1700,18 +1670,14 @@ static inline bool reserve(Factor &F, int m)
 {
   const int64_t cneed = F.nrows_total; // slots of the single-vector forward sweep (the block solves push coloured updates)
   if (cneed > F.contrib_cap) {
-    if (F.d_contrib) (void)hipFree(F.d_contrib);
-    F.d_contrib = nullptr;
     F.contrib_cap = 0;
-    if (hipMalloc((void **)&F.d_contrib, sizeof(double) * (size_t)std::max<int64_t>(cneed, 1)) != hipSuccess) return false;
+    if (F.d_contrib.alloc(cneed) != hipSuccess) return false;
     F.contrib_cap = cneed;
   }
   const int64_t need = F.max_big_tiles * SN_MAX_COLS * (int64_t)m;
   if (need <= F.partial_cap) return true;
-  if (F.d_partial) (void)hipFree(F.d_partial);
-  F.d_partial = nullptr;
   F.partial_cap = 0;
-  if (hipMalloc((void **)&F.d_partial, sizeof(double) * (size_t)std::max<int64_t>(need, 1)) != hipSuccess) return false;
+  if (F.d_partial.alloc(need) != hipSuccess) return false;
   F.partial_cap = need;
   return true;
 }
