@@ -162,6 +162,7 @@ SYMBOLS = {
     "ddm_galerkin_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_combined_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_cg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_gmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
     "ddm_cg_defect": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_double)]),
@@ -696,6 +697,22 @@ def cg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreco
     res = (SolveResult * max(m, 1))()
     hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
     ctx.check(ctx.lib.ddm_cg_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), _hp(hist), res))
+    out = [res[c] for c in range(m)]
+    if not history:
+        return out, None
+    iters = max([r.iterations for r in out] + [0])
+    return out, hist[:iters + 1, :m]
+
+
+def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,
+                      history=True):
+    """m independent RestartedGMResSolver::apply recurrences at once (ddm_gmres_solve_multi), restart cycles aligned.  X, B: (n, m)
+    row-major device tensors (B is overwritten).  Returns what cg_solve_multi returns: (list of m SolveResult, (iters + 1) x m history
+    whose entries after a column's last iteration are NaN)."""
+    m = _ncols(X, B)
+    res = (SolveResult * max(m, 1))()
+    hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
+    ctx.check(ctx.lib.ddm_gmres_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), int(restart), _hp(hist), res))
     out = [res[c] for c in range(m)]
     if not history:
         return out, None

@@ -1737,3 +1737,4 @@ extern "C" int ddm_synth_q1_matrix(int dim, const int64_t *bshape, const double 
 }
 
 #include "multi_rhs.hpp"
+#include "multi_gmres.hpp"

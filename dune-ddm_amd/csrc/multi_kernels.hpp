@@ -268,4 +268,105 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, i
   }
 }
 
+// ---- restarted GMRES vector work (csrc/multi_gmres.hpp) -----------------------------------------------------------------------------
+// per-column host scalars of one launch, passed by value (no upload, no synchronisation)
+struct MultiCoef {
+  double a[MULTI_MAX];
+};
+// One modified Gram-Schmidt step for columns [c0, c0 + CB): w -= h v with the coefficients h (m device doubles, already summed over
+// the ranks), and in the same pass the owner-masked partial sums of <z, w> for the updated w (z = the next basis block, or z = w for
+// the norm that ends the sweep).  The grid, the rows per thread and block_sum are those of k_dot_partial_multi and the build does not
+// contract a * b + c, so w and the partials are bit-identical to k_axpy_negdev_multi followed by k_dot_partial_multi.  Columns that
+// are not active are neither read nor written (their partials are 0).
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_mgs_step_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ h,
+                                                       const uint8_t *__restrict__ mask, const double *__restrict__ v, const double *z,
+                                                       double *w, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double hk[CB], s[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    hk[u] = h[c0 + u];
+    s[u] = 0.0;
+  }
+  const bool norm = z == w;
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    const int64_t o = i * m + c0;
+    const bool own = !MASKED || mask[i];
+    double wi[CB], vi[CB], zi[CB];
+#pragma unroll
+    for (int u = 0; u < CB; ++u) { // every load of the row is issued before the first use
+      wi[u] = on[u] ? w[o + u] : 0.0;
+      vi[u] = on[u] ? v[o + u] : 0.0;
+      zi[u] = on[u] && !norm ? z[o + u] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < CB; ++u)
+      if (on[u]) {
+        const double t = wi[u] - hk[u] * vi[u];
+        w[o + u] = t;
+        if (own) s[u] += (norm ? t : zi[u]) * t;
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double t = block_sum(s[u], red);
+    if (threadIdx.x == 0) partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = t;
+  }
+}
+// the unfused step (the default; DDM_GMRES_MULTI_FUSED=1 selects k_mgs_step_multi): k_axpy_negdev on every active column, one thread
+// per block entry
+__global__ void k_axpy_negdev_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ h, const double *__restrict__ v,
+                                    double *__restrict__ w)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) w[t] -= h[c] * v[t];
+  }
+}
+// dst = src * coef in the active columns (v_{i+1} = w / h_{i+1,i} with coef = 1 / h_{i+1,i}, the k_scal of the single-vector loop;
+// dst may be src)
+__global__ void k_scale_into_multi(int64_t n, int m, const int32_t *__restrict__ active, MultiCoef coef, const double *src, double *dst)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) dst[t] = src[t] * coef.a[c];
+  }
+}
+// End of a restart cycle: W_c = sum_{k < cnt_c} y_{k,c} v_{k,c} (terms added in ascending k, as the AXPY sequence of the
+// single-vector loop) and X_c += W_c for the columns with cnt_c > 0.  y: restart x m device doubles; cnt_c = Hessenberg columns of
+// column c in this cycle (0: frozen before the cycle, neither X nor the basis is touched).  Columns with keep_c == 0 (frozen, or
+// converged in this cycle) get W_c = 0 written, so that the B -= A W that follows leaves their column of B as it is.
+// V: basis blocks at stride vstride (= n * m).
+__global__ __launch_bounds__(WG) void k_gmres_update_multi(int64_t n, int m, const int32_t *__restrict__ cnt, const int32_t *__restrict__ keep,
+                                                           const double *__restrict__ y, const double *__restrict__ V, int64_t vstride,
+                                                           double *__restrict__ W, double *__restrict__ X)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    const int kc = cnt[c];
+    double s = 0.0;
+    if (kc > 0) {
+      const double *vt = V + t;
+      int k = 0;
+      for (; k + 3 < kc; k += 4) { // four basis blocks in flight per thread
+        double vv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vv[u] = __builtin_nontemporal_load(vt + (int64_t)(k + u) * vstride);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s += y[(int64_t)(k + u) * m + c] * vv[u];
+      }
+      for (; k < kc; ++k) s += y[(int64_t)k * m + c] * vt[(int64_t)k * vstride];
+      X[t] += s;
+    }
+    W[t] = keep[c] ? s : 0.0;
+  }
+}
+
 } // namespace ddm

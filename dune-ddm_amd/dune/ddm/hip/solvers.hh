@@ -125,8 +125,57 @@ public:
     if (verbose_ > 0) std::printf("=== device Krylov solve: %d iterations, reduction %.3e, %.3f s\n", r.iterations, r.reduction, r.elapsed_s);
   }
 
+  // Several right-hand sides at once: x.size() independent solves (1 to 32 columns) in one device loop (HipCGSolver: ddm_cg_solve_multi;
+  // HipRestartedGMResSolver: ddm_gmres_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
+  // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  A solver without a block
+  // loop (HipBiCGSTABSolver) throws Dune::NotImplemented.
+  void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
+  {
+    const std::size_t m = b.size();
+    if (m < 1 || m > 32 || x.size() != m) DUNE_THROW(InvalidStateException, "device Krylov block apply: 1 to 32 columns, as many x as b");
+    const std::size_t n = b[0].N();
+    for (std::size_t c = 0; c < m; ++c)
+      if (b[c].N() != n || x[c].N() != n) DUNE_THROW(InvalidStateException, "device Krylov block apply: the columns differ in size");
+    auto ctx = cprec->context();
+    ddm_hip::DeviceVector dX(ctx, n * m), dB(ctx, n * m);
+    std::vector<double> hx(n * m), hb(n * m);
+    for (std::size_t c = 0; c < m; ++c) {
+      prec->pre(x[c], b[c]);
+      for (std::size_t i = 0; i < n; ++i) {
+        hx[i * m + c] = x[c][i][0];
+        hb[i * m + c] = b[c][i][0];
+      }
+    }
+    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dX.data(), hx.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dB.data(), hb.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+    std::vector<ddm_solve_result> r(m);
+    ddm_hip::check(ctx->handle(), solve_block(ctx->handle(), dop->op_handle(), cprec->handle(n), (int)m, dX.data(), dB.data(), reduction, r.data()), "device block Krylov solve");
+    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hx.data(), dX.data(), (int64_t)(n * m * sizeof(double))), "d2h");
+    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hb.data(), dB.data(), (int64_t)(n * m * sizeof(double))), "d2h");
+    res.assign(m, InverseOperatorResult{});
+    for (std::size_t c = 0; c < m; ++c) {
+      for (std::size_t i = 0; i < n; ++i) {
+        x[c][i][0] = hx[i * m + c];
+        b[c][i][0] = hb[i * m + c];
+      }
+      prec->post(x[c]);
+      res[c].clear();
+      res[c].iterations = r[c].iterations;
+      res[c].converged = r[c].converged != 0;
+      res[c].reduction = r[c].reduction;
+      res[c].elapsed = r[c].elapsed_s;
+      res[c].conv_rate = r[c].iterations > 0 ? std::pow(r[c].reduction, 1.0 / r[c].iterations) : 0.0;
+    }
+    if (verbose_ > 0) std::printf("=== device block Krylov solve: %zu columns, %.3f s\n", m, m ? r[0].elapsed_s : 0.0);
+  }
+
 protected:
   virtual int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) = 0;
+  // the block loop of the solver on row-major n x m device blocks (r: m entries)
+  virtual int solve_block(ddm_ctx*, ddm_op*, ddm_combined*, int, double*, double*, double, ddm_solve_result*)
+  {
+    DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver and restartedgmressolver have one)");
+  }
   std::shared_ptr<LinearOperator<X, X>> op;
   std::shared_ptr<Preconditioner<X, X>> prec;
   ddm_hip::DeviceOperator* dop = nullptr;
@@ -147,53 +196,14 @@ public:
 
   using HipKrylovSolverBase<X>::apply;
 
-  // Several right-hand sides at once: x.size() independent CG solves (ddm_cg_solve_multi; 1 to 32 columns), each column as apply(x[c],
-  // b[c], reduction, res[c]) would run it.  One upload and one download of the whole row-major n x m block; b receives the defects.
-  void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
-  {
-    const std::size_t m = b.size();
-    if (m < 1 || m > 32 || x.size() != m) DUNE_THROW(InvalidStateException, "HipCGSolver::apply: 1 to 32 columns, as many x as b");
-    const std::size_t n = b[0].N();
-    for (std::size_t c = 0; c < m; ++c)
-      if (b[c].N() != n || x[c].N() != n) DUNE_THROW(InvalidStateException, "HipCGSolver::apply: the columns differ in size");
-    auto ctx = this->cprec->context();
-    ddm_hip::DeviceVector dX(ctx, n * m), dB(ctx, n * m);
-    std::vector<double> hx(n * m), hb(n * m);
-    for (std::size_t c = 0; c < m; ++c) {
-      this->prec->pre(x[c], b[c]);
-      for (std::size_t i = 0; i < n; ++i) {
-        hx[i * m + c] = x[c][i][0];
-        hb[i * m + c] = b[c][i][0];
-      }
-    }
-    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dX.data(), hx.data(), (int64_t)(n * m * sizeof(double))), "h2d");
-    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dB.data(), hb.data(), (int64_t)(n * m * sizeof(double))), "h2d");
-    std::vector<ddm_solve_result> r(m);
-    ddm_hip::check(ctx->handle(), ddm_cg_solve_multi(ctx->handle(), this->dop->op_handle(), this->cprec->handle(n), (int)m, dX.data(), dB.data(), reduction, this->maxit_,
-                                                     nullptr, r.data()), "device block CG solve");
-    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hx.data(), dX.data(), (int64_t)(n * m * sizeof(double))), "d2h");
-    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hb.data(), dB.data(), (int64_t)(n * m * sizeof(double))), "d2h");
-    res.assign(m, InverseOperatorResult{});
-    for (std::size_t c = 0; c < m; ++c) {
-      for (std::size_t i = 0; i < n; ++i) {
-        x[c][i][0] = hx[i * m + c];
-        b[c][i][0] = hb[i * m + c];
-      }
-      this->prec->post(x[c]);
-      res[c].clear();
-      res[c].iterations = r[c].iterations;
-      res[c].converged = r[c].converged != 0;
-      res[c].reduction = r[c].reduction;
-      res[c].elapsed = r[c].elapsed_s;
-      res[c].conv_rate = r[c].iterations > 0 ? std::pow(r[c].reduction, 1.0 / r[c].iterations) : 0.0;
-    }
-    if (this->verbose_ > 0) std::printf("=== device block CG solve: %zu columns, %.3f s\n", m, m ? r[0].elapsed_s : 0.0);
-  }
-
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
   {
     return ddm_cg_solve(ctx, o, p, x, b, reduction, this->maxit_, 0, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_cg_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, nullptr, r);
   }
 };
 
@@ -206,10 +216,16 @@ public:
   HipRestartedGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
       : HipRestartedGMResSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
 
+  using HipKrylovSolverBase<X>::apply;
+
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
   {
     return ddm_gmres_solve(ctx, o, p, x, b, reduction, this->maxit_, restart_, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_gmres_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, nullptr, r);
   }
   int restart_;
 };
@@ -222,6 +238,8 @@ public:
       : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose) {}
   HipBiCGSTABSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
       : HipBiCGSTABSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
+
+  using HipKrylovSolverBase<X>::apply; // (the block overload throws Dune::NotImplemented: no block BiCGSTAB loop yet)
 
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override

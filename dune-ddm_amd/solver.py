@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, cg_solve, cg_solve_multi, galerkin_products)
+               SchwarzPreconditioner, cg_solve, cg_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
 
@@ -288,10 +288,13 @@ class TwoLevelSchwarz:
         res, hist = cg_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, fixed_iterations, history)
         return res, hist, x
 
-    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None):
-        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi), each column as ``solve`` would run it.
+    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100):
+        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver", m independent
+        restarted GMRES solves with aligned restart cycles (ddm_gmres_solve_multi), each column as ``solve`` would run it.
         B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
         (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
+        if solver not in ("cgsolver", "restartedgmressolver"):
+            raise NotImplementedError("solver type '" + str(solver) + "' (cgsolver and restartedgmressolver are available for several right-hand sides)")
         torch = self.torch
         n_o = self.rl.n_o
         if B is None:
@@ -307,7 +310,10 @@ class TwoLevelSchwarz:
         X = torch.zeros_like(Bd) if X0 is None else block(X0)
         if X.shape != Bd.shape:
             raise ValueError(f"X0 {tuple(X.shape)} and B {tuple(Bd.shape)} differ")
-        res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
+        if solver == "restartedgmressolver":
+            res, hist = gmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
+        else:
+            res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
         return res, hist, X
 
 

@@ -456,6 +456,27 @@ int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X,
  * defect and when a local solve gave up (ddm_ilu0_peek_status), as ddm_cg_solve. */
 int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                        double *hist_host, ddm_solve_result *res);
+/* nrhs INDEPENDENT dune-istl RestartedGMResSolver::apply recurrences in one loop (the loop of ddm_gmres_solve per column: left
+ * preconditioning, modified Gram-Schmidt in the order k = 0..i, the same Givens rotations, the monitored norm is that of the
+ * preconditioned defect; not a block-Krylov method).  X, B, hist_host ((maxit + 1) x nrhs, entries after a column's last iteration are
+ * not written) and res (nrhs entries) as in ddm_cg_solve_multi.
+ *   Restart cycles are aligned: every column restarts at the iterations restart, 2 restart, ..., exactly where ddm_gmres_solve restarts it.
+ *   Stopping: column c stops on its own test (norm < reduction def0 or norm < 1e-30; def0 < 1e-30: converged at once, x untouched); its
+ *     solution update is formed from its own Hessenberg columns of the current cycle, at the end of that cycle.
+ *   Frozen columns: after a column stopped, its x, its history, its res entry and its column of B do not change any more (as the
+ *     single-vector solver does not apply b -= A w after the cycle in which it converged).  A frozen column is skipped by mask, never
+ *     multiplied by a zero coefficient: its basis entries may hold anything.
+ *   Errors: DDM_EINVAL (before any device work) for nrhs outside 1..32, restart < 1, maxit < 0, NULL pointers or X == B; DDM_ENUMERIC,
+ *     naming column and iteration, for a NaN norm or the |w| == 0 breakdown in an active column, and when a local solve gave up
+ *     (ddm_ilu0_peek_status on entry, ddm_ilu0_status at the end).
+ *   Memory: the Krylov basis is min(restart, maxit) + 1 blocks of n x nrhs doubles plus one work block, allocated per call and freed on
+ *     every return path.  When that exceeds the free device memory the call returns DDM_ENOTIMPL (the byte count is in the message)
+ *     before it allocates anything.
+ *   Host traffic: one read-back per iteration (the (i + 2) x nrhs fresh Hessenberg entries); the dots of one orthogonalisation step
+ *     travel as one all-reduce of nrhs doubles.  DDM_GMRES_MULTI_FUSED in the environment (read once per call): 0 (the default) runs every
+ *     orthogonalisation step as an AXPY and a separate dot, 1 as one fused kernel; the results are bit-identical. */
+int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                          int restart, double *hist_host, ddm_solve_result *res);
 
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,

@@ -1,0 +1,183 @@
+"""Restarted GMRES for several right-hand sides at once against sequential solves (ddm_gmres_solve_multi vs. m calls of ddm_gmres_solve).
+
+Problems, built as bench_convdiff.py builds them: BASELINE configs[3] (Q1-DG convection-diffusion 512^2, 8 subdomains, `umfpack` local
+solves, GenEO, additive, GMRES(100) to 1e-8; the default) and --problem elasticity (configs[4]: P1 elasticity bar, `cholmod`, restricted
+Schwarz, multiplicative GenEO level, GMRES(100) to 1e-6).  Right-hand sides: column 0 is the problem's, the others are seeded random
+consistent vectors.  For every m of --m the same m right-hand sides are solved (a) as one block and (b) one after the other (each column
+once; the sequential time of m columns is the sum over the first m).  Prints a table and one JSON line: RHS-iterations per second of
+both, their ratio, and the per-iteration breakdown of a --profile-iters run with the library's event timers (local solve, coarse level,
+operator, orthogonalisation; the single-vector loop has no orthogonalisation timer: its share is the rest of the wall time).
+--fused-reps R > 0 adds, at m = 8, R timed repetitions of a --profile-iters long block run with the fused Gram-Schmidt kernel and R
+with DDM_GMRES_MULTI_FUSED=0 (median and spread of both).
+
+The measurement runs in a child process under `timeout -k 10 --step-timeout`; the parent only starts it and passes its exit code on.
+
+    python tools/multi_gmres_bench.py [--problem dg|elasticity] [--m 1,4,8,16] [--fused-reps 5]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TIMERS = {"local solve": "Schwarz/local solve", "coarse": "GalerkinPrec/apply", "operator": "Operator/apply",
+          "orthogonalisation": "GMRES/orthogonalisation", "update": "GMRES/update", "preconditioner": "CombinedPreconditioner/apply"}
+
+
+def log(*a):
+    print("[multi_gmres_bench]", *a, file=sys.stderr, flush=True)
+
+
+def build(args):
+    from dune_ddm_amd import synth
+    from dune_ddm_amd.geneo import geneo_basis
+    from dune_ddm_amd.problem import build_structured
+    from dune_ddm_amd.solver import TwoLevelSchwarz
+    if args.problem == "dg":
+        grid = synth.StructuredDG2D((args.cells, args.cells), (4, 2))
+        dec = build_structured(grid, overlap=2, neumann=True)
+        cfg = dict(schwarz_type="standard", mode="additive", reduction=1e-8, tol=1e-5, nev=args.nev, local="umfpack")
+        workload = f"Q1-DG convection-diffusion {args.cells}^2 cells = {grid.nglobal} DoF, 8 subdomains (overlap 2), umfpack, GenEO nev {args.nev}, additive"
+    else:
+        grid = synth.StructuredElasticity(refine=args.refine, parts=8)
+        dec = build_structured(grid, overlap=1, neumann=True, second_region="all")
+        cfg = dict(schwarz_type="restricted", mode="multiplicative", reduction=1e-6, tol=1e-6, nev=min(args.nev, 12), local="cholmod")
+        workload = f"P1 elasticity bar, refine {args.refine} = {grid.nglobal} DoF, 8 subdomains (overlap 1), cholmod, GenEO nev {cfg['nev']}, restricted, multiplicative"
+    tl = TwoLevelSchwarz(dec, schwarz_type=cfg["schwarz_type"], mode=cfg["mode"], coarse="none", subdomain_solver=cfg["local"])
+    tl.set_coarse_basis(geneo_basis(tl, nev=cfg["nev"], tol=cfg["tol"]))
+    tl.rebuild_combined(cfg["mode"])
+    tl.schwarz.wait_setup()
+    tl.ctx.sync()
+    return dec, tl, cfg, workload + f", GMRES({args.restart}) to {cfg['reduction']:g}"
+
+
+def timers_per_iteration(tl, iters):
+    return {k: tl.ctx.timer(name)[0] / iters for k, name in TIMERS.items()}
+
+
+def worker(args):
+    import __graft_entry__ as ge
+    ge.import_package()
+    import torch
+    ms_ = sorted({int(v) for v in args.m.split(",")})
+    assert all(1 <= m <= 32 for m in ms_)
+    t0 = time.perf_counter()
+    dec, tl, cfg, workload = build(args)
+    log(f"setup {time.perf_counter() - t0:.1f} s, n_o = {tl.rl.n_o}, local engine {tl.schwarz.engine()}")
+    kw = dict(solver="restartedgmressolver", restart=args.restart)
+    mmax = max(ms_ + ([8] if args.fused_reps > 0 else []))
+    rng = np.random.default_rng(args.seed)
+    cols = [np.asarray(tl.rl.b, dtype=np.float64)]
+    for _ in range(mmax - 1):
+        xg = rng.standard_normal(dec.nglobal)
+        cols.append(tl.rl.cat_novlp([xg[sd.glob[:sd.n_o]] for sd in dec.subs]))
+    Bh = np.stack(cols, axis=1)
+    Bd = tl.to_device(Bh)
+    P = args.profile_iters
+
+    # (b) sequential single-vector solves, each column once
+    tl.solve(reduction=0.0, maxit=5, history=False, b=Bh[:, 0], **kw)          # warm-up
+    seq = []
+    for c in range(max(ms_)):
+        res, _, _ = tl.solve(reduction=cfg["reduction"], maxit=args.maxit, history=False, b=Bh[:, c], **kw)
+        seq.append((int(res.iterations), float(res.elapsed_s), bool(res.converged)))
+        log(f"single column {c}: {res.iterations} iterations, {res.elapsed_s * 1e3:.1f} ms")
+    tl.ctx.timing(True)
+    tl.ctx.timing_reset()
+    res, _, _ = tl.solve(reduction=0.0, maxit=P, history=False, b=Bh[:, 0], **kw)
+    tl.ctx.timing(False)
+    single_prof = timers_per_iteration(tl, P)
+    single_prof["wall"] = 1e3 * float(res.elapsed_s) / P
+
+    # (a) one block solve per width
+    rows = []
+    for m in ms_:
+        B = Bd[:, :m].contiguous()
+        tl.ctx.timing(True)
+        tl.ctx.timing_reset()
+        res, _, _ = tl.solve_multi(B, reduction=0.0, maxit=P, history=False, **kw)   # (also the warm-up of this width)
+        tl.ctx.timing(False)
+        prof = timers_per_iteration(tl, P)
+        prof["wall"] = 1e3 * float(res[0].elapsed_s) / P
+        res, _, X = tl.solve_multi(B, reduction=cfg["reduction"], maxit=args.maxit, history=False, **kw)
+        its = [int(r.iterations) for r in res]
+        el = float(res[0].elapsed_s)
+        seq_its = [s[0] for s in seq[:m]]
+        seq_el = sum(s[1] for s in seq[:m])
+        row = {"m": m, "iterations": its, "sequential_iterations": seq_its, "converged": all(r.converged for r in res),
+               "block_s": el, "sequential_s": seq_el, "ms_per_block_iteration": 1e3 * el / max(its),
+               "rhs_iterations_per_s": sum(its) / el, "sequential_rhs_iterations_per_s": sum(seq_its) / seq_el,
+               "ms_per_block_iteration_by_timer": prof}
+        row["ratio"] = row["rhs_iterations_per_s"] / row["sequential_rhs_iterations_per_s"]
+        rows.append(row)
+        del X
+    fused = None
+    if args.fused_reps > 0:
+        B = Bd[:, :8].contiguous()
+        fused = {"1": [], "0": []}
+        for _ in range(args.fused_reps + 1):                                    # interleaved: drift hits both alike
+            for flag in ("1", "0"):
+                os.environ["DDM_GMRES_MULTI_FUSED"] = flag
+                tl.ctx.timing(True)
+                tl.ctx.timing_reset()
+                res, _, _ = tl.solve_multi(B, reduction=0.0, maxit=P, history=False, **kw)
+                tl.ctx.timing(False)
+                fused[flag].append((1e3 * float(res[0].elapsed_s) / P, tl.ctx.timer(TIMERS["orthogonalisation"])[0] / P))
+        del os.environ["DDM_GMRES_MULTI_FUSED"]                                  # (back to the library's default)
+        fused = {("fused" if k == "1" else "unfused"): {"reps": len(v) - 1, "wall_ms_per_iteration": sorted(w for w, _ in v[1:]),
+                                                         "orthogonalisation_ms_per_iteration": sorted(o for _, o in v[1:])} for k, v in fused.items()}
+        for v in fused.values():                                                 # (the first repetition of each is a warm-up)
+            v["median_wall"] = float(np.median(v["wall_ms_per_iteration"]))
+            v["median_orthogonalisation"] = float(np.median(v["orthogonalisation_ms_per_iteration"]))
+    tl.prec.check_status()
+
+    hdr = f"{'m':>3} {'block it':>8} {'ms/it':>8} {'RHS-it/s':>10} {'seq RHS-it/s':>12} {'ratio':>6} | " + " ".join(f"{k[:9]:>9}" for k in TIMERS)
+    print(hdr)
+    print(f"{'seq':>3} {seq[0][0]:>8} {single_prof['wall']:>8.2f} {'':>10} {'':>12} {'':>6} | " + " ".join(f"{single_prof[k]:>9.3f}" for k in TIMERS))
+    for r in rows:
+        p = r["ms_per_block_iteration_by_timer"]
+        print(f"{r['m']:>3} {max(r['iterations']):>8} {r['ms_per_block_iteration']:>8.2f} {r['rhs_iterations_per_s']:>10.0f} "
+              f"{r['sequential_rhs_iterations_per_s']:>12.0f} {r['ratio']:>6.2f} | " + " ".join(f"{p[k]:>9.3f}" for k in TIMERS))
+    if fused:
+        for k, v in fused.items():
+            print(f"m = 8 {k}: wall {v['median_wall']:.3f} ms/it (min {v['wall_ms_per_iteration'][0]:.3f}, max {v['wall_ms_per_iteration'][-1]:.3f}), "
+                  f"orthogonalisation {v['median_orthogonalisation']:.3f} ms/it over {v['reps']} repetitions of {P} iterations")
+    out = {"workload": workload, "problem": args.problem, "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "restart": args.restart,
+           "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows, "fused_vs_unfused_m8": fused,
+           "what": "rhs_iterations_per_s = sum of the columns' GMRES iterations / wall time of the solve; sequential = the same columns solved one by one "
+                   "with ddm_gmres_solve; *_by_timer: ms per (block) iteration of a run of profile_iters iterations (reduction 0) with the event timers on"}
+    print(json.dumps(out))
+    tl.ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--problem", default="dg", choices=["dg", "elasticity"])
+    ap.add_argument("--cells", type=int, default=512)
+    ap.add_argument("--refine", type=int, default=1)
+    ap.add_argument("--nev", type=int, default=16)
+    ap.add_argument("--restart", type=int, default=100)
+    ap.add_argument("--m", default="1,4,8,16", help="block widths, comma separated (each <= 32)")
+    ap.add_argument("--maxit", type=int, default=1000)
+    ap.add_argument("--profile-iters", type=int, default=20, help="iterations of the timer runs")
+    ap.add_argument("--fused-reps", type=int, default=0, help="timed repetitions of the fused / unfused comparison at m = 8 (0 = none)")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--step-timeout", type=int, default=540, help="seconds the measuring child process may take")
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:]
+    sys.exit(subprocess.call(cmd, cwd=ROOT))
+
+
+if __name__ == "__main__":
+    main()
