@@ -1,0 +1,700 @@
+// The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES and BiCGSTAB for one right-hand side, CG and restarted GMRES
+// for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods).  All five share the frame around
+// the loop (solve_result_reset, classify_initial_defect, krylov_finish); both GMRES drivers run their host arithmetic through the
+// same GmresColumn, which is what keeps a block column bit-identical to the single-vector solve.  Needs preconditioners.hpp.
+#pragma once
+
+// synchronises the context's stream when it goes out of scope: the Krylov drivers declare it AFTER their work arrays, so that an
+// early return waits for the enqueued kernels before the arrays are released
+struct StreamDrain {
+  ddm_ctx *ctx;
+  ~StreamDrain() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
+// ---- the frame around every Krylov loop --------------------------------------------------------
+static void solve_result_reset(ddm_solve_result *res) { *res = ddm_solve_result{0, 0, 0.0, 1.0, 0.0}; }
+// what the initial defect norm says about the loop: do not start (NaN: an error; below 1e-30: already converged) or go
+enum class Defect0 { NaN, Zero, Go };
+static Defect0 classify_initial_defect(double def0) { return !(def0 == def0) ? Defect0::NaN : def0 < 1e-30 ? Defect0::Zero : Defect0::Go; }
+// End of a driver: drains the stream, stops the clock (*elapsed_s: seconds since t0), then asks whether a persistent local solve gave
+// up during the loop (its results are invalid then).  An earlier error rc is passed through.
+static int krylov_finish(ddm_ctx *ctx, const ddm_combined *prec, int rc, std::chrono::steady_clock::time_point t0, double *elapsed_s)
+{
+  (void)hipStreamSynchronize(ctx->stream);
+  *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (rc || !prec->schwarz) return rc;
+  int st = 0;
+  rc = ddm_ilu0_status(ctx, prec->schwarz->solver, &st);
+  if (!rc && st) rc = fail(ctx, DDM_ENUMERIC, "persistent triangular solve timed out waiting for a level (results invalid)");
+  return rc;
+}
+
+// ---- CG ----------------------------------------------------------------------------------------
+// dune-istl CGSolver::apply, split so that a caller can time an exact number of
+// iterations: begin = "b -= A x; def0 = ||b||", one step = "prec.apply; rho; [beta; p = beta p + q];
+// q = A p; alpha; lambda; x += lambda p; b -= lambda q; def = ||b||".
+struct ddm_cg {
+  ddm_op *op = nullptr;
+  ddm_combined *prec = nullptr;
+  double *x = nullptr, *b = nullptr; // the caller's
+  dbuf<double> p, q;
+  int64_t n = 0;
+  int it = 0;
+  double def0 = 0.0;
+};
+extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, ddm_cg **out)
+{
+  if (!ctx || !op || !prec || !x || !b || !out) return fail(ctx, DDM_EINVAL, "ddm_cg_begin: bad arguments");
+  ctx->piggy = nullptr; // (nothing rides on an all-reduce outside ddm_cg_steps)
+  auto S = std::make_unique<ddm_cg>();
+  S->op = op;
+  S->prec = prec;
+  S->x = x;
+  S->b = b;
+  S->n = op->n;
+  if (S->p.alloc(S->n) != hipSuccess || S->q.alloc(S->n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_cg_begin: allocation failed");
+  DDMCHECK(ddm_op_applyscaleadd(ctx, op, -1.0, x, b)); // prec.pre(x,b); b -= A x
+  double bb = 0.0;
+  DDMCHECK(dot_device(ctx, S->n, op->owner, b, b, ctx->scal + 5));
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double)));
+  S->def0 = std::sqrt(bb);
+  *out = S.release();
+  return DDM_OK;
+}
+extern "C" void ddm_cg_end(ddm_ctx *ctx, ddm_cg *S)
+{
+  if (ctx) ctx->piggy = nullptr;
+  if (!S) return;
+  if (ctx) (void)hipStreamSynchronize(ctx->stream);
+  delete S;
+}
+extern "C" double ddm_cg_def0(const ddm_cg *S) { return S->def0; }
+// Enqueues k iterations without synchronising; the squared defect of the last one is left in
+// device scalar 5 (read it with ddm_cg_defect).
+extern "C" int ddm_cg_steps(ddm_ctx *ctx, ddm_cg *S, int k)
+{
+  // ctx->piggy is set below between one iteration and the next preconditioner apply: whichever way this function returns, it must
+  // not stay set, or the next unrelated coarse_allreduce reduces K + 1 doubles on this rank and K on the others (a hang)
+  struct PiggyGuard { ddm_ctx *ctx; ~PiggyGuard() { ctx->piggy = nullptr; } } piggy_guard{ctx};
+  double *scal = ctx->scal;
+  const int G = grid_for(S->n);
+  for (int i = 0; i < k; ++i) {
+    const bool first = S->it == 0;
+    DDMCHECK(ddm_combined_apply(ctx, S->prec, first ? S->p : S->q, S->b));                 // q = M^-1 b  (p on the first step)
+    DDMCHECK(dot_device(ctx, S->n, S->op->owner, first ? S->p : S->q, S->b, scal + (first ? 0 : 3))); // rho = <q, b>
+    if (!first) {
+      hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(1), 0, ctx->stream, scal);                 // beta = rho / rholast; rholast = rho
+      hipLaunchKernelGGL(k_cg_direction, dim3(G), dim3(WG), 0, ctx->stream, S->n, scal, S->q, S->p); // p = beta p + q
+    }
+    DDMCHECK(ddm_op_apply(ctx, S->op, S->p, S->q));                                          // q = A p
+    DDMCHECK(dot_device(ctx, S->n, S->op->owner, S->p, S->q, scal + 1));                     // alpha = <p, q>
+    hipLaunchKernelGGL(k_cg_lambda, dim3(1), dim3(1), 0, ctx->stream, scal);                 // lambda = rholast / alpha
+    { // x += lambda p; b -= lambda q; def^2 = <b, b> (partial sums in the same kernel)
+      const int nb = grid_for(S->n, WG * 4, RED_MAX_BLOCKS);
+      if (S->op->owner)
+        hipLaunchKernelGGL(k_cg_update_norm<true>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial);
+      else
+        hipLaunchKernelGGL(k_cg_update_norm<false>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial);
+      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + 5);
+      // The rank-local sum is complete; its all-reduce rides on the coarse-defect all-reduce of the NEXT iteration's preconditioner
+      // (one RCCL launch saved per iteration) unless this is the chunk's last iteration -- whoever reads the defect (ddm_cg_defect)
+      // needs it now -- or there is no coarse level to ride on.
+      if (i + 1 < k && S->prec->galerkin) ctx->piggy = scal + 5;
+      else DDMCHECK(ctx_allreduce(ctx, scal + 5, 1, "scalar product"));
+    }
+    S->it += 1;
+  }
+  // (ctx->piggy is null here: the last iteration of a chunk reduces its own norm, every earlier one was consumed by the next apply)
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+extern "C" int ddm_cg_defect(ddm_ctx *ctx, ddm_cg *S, double *def_host) // synchronous
+{
+  double bb = 0.0;
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double)));
+  *def_host = std::sqrt(bb);
+  (void)S;
+  return DDM_OK;
+}
+
+extern "C" int ddm_cg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
+                            int fixed_iterations, double *hist_host, ddm_solve_result *res)
+{
+  if (!res) return fail(ctx, DDM_EINVAL, "ddm_cg_solve: bad arguments");
+  ddm_cg *S = nullptr;
+  DDMCHECK(ddm_cg_begin(ctx, op, prec, x, b, &S));
+  const double def0 = S->def0;
+  solve_result_reset(res);
+  res->def0 = def0;
+  if (hist_host) hist_host[0] = def0;
+  if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
+    ddm_cg_end(ctx, S);
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
+    res->converged = 1;
+    return DDM_OK;
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = DDM_OK;
+  double deff = def0;
+  if (fixed_iterations > 0 && !hist_host) {
+    rc = ddm_cg_steps(ctx, S, fixed_iterations);
+    if (!rc) rc = ddm_cg_defect(ctx, S, &deff);
+    res->iterations = fixed_iterations;
+  } else {
+    const int iters = fixed_iterations > 0 ? fixed_iterations : maxit;
+    for (int i = 1; i <= iters && !rc; ++i) {
+      rc = ddm_cg_steps(ctx, S, 1);
+      if (!rc) rc = ddm_cg_defect(ctx, S, &deff); // the Krylov loop tests the defect every iteration
+      if (rc) break;
+      res->iterations = i;
+      if (hist_host) hist_host[i] = deff;
+      if (!(deff == deff)) {
+        rc = fail(ctx, DDM_ENUMERIC, "defect is NaN in iteration %d", i);
+        break;
+      }
+      if (fixed_iterations <= 0 && (deff < def0 * reduction || deff < 1e-30)) {
+        res->converged = 1;
+        break;
+      }
+    }
+  }
+  rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
+  res->reduction = deff / def0;
+  ddm_cg_end(ctx, S);
+  return rc;
+}
+
+// ---- restarted GMRES -----------------------------------------------------------------------------
+// dune-istl RestartedGMResSolver::apply (DUNE 2.10 solvers.hh; not in the snapshot, restated from the
+// published implementation): left preconditioning, modified Gram-Schmidt, Givens rotations; the
+// monitored quantity is the norm of the PRECONDITIONED defect.  Selected by [solver] type =
+// restartedgmressolver in examples/poisson.ini:12-17 (restart = 100) and the default of
+// dune/ddm/twolevel_schwarz.hh:121-130 (restart = 30).  Krylov basis, dots and updates stay on the
+// device; per iteration the i+2 Hessenberg entries are read back for the rotations on the host.
+static void gmres_generate_rotation(double dx, double dy, double &cs, double &sn)
+{
+  const double ndx = std::fabs(dx), ndy = std::fabs(dy);
+  if (ndy < 1e-15) {
+    cs = 1.0;
+    sn = 0.0;
+  } else if (ndx < 1e-15) {
+    cs = 0.0;
+    sn = 1.0;
+  } else if (ndy > ndx) {
+    const double t = ndx / ndy;
+    cs = 1.0 / std::sqrt(1.0 + t * t);
+    sn = cs;
+    cs *= t;
+    sn *= dx / ndx;
+    sn *= dy / ndy;
+  } else {
+    const double t = ndy / ndx;
+    cs = 1.0 / std::sqrt(1.0 + t * t);
+    sn = cs;
+    sn *= dy / dx;
+  }
+}
+static void gmres_apply_rotation(double &dx, double &dy, double cs, double sn)
+{
+  const double t = cs * dx + sn * dy;
+  dy = -sn * dx + cs * dy;
+  dx = t;
+}
+
+// host state of one column: Hessenberg matrix (restart + 1) x restart, right-hand side s of the least-squares problem, rotations
+struct GmresColumn {
+  int R = 0;
+  std::vector<double> H, s, cs, sn;
+  double norm = 0.0, def0 = 0.0;
+  int cnt = 0; // Hessenberg columns of the current restart cycle
+  void init(int restart)
+  {
+    R = restart;
+    H.assign((size_t)(R + 1) * R, 0.0);
+    s.assign(R + 1, 0.0);
+    cs.assign(R, 0.0);
+    sn.assign(R, 0.0);
+  }
+  double &h(int r, int c) { return H[(size_t)r * R + c]; }
+  void start_cycle() { cnt = 0, std::fill(s.begin(), s.end(), 0.0), s[0] = norm; } // a restart cycle begins from the defect norm in `norm`
+  // Iteration i of the cycle, in two halves, because the driver normalises the next basis vector by |w| in between.  First half: the
+  // fresh Hessenberg column (hcol[k * stride]: the Gram-Schmidt coefficients k <= i, then <w, w>) goes into H; returns h_{i+1,i} = |w|.
+  double take_column(int i, const double *hcol, size_t stride)
+  {
+    for (int k = 0; k <= i; ++k) h(k, i) = hcol[(size_t)k * stride];
+    h(i + 1, i) = std::sqrt(hcol[(size_t)(i + 1) * stride]);
+    return h(i + 1, i);
+  }
+  // Second half: the old rotations applied to column i, the new one generated and applied to it and to s; returns the new defect norm.
+  double rotate(int i)
+  {
+    for (int k = 0; k < i; ++k) gmres_apply_rotation(h(k, i), h(k + 1, i), cs[k], sn[k]);
+    gmres_generate_rotation(h(i, i), h(i + 1, i), cs[i], sn[i]);
+    gmres_apply_rotation(h(i, i), h(i + 1, i), cs[i], sn[i]);
+    gmres_apply_rotation(s[i], s[i + 1], cs[i], sn[i]);
+    norm = std::fabs(s[i + 1]);
+    cnt = i + 1;
+    return norm;
+  }
+  // y[0, cnt) = solution of the triangular system of the cycle (update(w, i, H, s, v) of dune-istl)
+  void back_substitute(double *y)
+  {
+    for (int a = cnt - 1; a >= 0; --a) {
+      double t = s[a];
+      for (int b = a + 1; b < cnt; ++b) t -= h(a, b) * y[b];
+      y[a] = t / h(a, a);
+    }
+  }
+};
+
+extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
+                               int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !x || !b || !res || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_gmres_solve: bad arguments");
+  const int64_t n = op->n;
+  const int m = restart;
+  const int G = grid_for(n);
+  dbuf<double> V, w, hdev;
+  HIPCHECK(ctx, V.alloc(std::max<int64_t>(n, 1) * (m + 1)));
+  HIPCHECK(ctx, w.alloc(n));
+  HIPCHECK(ctx, hdev.alloc(m + 2));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
+  auto v = [&](int k) { return V + (size_t)k * (size_t)n; };
+  std::vector<double> hcol(m + 2), y(m);
+  GmresColumn q; // Hessenberg matrix, rotations and least-squares right-hand side (the block driver keeps one of these per column)
+  q.init(m);
+  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
+  if (!rc) rc = ddm_combined_apply(ctx, prec, v(0), b); // v0 = M^-1 b
+  double nn = 0.0;
+  if (!rc) rc = dot_device(ctx, n, op->owner, v(0), v(0), hdev);
+  if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
+  if (rc) return rc;
+  q.norm = std::sqrt(nn);
+  const double def0 = q.norm;
+  solve_result_reset(res);
+  res->def0 = def0;
+  if (hist_host) hist_host[0] = def0;
+  if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
+    res->converged = 1;
+    return DDM_OK;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  int j = 0;
+  bool conv = false;
+  while (j < maxit && !conv && !rc) {
+    hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / q.norm, v(0));
+    q.start_cycle();
+    int i = 0;
+    for (; i < m && j < maxit && !conv; ++i, ++j) {
+      rc = ddm_op_apply(ctx, op, v(i), v(i + 1));                 // v[i+1] = A v[i] (temporary)
+      if (!rc) rc = ddm_combined_apply(ctx, prec, w, v(i + 1));   // w = M^-1 A v[i]
+      for (int k = 0; k <= i && !rc; ++k) {                       // modified Gram-Schmidt
+        rc = dot_device(ctx, n, op->owner, v(k), w, hdev + k);
+        hipLaunchKernelGGL(k_axpy_negdev, dim3(G), dim3(WG), 0, ctx->stream, n, hdev + k, v(k), w);
+      }
+      if (!rc) rc = dot_device(ctx, n, op->owner, w, w, hdev + i + 1);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2));
+      if (rc) break;
+      const double wnorm = q.take_column(i, hcol.data(), 1);
+      if (std::fabs(wnorm) < 1e-80) {
+        rc = fail(ctx, DDM_ENUMERIC, "breakdown in GMRes - |w| == 0.0 after %d iterations", j);
+        break;
+      }
+      HIPCHECK(ctx, hipMemcpyAsync(v(i + 1), w, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+      hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / wnorm, v(i + 1));
+      const double norm = q.rotate(i);
+      res->iterations = j + 1;
+      if (hist_host) hist_host[j + 1] = norm;
+      if (!(norm == norm)) {
+        rc = fail(ctx, DDM_ENUMERIC, "defect is NaN in iteration %d", j + 1);
+        break;
+      }
+      if (norm < def0 * reduction || norm < 1e-30) conv = true;
+    }
+    if (rc) break;
+    // update(w, i, H, s, v): solve the triangular system, w = sum_k y_k v[k]; x += w
+    q.back_substitute(y.data());
+    HIPCHECK(ctx, hipMemsetAsync(w, 0, sizeof(double) * (size_t)n, ctx->stream));
+    for (int a = 0; a < i; ++a) hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, y[a], v(a), w);
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, w, x);
+    if (!conv && j < maxit) { // restart: b -= A w; v0 = M^-1 b
+      rc = ddm_op_applyscaleadd(ctx, op, -1.0, w, b);
+      if (!rc) rc = ddm_combined_apply(ctx, prec, v(0), b);
+      if (!rc) rc = dot_device(ctx, n, op->owner, v(0), v(0), hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
+      q.norm = std::sqrt(nn);
+    }
+  }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in GMRES");
+  rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
+  res->converged = conv ? 1 : 0;
+  res->reduction = q.norm / def0;
+  return rc;
+}
+
+// ---- BiCGSTAB ------------------------------------------------------------------------------------
+// dune-istl BiCGSTABSolver::apply ([solver] type = bicgstabsolver; DUNE 2.10 solvers.hh, not in the snapshot -- restated in
+// oracle/apply_oracle.py::bicgstab_solve): right-preconditioned, two half steps per iteration, the defect norm is tested after each
+// half step (hist_host receives both: up to 2 maxit + 1 entries); result.iterations = ceil of the half-step counter, as dune-istl reports.
+extern "C" int ddm_bicgstab_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, double *hist_host,
+                                  int32_t *nhist, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !x || !b || !res) return fail(ctx, DDM_EINVAL, "ddm_bicgstab_solve: bad arguments");
+  const int64_t n = op->n;
+  const int G = grid_for(n);
+  const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
+  dbuf<double> buf[5]; // rt, p, v, y, t
+  StreamDrain drain{ctx}; // (declared after the buffers: every return waits for the stream before they are released)
+  for (auto &q : buf)
+    if (q.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_bicgstab_solve: allocation failed");
+  double *rt = buf[0], *p = buf[1], *v = buf[2], *y = buf[3], *t = buf[4], *r = b;
+  const double EPS = 1e-80;
+  const bool verbose = std::getenv("DDM_KRYLOV_VERBOSE") != nullptr;
+  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, r); // r = b - A x (b is overwritten by the defect, as in dune-istl)
+  if (rc) return rc;
+  HIPCHECK(ctx, hipMemcpyAsync(rt, r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  double norm = 0.0;
+  if ((rc = ddm_norm(ctx, op, r, &norm))) return rc;
+  const double def0 = norm;
+  solve_result_reset(res);
+  res->def0 = def0;
+  int nh = 0;
+  if (hist_host) hist_host[nh] = def0;
+  ++nh;
+  if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
+    res->converged = 1;
+    if (nhist) *nhist = nh;
+    return DDM_OK;
+  }
+  HIPCHECK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+  HIPCHECK(ctx, hipMemsetAsync(v, 0, bytes, ctx->stream));
+  double rho = 1.0, alpha = 1.0, omega = 1.0, rho_new = 0.0, h = 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  double it = 0.5;
+  bool conv = false;
+  auto record = [&](double nrm) {
+    if (hist_host) hist_host[nh] = nrm;
+    ++nh;
+    res->reduction = nrm / def0;
+    return nrm <= def0 * reduction;
+  };
+  for (; it < maxit && !rc; it += 0.5) {
+    if ((rc = ddm_dot(ctx, op, rt, r, &rho_new))) break;
+    if (verbose) std::fprintf(stderr, "[ddm bicgstab] it %.1f rho_new %.17g rho %.17g alpha %.17g omega %.17g norm %.17g\n", it, rho_new, rho, alpha, omega, norm);
+    if (std::fabs(rho) <= EPS) { rc = fail(ctx, DDM_ENUMERIC, "breakdown in BiCGSTAB - rho %g <= EPSILON after %g iterations", rho, it); break; }
+    if (std::fabs(omega) <= EPS) { rc = fail(ctx, DDM_ENUMERIC, "breakdown in BiCGSTAB - omega %g <= EPSILON after %g iterations", omega, it); break; }
+    if (it < 1) {
+      HIPCHECK(ctx, hipMemcpyAsync(p, r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+      const double beta = (rho_new / rho) * (alpha / omega);
+      hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, -omega, (const double *)v, p); // p = r + beta (p - omega v)
+      hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, beta, p);
+      hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, (const double *)r, p);
+    }
+    if ((rc = ddm_combined_apply(ctx, prec, y, p))) break;  // y = W^-1 p
+    if ((rc = ddm_op_apply(ctx, op, y, v))) break;           // v = A y
+    if ((rc = ddm_dot(ctx, op, rt, v, &h))) break;
+    if (std::fabs(h) < EPS) { rc = fail(ctx, DDM_ENUMERIC, "abs(h) < EPSILON in BiCGSTAB - abort"); break; }
+    alpha = rho_new / h;
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, alpha, (const double *)y, x);
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, -alpha, (const double *)v, r);
+    if ((rc = ddm_norm(ctx, op, r, &norm))) break;
+    if (record(norm)) { conv = true; break; }
+    it += 0.5;
+    if ((rc = ddm_combined_apply(ctx, prec, y, r))) break;  // y = W^-1 r
+    if ((rc = ddm_op_apply(ctx, op, y, t))) break;           // t = A y
+    double tt = 0.0, tr = 0.0;
+    if ((rc = ddm_dot(ctx, op, t, t, &tt))) break;
+    if ((rc = ddm_dot(ctx, op, t, r, &tr))) break;
+    omega = tr / tt;
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, omega, (const double *)y, x);
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, -omega, (const double *)t, r);
+    rho = rho_new;
+    if ((rc = ddm_norm(ctx, op, r, &norm))) break;
+    if (record(norm)) { conv = true; break; }
+  }
+  if (rc) return rc;
+  rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
+  res->iterations = (int32_t)std::ceil(std::min(it, (double)maxit));
+  res->converged = conv ? 1 : 0;
+  if (nhist) *nhist = nh;
+  return rc;
+}
+
+// ---- CG for m right-hand sides ---------------------------------------------------------------------------------------------------------
+// m independent CGSolver::apply recurrences (the loop of ddm_cg_solve per column).  A column whose defect passed the test is frozen by
+// the device-side mask ctx->mactive: its x, defect, scalars and history stop changing while the other columns go on.  Per iteration
+// the host reads the m squared defects once (one all-reduce of m doubles each for <q, b>, <p, q> and <b, b>; no deferred norm).
+static int cg_multi_step(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int m, bool first, double *X, double *B, double *P, double *Q)
+{
+  double *scal = ctx->mscal;
+  const int64_t n = op->n;
+  DDMCHECK(combined_apply_multi_impl(ctx, prec, m, first ? P : Q, B));                                       // q = M^-1 b (p on the first step)
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, first ? P : Q, B, scal + (first ? 0 : 3 * MULTI_MAX))); // rho = <q, b>
+  if (!first) {
+    hipLaunchKernelGGL(k_cg_beta_multi, dim3(1), dim3(64), 0, ctx->stream, m, (const int32_t *)ctx->mactive, scal); // beta = rho / rholast
+    hipLaunchKernelGGL(k_cg_direction_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, (const double *)scal,
+                       (const double *)Q, P); // p = beta p + q
+  }
+  DDMCHECK(op_apply_multi(ctx, op, m, P, Q));                                           // q = A p
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, P, Q, scal + MULTI_MAX));           // alpha = <p, q>
+  hipLaunchKernelGGL(k_cg_lambda_multi, dim3(1), dim3(64), 0, ctx->stream, m, (const int32_t *)ctx->mactive, scal); // lambda = rholast / alpha
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  for_column_groups(m, [&](int c0, int cb) { // x += lambda p; b -= lambda q; <b, b> partials
+    DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
+                          (const double *)scal, (const uint8_t *)op->owner, (const double *)P, (const double *)Q, X, B, ctx->mpartial);
+  });
+  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + 5 * MULTI_MAX);
+  HIPCHECK(ctx, hipGetLastError());
+  return ctx_allreduce(ctx, scal + 5 * MULTI_MAX, m, "defect norms");
+}
+extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                                  double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0) return fail(ctx, DDM_EINVAL, "ddm_cg_solve_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_cg_solve_multi"));
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int m = nrhs;
+  const int64_t n = op->n;
+  for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
+  DDMCHECK(ctx_multi_scratch(ctx));
+  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // search directions p, q: block scratch of the preconditioner object
+  double *P = prec->mp, *Q = prec->mq;
+  double bb[MULTI_MAX], def0[MULTI_MAX], def[MULTI_MAX];
+  int32_t active[MULTI_MAX];
+  DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B)); // prec.pre(x, b); b -= A x
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, ctx->mscal + 5 * MULTI_MAX));
+  DDMCHECK(ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m));
+  int nactive = 0;
+  for (int c = 0; c < m; ++c) {
+    def0[c] = def[c] = std::sqrt(bb[c]);
+    res[c].def0 = def0[c];
+    if (hist_host) hist_host[c] = def0[c];
+    const Defect0 d = classify_initial_defect(def0[c]);
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN in column %d", c);
+    active[c] = d == Defect0::Go ? 1 : 0;
+    if (!active[c]) res[c].converged = 1;
+    nactive += active[c];
+  }
+  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
+  (void)hipStreamSynchronize(ctx->stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = DDM_OK;
+  for (int i = 1; i <= maxit && nactive > 0 && !rc; ++i) {
+    rc = cg_multi_step(ctx, op, prec, m, i == 1, X, B, P, Q);
+    if (!rc) rc = ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m); // the defects are tested every iteration
+    if (rc) break;
+    bool changed = false;
+    for (int c = 0; c < m; ++c) {
+      if (!active[c]) continue;
+      def[c] = std::sqrt(bb[c]);
+      res[c].iterations = i;
+      if (hist_host) hist_host[(int64_t)i * m + c] = def[c];
+      if (!(def[c] == def[c])) {
+        rc = fail(ctx, DDM_ENUMERIC, "defect is NaN in iteration %d (column %d)", i, c);
+        break;
+      }
+      if (def[c] < def0[c] * reduction || def[c] < 1e-30) {
+        res[c].converged = 1;
+        active[c] = 0;
+        nactive -= 1;
+        changed = true;
+      }
+    }
+    if (!rc && changed && nactive > 0) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
+  }
+  double elapsed = 0.0;
+  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
+  for (int c = 0; c < m; ++c) {
+    res[c].elapsed_s = elapsed;
+    if (def0[c] >= 1e-30) res[c].reduction = def[c] / def0[c];
+  }
+  return rc;
+}
+
+// ---- restarted GMRES for m right-hand sides --------------------------------------------------------
+// Every column is what ddm_gmres_solve computes on it (left preconditioning, modified Gram-Schmidt in the order k = 0..i, its own
+// GmresColumn), while the operator, the preconditioner and the orthogonalisation sweep run once for all columns.  The Krylov basis is
+// min(restart, maxit) + 1 row-major n x m blocks.  Per basis block the sweep is one AXPY over the block with the coefficients in
+// device memory, the block dot (one kernel per column group, k_reduce_final_multi) and one all-reduce of m doubles; with
+// DDM_GMRES_MULTI_FUSED=1 the AXPY and the partial sums of the next dot are one kernel (k_mgs_step_multi: bit-identical, 32 instead
+// of 40 bytes per block entry, but measured slower on MI355X -- DESIGN.md section 9).  The host reads the (i + 2) x m fresh Hessenberg
+// entries once per iteration and nothing else synchronises inside an iteration.
+//
+// Frozen columns: a column that passed its test is masked out (ctx->mactive) of every kernel of this driver; the operator and the
+// preconditioner still run on its (stale) basis entries, whose results nobody reads.
+// the sweep of iteration i: hdev[k * m + c] = h_{k,i} of column c for k <= i, hdev[(i + 1) * m + c] = <w, w>; w orthogonalised in place
+static int gmres_mgs_multi(ddm_ctx *ctx, ddm_op *op, int m, int i, bool fused, const double *V, int64_t vstride, double *W, double *hdev)
+{
+  ScopedTimer t(ctx, "GMRES/orthogonalisation");
+  const int64_t n = op->n;
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  const int32_t *active = ctx->mactive;
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, V, W, hdev)); // h_0 = <v_0, w>
+  for (int k = 0; k <= i; ++k) {
+    const double *vk = V + (int64_t)k * vstride;
+    const double *z = k < i ? V + (int64_t)(k + 1) * vstride : W; // next dot: <v_{k+1}, w>, or <w, w> at the end
+    double *out = hdev + (int64_t)(k + 1) * m;
+    if (!fused) {
+      hipLaunchKernelGGL(k_axpy_negdev_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, active, (const double *)(hdev + (int64_t)k * m), vk, W);
+      DDMCHECK(dot_multi_device(ctx, n, op->owner, m, z, W, out));
+      continue;
+    }
+    for_column_groups(m, [&](int c0, int cb) {
+      DDM_MULTI_CB_DISPATCH(k_mgs_step_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, active,
+                            (const double *)(hdev + (int64_t)k * m), (const uint8_t *)op->owner, vk, z, W, ctx->mpartial);
+    });
+    hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
+    HIPCHECK(ctx, hipGetLastError());
+    DDMCHECK(ctx_allreduce(ctx, out, m, "Gram-Schmidt coefficients"));
+  }
+  return DDM_OK;
+}
+
+extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                                     int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
+    return fail(ctx, DDM_EINVAL, "ddm_gmres_solve_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_gmres_solve_multi"));
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int m = nrhs;
+  const int64_t n = op->n;
+  const int64_t vstride = std::max<int64_t>(n, 1) * m;
+  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis block beyond that
+  { // R + 1 basis blocks and the work block must fit into the free device memory: refuse before anything is allocated
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+    const double need = ((double)R + 2.0) * (double)vstride * sizeof(double);
+    if (need > (double)free_b)
+      return fail(ctx, DDM_ENOTIMPL, "ddm_gmres_solve_multi: the Krylov basis of %d + 1 blocks of %lld x %d doubles and the work block need %.0f bytes, %zu are free",
+                  R, (long long)n, m, need, free_b);
+  }
+  const bool fused = [] { // read once per solve; the unfused composition is the default (it measured faster)
+    const char *e = std::getenv("DDM_GMRES_MULTI_FUSED");
+    return e && e[0] == '1';
+  }();
+  for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
+  DDMCHECK(ctx_multi_scratch(ctx));
+  dbuf<double> Vb, Wb, hdev, ydev;
+  dbuf<int32_t> cdev; // [0, m): Hessenberg columns per column in the cycle, [m, 2m): keep W (still running)
+  HIPCHECK(ctx, Vb.alloc(vstride * (R + 1)));
+  HIPCHECK(ctx, Wb.alloc(vstride));
+  HIPCHECK(ctx, hdev.alloc((int64_t)(R + 2) * m));
+  HIPCHECK(ctx, ydev.alloc((int64_t)R * m));
+  HIPCHECK(ctx, cdev.alloc(2 * m));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
+  double *V = Vb, *W = Wb;
+  auto v = [&](int k) { return V + (int64_t)k * vstride; };
+  std::vector<GmresColumn> col(m);
+  for (auto &q : col) q.init(R);
+  std::vector<double> hcol((size_t)(R + 2) * m), yhost((size_t)R * m), ycol(R);
+  int32_t active[MULTI_MAX], cflags[2 * MULTI_MAX];
+  MultiCoef coef;
+  const int GE = grid_for(n * m);
+
+  // b -= A x; v0 = M^-1 b; def0 = |v0| per column
+  DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B));
+  DDMCHECK(combined_apply_multi_impl(ctx, prec, m, v(0), B));
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, v(0), v(0), hdev));
+  DDMCHECK(ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m));
+  int nactive = 0;
+  for (int c = 0; c < m; ++c) {
+    col[c].norm = col[c].def0 = std::sqrt(hcol[c]);
+    res[c].def0 = col[c].def0;
+    if (hist_host) hist_host[c] = col[c].def0;
+    const Defect0 d = classify_initial_defect(col[c].def0);
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: initial defect is NaN in column %d", c);
+    active[c] = d == Defect0::Go ? 1 : 0;
+    if (!active[c]) res[c].converged = 1;
+    nactive += active[c];
+  }
+  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = DDM_OK, j = 0;
+  while (j < maxit && nactive > 0 && !rc) {
+    for (int c = 0; c < m; ++c) {
+      GmresColumn &q = col[c];
+      q.cnt = 0;
+      coef.a[c] = active[c] ? 1.0 / q.norm : 0.0;
+      if (active[c]) q.start_cycle();
+    }
+    hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)v(0), v(0));
+    int i = 0;
+    for (; i < R && j < maxit && nactive > 0; ++i, ++j) {
+      rc = op_apply_multi(ctx, op, m, v(i), v(i + 1));                      // v[i+1] = A v[i] (temporary)
+      if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, W, v(i + 1));   // w = M^-1 A v[i]
+      if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, fused, V, vstride, W, hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2) * m); // the one read-back of the iteration
+      if (rc) break;
+      for (int c = 0; c < m && !rc; ++c) {
+        coef.a[c] = 0.0;
+        if (!active[c]) continue;
+        const double wnorm = col[c].take_column(i, hcol.data() + c, (size_t)m);
+        if (std::fabs(wnorm) < 1e-80)
+          rc = fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: breakdown in GMRes - |w| == 0.0 after %d iterations (column %d)", j, c);
+        coef.a[c] = 1.0 / wnorm;
+      }
+      if (rc) break;
+      hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)W, v(i + 1));
+      bool changed = false;
+      for (int c = 0; c < m; ++c) {
+        if (!active[c]) continue;
+        GmresColumn &q = col[c];
+        q.rotate(i);
+        res[c].iterations = j + 1;
+        if (hist_host) hist_host[(int64_t)(j + 1) * m + c] = q.norm;
+        if (!(q.norm == q.norm)) {
+          rc = fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: defect is NaN in iteration %d (column %d)", j + 1, c);
+          break;
+        }
+        if (q.norm < q.def0 * reduction || q.norm < 1e-30) {
+          res[c].converged = 1;
+          active[c] = 0;
+          nactive -= 1;
+          changed = true;
+        }
+      }
+      if (rc) break;
+      if (changed) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
+      if (rc) break;
+    }
+    if (rc) break;
+    // update(w, i, H, s, v) per column: solve its triangular system of cnt_c unknowns; W_c = sum_k y_k v[k]; X_c += W_c
+    std::fill(yhost.begin(), yhost.end(), 0.0);
+    for (int c = 0; c < m; ++c) {
+      GmresColumn &q = col[c];
+      cflags[c] = q.cnt;
+      cflags[m + c] = active[c];
+      q.back_substitute(ycol.data());
+      for (int a = 0; a < q.cnt; ++a) yhost[(size_t)a * m + c] = ycol[a];
+    }
+    rc = ddm_memcpy_h2d(ctx, ydev, yhost.data(), sizeof(double) * (size_t)i * m);
+    if (!rc) rc = ddm_memcpy_h2d(ctx, cdev, cflags, sizeof(int32_t) * (size_t)(2 * m));
+    if (rc) break;
+    {
+      ScopedTimer t(ctx, "GMRES/update");
+      hipLaunchKernelGGL(k_gmres_update_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)cdev, (const int32_t *)(cdev + m), (const double *)ydev,
+                         (const double *)V, vstride, W, X);
+    }
+    if (nactive > 0 && j < maxit) { // restart: b -= A w (w = 0 in the columns that are done); v0 = M^-1 b
+      rc = op_applyscaleadd_multi(ctx, op, m, -1.0, W, B);
+      if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, v(0), B);
+      if (!rc) rc = dot_multi_device(ctx, n, op->owner, m, v(0), v(0), hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m);
+      for (int c = 0; c < m && !rc; ++c)
+        if (active[c]) col[c].norm = std::sqrt(hcol[c]);
+    }
+  }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_gmres_solve_multi");
+  double elapsed = 0.0;
+  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
+  for (int c = 0; c < m; ++c) {
+    res[c].elapsed_s = elapsed;
+    if (col[c].def0 >= 1e-30) res[c].reduction = col[c].norm / col[c].def0;
+  }
+  return rc;
+}

@@ -1,4 +1,4 @@
-// The local solver of the Schwarz level (included by ddm_hip.hip; C ABI: the ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*
+// The local solver of the Schwarz level (included by ddm_hip.hip after context.hpp and csr.hpp; C ABI: the ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*
 // functions of include/ddm_hip.h): ILU(0) and sparse direct factors and their triangular-solve engines.
 //
 // A factor (struct ddm_ilu0) holds what all engines share and one part per engine it has: LevelEngine (one launch per level; every

@@ -1,4 +1,4 @@
-// Device kernels of the multi-right-hand-side path (ddm_*_multi, csrc/multi_rhs.hpp): m independent columns stored as a row-major
+// Device kernels of the multi-right-hand-side path (ddm_*_multi: the block applies of csrc/halo.hpp and csrc/preconditioners.hpp, the block drivers of csrc/krylov.hpp): m independent columns stored as a row-major
 // n x m block (entry (i, c) at i * m + c, the layout of ddm_csr_mm and ddm_ilu0_solve_multi), 1 <= m <= MULTI_MAX.
 // Element-wise kernels run one thread per block entry (consecutive threads = consecutive addresses).  Reductions keep the tree of
 // the single-vector kernels where that costs nothing: the owner-masked dots and the fused CG update use the grid, the thread-to-row
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, i
   }
 }
 
-// ---- restarted GMRES vector work (csrc/multi_gmres.hpp) -----------------------------------------------------------------------------
+// ---- restarted GMRES vector work (ddm_gmres_solve_multi, csrc/krylov.hpp) -----------------------------------------------------------------------------
 // per-column host scalars of one launch, passed by value (no upload, no synchronisation)
 struct MultiCoef {
   double a[MULTI_MAX];

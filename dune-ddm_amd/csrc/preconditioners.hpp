@@ -1,0 +1,678 @@
+// The objects a Krylov driver applies: the owner-masked dot products, NonOverlappingOperator (ddm_op), SchwarzPreconditioner
+// (ddm_schwarz), GalerkinPreconditioner (ddm_galerkin, with ddm_galerkin_products) and CombinedPreconditioner (ddm_combined).  Each
+// object's single-vector apply is followed by its apply to m columns (the ddm_*_multi entry points).  Block vectors are row-major
+// n x m (entry (i, c) at i * m + c), 1 <= m <= MULTI_MAX; every object keeps its own block scratch, allocated on first use for the
+// widest m seen so far.  The single-vector applies are NOT the block applies at m = 1: they use the fused epilogue of the pipe engine
+// and the all-reduce a scalar can ride on (coarse_allreduce); the headline number depends on them.  Needs halo.hpp, local_solver.hpp.
+#pragma once
+
+// ---- reductions --------------------------------------------------------------------------------
+// result (device scalar) = sum over ranks of sum_i [mask_i] x_i y_i
+static int dot_device(ddm_ctx *ctx, int64_t n, const uint8_t *mask, const double *x, const double *y, double *result_dev)
+{
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  if (mask)
+    hipLaunchKernelGGL(k_dot_partial<true>, dim3(nb), dim3(WG), 0, ctx->stream, n, mask, x, y, ctx->partial);
+  else
+    hipLaunchKernelGGL(k_dot_partial<false>, dim3(nb), dim3(WG), 0, ctx->stream, n, mask, x, y, ctx->partial);
+  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, result_dev);
+  HIPCHECK(ctx, hipGetLastError());
+  DDMCHECK(ctx_allreduce(ctx, result_dev, 1, "scalar product"));
+  return DDM_OK;
+}
+
+// ... and for m columns: m owner-masked dots, one kernel per group of up to 8 columns, one all-reduce of m doubles
+template <class Launch>
+static void for_column_groups(int m, Launch &&launch)
+{
+  for (int c0 = 0; c0 < m;) {
+    const int cb = m - c0 >= 8 ? 8 : m - c0 >= 4 ? 4 : m - c0 >= 2 ? 2 : 1;
+    launch(c0, cb);
+    c0 += cb;
+  }
+}
+#define DDM_MULTI_CB_DISPATCH(KERNEL, MASKED, cb, ...)                                                                 \
+  do {                                                                                                                 \
+    if (MASKED) {                                                                                                      \
+      if (cb == 8) hipLaunchKernelGGL((KERNEL<8, true>), __VA_ARGS__);                                                 \
+      else if (cb == 4) hipLaunchKernelGGL((KERNEL<4, true>), __VA_ARGS__);                                            \
+      else if (cb == 2) hipLaunchKernelGGL((KERNEL<2, true>), __VA_ARGS__);                                            \
+      else hipLaunchKernelGGL((KERNEL<1, true>), __VA_ARGS__);                                                         \
+    } else {                                                                                                           \
+      if (cb == 8) hipLaunchKernelGGL((KERNEL<8, false>), __VA_ARGS__);                                                \
+      else if (cb == 4) hipLaunchKernelGGL((KERNEL<4, false>), __VA_ARGS__);                                           \
+      else if (cb == 2) hipLaunchKernelGGL((KERNEL<2, false>), __VA_ARGS__);                                           \
+      else hipLaunchKernelGGL((KERNEL<1, false>), __VA_ARGS__);                                                        \
+    }                                                                                                                  \
+  } while (0)
+
+// out (m device doubles) = sum over ranks of sum_i [mask_i] x_ic y_ic; per column bit-identical to dot_device
+static int dot_multi_device(ddm_ctx *ctx, int64_t n, const uint8_t *mask, int m, const double *X, const double *Y, double *out)
+{
+  DDMCHECK(ctx_multi_scratch(ctx));
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  double *partial = ctx->mpartial;
+  for_column_groups(m, [&](int c0, int cb) {
+    DDM_MULTI_CB_DISPATCH(k_dot_partial_multi, mask != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, mask, X, Y, partial);
+  });
+  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)partial, out);
+  HIPCHECK(ctx, hipGetLastError());
+  return ctx_allreduce(ctx, out, m, "scalar products");
+}
+
+// ---- NonOverlappingOperator --------------------------------------------------------------------
+struct ddm_op {
+  const ddm_csr *A = nullptr;
+  ddm_halo *halo = nullptr;
+  dbuf<uint8_t> owner;
+  int64_t n = 0;
+  dbuf<double> tmp;
+  dbuf<double> mtmp; // multi-RHS block (mcols columns)
+  int mcols = 0;
+};
+extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out)
+{
+  if (!ctx || !A || !out || !owner_mask_host) return fail(ctx, DDM_EINVAL, "ddm_op_create: bad arguments");
+  if (A->nrows != A->ncols) return fail(ctx, DDM_EINVAL, "operator matrix must be square");
+  if (novlp_add && novlp_add->mode != 1) return fail(ctx, DDM_EINVAL, "operator halo must be an 'add' halo");
+  auto op = std::make_unique<ddm_op>();
+  op->A = A;
+  op->halo = novlp_add;
+  op->n = A->nrows;
+  int rc = upload(ctx, owner_mask_host, op->n, op->owner);
+  if (!rc && op->tmp.alloc(op->n) != hipSuccess) rc = DDM_EHIP;
+  if (rc) return fail(ctx, rc, "ddm_op_create: allocation failed");
+  *out = op.release();
+  return DDM_OK;
+}
+extern "C" void ddm_op_destroy(ddm_op *op) { delete op; }
+extern "C" int ddm_op_apply(ddm_ctx *ctx, ddm_op *op, const double *x, double *y)
+{
+  ScopedTimer t(ctx, "Operator/apply");
+  DDMCHECK(ddm_csr_mv(ctx, op->A, x, y));           // A->mv(x, y)
+  return ddm_halo_exchange(ctx, op->halo, y);       // comm->addOwnerCopyToOwnerCopy(y, y)
+}
+extern "C" int ddm_op_applyscaleadd(ddm_ctx *ctx, ddm_op *op, double alpha, const double *x, double *y)
+{
+  ScopedTimer t(ctx, "Operator/applyscaleadd");
+  // y1 = y; y = 0; usmv; halo; y += y1   (only alpha*A*x is communicated, y is already consistent)
+  DDMCHECK(ddm_csr_mv(ctx, op->A, x, op->tmp));
+  DDMCHECK(ddm_halo_exchange(ctx, op->halo, op->tmp));
+  hipLaunchKernelGGL(k_axpy, dim3(grid_for(op->n)), dim3(WG), 0, ctx->stream, op->n, alpha, op->tmp, y);
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+extern "C" int ddm_dot(ddm_ctx *ctx, ddm_op *op, const double *x, const double *y, double *result_host)
+{
+  DDMCHECK(dot_device(ctx, op->n, op->owner, x, y, ctx->scal + 8));
+  return ddm_memcpy_d2h(ctx, result_host, ctx->scal + 8, sizeof(double));
+}
+extern "C" int ddm_norm(ddm_ctx *ctx, ddm_op *op, const double *x, double *result_host)
+{
+  DDMCHECK(ddm_dot(ctx, op, x, x, result_host));
+  *result_host = std::sqrt(*result_host);
+  return DDM_OK;
+}
+// ... and for m columns
+static int op_apply_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *X, double *Y)
+{
+  ScopedTimer t(ctx, "Operator/apply");
+  DDMCHECK(csr_mm_ld(ctx, op->A, m, X, m, Y, m)); // A->mv(x, y) for every column
+  return halo_exchange_multi(ctx, op->halo, m, Y); // comm->addOwnerCopyToOwnerCopy(y, y)
+}
+static int op_applyscaleadd_multi(ddm_ctx *ctx, ddm_op *op, int m, double alpha, const double *X, double *Y)
+{
+  ScopedTimer t(ctx, "Operator/applyscaleadd");
+  HIPCHECK(ctx, reserve_cols(op->mcols, m, op->mtmp, op->n));
+  DDMCHECK(csr_mm_ld(ctx, op->A, m, X, m, op->mtmp, m));
+  DDMCHECK(halo_exchange_multi(ctx, op->halo, m, op->mtmp));
+  hipLaunchKernelGGL(k_axpy, dim3(grid_for(op->n * m)), dim3(WG), 0, ctx->stream, op->n * m, alpha, (const double *)op->mtmp, Y); // element-wise: y += alpha t
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+extern "C" int ddm_op_apply_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X, double *Y)
+{
+  if (!ctx || !op || !X || !Y || X == Y) return fail(ctx, DDM_EINVAL, "ddm_op_apply_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_op_apply_multi"));
+  return op_apply_multi(ctx, op, nrhs, X, Y);
+}
+extern "C" int ddm_op_applyscaleadd_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, double alpha, const double *X, double *Y)
+{
+  if (!ctx || !op || !X || !Y || X == Y) return fail(ctx, DDM_EINVAL, "ddm_op_applyscaleadd_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_op_applyscaleadd_multi"));
+  return op_applyscaleadd_multi(ctx, op, nrhs, alpha, X, Y);
+}
+extern "C" int ddm_dot_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X, const double *Y, double *result_host)
+{
+  if (!ctx || !op || !X || !Y || !result_host) return fail(ctx, DDM_EINVAL, "ddm_dot_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_dot_multi"));
+  DDMCHECK(ctx_multi_scratch(ctx));
+  double *out = ctx->mscal + 6 * MULTI_MAX;
+  DDMCHECK(dot_multi_device(ctx, op->n, op->owner, nrhs, X, Y, out));
+  return ddm_memcpy_d2h(ctx, result_host, out, sizeof(double) * (size_t)nrhs);
+}
+
+// ---- SchwarzPreconditioner ---------------------------------------------------------------------
+struct ddm_schwarz {
+  int64_t n = 0, n_novlp = 0;
+  int type = 1;
+  ddm_ilu0 *solver = nullptr; // owned
+  dbuf<int32_t> ext_map;
+  dbuf<double> pou;
+  dbuf<double> d_ovlp, x_ovlp;
+  ddm_halo *copy = nullptr, *add = nullptr;
+  dbuf<double> md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
+  int mcols = 0;
+  ~ddm_schwarz() { ddm_ilu0_destroy(solver); }
+};
+extern "C" int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
+                                  const int32_t *ext_map_host, const double *pou_host, int type, ddm_halo *ovlp_copy,
+                                  ddm_halo *ovlp_add, ddm_schwarz **out)
+{
+  return ddm_schwarz_create_ex(ctx, A_dir, nblocks, block_ptr, n_novlp, ext_map_host, pou_host, type, "ilu0", ovlp_copy, ovlp_add, out);
+}
+// subdomain_solver: the `type` key of the [schwarz.subdomain_solver] sub-tree (schwarz.hh:85-92): "ilu0" (dune-istl's SeqILU,
+// n = 0) or one of "cholmod" / "ldl" / "spqr"-less synonyms "direct", "cholesky" for the sparse direct solver of this library
+// (SPD matrices; "umfpack" is accepted for symmetric positive definite input only).
+extern "C" int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
+                                     const int32_t *ext_map_host, const double *pou_host, int type, const char *subdomain_solver,
+                                     ddm_halo *ovlp_copy, ddm_halo *ovlp_add, ddm_schwarz **out)
+{
+  if (!ctx || !A_dir || !out || !ext_map_host) return fail(ctx, DDM_EINVAL, "ddm_schwarz_create: bad arguments");
+  const std::string st = subdomain_solver ? subdomain_solver : "ilu0";
+  const bool direct = st == "cholmod" || st == "direct" || st == "cholesky" || st == "umfpack" || st == "ldl";
+  if (!direct && st != "ilu0" && st != "ilu") return fail(ctx, DDM_ENOTIMPL, "Unknown subdomain solver type '%s'", st.c_str()); // solver factory lookup (:85-92)
+  bool general = st == "umfpack";
+  if (st == "direct") { // pick the factorisation by looking at the values: symmetric -> Cholesky
+    general = false;
+    const int64_t nn = A_dir->nrows;
+    for (int64_t i = 0; i < nn && !general; ++i)
+      for (int64_t k = A_dir->h_rp[i]; k < A_dir->h_rp[i + 1] && !general; ++k) {
+        const int64_t j = A_dir->h_ci[k];
+        if (j <= i) continue;
+        const auto b = A_dir->h_ci.begin() + A_dir->h_rp[j], e = A_dir->h_ci.begin() + A_dir->h_rp[j + 1];
+        const auto it = std::lower_bound(b, e, (int32_t)i);
+        const double vt = (it != e && *it == i) ? A_dir->h_va[(size_t)(it - A_dir->h_ci.begin())] : 0.0;
+        if (std::fabs(vt - A_dir->h_va[k]) > 1e-12 * (std::fabs(vt) + std::fabs(A_dir->h_va[k]))) general = true;
+      }
+  }
+  if (type != 0 && type != 1) return fail(ctx, DDM_ENOTIMPL, "Unknown Schwarz type %d", type); // schwarz.hh:83
+  if (ovlp_copy && ovlp_copy->mode != 0) return fail(ctx, DDM_EINVAL, "ovlp_copy must be a 'copy' halo");
+  if (ovlp_add && ovlp_add->mode != 1) return fail(ctx, DDM_EINVAL, "ovlp_add must be an 'add' halo");
+  const int64_t n = A_dir->nrows;
+  for (int64_t i = 0; i < n; ++i)
+    if (ext_map_host[i] >= n_novlp) return fail(ctx, DDM_EINVAL, "ext_map entry out of range"); // size checks, schwarz.hh:186-193
+  auto S = std::make_unique<ddm_schwarz>();
+  S->n = n;
+  S->n_novlp = n_novlp;
+  S->type = type;
+  S->copy = ovlp_copy;
+  S->add = ovlp_add;
+  DDMCHECK(direct ? ddm_direct_create(ctx, A_dir, nblocks, block_ptr, general ? 1 : 0, 0.0, &S->solver)
+                  : ddm_ilu0_create(ctx, A_dir, nblocks, block_ptr, &S->solver)); // factorisation happens in the ctor (:92)
+  DDMCHECK(upload(ctx, ext_map_host, n, S->ext_map));
+  if (pou_host) DDMCHECK(upload(ctx, pou_host, n, S->pou));
+  if (S->d_ovlp.alloc(n) != hipSuccess || S->x_ovlp.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "alloc");
+  *out = S.release();
+  return DDM_OK;
+}
+extern "C" void ddm_schwarz_destroy(ddm_schwarz *S) { delete S; }
+extern "C" int64_t ddm_schwarz_num_levels(const ddm_schwarz *S, int upper) { return ddm_ilu0_num_levels(S->solver, upper); }
+extern "C" int64_t ddm_schwarz_factor_nnz(const ddm_schwarz *S) { return (S && S->solver) ? S->solver->nnz : 0; } // stored entries of L + U (+ diagonal)
+extern "C" int ddm_schwarz_engine(const ddm_schwarz *S) { return S ? ddm_ilu0_engine(S->solver) : -1; }
+// Synchronous.  DDM_OK, or DDM_ENUMERIC when a single-launch local solve gave up waiting (its results are invalid: the
+// GPU is shared with another process, or the grid was not co-resident) -- the reference's apply has no error return
+// (schwarz.hh:131 discards the InverseOperatorResult), so the adaptors poll this in post() and the Krylov drivers at the end.
+extern "C" ddm_ilu0 *ddm_schwarz_local_solver(ddm_schwarz *S) { return S ? S->solver : nullptr; } // borrowed (owned by S)
+extern "C" int ddm_schwarz_status(ddm_ctx *ctx, const ddm_schwarz *S)
+{
+  if (!S) return fail(ctx, DDM_EINVAL, "ddm_schwarz_status: bad arguments");
+  int st = 0;
+  DDMCHECK(ddm_ilu0_status(ctx, S->solver, &st));
+  if (st) return fail(ctx, DDM_ENUMERIC, "local triangular solve timed out waiting for a dependency (code %d): results are invalid", st);
+  return DDM_OK;
+}
+// Every apply and every block driver starts with this (S may be null: nothing to check).
+static int local_status_check(ddm_ctx *ctx, const ddm_schwarz *S)
+{
+  if (const unsigned e = S ? ilu0_peek_status(S->solver) : 0u) // fail fast: an earlier local solve gave up (no stream synchronisation here)
+    return fail(ctx, DDM_ENUMERIC, "an earlier local triangular solve timed out waiting for a dependency (code %u): results since then are invalid", e);
+  return DDM_OK;
+}
+// x (= or +=) R~^T [D] A_dir^-1 R~ d
+static int schwarz_apply_impl(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d, bool acc)
+{
+  DDMCHECK(local_status_check(ctx, S));
+  {
+    ScopedTimer t(ctx, "Schwarz/get defect");
+    hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp); // :121-122
+    DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));                                                          // :125
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/local solve");
+    DDMCHECK(ddm_ilu0_solve(ctx, S->solver, S->d_ovlp, S->x_ovlp)); // :131-133
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/add solution");
+    if (S->type == 1 && S->pou)
+      hipLaunchKernelGGL(k_scale, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->pou, S->x_ovlp); // :139-141
+    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));                                                     // :138/:142
+    if (acc)
+      hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
+    else
+      hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x); // :146
+    HIPCHECK(ctx, hipGetLastError());
+  }
+  return DDM_OK;
+}
+extern "C" int ddm_schwarz_apply(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d)
+{
+  ScopedTimer t(ctx, "Schwarz/apply");
+  return schwarz_apply_impl(ctx, S, x, d, false);
+}
+// ... and for m columns
+static int schwarz_multi_scratch(ddm_ctx *ctx, ddm_schwarz *S, int m)
+{
+  HIPCHECK(ctx, reserve_cols<double>(S->mcols, m, {{S->md_ovlp, S->n}, {S->mx_ovlp, S->n}}));
+  return DDM_OK;
+}
+// X (= or +=) R~^T [D] A_dir^-1 R~ D for m columns (schwarz.hh:115-149)
+static int schwarz_apply_multi_impl(ddm_ctx *ctx, ddm_schwarz *S, int m, double *X, const double *D, bool acc)
+{
+  DDMCHECK(local_status_check(ctx, S));
+  DDMCHECK(schwarz_multi_scratch(ctx, S, m));
+  {
+    ScopedTimer t(ctx, "Schwarz/get defect");
+    hipLaunchKernelGGL(k_extend_multi, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, S->ext_map, D, S->md_ovlp); // :121-122
+    DDMCHECK(halo_exchange_multi(ctx, S->copy, m, S->md_ovlp));                                                                // :125
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/local solve");
+    DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m)); // :131-133 (level engine / direct multi-RHS solve)
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/add solution");
+    if (S->type == 1 && S->pou)
+      hipLaunchKernelGGL(k_scale_add_multi, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, (const double *)S->pou, (const double *)nullptr, S->mx_ovlp); // :139-141
+    DDMCHECK(halo_exchange_multi(ctx, S->add, m, S->mx_ovlp)); // :138/:142
+    if (acc) hipLaunchKernelGGL(k_restrict_multi<true>, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, S->ext_map, (const double *)S->mx_ovlp, X);
+    else hipLaunchKernelGGL(k_restrict_multi<false>, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, S->ext_map, (const double *)S->mx_ovlp, X); // :146
+    HIPCHECK(ctx, hipGetLastError());
+  }
+  return DDM_OK;
+}
+extern "C" int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, double *X, const double *D)
+{
+  if (!ctx || !S || !X || !D || X == D) return fail(ctx, DDM_EINVAL, "ddm_schwarz_apply_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_schwarz_apply_multi"));
+  ScopedTimer t(ctx, "Schwarz/apply");
+  return schwarz_apply_multi_impl(ctx, S, nrhs, X, D, false);
+}
+// diagnostic: overwrite the status word of a local solver (0 clears it) -- lets a caller exercise the fail-fast path of the applies
+extern "C" int ddm_ilu0_set_status(ddm_ilu0 *F, int status)
+{
+  if (!F || !F->err) return DDM_EINVAL;
+  *(volatile unsigned *)F->err = (unsigned)status;
+  return DDM_OK;
+}
+
+// ---- GalerkinPreconditioner --------------------------------------------------------------------
+struct ddm_galerkin {
+  int64_t n = 0, n_novlp = 0, nsub = 0, kmax = 0, K = 0, ld = 0;
+  dbuf<int32_t> ext_map;
+  dbuf<double> basis;       // kmax x ld
+  dbuf<int64_t> coarse_index;
+  dbuf<double> a0inv;
+  dbuf<RowChunk> chunks;
+  dbuf<int32_t> sub_chunk_ptr;
+  int nchunk = 0;
+  dbuf<double> partial, d0, x0;
+  dbuf<double> d_ovlp, x_ovlp;
+  ddm_halo *copy = nullptr, *add = nullptr;
+  dbuf<double> mpartial, md0, mx0, md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
+  int mcols = 0;
+};
+static constexpr int64_t COARSE_CHUNK_ROWS = 8192;
+
+extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, const int32_t *ext_map_host, int64_t nsub,
+                                   const int64_t *sub_ptr, int64_t kmax, const double *basis_host, const int64_t *coarse_index,
+                                   int64_t K, const double *a0inv_host, ddm_halo *ovlp_copy, ddm_halo *ovlp_add,
+                                   ddm_galerkin **out)
+{
+  if (!ctx || !out || !ext_map_host || !sub_ptr || !basis_host || !coarse_index || !a0inv_host)
+    return fail(ctx, DDM_EINVAL, "ddm_galerkin_create: bad arguments");
+  if (kmax < 1) return fail(ctx, DDM_EINVAL, "Must at least pass one template vector"); // galerkin_preconditioner.hh:129
+  if (kmax > COARSE_KMAX) return fail(ctx, DDM_ENOTIMPL, "more than %d basis vectors per subdomain are not supported", COARSE_KMAX);
+  if (sub_ptr[0] != 0 || sub_ptr[nsub] != n) return fail(ctx, DDM_EINVAL, "Template vectors must match size of matrix"); // :131
+  for (int64_t t = 0; t < nsub * kmax; ++t)
+    if (coarse_index[t] >= K) return fail(ctx, DDM_EINVAL, "coarse_index out of range");
+  auto G = std::make_unique<ddm_galerkin>();
+  G->n = n;
+  G->n_novlp = n_novlp;
+  G->nsub = nsub;
+  G->kmax = kmax;
+  G->K = K;
+  G->ld = (n + 63) / 64 * 64;
+  G->copy = ovlp_copy;
+  G->add = ovlp_add;
+  std::vector<RowChunk> chunks;
+  std::vector<int32_t> scp(nsub + 1, 0);
+  for (int64_t s = 0; s < nsub; ++s) {
+    for (int64_t r = sub_ptr[s]; r < sub_ptr[s + 1]; r += COARSE_CHUNK_ROWS)
+      chunks.push_back(RowChunk{r, std::min(r + COARSE_CHUNK_ROWS, sub_ptr[s + 1]), (int32_t)s, 0});
+    scp[s + 1] = (int32_t)chunks.size();
+  }
+  G->nchunk = (int)chunks.size();
+  DDMCHECK(upload(ctx, ext_map_host, n, G->ext_map));
+  DDMCHECK(upload(ctx, coarse_index, nsub * kmax, G->coarse_index));
+  DDMCHECK(upload(ctx, a0inv_host, K * K, G->a0inv));
+  DDMCHECK(upload(ctx, chunks.data(), (int64_t)chunks.size(), G->chunks));
+  DDMCHECK(upload(ctx, scp.data(), nsub + 1, G->sub_chunk_ptr));
+  if (G->basis.alloc(kmax * G->ld) != hipSuccess || G->partial.alloc((int64_t)G->nchunk * kmax) != hipSuccess ||
+      G->d0.alloc(K + 1) != hipSuccess || // (+ 1: a scalar may ride on the all-reduce, coarse_allreduce)
+      G->x0.alloc(K) != hipSuccess || G->d_ovlp.alloc(n) != hipSuccess || G->x_ovlp.alloc(n) != hipSuccess)
+    return fail(ctx, DDM_EHIP, "galerkin: allocation failed");
+  if (hipMemset(G->basis, 0, sizeof(double) * (size_t)(kmax * G->ld)) != hipSuccess) return DDM_EHIP;
+  if (hipMemcpy2D(G->basis, sizeof(double) * (size_t)G->ld, basis_host, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n,
+                  (size_t)kmax, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ctx, DDM_EHIP, "galerkin: basis upload failed");
+  *out = G.release();
+  return DDM_OK;
+}
+extern "C" void ddm_galerkin_destroy(ddm_galerkin *G) { delete G; }
+// restrict -> all-reduce (a scalar waiting in ctx->piggy rides along) -> A0^-1 d0 -> prolong into G->x_ovlp, on the context's current
+// stream.  `grid`: workgroups of the two passes over the basis (G->nchunk, or fewer when the chain runs beside the local solve).
+// Not timed here: the callers' "GalerkinPrec/apply" scopes differ.
+static int coarse_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *dov, int grid)
+{
+  hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(grid), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk); // :165-167
+  hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, ctx->stream, (int)G->nsub, (int)G->kmax, G->sub_chunk_ptr, G->partial, G->coarse_index, G->K, G->d0);
+  HIPCHECK(ctx, hipGetLastError());
+  DDMCHECK(coarse_allreduce(ctx, G->d0, G->K)); // replaces MPI_Gatherv (:170-171): every rank obtains the full coarse defect
+  hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((G->K + 3) / 4)), dim3(WG), 0, ctx->stream, G->K, G->a0inv, G->d0, G->x0); // :174-179 (replicated)
+  hipLaunchKernelGGL(k_coarse_prolong, dim3(grid), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk); // :186-188
+  return DDM_OK;
+}
+// d_ovlp_ready: the overlapping defect (extended + owner values copied to all holders) if the caller already has it -- in the
+// additive combination both levels start from the same defect (schwarz.hh:121-125 and galerkin_preconditioner.hh:159-162)
+static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d, bool acc, const double *d_ovlp_ready = nullptr)
+{
+  ScopedTimer t(ctx, "GalerkinPrec/apply");
+  const double *dov = d_ovlp_ready;
+  if (!dov) {
+    hipLaunchKernelGGL(k_extend, dim3(grid_for(G->n)), dim3(WG), 0, ctx->stream, G->n, G->ext_map, d, G->d_ovlp); // :159
+    DDMCHECK(ddm_halo_exchange(ctx, G->copy, G->d_ovlp));                                                         // :162
+    dov = G->d_ovlp;
+  }
+  DDMCHECK(coarse_chain(ctx, G, dov, G->nchunk));
+  DDMCHECK(ddm_halo_exchange(ctx, G->add, G->x_ovlp)); // :190
+  if (acc)
+    hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(G->n)), dim3(WG), 0, ctx->stream, G->n, G->ext_map, G->x_ovlp, (const double *)nullptr, x);
+  else
+    hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(G->n)), dim3(WG), 0, ctx->stream, G->n, G->ext_map, G->x_ovlp, (const double *)nullptr, x); // :193
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+extern "C" int ddm_galerkin_apply(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d)
+{
+  return galerkin_apply_impl(ctx, G, x, d, false);
+}
+// ... and for m columns
+static int galerkin_multi_scratch(ddm_ctx *ctx, ddm_galerkin *G, int m)
+{
+  HIPCHECK(ctx, reserve_cols<double>(G->mcols, m, {{G->mpartial, (int64_t)G->nchunk * G->kmax}, {G->md0, G->K}, {G->mx0, G->K}, {G->md_ovlp, G->n}, {G->mx_ovlp, G->n}}));
+  return DDM_OK;
+}
+// restrict (one pass over the basis for all columns) -> one all-reduce of K x m doubles -> A0^-1 D0 -> prolong into G->mx_ovlp
+static int coarse_chain_multi(ddm_ctx *ctx, ddm_galerkin *G, int m, const double *dov)
+{
+  ScopedTimer t(ctx, "GalerkinPrec/apply");
+  hipLaunchKernelGGL(k_coarse_restrict_partial_multi, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, (const double *)G->basis, m, dov,
+                     (const RowChunk *)G->chunks, G->mpartial, G->nchunk); // :165-167
+  hipLaunchKernelGGL(k_coarse_restrict_final_multi, dim3(1), dim3(WG), 0, ctx->stream, (int)G->nsub, (int)G->kmax, m, (const int32_t *)G->sub_chunk_ptr,
+                     (const double *)G->mpartial, (const int64_t *)G->coarse_index, G->K, G->md0);
+  HIPCHECK(ctx, hipGetLastError());
+  DDMCHECK(ctx_allreduce(ctx, G->md0, G->K * m, "coarse defect block")); // :170-171 (replicated coarse problem)
+  if (G->K > 0)
+    hipLaunchKernelGGL(k_dense_mm, dim3((unsigned)((G->K * m + WG - 1) / WG)), dim3(WG), 0, ctx->stream, G->K, m, (const double *)G->a0inv, (const double *)G->md0, G->mx0); // :174-179
+  hipLaunchKernelGGL(k_coarse_prolong_multi, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, (const double *)G->basis, m, (const double *)G->mx0,
+                     (const int64_t *)G->coarse_index, (const RowChunk *)G->chunks, G->mx_ovlp, G->nchunk); // :186-188
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+static int galerkin_apply_multi_impl(ddm_ctx *ctx, ddm_galerkin *G, int m, double *X, const double *D, bool acc, const double *dov_ready = nullptr)
+{
+  DDMCHECK(galerkin_multi_scratch(ctx, G, m));
+  const double *dov = dov_ready;
+  if (!dov) {
+    hipLaunchKernelGGL(k_extend_multi, dim3(grid_for(G->n * m)), dim3(WG), 0, ctx->stream, G->n, m, G->ext_map, D, G->md_ovlp); // :159
+    DDMCHECK(halo_exchange_multi(ctx, G->copy, m, G->md_ovlp));                                                                // :162
+    dov = G->md_ovlp;
+  }
+  DDMCHECK(coarse_chain_multi(ctx, G, m, dov));
+  DDMCHECK(halo_exchange_multi(ctx, G->add, m, G->mx_ovlp)); // :190
+  if (acc) hipLaunchKernelGGL(k_restrict_multi<true>, dim3(grid_for(G->n * m)), dim3(WG), 0, ctx->stream, G->n, m, G->ext_map, (const double *)G->mx_ovlp, X);
+  else hipLaunchKernelGGL(k_restrict_multi<false>, dim3(grid_for(G->n * m)), dim3(WG), 0, ctx->stream, G->n, m, G->ext_map, (const double *)G->mx_ovlp, X); // :193
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+extern "C" int ddm_galerkin_apply_multi(ddm_ctx *ctx, ddm_galerkin *G, int nrhs, double *X, const double *D)
+{
+  if (!ctx || !G || !X || !D || X == D) return fail(ctx, DDM_EINVAL, "ddm_galerkin_apply_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_galerkin_apply_multi"));
+  return galerkin_apply_multi_impl(ctx, G, nrhs, X, D, false);
+}
+
+extern "C" int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nleft, const double *left, int64_t nright,
+                                     const double *right, int64_t row0, int64_t row1, double *out_host)
+{
+  // out[j*nleft + i] = <left_i, A_dir right_j> over rows [row0,row1)   (column-major nleft x nright,
+  // the slab layout of galerkin_preconditioner.hh:294 / helpers.hh:252)
+  if (!A_dir || !left || !right || !out_host || nleft < 1 || nleft > COARSE_KMAX || nright < 1 || row0 < 0 || row1 > A_dir->nrows || row0 > row1)
+    return fail(ctx, DDM_EINVAL, "ddm_galerkin_products: bad arguments");
+  if (A_dir->host_only) return fail(ctx, DDM_EINVAL, "the matrix was created without device arrays (ddm_csr_create_host)");
+  const int64_t n = A_dir->nrows;
+  dbuf<double> y, partial, outd;
+  dbuf<RowChunk> chunks;
+  std::vector<RowChunk> hc;
+  for (int64_t r = row0; r < row1; r += COARSE_CHUNK_ROWS) hc.push_back(RowChunk{r, std::min(r + COARSE_CHUNK_ROWS, row1), 0, 0});
+  const int nchunk = (int)hc.size();
+  HIPCHECK(ctx, y.alloc(n));
+  HIPCHECK(ctx, partial.alloc((int64_t)nchunk * nleft));
+  HIPCHECK(ctx, outd.alloc(nleft * nright));
+  int rc = upload(ctx, hc.data(), (int64_t)hc.size(), chunks);
+  std::vector<int32_t> scp = {0, nchunk};
+  std::vector<int64_t> cidx(nleft);
+  dbuf<int32_t> d_scp;
+  dbuf<int64_t> d_cidx;
+  if (!rc) rc = upload(ctx, scp.data(), 2, d_scp);
+  for (int64_t j = 0; j < nright && !rc; ++j) {
+    // y[row0:row1) = (A_dir right_j)[row0:row1): only the rows the products below read (a whole-matrix product per vector and call
+    // was 1 s of the headline setup: 1 280 passes over 3.5 GB); same row sums in the same order as ddm_csr_mv
+    if (row1 > row0)
+      hipLaunchKernelGGL(k_spmm_rowmajor, dim3((unsigned)((row1 - row0 + WG - 1) / WG)), dim3(WG), 0, ctx->stream, row1 - row0, 1, A_dir->rp + row0, A_dir->ci, A_dir->va,
+                         right + j * n, (int64_t)1, y + row0, (int64_t)1);
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "ddm_galerkin_products: kernel launch failed");
+    for (int64_t i = 0; i < nleft; ++i) cidx[i] = i;
+    if (!d_cidx) rc = upload(ctx, cidx.data(), nleft, d_cidx);
+    if (rc) break;
+    if (nchunk > 0)
+      hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(nchunk), dim3(WG), 0, ctx->stream, (int)nleft, n, left, y, chunks, partial, nchunk);
+    hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, ctx->stream, 1, (int)nleft, d_scp, partial, d_cidx, nleft, outd + j * nleft);
+  }
+  if (!rc) rc = ddm_memcpy_d2h(ctx, out_host, outd, sizeof(double) * (size_t)(nleft * nright));
+  return rc;
+}
+
+// ---- CombinedPreconditioner --------------------------------------------------------------------
+struct ddm_combined {
+  int mode = 0;
+  ddm_op *op = nullptr;
+  ddm_schwarz *schwarz = nullptr;
+  ddm_galerkin *galerkin = nullptr;
+  dbuf<double> dnext;
+  int64_t n = 0;
+  bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
+  bool overlap = false; // ... and the coarse chain runs on a side stream beside the local solve (measured slower: off by default)
+  dbuf<double> mdnext, mp, mq; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
+  int mcols = 0, mcg_cols = 0;
+};
+extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)
+{
+  if (!ctx || !out || !schwarz) return fail(ctx, DDM_EINVAL, "ERROR: No preconditioners added yet"); // combined_preconditioner.hh:77
+  if (mode != 0 && mode != 1) return fail(ctx, DDM_ENOTIMPL, "Unknown apply mode in CombinedPreconditioner, use either additive or multiplicative"); // :68
+  if (mode == 1 && galerkin && !op) return fail(ctx, DDM_EINVAL, "ERROR: ApplyMode is multiplicative but operator A is not provided. Set with `set_op`"); // :146
+  auto C = std::make_unique<ddm_combined>();
+  C->mode = mode;
+  C->op = op;
+  C->schwarz = schwarz;
+  C->galerkin = galerkin;
+  C->n = schwarz->n_novlp;
+  if (mode == 0 && galerkin) {
+    const char *f = std::getenv("DDM_FUSE_LEVELS");    // "0": the two levels one after the other (two halo adds: the reference's order of sums)
+    const char *e = std::getenv("DDM_OVERLAP_COARSE"); // "1": coarse chain on a side stream
+    C->fused = !(f && f[0] == '0') && galerkin->copy == schwarz->copy && galerkin->add == schwarz->add && galerkin->n == schwarz->n && galerkin->n_novlp == schwarz->n_novlp;
+    C->overlap = C->fused && e && e[0] == '1' && (ctx->nranks == 1 || ctx->rccl);
+  }
+  if (C->dnext.alloc(C->n) != hipSuccess) return fail(ctx, DDM_EHIP, "combined: allocation failed");
+  *out = C.release();
+  return DDM_OK;
+}
+extern "C" int ddm_combined_status(ddm_ctx *ctx, const ddm_combined *C)
+{
+  if (!C) return fail(ctx, DDM_EINVAL, "ddm_combined_status: bad arguments");
+  return C->schwarz ? ddm_schwarz_status(ctx, C->schwarz) : DDM_OK;
+}
+extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
+// Additive combination, fused: both levels start from the same extended defect and add over the same interface, so their
+// overlapping results are summed BEFORE the exchange (linearity of addOwnerCopyToAll; schwarz.hh:138-146 +
+// galerkin_preconditioner.hh:190-193 + combined_preconditioner.hh:136-142) -- one extend, one copy-halo, one halo add and one restrict
+// instead of two each; the result differs from the two-pass order by rounding only (measured: 5.54 -> 5.31 ms per iteration at 216^3).
+//   extend + copy-halo -> local solve -> (POU scale) -> R d -> all-reduce -> A0^-1 -> R^T x0 -> x_s += x_c -> halo add -> restrict
+// two_streams (DDM_OVERLAP_COARSE=1; needs the in-library exchange or a single rank): the coarse chain runs on a side stream BESIDE the
+// local solve -- the local solves are latency-bound and leave 85 % of the HBM bandwidth idle, the coarse level is bandwidth-bound.
+// Measured at 216^3 it LOSES: the local solve slows from 3.39 to 4.34 ms (its dependent L2 / HBM round trips queue behind the
+// basis stream), the coarse chain from 0.87 to 2.2 ms, 5.58 ms per iteration against 5.31 -- off by default.
+static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, bool two_streams)
+{
+  ddm_schwarz *S = C->schwarz;
+  ddm_galerkin *G = C->galerkin;
+  if (two_streams && !ctx->side) {
+    HIPCHECK(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+    HIPCHECK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    HIPCHECK(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/get defect");
+    hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp);
+    DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));
+  }
+  auto timed_chain = [&](int grid) -> int { // (the timer records on whichever stream the chain is enqueued on)
+    ScopedTimer t(ctx, "GalerkinPrec/apply");
+    return coarse_chain(ctx, G, S->d_ovlp, grid);
+  };
+  if (two_streams) {
+    // inter-rank operations stay totally ordered: copy-halo (main) -> all-reduce (side) -> [join] -> halo add (main)
+    HIPCHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+    hipStream_t main = ctx->stream;
+    HIPCHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    ctx->stream = ctx->side; // the coarse chain is enqueued on the side stream (kernels, RCCL all-reduce, timer)
+    // a small grid: the chain only has to finish within the (latency-bound, ~3 ms) local solve, and a full-rate basis stream would
+    // queue in front of the pipe kernel's dependent L2 / HBM round trips (DDM_OVERLAP_GRID: workgroups, default 64)
+    static const int side_grid = std::getenv("DDM_OVERLAP_GRID") ? std::max(1, std::atoi(std::getenv("DDM_OVERLAP_GRID"))) : 64;
+    const int rc = timed_chain(std::min(G->nchunk, side_grid));
+    const hipError_t e = hipEventRecord(ctx->ev_join, ctx->side);
+    ctx->stream = main;
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, DDM_EHIP, "hipEventRecord failed: %s", hipGetErrorString(e));
+  }
+  const double *pou = S->type == 1 ? S->pou : nullptr;
+  // one stream: the coarse chain runs first, so that the local solve's last kernel can also apply "x *= pou; x += x_coarse"
+  if (!two_streams) DDMCHECK(timed_chain(G->nchunk));
+  {
+    ScopedTimer t(ctx, "Schwarz/local solve");
+    DDMCHECK(ilu0_solve_epilogue(ctx, S->solver, S->d_ovlp, S->x_ovlp, two_streams ? nullptr : pou, two_streams ? nullptr : (const double *)G->x_ovlp));
+  }
+  {
+    ScopedTimer t(ctx, "Schwarz/add solution");
+    if (two_streams) {
+      if (pou) hipLaunchKernelGGL(k_scale, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, pou, S->x_ovlp);
+      HIPCHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+      hipLaunchKernelGGL(k_axpy, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, 1.0, (const double *)G->x_ovlp, S->x_ovlp);
+    }
+    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));
+    hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
+    HIPCHECK(ctx, hipGetLastError());
+  }
+  return DDM_OK;
+}
+
+extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d)
+{
+  ScopedTimer t(ctx, "CombinedPreconditioner/apply");
+  DDMCHECK(local_status_check(ctx, C->schwarz));
+  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d, C->overlap);
+  // x = 0; precs[0]->apply(x, d)  (:133-134)  -- the restrict kernel overwrites every entry of x
+  DDMCHECK(schwarz_apply_impl(ctx, C->schwarz, x, d, false));
+  if (!C->galerkin) return DDM_OK;
+  if (C->mode == 0) { // additive: xnext = P1 d; x += xnext (:136-142) -- fused into the restrict of the coarse level
+    // both levels extend the same defect over the same interface: the Schwarz level's copy is reused (the local solves read it only)
+    static const bool no_share = std::getenv("DDM_NO_SHARED_DEFECT") != nullptr; // diagnostic switch
+    const bool share = !no_share && C->galerkin->copy == C->schwarz->copy && C->galerkin->n == C->schwarz->n && C->galerkin->n_novlp == C->schwarz->n_novlp;
+    return galerkin_apply_impl(ctx, C->galerkin, x, d, true, share ? C->schwarz->d_ovlp : nullptr);
+  }
+  // multiplicative: dnext = d - A x; x += P1 dnext (:149-158)
+  HIPCHECK(ctx, hipMemcpyAsync(C->dnext, d, sizeof(double) * (size_t)C->n, hipMemcpyDeviceToDevice, ctx->stream));
+  DDMCHECK(ddm_op_applyscaleadd(ctx, C->op, -1.0, x, C->dnext));
+  return galerkin_apply_impl(ctx, C->galerkin, x, C->dnext, true);
+}
+// ... and for m columns (combined_preconditioner.hh:127-163)
+static int combined_apply_multi_impl(ddm_ctx *ctx, ddm_combined *C, int m, double *X, const double *D)
+{
+  ScopedTimer t(ctx, "CombinedPreconditioner/apply");
+  ddm_schwarz *S = C->schwarz;
+  ddm_galerkin *G = C->galerkin;
+  DDMCHECK(local_status_check(ctx, S));
+  if (C->mode == 0 && G && C->fused) {
+    // the fused order of combined_apply_fused (one stream): extend + copy-halo -> coarse chain -> local solve -> (POU) + coarse ->
+    // one halo add -> restrict
+    DDMCHECK(schwarz_multi_scratch(ctx, S, m));
+    DDMCHECK(galerkin_multi_scratch(ctx, G, m));
+    {
+      ScopedTimer t2(ctx, "Schwarz/get defect");
+      hipLaunchKernelGGL(k_extend_multi, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, S->ext_map, D, S->md_ovlp);
+      DDMCHECK(halo_exchange_multi(ctx, S->copy, m, S->md_ovlp));
+    }
+    DDMCHECK(coarse_chain_multi(ctx, G, m, S->md_ovlp));
+    {
+      ScopedTimer t2(ctx, "Schwarz/local solve");
+      DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m));
+    }
+    {
+      ScopedTimer t2(ctx, "Schwarz/add solution");
+      const double *pou = S->type == 1 ? S->pou : nullptr;
+      hipLaunchKernelGGL(k_scale_add_multi, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, pou, (const double *)G->mx_ovlp, S->mx_ovlp);
+      DDMCHECK(halo_exchange_multi(ctx, S->add, m, S->mx_ovlp));
+      hipLaunchKernelGGL(k_restrict_multi<false>, dim3(grid_for(S->n * m)), dim3(WG), 0, ctx->stream, S->n, m, S->ext_map, (const double *)S->mx_ovlp, X);
+      HIPCHECK(ctx, hipGetLastError());
+    }
+    return DDM_OK;
+  }
+  DDMCHECK(schwarz_apply_multi_impl(ctx, S, m, X, D, false)); // x = 0; precs[0]->apply(x, d)  (:133-134)
+  if (!G) return DDM_OK;
+  if (C->mode == 0) { // additive (:136-142); the Schwarz level's extended defect is shared when both levels use the same interface
+    const bool share = G->copy == S->copy && G->n == S->n && G->n_novlp == S->n_novlp;
+    return galerkin_apply_multi_impl(ctx, G, m, X, D, true, share ? S->md_ovlp : nullptr);
+  }
+  // multiplicative: dnext = d - A x; x += P1 dnext (:149-158)
+  HIPCHECK(ctx, reserve_cols(C->mcols, m, C->mdnext, C->n));
+  HIPCHECK(ctx, hipMemcpyAsync(C->mdnext, D, sizeof(double) * (size_t)(C->n * m), hipMemcpyDeviceToDevice, ctx->stream));
+  DDMCHECK(op_applyscaleadd_multi(ctx, C->op, m, -1.0, X, C->mdnext));
+  return galerkin_apply_multi_impl(ctx, G, m, X, C->mdnext, true);
+}
+extern "C" int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X, const double *D)
+{
+  if (!ctx || !C || !X || !D || X == D) return fail(ctx, DDM_EINVAL, "ddm_combined_apply_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_combined_apply_multi"));
+  return combined_apply_multi_impl(ctx, C, nrhs, X, D);
+}

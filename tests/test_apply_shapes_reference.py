@@ -28,7 +28,7 @@ import pytest
 from tests.test_gpu_parity import RTOL_VEC, _build
 
 RTOL_PREC = 1e-10                      # a preconditioner apply against the oracle (tests/test_gpu_parity.py, relative to the largest entry)
-CHUNK_ROWS = 8192                      # COARSE_CHUNK_ROWS of csrc/ddm_hip.hip: rows of one coarse restriction / prolongation chunk
+CHUNK_ROWS = 8192                      # COARSE_CHUNK_ROWS of csrc/preconditioners.hpp: rows of one coarse restriction / prolongation chunk
 GRID_PASS = 2048 * 256                 # entries that one pass of an element-wise kernel covers (grid_for caps the grid at 2048 workgroups)
 PARTS = (2, 2, 2)
 SMALL, LARGE = (13, 12, 11), (44, 42, 40)

@@ -1,4 +1,4 @@
-"""CPU: the cache-blocked processing order of the GenEO block products (csrc/ddm_hip.hip: csr_row_order_tiled; kernels.hpp:
+"""CPU: the cache-blocked processing order of the GenEO block products (csrc/csr.hpp: csr_row_order_tiled; kernels.hpp:
 k_spmm_rowmajor4_tiled).  The order is a performance hint -- it must be a permutation whatever the matrix looks like -- and on the
 matrices of the benchmark (27-point stencil on a lexicographic box, overlap shell appended) it must find the grid strides and visit
 the rows brick by brick."""
