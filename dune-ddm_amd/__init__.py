@@ -163,6 +163,10 @@ SYMBOLS = {
     "ddm_combined_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_cg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_gmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_fgmres_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_fgmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_fgmres_defect_multi": (_I32, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
+    "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
     "ddm_cg_defect": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_double)]),
@@ -587,6 +591,11 @@ class SchwarzPreconditioner:
     def apply_multi(self, X, D):
         self.ctx.check(self.ctx.lib.ddm_schwarz_apply_multi(self.ctx.h, self.h, _ncols(X, D), _ptr(X), _ptr(D)))
 
+    def set_multi_precision(self, f32):
+        """f32 true: the block applies run their local solve with single-precision sweeps (ddm_schwarz_set_multi_precision; meant for
+        the flexible drivers only); false (the default): double"""
+        self.ctx.check(self.ctx.lib.ddm_schwarz_set_multi_precision(self.h, 1 if f32 else 0))
+
     def local_solver(self):
         """the local solver object (ddm_ilu0 *, borrowed) as a raw pointer"""
         return self.ctx.lib.ddm_schwarz_local_solver(self.h)
@@ -718,6 +727,43 @@ def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPr
         return out, None
     iters = max([r.iterations for r in out] + [0])
     return out, hist[:iters + 1, :m]
+
+
+def fgmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,
+                 history=True):
+    """dune-istl RestartedFlexibleGMResSolver::apply ([solver] type = restartedflexiblegmressolver): right-preconditioned restarted
+    GMRES that keeps the preconditioned directions; the history holds (estimates of) the TRUE defect norm (ddm_fgmres_solve)."""
+    res = SolveResult()
+    hist = np.zeros(maxit + 1, dtype=np.float64) if history else None
+    ctx.check(ctx.lib.ddm_fgmres_solve(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(restart), _hp(hist),
+                                       ctypes.byref(res)))
+    return res, (hist[:res.iterations + 1] if history else None)
+
+
+def fgmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,
+                       history=True):
+    """m independent flexible restarted GMRES recurrences at once (ddm_fgmres_solve_multi), restart cycles aligned.  Arguments and
+    return value as gmres_solve_multi."""
+    m = _ncols(X, B)
+    res = (SolveResult * max(m, 1))()
+    hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
+    ctx.check(ctx.lib.ddm_fgmres_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), int(restart), _hp(hist), res))
+    out = [res[c] for c in range(m)]
+    if not history:
+        return out, None
+    iters = max([r.iterations for r in out] + [0])
+    return out, hist[:iters + 1, :m]
+
+
+def fgmres_defect_multi(ctx: Context, op: NonOverlappingOperator, active, T, B, fused=True):
+    """the restart step of ddm_fgmres_solve_multi on its own: B -= T in the columns with active[c] != 0; returns the m squared
+    owner-masked norms of B afterwards (ddm_fgmres_defect_multi)"""
+    m = _ncols(T, B)
+    act = _np(active, np.int32)
+    assert act.shape == (m,)
+    r = np.zeros(max(m, 1), dtype=np.float64)
+    ctx.check(ctx.lib.ddm_fgmres_defect_multi(ctx.h, op.h, m, _hp(act), _ptr(T), _ptr(B), 1 if fused else 0, _hp(r)))
+    return r[:m]
 
 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,

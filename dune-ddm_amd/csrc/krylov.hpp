@@ -1,7 +1,8 @@
-// The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES and BiCGSTAB for one right-hand side, CG and restarted GMRES
-// for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods).  All five share the frame around
-// the loop (solve_result_reset, classify_initial_defect, krylov_finish); both GMRES drivers run their host arithmetic through the
-// same GmresColumn, which is what keeps a block column bit-identical to the single-vector solve.  Needs preconditioners.hpp.
+// The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES, flexible restarted GMRES and BiCGSTAB for one right-hand
+// side; CG, restarted GMRES and flexible restarted GMRES for m right-hand sides at once (m independent recurrences in one loop, not
+// block-Krylov methods).  All of them share the frame around the loop (solve_result_reset, classify_initial_defect, krylov_finish);
+// the four GMRES drivers run their host arithmetic through the same GmresColumn, which is what keeps the host side of a block column
+// bit-identical to the single-vector solve.  Needs preconditioners.hpp.
 #pragma once
 
 // synchronises the context's stream when it goes out of scope: the Krylov drivers declare it AFTER their work arrays, so that an
@@ -554,6 +555,13 @@ static int gmres_mgs_multi(ddm_ctx *ctx, ddm_op *op, int m, int i, bool fused, c
   return DDM_OK;
 }
 
+// DDM_GMRES_MULTI_FUSED, read once per solve; the unfused composition is the default (it measured faster)
+static bool gmres_multi_fused_env()
+{
+  const char *e = std::getenv("DDM_GMRES_MULTI_FUSED");
+  return e && e[0] == '1';
+}
+
 extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                                      int restart, double *hist_host, ddm_solve_result *res)
 {
@@ -573,10 +581,7 @@ extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *pre
       return fail(ctx, DDM_ENOTIMPL, "ddm_gmres_solve_multi: the Krylov basis of %d + 1 blocks of %lld x %d doubles and the work block need %.0f bytes, %zu are free",
                   R, (long long)n, m, need, free_b);
   }
-  const bool fused = [] { // read once per solve; the unfused composition is the default (it measured faster)
-    const char *e = std::getenv("DDM_GMRES_MULTI_FUSED");
-    return e && e[0] == '1';
-  }();
+  const bool fused = gmres_multi_fused_env();
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
   dbuf<double> Vb, Wb, hdev, ydev;
@@ -690,6 +695,300 @@ extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *pre
     }
   }
   if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_gmres_solve_multi");
+  double elapsed = 0.0;
+  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
+  for (int c = 0; c < m; ++c) {
+    res[c].elapsed_s = elapsed;
+    if (col[c].def0 >= 1e-30) res[c].reduction = col[c].norm / col[c].def0;
+  }
+  return rc;
+}
+
+// ---- flexible restarted GMRES ------------------------------------------------------------------------------------------------------
+// dune-istl RestartedFlexibleGMResSolver::apply ([solver] type = restartedflexiblegmressolver; DUNE 2.10 solvers.hh, not in the
+// snapshot -- the algorithm is written out in include/ddm_hip.h and restated in tests/fgmres_reference.py): RIGHT preconditioning
+// with the preconditioned directions z_i = M^-1 v_i kept next to the Krylov basis, so that the solution update x += sum_k y_k z_k
+// needs no further preconditioner apply and M^-1 may be a different operator in every iteration; modified Gram-Schmidt and the Givens
+// rotations of ddm_gmres_solve (the same GmresColumn); the monitored quantity |s_{i+1}| estimates the norm of the TRUE defect
+// b - A x.  Two bases: V with min(restart, maxit) + 1 and Z with min(restart, maxit) vectors, and one work vector.
+
+// what the two bases and the work block need against the free device memory: DDM_ENOTIMPL before anything is allocated
+static int fgmres_memory_check(ddm_ctx *ctx, const char *what, int R, int64_t n, int m)
+{
+  size_t free_b = 0, total_b = 0;
+  HIPCHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+  const double need = (2.0 * (double)R + 2.0) * (double)(std::max<int64_t>(n, 1) * m) * sizeof(double);
+  if (need > (double)free_b)
+    return fail(ctx, DDM_ENOTIMPL, "%s: the two bases of %d + 1 and %d blocks of %lld x %d doubles and the work block need %.0f bytes, %zu are free", what, R, R,
+                (long long)n, m, need, free_b);
+  return DDM_OK;
+}
+
+extern "C" int ddm_fgmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, int restart,
+                                double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !x || !b || !res || x == b || maxit < 0 || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve: bad arguments");
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int64_t n = op->n, stride = std::max<int64_t>(n, 1);
+  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations
+  const int G = grid_for(n);
+  DDMCHECK(fgmres_memory_check(ctx, "ddm_fgmres_solve", R, n, 1));
+  solve_result_reset(res);
+  dbuf<double> V, Z, w, hdev;
+  HIPCHECK(ctx, V.alloc(stride * (R + 1)));
+  HIPCHECK(ctx, Z.alloc(stride * R));
+  HIPCHECK(ctx, w.alloc(n));
+  HIPCHECK(ctx, hdev.alloc(R + 2));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
+  auto v = [&](int k) { return V + (size_t)k * (size_t)stride; };
+  auto z = [&](int k) { return Z + (size_t)k * (size_t)stride; };
+  const size_t bytes = sizeof(double) * (size_t)n;
+  std::vector<double> hcol(R + 2), y(R);
+  GmresColumn q;
+  q.init(R);
+  double nn = 0.0;
+  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
+  if (!rc) rc = dot_device(ctx, n, op->owner, b, b, hdev);
+  if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
+  if (rc) return rc;
+  q.norm = std::sqrt(nn); // beta = ||b||: the true defect norm
+  const double def0 = q.norm;
+  res->def0 = def0;
+  if (hist_host) hist_host[0] = def0;
+  if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: initial defect is NaN");
+    res->converged = 1;
+    return DDM_OK;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  int j = 0;
+  bool conv = false;
+  while (j < maxit && !conv && !rc) {
+    HIPCHECK(ctx, hipMemcpyAsync(v(0), b, bytes, hipMemcpyDeviceToDevice, ctx->stream)); // v0 = b / beta
+    hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / q.norm, v(0));
+    q.start_cycle();
+    int i = 0;
+    for (; i < R && j < maxit && !conv; ++i, ++j) {
+      rc = ddm_combined_apply(ctx, prec, z(i), v(i));   // z_i = M^-1 v_i, kept
+      if (!rc) rc = ddm_op_apply(ctx, op, z(i), w);     // w = A z_i
+      for (int k = 0; k <= i && !rc; ++k) {             // modified Gram-Schmidt
+        rc = dot_device(ctx, n, op->owner, v(k), w, hdev + k);
+        hipLaunchKernelGGL(k_axpy_negdev, dim3(G), dim3(WG), 0, ctx->stream, n, hdev + k, v(k), w);
+      }
+      if (!rc) rc = dot_device(ctx, n, op->owner, w, w, hdev + i + 1);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2));
+      if (rc) break;
+      const double wnorm = q.take_column(i, hcol.data(), 1);
+      if (std::fabs(wnorm) < 1e-80) {
+        rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: breakdown in GMRes - |w| == 0.0 after %d iterations", j);
+        break;
+      }
+      HIPCHECK(ctx, hipMemcpyAsync(v(i + 1), w, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+      hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / wnorm, v(i + 1));
+      const double norm = q.rotate(i);
+      res->iterations = j + 1;
+      if (hist_host) hist_host[j + 1] = norm;
+      if (!(norm == norm)) {
+        rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: defect is NaN in iteration %d", j + 1);
+        break;
+      }
+      if (norm < def0 * reduction || norm < 1e-30) conv = true;
+    }
+    if (rc) break;
+    // solve the triangular system; w = sum_k y_k z_k; x += w (no preconditioner apply: the z_k were kept)
+    q.back_substitute(y.data());
+    HIPCHECK(ctx, hipMemsetAsync(w, 0, bytes, ctx->stream));
+    for (int a = 0; a < i; ++a) hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, y[a], (const double *)z(a), w);
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, (const double *)w, x);
+    if (!conv && j < maxit) { // restart: b -= A w; beta = ||b||
+      rc = ddm_op_applyscaleadd(ctx, op, -1.0, w, b);
+      if (!rc) rc = dot_device(ctx, n, op->owner, b, b, hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
+      q.norm = std::sqrt(nn);
+    }
+  }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_fgmres_solve");
+  rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
+  res->converged = conv ? 1 : 0;
+  res->reduction = q.norm / def0;
+  return rc;
+}
+
+// ---- flexible restarted GMRES for m right-hand sides ---------------------------------------------------------------------------------
+// Every column is what ddm_fgmres_solve computes on it, under the rules of ddm_gmres_solve_multi: aligned restart cycles, columns
+// frozen by mask, one read-back of the fresh Hessenberg entries per iteration, one all-reduce of m doubles per orthogonalisation step
+// (gmres_mgs_multi).  The cycle end is k_gmres_update_multi pointed at Z (W = sum_k y_k z_k; X += W), one block operator apply
+// T = A W into the basis block that the next cycle overwrites anyway, and k_defect_norm_multi (B -= T and the partial sums of the
+// new defect norms in one pass; frozen columns of B untouched).
+
+// B -= T in the columns of ctx->mactive; out (m device doubles) = owner-masked <B_c, B_c>, summed over the ranks
+static int fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *T, double *B, double *out)
+{
+  const int64_t n = op->n;
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  for_column_groups(m, [&](int c0, int cb) {
+    DDM_MULTI_CB_DISPATCH(k_defect_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
+                          (const uint8_t *)op->owner, T, B, ctx->mpartial);
+  });
+  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
+  HIPCHECK(ctx, hipGetLastError());
+  return ctx_allreduce(ctx, out, m, "defect norms");
+}
+// The restart step on its own, for tests: B -= T in the columns with active_host[c] != 0, norm2_host[c] = <B_c, B_c> of every column
+// afterwards.  fused != 0: k_defect_norm_multi; fused == 0: the kernels it replaces (k_axpy_negdev_multi with unit coefficients, then
+// the block dot of ddm_dot_multi).  Synchronous.
+extern "C" int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const int32_t *active_host, const double *T, double *B, int fused,
+                                       double *norm2_host)
+{
+  if (!ctx || !op || !active_host || !T || !B || T == B || !norm2_host) return fail(ctx, DDM_EINVAL, "ddm_fgmres_defect_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_fgmres_defect_multi"));
+  DDMCHECK(ctx_multi_scratch(ctx));
+  const int m = nrhs;
+  const int64_t n = op->n;
+  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active_host, sizeof(int32_t) * (size_t)m));
+  double *out = ctx->mscal + 6 * MULTI_MAX;
+  if (fused) {
+    DDMCHECK(fgmres_defect_multi(ctx, op, m, T, B, out));
+  } else {
+    dbuf<double> one;
+    HIPCHECK(ctx, one.alloc(m));
+    StreamDrain drain{ctx};
+    const std::vector<double> ones(m, 1.0);
+    DDMCHECK(ddm_memcpy_h2d(ctx, one, ones.data(), sizeof(double) * (size_t)m));
+    hipLaunchKernelGGL(k_axpy_negdev_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, (const double *)one, T, B);
+    DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, out));
+  }
+  return ddm_memcpy_d2h(ctx, norm2_host, out, sizeof(double) * (size_t)m);
+}
+
+extern "C" int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                                      int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
+    return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_fgmres_solve_multi"));
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int m = nrhs;
+  const int64_t n = op->n;
+  const int64_t vstride = std::max<int64_t>(n, 1) * m;
+  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis block beyond that
+  DDMCHECK(fgmres_memory_check(ctx, "ddm_fgmres_solve_multi", R, n, m));
+  const bool fused = gmres_multi_fused_env();
+  for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
+  DDMCHECK(ctx_multi_scratch(ctx));
+  dbuf<double> Vb, Zb, Wb, hdev, ydev;
+  dbuf<int32_t> cdev; // [0, m): Hessenberg columns per column in the cycle, [m, 2m): keep W (still running)
+  HIPCHECK(ctx, Vb.alloc(vstride * (R + 1)));
+  HIPCHECK(ctx, Zb.alloc(vstride * R));
+  HIPCHECK(ctx, Wb.alloc(vstride));
+  HIPCHECK(ctx, hdev.alloc((int64_t)(R + 2) * m));
+  HIPCHECK(ctx, ydev.alloc((int64_t)R * m));
+  HIPCHECK(ctx, cdev.alloc(2 * m));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
+  double *V = Vb, *Z = Zb, *W = Wb;
+  auto v = [&](int k) { return V + (int64_t)k * vstride; };
+  auto z = [&](int k) { return Z + (int64_t)k * vstride; };
+  std::vector<GmresColumn> col(m);
+  for (auto &q : col) q.init(R);
+  std::vector<double> hcol((size_t)(R + 2) * m), yhost((size_t)R * m), ycol(R);
+  int32_t active[MULTI_MAX], cflags[2 * MULTI_MAX];
+  MultiCoef coef;
+  const int GE = grid_for(n * m);
+  // the basis is written through the mask only: a frozen column's entries, which the preconditioner still reads, start as zeros
+  HIPCHECK(ctx, hipMemsetAsync(V, 0, sizeof(double) * (size_t)(vstride * (R + 1)), ctx->stream));
+
+  // b -= A x; def0 = |b| per column
+  DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B));
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, hdev));
+  DDMCHECK(ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m));
+  int nactive = 0;
+  for (int c = 0; c < m; ++c) {
+    col[c].norm = col[c].def0 = std::sqrt(hcol[c]);
+    res[c].def0 = col[c].def0;
+    if (hist_host) hist_host[c] = col[c].def0;
+    const Defect0 d = classify_initial_defect(col[c].def0);
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: initial defect is NaN in column %d", c);
+    active[c] = d == Defect0::Go ? 1 : 0;
+    if (!active[c]) res[c].converged = 1;
+    nactive += active[c];
+  }
+  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = DDM_OK, j = 0;
+  while (j < maxit && nactive > 0 && !rc) {
+    for (int c = 0; c < m; ++c) {
+      GmresColumn &q = col[c];
+      q.cnt = 0;
+      coef.a[c] = active[c] ? 1.0 / q.norm : 0.0;
+      if (active[c]) q.start_cycle();
+    }
+    hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)B, v(0)); // v0 = b / beta
+    int i = 0;
+    for (; i < R && j < maxit && nactive > 0; ++i, ++j) {
+      rc = combined_apply_multi_impl(ctx, prec, m, z(i), v(i));            // z_i = M^-1 v_i, kept
+      if (!rc) rc = op_apply_multi(ctx, op, m, z(i), W);                    // w = A z_i
+      if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, fused, V, vstride, W, hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2) * m); // the one read-back of the iteration
+      if (rc) break;
+      for (int c = 0; c < m && !rc; ++c) {
+        coef.a[c] = 0.0;
+        if (!active[c]) continue;
+        const double wnorm = col[c].take_column(i, hcol.data() + c, (size_t)m);
+        if (std::fabs(wnorm) < 1e-80)
+          rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: breakdown in GMRes - |w| == 0.0 after %d iterations (column %d)", j, c);
+        coef.a[c] = 1.0 / wnorm;
+      }
+      if (rc) break;
+      hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)W, v(i + 1));
+      bool changed = false;
+      for (int c = 0; c < m; ++c) {
+        if (!active[c]) continue;
+        GmresColumn &q = col[c];
+        q.rotate(i);
+        res[c].iterations = j + 1;
+        if (hist_host) hist_host[(int64_t)(j + 1) * m + c] = q.norm;
+        if (!(q.norm == q.norm)) {
+          rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: defect is NaN in iteration %d (column %d)", j + 1, c);
+          break;
+        }
+        if (q.norm < q.def0 * reduction || q.norm < 1e-30) {
+          res[c].converged = 1;
+          active[c] = 0;
+          nactive -= 1;
+          changed = true;
+        }
+      }
+      if (rc) break;
+      if (changed) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
+      if (rc) break;
+    }
+    if (rc) break;
+    // per column: solve its triangular system of cnt_c unknowns; W_c = sum_k y_k z_k; X_c += W_c
+    std::fill(yhost.begin(), yhost.end(), 0.0);
+    for (int c = 0; c < m; ++c) {
+      GmresColumn &q = col[c];
+      cflags[c] = q.cnt;
+      cflags[m + c] = active[c];
+      q.back_substitute(ycol.data());
+      for (int a = 0; a < q.cnt; ++a) yhost[(size_t)a * m + c] = ycol[a];
+    }
+    rc = ddm_memcpy_h2d(ctx, ydev, yhost.data(), sizeof(double) * (size_t)i * m);
+    if (!rc) rc = ddm_memcpy_h2d(ctx, cdev, cflags, sizeof(int32_t) * (size_t)(2 * m));
+    if (rc) break;
+    {
+      ScopedTimer t(ctx, "GMRES/update");
+      hipLaunchKernelGGL(k_gmres_update_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)cdev, (const int32_t *)(cdev + m), (const double *)ydev,
+                         (const double *)Z, vstride, W, X);
+    }
+    if (nactive > 0 && j < maxit) { // restart: t = A w into v0 (overwritten by the next cycle); b -= t and beta = |b| in the running columns
+      rc = op_apply_multi(ctx, op, m, W, v(0));
+      if (!rc) rc = fgmres_defect_multi(ctx, op, m, v(0), B, hdev);
+      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m);
+      for (int c = 0; c < m && !rc; ++c)
+        if (active[c]) col[c].norm = std::sqrt(hcol[c]);
+    }
+  }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_fgmres_solve_multi");
   double elapsed = 0.0;
   rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
   for (int c = 0; c < m; ++c) {

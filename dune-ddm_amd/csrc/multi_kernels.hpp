@@ -369,4 +369,47 @@ __global__ __launch_bounds__(WG) void k_gmres_update_multi(int64_t n, int m, con
   }
 }
 
+// ---- flexible restarted GMRES (ddm_fgmres_solve_multi, csrc/krylov.hpp) -------------------------------------------------------------
+// Restart of the flexible driver for columns [c0, c0 + CB): b -= t (t = A W, the operator applied to the cycle's solution update) in
+// the active columns and, in the same pass, the owner-masked partial sums of <b, b> -- the true defect norms the next cycle starts
+// from.  The grid, the rows per thread and block_sum are those of k_dot_partial_multi, so b and the sums are bit-identical to
+// k_axpy_negdev_multi with unit coefficients followed by k_dot_partial_multi(b, b).  A column that is not active is not written; its
+// sum is that of the column as it stands (nobody reads it in the driver).  16 (active) or 8 bytes per block entry instead of 24 + 16.
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_defect_norm_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const uint8_t *__restrict__ mask,
+                                                          const double *__restrict__ t, double *__restrict__ b, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double s[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    s[u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    const int64_t o = i * m + c0;
+    const bool own = !MASKED || mask[i];
+    double bi[CB], ti[CB];
+#pragma unroll
+    for (int u = 0; u < CB; ++u) { // every load of the row is issued before the first use
+      bi[u] = b[o + u];
+      ti[u] = on[u] ? t[o + u] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < CB; ++u) {
+      if (on[u]) {
+        bi[u] -= ti[u];
+        b[o + u] = bi[u];
+      }
+      if (own) s[u] += bi[u] * bi[u];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double r = block_sum(s[u], red);
+    if (threadIdx.x == 0) partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = r;
+  }
+}
+
 } // namespace ddm

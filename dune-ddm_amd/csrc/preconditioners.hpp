@@ -163,6 +163,7 @@ struct ddm_schwarz {
   ddm_halo *copy = nullptr, *add = nullptr;
   dbuf<double> md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
   int mcols = 0;
+  bool multi_f32 = false; // ddm_schwarz_set_multi_precision: single-precision sweeps in the block local solve
   ~ddm_schwarz() { ddm_ilu0_destroy(solver); }
 };
 extern "C" int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
@@ -288,7 +289,7 @@ static int schwarz_apply_multi_impl(ddm_ctx *ctx, ddm_schwarz *S, int m, double 
   }
   {
     ScopedTimer t(ctx, "Schwarz/local solve");
-    DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m)); // :131-133 (level engine / direct multi-RHS solve)
+    DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m, S->multi_f32)); // :131-133 (level engine / direct multi-RHS solve)
   }
   {
     ScopedTimer t(ctx, "Schwarz/add solution");
@@ -307,6 +308,14 @@ extern "C" int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, d
   DDMCHECK(multi_check(ctx, nrhs, "ddm_schwarz_apply_multi"));
   ScopedTimer t(ctx, "Schwarz/apply");
   return schwarz_apply_multi_impl(ctx, S, nrhs, X, D, false);
+}
+// f32 != 0: the block applies (ddm_schwarz_apply_multi, and ddm_combined_apply_multi with it) run their local solve on the path of
+// ddm_ilu0_solve_multi_f32, which falls back to the double sweeps under its own conditions; the single-vector apply is not affected
+extern "C" int ddm_schwarz_set_multi_precision(ddm_schwarz *S, int f32)
+{
+  if (!S) return DDM_EINVAL;
+  S->multi_f32 = f32 != 0;
+  return DDM_OK;
 }
 // diagnostic: overwrite the status word of a local solver (0 clears it) -- lets a caller exercise the fail-fast path of the applies
 extern "C" int ddm_ilu0_set_status(ddm_ilu0 *F, int status)
@@ -646,7 +655,7 @@ static int combined_apply_multi_impl(ddm_ctx *ctx, ddm_combined *C, int m, doubl
     DDMCHECK(coarse_chain_multi(ctx, G, m, S->md_ovlp));
     {
       ScopedTimer t2(ctx, "Schwarz/local solve");
-      DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m));
+      DDMCHECK(ilu0_solve_multi_ld(ctx, S->solver, m, S->md_ovlp, m, S->mx_ovlp, m, S->multi_f32));
     }
     {
       ScopedTimer t2(ctx, "Schwarz/add solution");

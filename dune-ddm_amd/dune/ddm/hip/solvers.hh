@@ -7,7 +7,8 @@
 //     host factorisation and device triangular solves) for a flattened BCRSMatrix; registered under "hip_ilu0", "hip_cholesky",
 //     "hip_lu" when the dune-istl factory macros are visible.
 // (2) the outer Krylov solver (examples/poisson.cc:311-319 obtains it from the same factory): Dune::HipCGSolver /
-//     Dune::HipRestartedGMResSolver run the WHOLE loop on the device (ddm_cg_solve / ddm_gmres_solve: dune-istl's recurrences,
+//     Dune::HipRestartedGMResSolver / Dune::HipRestartedFlexibleGMResSolver / Dune::HipBiCGSTABSolver run the WHOLE loop on the device
+//     (ddm_cg_solve / ddm_gmres_solve / ddm_fgmres_solve / ddm_bicgstab_solve: dune-istl's recurrences,
 //     SURVEY.md 3.2) -- one upload of x and b, one download of x and the defect, instead of two PCIe copies of n_o doubles per
 //     virtual apply() when dune-istl's own host solvers drive the adaptors.
 #pragma once
@@ -126,7 +127,7 @@ public:
   }
 
   // Several right-hand sides at once: x.size() independent solves (1 to 32 columns) in one device loop (HipCGSolver: ddm_cg_solve_multi;
-  // HipRestartedGMResSolver: ddm_gmres_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
+  // HipRestartedGMResSolver: ddm_gmres_solve_multi; HipRestartedFlexibleGMResSolver: ddm_fgmres_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
   // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  A solver without a block
   // loop (HipBiCGSTABSolver) throws Dune::NotImplemented.
   void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
@@ -174,7 +175,7 @@ protected:
   // the block loop of the solver on row-major n x m device blocks (r: m entries)
   virtual int solve_block(ddm_ctx*, ddm_op*, ddm_combined*, int, double*, double*, double, ddm_solve_result*)
   {
-    DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver and restartedgmressolver have one)");
+    DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver, restartedgmressolver and restartedflexiblegmressolver have one)");
   }
   std::shared_ptr<LinearOperator<X, X>> op;
   std::shared_ptr<Preconditioner<X, X>> prec;
@@ -230,6 +231,31 @@ protected:
   int restart_;
 };
 
+// [solver] type = restartedflexiblegmressolver: dune-istl RestartedFlexibleGMResSolver::apply -- right-preconditioned, the TRUE defect is
+// monitored (as in HipCGSolver), and the preconditioner may change between iterations (ddm_schwarz_set_multi_precision); twice the
+// basis memory of HipRestartedGMResSolver
+template <class X>
+class HipRestartedFlexibleGMResSolver : public HipKrylovSolverBase<X> {
+public:
+  HipRestartedFlexibleGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int restart, int maxit, int verbose = 0)
+      : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), restart_(restart) {}
+  HipRestartedFlexibleGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
+      : HipRestartedFlexibleGMResSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
+
+  using HipKrylovSolverBase<X>::apply;
+
+protected:
+  int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_fgmres_solve(ctx, o, p, x, b, reduction, this->maxit_, restart_, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_fgmres_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, nullptr, r);
+  }
+  int restart_;
+};
+
 // [solver] type = bicgstabsolver: dune-istl BiCGSTABSolver::apply
 template <class X>
 class HipBiCGSTABSolver : public HipKrylovSolverBase<X> {
@@ -255,8 +281,9 @@ std::shared_ptr<InverseOperator<X, X>> getHipSolver(std::shared_ptr<LinearOperat
   const auto type = cfg.get("type", std::string("cgsolver"));
   if (type == "cgsolver") return std::make_shared<HipCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "restartedgmressolver") return std::make_shared<HipRestartedGMResSolver<X>>(std::move(op), std::move(prec), cfg);
+  if (type == "restartedflexiblegmressolver") return std::make_shared<HipRestartedFlexibleGMResSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "bicgstabsolver") return std::make_shared<HipBiCGSTABSolver<X>>(std::move(op), std::move(prec), cfg);
-  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, bicgstabsolver)");
+  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, bicgstabsolver)");
 }
 
 }  // namespace Dune

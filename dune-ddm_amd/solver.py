@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, cg_solve, cg_solve_multi, galerkin_products, gmres_solve_multi)
+               SchwarzPreconditioner, cg_solve, cg_solve_multi, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
 
@@ -272,29 +272,38 @@ class TwoLevelSchwarz:
         return cache[dst][src]
 
     # -- solve -------------------------------------------------------------------------------
+    SOLVERS = ("cgsolver", "restartedgmressolver", "restartedflexiblegmressolver", "bicgstabsolver")
+    SOLVERS_MULTI = SOLVERS[:3]   # (no block BiCGSTAB loop)
+
     def solve(self, reduction=1e-10, maxit=1000, fixed_iterations=0, history=True, x0=None, b=None, solver="cgsolver", restart=100):
-        """v = 0; solver->apply(v, b, res)  (examples/poisson.cc:318-319).  solver: "cgsolver" or
-        "restartedgmressolver" (the [solver] type keys of examples/poisson.ini).  Returns (res, hist, x)."""
+        """v = 0; solver->apply(v, b, res)  (examples/poisson.cc:318-319).  solver: "cgsolver", "restartedgmressolver",
+        "restartedflexiblegmressolver" or "bicgstabsolver" (the [solver] type keys of dune-istl's solver factory).  Returns (res, hist, x)."""
+        if solver not in self.SOLVERS:
+            raise NotImplementedError("solver type '" + str(solver) + "' (" + ", ".join(self.SOLVERS[:-1]) + " and " + self.SOLVERS[-1]
+                                      + " are available on the device)")
         x = self.zeros(self.rl.n_o) if x0 is None else self.to_device(x0)
         bd = self.to_device(self.rl.b if b is None else b)
+        if solver == "restartedflexiblegmressolver":
+            res, hist = fgmres_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, restart, history)
+            return res, hist, x
         if solver == "restartedgmressolver":
             res, hist = gmres_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, restart, history)
             return res, hist, x
         if solver == "bicgstabsolver":
             res, hist = bicgstab_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, history)
             return res, hist, x
-        if solver != "cgsolver":
-            raise NotImplementedError("solver type '" + str(solver) + "' (cgsolver, restartedgmressolver and bicgstabsolver are available on the device)")
         res, hist = cg_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, fixed_iterations, history)
         return res, hist, x
 
     def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100):
-        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver", m independent
-        restarted GMRES solves with aligned restart cycles (ddm_gmres_solve_multi), each column as ``solve`` would run it.
+        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver" /
+        "restartedflexiblegmressolver", m independent (flexible) restarted GMRES solves with aligned restart cycles
+        (ddm_gmres_solve_multi / ddm_fgmres_solve_multi), each column as ``solve`` would run it.
         B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
         (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
-        if solver not in ("cgsolver", "restartedgmressolver"):
-            raise NotImplementedError("solver type '" + str(solver) + "' (cgsolver and restartedgmressolver are available for several right-hand sides)")
+        if solver not in self.SOLVERS_MULTI:
+            raise NotImplementedError("solver type '" + str(solver) + "' (of the four device solvers " + ", ".join(self.SOLVERS)
+                                      + ", all but bicgstabsolver are available for several right-hand sides)")
         torch = self.torch
         n_o = self.rl.n_o
         if B is None:
@@ -312,6 +321,8 @@ class TwoLevelSchwarz:
             raise ValueError(f"X0 {tuple(X.shape)} and B {tuple(Bd.shape)} differ")
         if solver == "restartedgmressolver":
             res, hist = gmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
+        elif solver == "restartedflexiblegmressolver":
+            res, hist = fgmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
         else:
             res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
         return res, hist, X

@@ -418,6 +418,28 @@ int ddm_cg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double
 int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
                     int restart, double *hist_host, ddm_solve_result *res);
 
+/* dune-istl RestartedFlexibleGMResSolver::apply ([solver] type = restartedflexiblegmressolver; DUNE 2.10 solvers.hh, not in the
+ * reference snapshot, restated here): RIGHT-preconditioned restarted GMRES that keeps the preconditioned directions.  The monitored
+ * norm estimates the TRUE defect ||b - A x|| -- the quantity ddm_cg_solve and ddm_bicgstab_solve test, not the preconditioned defect
+ * of ddm_gmres_solve -- and the preconditioner may be a different operator in every iteration.
+ *   1. b -= A x; beta = ||b|| (the owner-masked norm of ddm_norm); def0 = beta; def0 < 1e-30: converged at once, x untouched.
+ *   2. per restart cycle: v_0 = b / beta; for i = 0 .. restart - 1:
+ *        z_i = M^-1 v_i (ddm_combined_apply; z_i is STORED); w = A z_i;
+ *        modified Gram-Schmidt against v_0 .. v_i in the order k = 0 .. i: h_{k,i} = <v_k, w>, w -= h_{k,i} v_k;
+ *        h_{i+1,i} = ||w||; v_{i+1} = w / h_{i+1,i};
+ *        the Givens rotations of ddm_gmres_solve applied to column i of H and to s (s = beta e_0 at the start of the cycle);
+ *        norm = |s_{i+1}|, written to hist_host[j] (j = global iteration); the column stops when norm < reduction def0 or norm < 1e-30.
+ *      at the end of the cycle, or at the stop: H y = s solved by back substitution, x += sum_{k < i} y_k z_k (no preconditioner apply);
+ *      if the solve has not stopped: b -= A (sum_k y_k z_k), beta = ||b||.
+ *   3. res->reduction = norm / def0 (after a restart: the recomputed beta / def0), res->iterations = j.
+ * DDM_EINVAL (before any device work) for NULL pointers, x == b, restart < 1 or maxit < 0; DDM_ENUMERIC for |w| == 0 before the
+ * normalisation, a NaN norm, and when a local solve gave up (ddm_ilu0_peek_status on entry, ddm_ilu0_status at the end).
+ * Memory: TWO bases, V of min(restart, maxit) + 1 and Z of min(restart, maxit) vectors, plus one work vector, allocated per call and
+ * freed on every return path; DDM_ENOTIMPL (the byte count is in the message) before anything is allocated when they exceed the free
+ * device memory.  hist_host (may be NULL): maxit + 1 doubles. */
+int ddm_fgmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, int restart,
+                     double *hist_host, ddm_solve_result *res);
+
 /* dune-istl BiCGSTABSolver::apply ([solver] type = bicgstabsolver): right-preconditioned, two half steps per iteration, the defect norm
  * is tested after each half step.  hist_host (may be NULL): up to 2 maxit + 1 doubles (one per half step), *nhist receives the count;
  * res->iterations = ceil of the half-step counter (what dune-istl reports).  DDM_ENUMERIC on the breakdowns dune-istl aborts on. */
@@ -446,6 +468,14 @@ int ddm_op_applyscaleadd_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, double alpha,
 /* result_host[c] = <X_c, Y_c> (owner-masked, :76-81): one reduction kernel, one all-reduce of nrhs doubles; synchronous */
 int ddm_dot_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X, const double *Y, double *result_host);
 int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, double *X, const double *D);   /* schwarz.hh:115-149 */
+/* Precision of the local solve inside the BLOCK applies of S (ddm_schwarz_apply_multi, ddm_combined_apply_multi and the block Krylov
+ * drivers): f32 = 0 (the default) double sweeps, f32 = 1 the single-precision sweeps of ddm_ilu0_solve_multi_f32 (preconditioner grade,
+ * relative error ~1e-6; double sweeps all the same when nrhs % 4 != 0 or the local solver is a sparse direct factor -- the conditions
+ * of ddm_ilu0_solve_multi_f32).  May be switched between two applies, also inside a solve: the preconditioner is then no longer one
+ * fixed linear operator, and with f32 = 1 it differs from the single-vector apply.  Only the flexible drivers (ddm_fgmres_solve_multi)
+ * are meant to be combined with it: they keep M^-1 v and test the true defect; CG and left-preconditioned GMRES assume a fixed M^-1 and
+ * would report the defect of a system preconditioned in single precision.  The single-vector apply never changes.  DDM_EINVAL for S == NULL. */
+int ddm_schwarz_set_multi_precision(ddm_schwarz *S, int f32);
 int ddm_galerkin_apply_multi(ddm_ctx *ctx, ddm_galerkin *G, int nrhs, double *X, const double *D); /* galerkin_preconditioner.hh:151-194 */
 int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X, const double *D); /* combined_preconditioner.hh:127-163 */
 /* nrhs INDEPENDENT dune-istl CGSolver::apply recurrences (the loop of ddm_cg_solve per column; not a block-Krylov method).  X: initial
@@ -477,6 +507,27 @@ int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, d
  *     orthogonalisation step as an AXPY and a separate dot, 1 as one fused kernel; the results are bit-identical. */
 int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                           int restart, double *hist_host, ddm_solve_result *res);
+/* nrhs INDEPENDENT ddm_fgmres_solve recurrences in one loop (flexible restarted GMRES: right preconditioning, the true defect is
+ * monitored; not a block-Krylov method), under every rule of ddm_gmres_solve_multi: aligned restart cycles; a column stops on its own
+ * test and is then frozen by mask (its x, history, res entry and column of B do not change any more; it is never multiplied by a zero
+ * coefficient); one read-back of the (i + 2) x nrhs fresh Hessenberg entries per iteration; one all-reduce of nrhs doubles per
+ * orthogonalisation step (DDM_GMRES_MULTI_FUSED as there); DDM_EINVAL before any device work for nrhs outside 1..32, restart < 1,
+ * maxit < 0, NULL pointers or X == B; DDM_ENUMERIC, naming column and iteration, for a NaN norm or |w| == 0 in an active column and
+ * when a local solve gave up.  X, B, hist_host ((maxit + 1) x nrhs) and res as in ddm_cg_solve_multi.
+ *   Memory: two bases, min(restart, maxit) + 1 and min(restart, maxit) blocks of n x nrhs doubles, plus one work block -- twice what
+ *     ddm_gmres_solve_multi needs -- allocated per call and freed on every return path; DDM_ENOTIMPL (byte count in the message) before
+ *     anything is allocated when that exceeds the free device memory.
+ *   The restart (B -= A W with the new defect norms) is one operator apply and ONE element-wise kernel that also forms the partial sums
+ *     of the norms, in the summation order of ddm_dot_multi.
+ *   With ddm_schwarz_set_multi_precision(S, 1) the local solves run in single precision; the test is still on the true defect. */
+int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                           int restart, double *hist_host, ddm_solve_result *res);
+/* The restart step of ddm_fgmres_solve_multi on its own (for tests): B -= T in the columns with active_host[c] != 0 (the others are not
+ * written), norm2_host[c] = <B_c, B_c> (owner-masked, summed over the ranks) of EVERY column afterwards.  fused != 0: the kernel the
+ * driver uses; fused == 0: the kernels it replaces (an AXPY with unit coefficients over the active columns, then the block dot of
+ * ddm_dot_multi); the results are bit-identical.  Synchronous. */
+int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const int32_t *active_host, const double *T, double *B, int fused,
+                            double *norm2_host);
 
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,

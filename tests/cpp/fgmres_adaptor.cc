@@ -1,0 +1,184 @@
+// Drives Dune::HipRestartedFlexibleGMResSolver ([solver] type = restartedflexiblegmressolver) the way examples/poisson.cc:229-321 builds
+// its solver: restricted SchwarzPreconditioner (ILU(0)) + POU GalerkinPreconditioner in a multiplicative CombinedPreconditioner,
+// NonOverlappingOperator, the solver from getHipSolver with restart = 6 so that the solves restart.  Single rank (mock communication,
+// see mock/).  The factory must return the new class for the new key; the single-vector and the block apply are checked BITWISE
+// against ddm_fgmres_solve / ddm_fgmres_solve_multi called on the same device objects.
+//   usage: fgmres_adaptor <dir with rowptr.bin col.bin val.bin b.bin dirichlet.bin pou.bin> <m>
+// prints "single <iterations adaptor> <iterations C ABI> <entries of x that differ> <entries of b that differ>", then per column
+// "col <c> <iterations adaptor> <iterations C ABI> <entries of x that differ> <entries of b that differ>", then "fgmres_ok".
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include <dune/istl/bcrsmatrix.hh>
+#include <dune/istl/bvector.hh>
+#include <dune/istl/owneroverlapcopy.hh>
+
+#include <dune/ddm/hip/combined_preconditioner.hh>
+#include <dune/ddm/hip/galerkin_preconditioner.hh>
+#include <dune/ddm/hip/nonoverlapping_operator.hh>
+#include <dune/ddm/hip/schwarz.hh>
+#include <dune/ddm/hip/coarse_spaces.hh>
+#include <dune/ddm/hip/solvers.hh>
+
+template <class T>
+static std::vector<T> slurp(const std::string& f)
+{
+  std::ifstream in(f, std::ios::binary | std::ios::ate);
+  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
+  const std::size_t bytes = in.tellg();
+  in.seekg(0);
+  std::vector<T> v(bytes / sizeof(T));
+  in.read(reinterpret_cast<char*>(v.data()), bytes);
+  return v;
+}
+
+static std::size_t differing(const double* a, const double* b, std::size_t n)
+{
+  std::size_t d = 0;
+  for (std::size_t i = 0; i < n; ++i) d += std::memcmp(a + i, b + i, sizeof(double)) != 0;
+  return d;
+}
+
+int main(int argc, char** argv)
+{
+  if (argc < 3) return 2;
+  const std::string dir = argv[1];
+  const int m = std::atoi(argv[2]);
+  using Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
+  using Mat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
+  using Comm = Dune::OwnerOverlapCopyCommunication<std::size_t, int>;
+  try {
+    auto rp64 = slurp<int64_t>(dir + "/rowptr.bin");
+    auto ci32 = slurp<int32_t>(dir + "/col.bin");
+    auto va = slurp<double>(dir + "/val.bin");
+    auto bb = slurp<double>(dir + "/b.bin");
+    auto dm = slurp<unsigned char>(dir + "/dirichlet.bin");
+    auto pw = slurp<double>(dir + "/pou.bin");
+    const std::size_t n = rp64.size() - 1;
+    auto A = std::make_shared<Mat>(n, n, std::vector<std::size_t>(rp64.begin(), rp64.end()), std::vector<std::size_t>(ci32.begin(), ci32.end()), va);
+    auto comm = std::make_shared<Comm>();
+    for (std::size_t i = 0; i < n; ++i) comm->indexSet().v.push_back({i, {i, Dune::OwnerOverlapCopyAttributeSet::owner}});
+
+    Dune::ParameterTree ptree;
+    ptree.sub("schwarz")["type"] = "restricted";
+    ptree.sub("schwarz").sub("subdomain_solver")["type"] = "ilu0";
+    ptree.sub("combined_preconditioner")["mode"] = "multiplicative";
+    ptree.sub("coarse_solver")["type"] = "umfpack";
+    ptree.sub("solver")["type"] = "restartedflexiblegmressolver";
+    ptree.sub("solver")["restart"] = "6";
+    ptree.sub("solver")["maxit"] = "500";
+    ptree.sub("solver")["reduction"] = "1e-10";
+    auto pou = std::make_shared<PartitionOfUnity>(pw);
+    auto schwarz = std::make_shared<SchwarzPreconditioner<Mat, Vec, Comm>>(A, comm, pou, ptree);
+    tf::Taskflow taskflow("Main taskflow");
+    auto coarse_space = std::make_unique<POUCoarseSpace<Vec>>(pou, taskflow);
+    std::shared_ptr<GalerkinPreconditioner<Vec, Comm>> coarse;
+    auto task = taskflow.emplace([&]() {
+      auto basis = coarse_space->get_basis();
+      for (auto& v : basis)
+        for (std::size_t i = 0; i < n; ++i)
+          if (dm[i]) v[i] = 0.0;   // zero_at_dirichlet (poisson.cc:235-238)
+      coarse = std::make_shared<GalerkinPreconditioner<Vec, Comm>>(*A, basis, comm, ptree, "coarse_solver");
+    });
+    task.name("Build coarse preconditioner").succeed(coarse_space->get_setup_task());
+    tf::Executor executor(1);
+    executor.run(taskflow).get();
+    auto op = std::make_shared<NonOverlappingOperator<Mat, Vec, Vec, Comm>>(A, comm);
+    auto prec = std::make_shared<CombinedPreconditioner<Vec>>(ptree);
+    prec->set_op(op);
+    prec->add(schwarz);
+    prec->add(coarse);
+
+    // the factory knows the key and returns the flexible solver; an unknown key still throws, naming the four solvers
+    std::shared_ptr<Dune::InverseOperator<Vec, Vec>> made =
+        Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(op), ptree.sub("solver"), std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(prec));
+    auto solver = std::dynamic_pointer_cast<Dune::HipRestartedFlexibleGMResSolver<Vec>>(made);
+    std::printf("factory %d\n", solver ? 1 : 0);
+    if (!solver) return 1;
+    int caught = 0;
+    try {
+      Dune::ParameterTree other;
+      other["type"] = "minressolver";
+      Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(op), other, std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(prec));
+    } catch (Dune::NotImplemented& e) {
+      if (std::string(e.what()).find("restartedflexiblegmressolver") != std::string::npos) ++caught;
+    }
+
+    // right-hand sides: the problem's, then seeded pseudo-random ones (zero on the Dirichlet rows like the problem's)
+    std::vector<Vec> B(m, Vec(n)), X(m, Vec(n));
+    std::vector<double> hb(n * m), hx(n * m, 0.0);
+    unsigned long long s = 12345;
+    for (int c = 0; c < m; ++c)
+      for (std::size_t i = 0; i < n; ++i) {
+        s = s * 6364136223846793005ULL + 1442695040888963407ULL;
+        const double r = (double)(s >> 11) / 9007199254740992.0 - 0.5;
+        B[c][i] = c == 0 ? bb[i] : (dm[i] ? 0.0 : r);
+        X[c][i] = 0.0;
+        hb[i * m + c] = B[c][i];
+      }
+    const std::vector<Vec> Bsave = B;
+
+    // the same device objects through the C ABI
+    auto ctx = prec->context();
+    ddm_ctx* h = ctx->handle();
+    ddm_op* oh = op->op_handle();
+    ddm_combined* ph = prec->handle(n);
+    bool ok = true;
+    {
+      Vec x1(n), b1 = Bsave[0];
+      x1 = 0;
+      Dune::InverseOperatorResult r1;
+      solver->apply(x1, b1, 1e-10, r1);
+      ddm_hip::DeviceVector dx(ctx, n), db(ctx, n);
+      std::vector<double> cx(n, 0.0), cb(n);
+      for (std::size_t i = 0; i < n; ++i) cb[i] = Bsave[0][i];
+      ddm_hip::check(h, ddm_memcpy_h2d(h, dx.data(), cx.data(), (int64_t)(n * sizeof(double))), "h2d");
+      ddm_hip::check(h, ddm_memcpy_h2d(h, db.data(), cb.data(), (int64_t)(n * sizeof(double))), "h2d");
+      ddm_solve_result rr{};
+      ddm_hip::check(h, ddm_fgmres_solve(h, oh, ph, dx.data(), db.data(), 1e-10, 500, 6, nullptr, &rr), "ddm_fgmres_solve");
+      ddm_hip::check(h, ddm_memcpy_d2h(h, cx.data(), dx.data(), (int64_t)(n * sizeof(double))), "d2h");
+      ddm_hip::check(h, ddm_memcpy_d2h(h, cb.data(), db.data(), (int64_t)(n * sizeof(double))), "d2h");
+      std::vector<double> ax(n), ab(n);
+      for (std::size_t i = 0; i < n; ++i) { ax[i] = x1[i]; ab[i] = b1[i]; }
+      const std::size_t dxn = differing(ax.data(), cx.data(), n), dbn = differing(ab.data(), cb.data(), n);
+      std::printf("single %d %d %zu %zu\n", r1.iterations, rr.iterations, dxn, dbn);
+      ok = ok && r1.converged && rr.converged && r1.iterations == rr.iterations && r1.iterations > 6 && r1.reduction == rr.reduction && dxn == 0 && dbn == 0;
+    }
+    {
+      std::vector<Dune::InverseOperatorResult> res;
+      solver->apply(X, B, 1e-10, res);   // one upload, one block solve, one download
+      ddm_hip::DeviceVector dX(ctx, n * m), dB(ctx, n * m);
+      ddm_hip::check(h, ddm_memcpy_h2d(h, dX.data(), hx.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+      ddm_hip::check(h, ddm_memcpy_h2d(h, dB.data(), hb.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+      std::vector<ddm_solve_result> rr(m);
+      ddm_hip::check(h, ddm_fgmres_solve_multi(h, oh, ph, m, dX.data(), dB.data(), 1e-10, 500, 6, nullptr, rr.data()), "ddm_fgmres_solve_multi");
+      ddm_hip::check(h, ddm_memcpy_d2h(h, hx.data(), dX.data(), (int64_t)(n * m * sizeof(double))), "d2h");
+      ddm_hip::check(h, ddm_memcpy_d2h(h, hb.data(), dB.data(), (int64_t)(n * m * sizeof(double))), "d2h");
+      ok = ok && res.size() == (std::size_t)m;
+      for (int c = 0; c < m && ok; ++c) {
+        std::size_t dxn = 0, dbn = 0;
+        for (std::size_t i = 0; i < n; ++i) {
+          const double xa = X[c][i], ba = B[c][i];
+          dxn += std::memcmp(&xa, &hx[i * m + c], sizeof(double)) != 0;
+          dbn += std::memcmp(&ba, &hb[i * m + c], sizeof(double)) != 0;
+        }
+        std::printf("col %d %d %d %zu %zu\n", c, res[c].iterations, rr[c].iterations, dxn, dbn);
+        ok = ok && res[c].converged && rr[c].converged && res[c].iterations == rr[c].iterations && res[c].reduction == rr[c].reduction && dxn == 0 && dbn == 0;
+      }
+    }
+    std::printf("errors_caught %d\n", caught);
+    if (ok && caught == 1) std::printf("fgmres_ok\n");
+    return ok && caught == 1 ? 0 : 1;
+  } catch (Dune::Exception& e) {
+    std::cerr << "Dune exception: " << e.what() << "\n";
+    return 1;
+  }
+}

@@ -7,6 +7,8 @@ consistent vectors.  For every m of --m the same m right-hand sides are solved (
 once; the sequential time of m columns is the sum over the first m).  Prints a table and one JSON line: RHS-iterations per second of
 both, their ratio, and the per-iteration breakdown of a --profile-iters run with the library's event timers (local solve, coarse level,
 operator, orthogonalisation; the single-vector loop has no orthogonalisation timer: its share is the rest of the wall time).
+--solver restartedflexiblegmressolver measures ddm_fgmres_solve_multi / ddm_fgmres_solve instead.  Every row also carries the largest
+reported and the largest recomputed true reduction ||b - A x|| / ||b|| of its columns and the bytes of the Krylov bases.
 --fused-reps R > 0 adds, at m = 8, R timed repetitions of a --profile-iters long block run with the fused Gram-Schmidt kernel and R
 with DDM_GMRES_MULTI_FUSED=0 (median and spread of both).
 
@@ -56,7 +58,8 @@ def build(args):
     tl.rebuild_combined(cfg["mode"])
     tl.schwarz.wait_setup()
     tl.ctx.sync()
-    return dec, tl, cfg, workload + f", GMRES({args.restart}) to {cfg['reduction']:g}"
+    name = "flexible GMRES" if args.solver == "restartedflexiblegmressolver" else "GMRES"
+    return dec, tl, cfg, workload + f", {name}({args.restart}) to {cfg['reduction']:g}"
 
 
 def timers_per_iteration(tl, iters):
@@ -72,7 +75,15 @@ def worker(args):
     t0 = time.perf_counter()
     dec, tl, cfg, workload = build(args)
     log(f"setup {time.perf_counter() - t0:.1f} s, n_o = {tl.rl.n_o}, local engine {tl.schwarz.engine()}")
-    kw = dict(solver="restartedgmressolver", restart=args.restart)
+    kw = dict(solver=args.solver, restart=args.restart)
+    flexible = args.solver == "restartedflexiblegmressolver"
+
+    def true_reductions(X, B0):
+        """||b - A x|| / ||b|| per column, recomputed"""
+        Y = torch.zeros_like(X)
+        tl.op.apply_multi(X, Y)
+        R = B0 - Y
+        return np.sqrt(tl.op.dot_multi(R, R) / tl.op.dot_multi(B0, B0))
     mmax = max(ms_ + ([8] if args.fused_reps > 0 else []))
     rng = np.random.default_rng(args.seed)
     cols = [np.asarray(tl.rl.b, dtype=np.float64)]
@@ -110,12 +121,15 @@ def worker(args):
         res, _, X = tl.solve_multi(B, reduction=cfg["reduction"], maxit=args.maxit, history=False, **kw)
         its = [int(r.iterations) for r in res]
         el = float(res[0].elapsed_s)
+        true_red = true_reductions(X, B)
         seq_its = [s[0] for s in seq[:m]]
         seq_el = sum(s[1] for s in seq[:m])
         row = {"m": m, "iterations": its, "sequential_iterations": seq_its, "converged": all(r.converged for r in res),
                "block_s": el, "sequential_s": seq_el, "ms_per_block_iteration": 1e3 * el / max(its),
                "rhs_iterations_per_s": sum(its) / el, "sequential_rhs_iterations_per_s": sum(seq_its) / seq_el,
-               "ms_per_block_iteration_by_timer": prof}
+               "ms_per_block_iteration_by_timer": prof, "reported_reduction_max": max(float(r.reduction) for r in res),
+               "true_reduction_max": float(np.max(true_red)),
+               "basis_bytes": ((2 if flexible else 1) * min(args.restart, args.maxit) + 2) * int(tl.rl.n_o) * m * 8}
         row["ratio"] = row["rhs_iterations_per_s"] / row["sequential_rhs_iterations_per_s"]
         rows.append(row)
         del X
@@ -150,7 +164,10 @@ def worker(args):
         for k, v in fused.items():
             print(f"m = 8 {k}: wall {v['median_wall']:.3f} ms/it (min {v['wall_ms_per_iteration'][0]:.3f}, max {v['wall_ms_per_iteration'][-1]:.3f}), "
                   f"orthogonalisation {v['median_orthogonalisation']:.3f} ms/it over {v['reps']} repetitions of {P} iterations")
-    out = {"workload": workload, "problem": args.problem, "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "restart": args.restart,
+    for r in rows:
+        print(f"m = {r['m']}: reported reduction (max over the columns) {r['reported_reduction_max']:.3e}, recomputed true reduction {r['true_reduction_max']:.3e}, "
+              f"basis and work blocks {r['basis_bytes'] / 2**20:.1f} MiB")
+    out = {"workload": workload, "solver": args.solver, "problem": args.problem, "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "restart": args.restart,
            "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows, "fused_vs_unfused_m8": fused,
            "what": "rhs_iterations_per_s = sum of the columns' GMRES iterations / wall time of the solve; sequential = the same columns solved one by one "
                    "with ddm_gmres_solve; *_by_timer: ms per (block) iteration of a run of profile_iters iterations (reduction 0) with the event timers on"}
@@ -165,6 +182,8 @@ def main():
     ap.add_argument("--refine", type=int, default=1)
     ap.add_argument("--nev", type=int, default=16)
     ap.add_argument("--restart", type=int, default=100)
+    ap.add_argument("--solver", default="restartedgmressolver", choices=["restartedgmressolver", "restartedflexiblegmressolver"],
+                    help="restartedflexiblegmressolver: ddm_fgmres_solve(_multi), right-preconditioned, two bases")
     ap.add_argument("--m", default="1,4,8,16", help="block widths, comma separated (each <= 32)")
     ap.add_argument("--maxit", type=int, default=1000)
     ap.add_argument("--profile-iters", type=int, default=20, help="iterations of the timer runs")
