@@ -698,19 +698,33 @@ def cg_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditio
     return res, (hist[:res.iterations + 1] if history else None)
 
 
-def cg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, history=True):
-    """m independent CGSolver::apply recurrences at once (ddm_cg_solve_multi).  X, B: (n, m) row-major device tensors (B is overwritten by
-    the defects).  Returns (list of m SolveResult, history): history is (iters + 1) x m with iters the largest iteration count; the
-    entries of a column after it converged are NaN (its history stops there)."""
+def _solve_multi(ctx: Context, fn, op, prec, X, B, reduction, maxit, extra, history):
+    """behind the *_solve_multi wrappers: the result array, the NaN-filled history, the call (extra: the driver's integer arguments after
+    maxit) and the trimming of the history to the largest iteration count"""
     m = _ncols(X, B)
     res = (SolveResult * max(m, 1))()
     hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
-    ctx.check(ctx.lib.ddm_cg_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), _hp(hist), res))
+    ctx.check(fn(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), *extra, _hp(hist), res))
     out = [res[c] for c in range(m)]
     if not history:
         return out, None
     iters = max([r.iterations for r in out] + [0])
     return out, hist[:iters + 1, :m]
+
+
+def _gmres_solve(ctx: Context, fn, op, prec, x, b, reduction, maxit, restart, history):
+    """behind gmres_solve and fgmres_solve"""
+    res = SolveResult()
+    hist = np.zeros(maxit + 1, dtype=np.float64) if history else None
+    ctx.check(fn(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(restart), _hp(hist), ctypes.byref(res)))
+    return res, (hist[:res.iterations + 1] if history else None)
+
+
+def cg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, history=True):
+    """m independent CGSolver::apply recurrences at once (ddm_cg_solve_multi).  X, B: (n, m) row-major device tensors (B is overwritten by
+    the defects).  Returns (list of m SolveResult, history): history is (iters + 1) x m with iters the largest iteration count; the
+    entries of a column after it converged are NaN (its history stops there)."""
+    return _solve_multi(ctx, ctx.lib.ddm_cg_solve_multi, op, prec, X, B, reduction, maxit, (), history)
 
 
 def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,
@@ -718,41 +732,21 @@ def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPr
     """m independent RestartedGMResSolver::apply recurrences at once (ddm_gmres_solve_multi), restart cycles aligned.  X, B: (n, m)
     row-major device tensors (B is overwritten).  Returns what cg_solve_multi returns: (list of m SolveResult, (iters + 1) x m history
     whose entries after a column's last iteration are NaN)."""
-    m = _ncols(X, B)
-    res = (SolveResult * max(m, 1))()
-    hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
-    ctx.check(ctx.lib.ddm_gmres_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), int(restart), _hp(hist), res))
-    out = [res[c] for c in range(m)]
-    if not history:
-        return out, None
-    iters = max([r.iterations for r in out] + [0])
-    return out, hist[:iters + 1, :m]
+    return _solve_multi(ctx, ctx.lib.ddm_gmres_solve_multi, op, prec, X, B, reduction, maxit, (int(restart),), history)
 
 
 def fgmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,
                  history=True):
     """dune-istl RestartedFlexibleGMResSolver::apply ([solver] type = restartedflexiblegmressolver): right-preconditioned restarted
     GMRES that keeps the preconditioned directions; the history holds (estimates of) the TRUE defect norm (ddm_fgmres_solve)."""
-    res = SolveResult()
-    hist = np.zeros(maxit + 1, dtype=np.float64) if history else None
-    ctx.check(ctx.lib.ddm_fgmres_solve(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(restart), _hp(hist),
-                                       ctypes.byref(res)))
-    return res, (hist[:res.iterations + 1] if history else None)
+    return _gmres_solve(ctx, ctx.lib.ddm_fgmres_solve, op, prec, x, b, reduction, maxit, restart, history)
 
 
 def fgmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,
                        history=True):
     """m independent flexible restarted GMRES recurrences at once (ddm_fgmres_solve_multi), restart cycles aligned.  Arguments and
     return value as gmres_solve_multi."""
-    m = _ncols(X, B)
-    res = (SolveResult * max(m, 1))()
-    hist = np.full((maxit + 1, max(m, 1)), np.nan) if history else None
-    ctx.check(ctx.lib.ddm_fgmres_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), int(restart), _hp(hist), res))
-    out = [res[c] for c in range(m)]
-    if not history:
-        return out, None
-    iters = max([r.iterations for r in out] + [0])
-    return out, hist[:iters + 1, :m]
+    return _solve_multi(ctx, ctx.lib.ddm_fgmres_solve_multi, op, prec, X, B, reduction, maxit, (int(restart),), history)
 
 
 def fgmres_defect_multi(ctx: Context, op: NonOverlappingOperator, active, T, B, fused=True):
@@ -769,11 +763,7 @@ def fgmres_defect_multi(ctx: Context, op: NonOverlappingOperator, active, T, B, 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,
                 history=True):
     """dune-istl RestartedGMResSolver::apply ([solver] type = restartedgmressolver, examples/poisson.ini:12-17)."""
-    res = SolveResult()
-    hist = np.zeros(maxit + 1, dtype=np.float64) if history else None
-    ctx.check(ctx.lib.ddm_gmres_solve(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(restart), _hp(hist),
-                                      ctypes.byref(res)))
-    return res, (hist[:res.iterations + 1] if history else None)
+    return _gmres_solve(ctx, ctx.lib.ddm_gmres_solve, op, prec, x, b, reduction, maxit, restart, history)
 
 
 def bicgstab_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, history=True):

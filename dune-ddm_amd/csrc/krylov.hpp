@@ -1,8 +1,10 @@
-// The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES, flexible restarted GMRES and BiCGSTAB for one right-hand
-// side; CG, restarted GMRES and flexible restarted GMRES for m right-hand sides at once (m independent recurrences in one loop, not
-// block-Krylov methods).  All of them share the frame around the loop (solve_result_reset, classify_initial_defect, krylov_finish);
-// the four GMRES drivers run their host arithmetic through the same GmresColumn, which is what keeps the host side of a block column
-// bit-identical to the single-vector solve.  Needs preconditioners.hpp.
+// The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES and BiCGSTAB for one right-hand side; CG and restarted GMRES
+// for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods).  Restarted GMRES is one algorithm
+// with two variants, left-preconditioned and flexible (right-preconditioned, the preconditioned directions kept): one loop per vector
+// count (gmres_loop, gmres_loop_multi) behind the four entry points ddm_gmres_solve, ddm_fgmres_solve, ddm_gmres_solve_multi and
+// ddm_fgmres_solve_multi.  All drivers share the frame around the loop (solve_result_reset, classify_initial_defect, krylov_finish), the
+// block drivers the MultiFrame as well; both GMRES loops run their host arithmetic through the same GmresColumn, which is what keeps
+// the host side of a block column bit-identical to the single-vector solve.  Needs preconditioners.hpp.
 #pragma once
 
 // synchronises the context's stream when it goes out of scope: the Krylov drivers declare it AFTER their work arrays, so that an
@@ -27,6 +29,71 @@ static int krylov_finish(ddm_ctx *ctx, const ddm_combined *prec, int rc, std::ch
   int st = 0;
   rc = ddm_ilu0_status(ctx, prec->schwarz->solver, &st);
   if (!rc && st) rc = fail(ctx, DDM_ENUMERIC, "persistent triangular solve timed out waiting for a level (results invalid)");
+  return rc;
+}
+
+// ---- the frame around every block loop (m right-hand sides) ---------------------------------------
+// What a block driver keeps per column next to its recurrence: the host copy of the device-side mask ctx->mactive (a column that is
+// done is frozen through it) and the latest defect norm.
+struct MultiFrame {
+  ddm_ctx *ctx;
+  const char *what; // the exported function's name, for messages
+  int m;
+  double reduction;
+  double *hist_host; // (maxit + 1) x m, row-major, or null
+  ddm_solve_result *res;
+  int32_t active[MULTI_MAX];
+  double def[MULTI_MAX];
+  int nactive = 0;
+  bool changed = false; // active[] differs from ctx->mactive
+};
+// The initial defects (norm2[c]: the squared norm of column c): def0 and the first history row; a column that needs no iteration is
+// converged and masked out from the start; the mask goes to the device.
+static int multi_start(MultiFrame &f, const double *norm2)
+{
+  for (int c = 0; c < f.m; ++c) {
+    const double def0 = f.def[c] = std::sqrt(norm2[c]);
+    f.res[c].def0 = def0;
+    if (f.hist_host) f.hist_host[c] = def0;
+    const Defect0 d = classify_initial_defect(def0);
+    if (d == Defect0::NaN) return fail(f.ctx, DDM_ENUMERIC, "%s: initial defect is NaN in column %d", f.what, c);
+    f.active[c] = d == Defect0::Go ? 1 : 0;
+    if (!f.active[c]) f.res[c].converged = 1;
+    f.nactive += f.active[c];
+  }
+  return ddm_memcpy_h2d(f.ctx, f.ctx->mactive, f.active, sizeof(int32_t) * (size_t)f.m);
+}
+// A running column after iteration `it`: its defect norm goes into the result and the history; NaN is an error; a column that passes
+// the stop test leaves the mask (multi_upload_mask sends the mask once all columns of the iteration are through).
+static int multi_record(MultiFrame &f, int c, int it, double def)
+{
+  f.def[c] = def;
+  f.res[c].iterations = it;
+  if (f.hist_host) f.hist_host[(int64_t)it * f.m + c] = def;
+  if (!(def == def)) return fail(f.ctx, DDM_ENUMERIC, "%s: defect is NaN in iteration %d (column %d)", f.what, it, c);
+  if (def < f.res[c].def0 * f.reduction || def < 1e-30) {
+    f.res[c].converged = 1;
+    f.active[c] = 0;
+    f.nactive -= 1;
+    f.changed = true;
+  }
+  return DDM_OK;
+}
+static int multi_upload_mask(MultiFrame &f)
+{
+  if (!f.changed) return DDM_OK;
+  f.changed = false;
+  return ddm_memcpy_h2d(f.ctx, f.ctx->mactive, f.active, sizeof(int32_t) * (size_t)f.m);
+}
+// krylov_finish for m columns: the elapsed time and the reduction reached go into every result
+static int multi_finish(MultiFrame &f, const ddm_combined *prec, int rc, std::chrono::steady_clock::time_point t0)
+{
+  double elapsed = 0.0;
+  rc = krylov_finish(f.ctx, prec, rc, t0, &elapsed);
+  for (int c = 0; c < f.m; ++c) {
+    f.res[c].elapsed_s = elapsed;
+    if (f.res[c].def0 >= 1e-30) f.res[c].reduction = f.def[c] / f.res[c].def0;
+  }
   return rc;
 }
 
@@ -166,13 +233,21 @@ extern "C" int ddm_cg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double
   return rc;
 }
 
-// ---- restarted GMRES -----------------------------------------------------------------------------
-// dune-istl RestartedGMResSolver::apply (DUNE 2.10 solvers.hh; not in the snapshot, restated from the
-// published implementation): left preconditioning, modified Gram-Schmidt, Givens rotations; the
-// monitored quantity is the norm of the PRECONDITIONED defect.  Selected by [solver] type =
-// restartedgmressolver in examples/poisson.ini:12-17 (restart = 100) and the default of
-// dune/ddm/twolevel_schwarz.hh:121-130 (restart = 30).  Krylov basis, dots and updates stay on the
-// device; per iteration the i+2 Hessenberg entries are read back for the rotations on the host.
+// ---- restarted GMRES, left-preconditioned and flexible ------------------------------------------------
+// dune-istl RestartedGMResSolver::apply and RestartedFlexibleGMResSolver::apply (DUNE 2.10 solvers.hh; not in the snapshot, restated
+// from the published implementation, in oracle/apply_oracle.py and in tests/fgmres_reference.py): modified Gram-Schmidt in the order
+// k = 0..i, Givens rotations, restart after `restart` iterations.  Selected by [solver] type = restartedgmressolver
+// (examples/poisson.ini:12-17, restart = 100; the default of dune/ddm/twolevel_schwarz.hh:121-130, restart = 30) or
+// restartedflexiblegmressolver.  Krylov basis, dots and updates stay on the device; per iteration the i + 2 Hessenberg entries are
+// read back for the rotations on the host.  The two variants differ at five points (R = min(restart, max(maxit, 1))):
+//                            left                                         flexible
+//   initial and restart norm v0 = M^-1 b, ||v0||: the PRECONDITIONED      ||b||: (an estimate of) the TRUE defect b - A x is
+//                            defect is monitored                          monitored
+//   cycle start              v0 scaled in place                           v0 = b / ||b||
+//   step                     v[i+1] = A v[i] (temporary), w = M^-1 v[i+1] z[i] = M^-1 v[i] (kept), w = A z[i]
+//   update basis             V (R + 1 vectors): x += sum_k y_k v[k]       Z (R more vectors): x += sum_k y_k z[k]; no further
+//                                                                         preconditioner apply, so M^-1 may change between iterations
+//   restart                  b -= A w, then M^-1 and the dot              b -= A w, then the dot of b
 static void gmres_generate_rotation(double dx, double dy, double &cs, double &sn)
 {
   const double ndx = std::fabs(dx), ndy = std::fabs(dy);
@@ -207,7 +282,7 @@ static void gmres_apply_rotation(double &dx, double &dy, double cs, double sn)
 struct GmresColumn {
   int R = 0;
   std::vector<double> H, s, cs, sn;
-  double norm = 0.0, def0 = 0.0;
+  double norm = 0.0;
   int cnt = 0; // Hessenberg columns of the current restart cycle
   void init(int restart)
   {
@@ -249,35 +324,57 @@ struct GmresColumn {
   }
 };
 
-extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
-                               int restart, double *hist_host, ddm_solve_result *res)
+// what the basis (bases) and the work block need against the free device memory: DDM_ENOTIMPL before anything is allocated.
+// blocks: R + 2 (left), 2 R + 2 (flexible) of n x m doubles
+static int gmres_memory_check(ddm_ctx *ctx, const char *what, int64_t blocks, int64_t n, int m)
 {
-  if (!ctx || !op || !prec || !x || !b || !res || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_gmres_solve: bad arguments");
-  const int64_t n = op->n;
-  const int m = restart;
+  size_t free_b = 0, total_b = 0;
+  HIPCHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+  const double need = (double)blocks * (double)(std::max<int64_t>(n, 1) * m) * sizeof(double);
+  if (need > (double)free_b)
+    return fail(ctx, DDM_ENOTIMPL, "%s: the Krylov basis and the work block, %lld blocks of %lld x %d doubles, need %.0f bytes, %zu are free", what,
+                (long long)blocks, (long long)n, m, need, free_b);
+  return DDM_OK;
+}
+
+// the loop for one right-hand side; what: the exported function's name, for messages
+static int gmres_loop(ddm_ctx *ctx, const char *what, bool flexible, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
+                      int restart, double *hist_host, ddm_solve_result *res)
+{
+  const int64_t n = op->n, stride = std::max<int64_t>(n, 1);
+  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis vector beyond that
   const int G = grid_for(n);
-  dbuf<double> V, w, hdev;
-  HIPCHECK(ctx, V.alloc(std::max<int64_t>(n, 1) * (m + 1)));
-  HIPCHECK(ctx, w.alloc(n));
-  HIPCHECK(ctx, hdev.alloc(m + 2));
-  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
-  auto v = [&](int k) { return V + (size_t)k * (size_t)n; };
-  std::vector<double> hcol(m + 2), y(m);
-  GmresColumn q; // Hessenberg matrix, rotations and least-squares right-hand side (the block driver keeps one of these per column)
-  q.init(m);
-  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
-  if (!rc) rc = ddm_combined_apply(ctx, prec, v(0), b); // v0 = M^-1 b
-  double nn = 0.0;
-  if (!rc) rc = dot_device(ctx, n, op->owner, v(0), v(0), hdev);
-  if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
-  if (rc) return rc;
-  q.norm = std::sqrt(nn);
-  const double def0 = q.norm;
+  DDMCHECK(gmres_memory_check(ctx, what, (flexible ? 2 : 1) * (int64_t)R + 2, n, 1));
   solve_result_reset(res);
+  dbuf<double> V, Z, w, hdev;
+  HIPCHECK(ctx, V.alloc(stride * (R + 1)));
+  if (flexible) HIPCHECK(ctx, Z.alloc(stride * R));
+  HIPCHECK(ctx, w.alloc(n));
+  HIPCHECK(ctx, hdev.alloc(R + 2));
+  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
+  auto v = [&](int k) { return V + (size_t)k * (size_t)stride; };
+  auto z = [&](int k) { return Z + (size_t)k * (size_t)stride; };
+  const size_t bytes = sizeof(double) * (size_t)n;
+  std::vector<double> hcol(R + 2), y(R);
+  GmresColumn q; // Hessenberg matrix, rotations and least-squares right-hand side (the block loop keeps one of these per column)
+  q.init(R);
+  // the norm a cycle starts from, b being the defect: left v0 = M^-1 b and ||v0||, flexible ||b||
+  auto start_norm = [&]() {
+    double nn = 0.0;
+    int rc = flexible ? DDM_OK : ddm_combined_apply(ctx, prec, v(0), b);
+    if (!rc) rc = dot_device(ctx, n, op->owner, flexible ? b : v(0), flexible ? b : v(0), hdev);
+    if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
+    q.norm = std::sqrt(nn);
+    return rc;
+  };
+  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
+  if (!rc) rc = start_norm();
+  if (rc) return rc;
+  const double def0 = q.norm;
   res->def0 = def0;
   if (hist_host) hist_host[0] = def0;
   if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
-    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN");
+    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "%s: initial defect is NaN", what);
     res->converged = 1;
     return DDM_OK;
   }
@@ -285,13 +382,19 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
   int j = 0;
   bool conv = false;
   while (j < maxit && !conv && !rc) {
+    if (flexible) HIPCHECK(ctx, hipMemcpyAsync(v(0), b, bytes, hipMemcpyDeviceToDevice, ctx->stream)); // v0 = b / beta
     hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / q.norm, v(0));
     q.start_cycle();
     int i = 0;
-    for (; i < m && j < maxit && !conv; ++i, ++j) {
-      rc = ddm_op_apply(ctx, op, v(i), v(i + 1));                 // v[i+1] = A v[i] (temporary)
-      if (!rc) rc = ddm_combined_apply(ctx, prec, w, v(i + 1));   // w = M^-1 A v[i]
-      for (int k = 0; k <= i && !rc; ++k) {                       // modified Gram-Schmidt
+    for (; i < R && j < maxit && !conv; ++i, ++j) {
+      if (flexible) {
+        rc = ddm_combined_apply(ctx, prec, z(i), v(i));             // z_i = M^-1 v_i, kept
+        if (!rc) rc = ddm_op_apply(ctx, op, z(i), w);               // w = A z_i
+      } else {
+        rc = ddm_op_apply(ctx, op, v(i), v(i + 1));                 // v[i+1] = A v[i] (temporary)
+        if (!rc) rc = ddm_combined_apply(ctx, prec, w, v(i + 1));   // w = M^-1 A v[i]
+      }
+      for (int k = 0; k <= i && !rc; ++k) {                         // modified Gram-Schmidt
         rc = dot_device(ctx, n, op->owner, v(k), w, hdev + k);
         hipLaunchKernelGGL(k_axpy_negdev, dim3(G), dim3(WG), 0, ctx->stream, n, hdev + k, v(k), w);
       }
@@ -300,39 +403,51 @@ extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, dou
       if (rc) break;
       const double wnorm = q.take_column(i, hcol.data(), 1);
       if (std::fabs(wnorm) < 1e-80) {
-        rc = fail(ctx, DDM_ENUMERIC, "breakdown in GMRes - |w| == 0.0 after %d iterations", j);
+        rc = fail(ctx, DDM_ENUMERIC, "%s: breakdown in GMRes - |w| == 0.0 after %d iterations", what, j);
         break;
       }
-      HIPCHECK(ctx, hipMemcpyAsync(v(i + 1), w, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHECK(ctx, hipMemcpyAsync(v(i + 1), w, bytes, hipMemcpyDeviceToDevice, ctx->stream));
       hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / wnorm, v(i + 1));
       const double norm = q.rotate(i);
       res->iterations = j + 1;
       if (hist_host) hist_host[j + 1] = norm;
       if (!(norm == norm)) {
-        rc = fail(ctx, DDM_ENUMERIC, "defect is NaN in iteration %d", j + 1);
+        rc = fail(ctx, DDM_ENUMERIC, "%s: defect is NaN in iteration %d", what, j + 1);
         break;
       }
       if (norm < def0 * reduction || norm < 1e-30) conv = true;
     }
     if (rc) break;
-    // update(w, i, H, s, v): solve the triangular system, w = sum_k y_k v[k]; x += w
+    // update(w, i, H, s, v) of dune-istl: solve the triangular system; w = sum_k y_k u_k with u = v (left) or z (flexible); x += w
     q.back_substitute(y.data());
-    HIPCHECK(ctx, hipMemsetAsync(w, 0, sizeof(double) * (size_t)n, ctx->stream));
-    for (int a = 0; a < i; ++a) hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, y[a], v(a), w);
-    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, w, x);
-    if (!conv && j < maxit) { // restart: b -= A w; v0 = M^-1 b
+    HIPCHECK(ctx, hipMemsetAsync(w, 0, bytes, ctx->stream));
+    for (int a = 0; a < i; ++a) hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, y[a], (const double *)(flexible ? z(a) : v(a)), w);
+    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, (const double *)w, x);
+    if (!conv && j < maxit) { // restart: b -= A w, then the norm of the next cycle
       rc = ddm_op_applyscaleadd(ctx, op, -1.0, w, b);
-      if (!rc) rc = ddm_combined_apply(ctx, prec, v(0), b);
-      if (!rc) rc = dot_device(ctx, n, op->owner, v(0), v(0), hdev);
-      if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
-      q.norm = std::sqrt(nn);
+      if (!rc) rc = start_norm();
     }
   }
-  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in GMRES");
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in %s", what);
   rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
   res->converged = conv ? 1 : 0;
   res->reduction = q.norm / def0;
   return rc;
+}
+
+extern "C" int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
+                               int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !x || !b || !res || x == b || maxit < 0 || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_gmres_solve: bad arguments");
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  return gmres_loop(ctx, "ddm_gmres_solve", false, op, prec, x, b, reduction, maxit, restart, hist_host, res);
+}
+extern "C" int ddm_fgmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, int restart,
+                                double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !x || !b || !res || x == b || maxit < 0 || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve: bad arguments");
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  return gmres_loop(ctx, "ddm_fgmres_solve", true, op, prec, x, b, reduction, maxit, restart, hist_host, res);
 }
 
 // ---- BiCGSTAB ------------------------------------------------------------------------------------
@@ -464,69 +579,43 @@ extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   DDMCHECK(ctx_multi_scratch(ctx));
   HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // search directions p, q: block scratch of the preconditioner object
   double *P = prec->mp, *Q = prec->mq;
-  double bb[MULTI_MAX], def0[MULTI_MAX], def[MULTI_MAX];
-  int32_t active[MULTI_MAX];
+  double bb[MULTI_MAX];
+  MultiFrame f{ctx, "ddm_cg_solve_multi", m, reduction, hist_host, res};
   DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B)); // prec.pre(x, b); b -= A x
   DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, ctx->mscal + 5 * MULTI_MAX));
   DDMCHECK(ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m));
-  int nactive = 0;
-  for (int c = 0; c < m; ++c) {
-    def0[c] = def[c] = std::sqrt(bb[c]);
-    res[c].def0 = def0[c];
-    if (hist_host) hist_host[c] = def0[c];
-    const Defect0 d = classify_initial_defect(def0[c]);
-    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "initial defect is NaN in column %d", c);
-    active[c] = d == Defect0::Go ? 1 : 0;
-    if (!active[c]) res[c].converged = 1;
-    nactive += active[c];
-  }
-  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
+  DDMCHECK(multi_start(f, bb));
   (void)hipStreamSynchronize(ctx->stream);
   const auto t0 = std::chrono::steady_clock::now();
   int rc = DDM_OK;
-  for (int i = 1; i <= maxit && nactive > 0 && !rc; ++i) {
+  for (int i = 1; i <= maxit && f.nactive > 0 && !rc; ++i) {
     rc = cg_multi_step(ctx, op, prec, m, i == 1, X, B, P, Q);
     if (!rc) rc = ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m); // the defects are tested every iteration
-    if (rc) break;
-    bool changed = false;
-    for (int c = 0; c < m; ++c) {
-      if (!active[c]) continue;
-      def[c] = std::sqrt(bb[c]);
-      res[c].iterations = i;
-      if (hist_host) hist_host[(int64_t)i * m + c] = def[c];
-      if (!(def[c] == def[c])) {
-        rc = fail(ctx, DDM_ENUMERIC, "defect is NaN in iteration %d (column %d)", i, c);
-        break;
-      }
-      if (def[c] < def0[c] * reduction || def[c] < 1e-30) {
-        res[c].converged = 1;
-        active[c] = 0;
-        nactive -= 1;
-        changed = true;
-      }
-    }
-    if (!rc && changed && nactive > 0) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
+    for (int c = 0; c < m && !rc; ++c)
+      if (f.active[c]) rc = multi_record(f, c, i, std::sqrt(bb[c]));
+    if (!rc && f.nactive > 0) rc = multi_upload_mask(f);
   }
-  double elapsed = 0.0;
-  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
-  for (int c = 0; c < m; ++c) {
-    res[c].elapsed_s = elapsed;
-    if (def0[c] >= 1e-30) res[c].reduction = def[c] / def0[c];
-  }
-  return rc;
+  return multi_finish(f, prec, rc, t0);
 }
 
-// ---- restarted GMRES for m right-hand sides --------------------------------------------------------
-// Every column is what ddm_gmres_solve computes on it (left preconditioning, modified Gram-Schmidt in the order k = 0..i, its own
-// GmresColumn), while the operator, the preconditioner and the orthogonalisation sweep run once for all columns.  The Krylov basis is
-// min(restart, maxit) + 1 row-major n x m blocks.  Per basis block the sweep is one AXPY over the block with the coefficients in
-// device memory, the block dot (one kernel per column group, k_reduce_final_multi) and one all-reduce of m doubles; with
-// DDM_GMRES_MULTI_FUSED=1 the AXPY and the partial sums of the next dot are one kernel (k_mgs_step_multi: bit-identical, 32 instead
-// of 40 bytes per block entry, but measured slower on MI355X -- DESIGN.md section 9).  The host reads the (i + 2) x m fresh Hessenberg
-// entries once per iteration and nothing else synchronises inside an iteration.
+// ---- restarted GMRES for m right-hand sides, left-preconditioned and flexible ------------------------
+// Every column is what gmres_loop computes on it (the same variant, modified Gram-Schmidt in the order k = 0..i, its own GmresColumn),
+// while the operator, the preconditioner and the orthogonalisation sweep run once for all columns.  Restart cycles are aligned.  A
+// basis is min(restart, maxit) blocks (V: one more) of n x m doubles, row-major.  Per basis block the sweep is one AXPY over the
+// block with the coefficients in device memory, the block dot (one kernel per column group, k_reduce_final_multi) and one all-reduce
+// of m doubles; with DDM_GMRES_MULTI_FUSED=1 the AXPY and the partial sums of the next dot are one kernel (k_mgs_step_multi:
+// bit-identical, 32 instead of 40 bytes per block entry, but measured slower on MI355X -- DESIGN.md section 9).  The host reads the
+// (i + 2) x m fresh Hessenberg entries once per iteration and nothing else synchronises inside an iteration.
 //
-// Frozen columns: a column that passed its test is masked out (ctx->mactive) of every kernel of this driver; the operator and the
-// preconditioner still run on its (stale) basis entries, whose results nobody reads.
+// Frozen columns: a column that passed its test is masked out (ctx->mactive) of every kernel of the loop; the operator and the
+// preconditioner still run on its (stale) basis entries, whose results nobody reads.  The flexible variant writes V through the mask
+// only (v0 comes straight from B), so it zeroes V once per call; the left variant's v0 = M^-1 B is written in every column.
+//
+// The cycle end is k_gmres_update_multi over V (left) or Z (flexible): W = sum_k y_k u_k; X += W.  The restart of the left variant is
+// B -= A W (W = 0 in the columns that are done), v0 = M^-1 B and the block dot; the flexible one puts T = A W into the basis block
+// that the next cycle overwrites anyway and runs k_defect_norm_multi (B -= T and the partial sums of the new defect norms in one
+// pass; frozen columns of B untouched).
+
 // the sweep of iteration i: hdev[k * m + c] = h_{k,i} of column c for k <= i, hdev[(i + 1) * m + c] = <w, w>; w orthogonalised in place
 static int gmres_mgs_multi(ddm_ctx *ctx, ddm_op *op, int m, int i, bool fused, const double *V, int64_t vstride, double *W, double *hdev)
 {
@@ -561,265 +650,6 @@ static bool gmres_multi_fused_env()
   const char *e = std::getenv("DDM_GMRES_MULTI_FUSED");
   return e && e[0] == '1';
 }
-
-extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
-                                     int restart, double *hist_host, ddm_solve_result *res)
-{
-  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
-    return fail(ctx, DDM_EINVAL, "ddm_gmres_solve_multi: bad arguments");
-  DDMCHECK(multi_check(ctx, nrhs, "ddm_gmres_solve_multi"));
-  DDMCHECK(local_status_check(ctx, prec->schwarz));
-  const int m = nrhs;
-  const int64_t n = op->n;
-  const int64_t vstride = std::max<int64_t>(n, 1) * m;
-  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis block beyond that
-  { // R + 1 basis blocks and the work block must fit into the free device memory: refuse before anything is allocated
-    size_t free_b = 0, total_b = 0;
-    HIPCHECK(ctx, hipMemGetInfo(&free_b, &total_b));
-    const double need = ((double)R + 2.0) * (double)vstride * sizeof(double);
-    if (need > (double)free_b)
-      return fail(ctx, DDM_ENOTIMPL, "ddm_gmres_solve_multi: the Krylov basis of %d + 1 blocks of %lld x %d doubles and the work block need %.0f bytes, %zu are free",
-                  R, (long long)n, m, need, free_b);
-  }
-  const bool fused = gmres_multi_fused_env();
-  for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
-  DDMCHECK(ctx_multi_scratch(ctx));
-  dbuf<double> Vb, Wb, hdev, ydev;
-  dbuf<int32_t> cdev; // [0, m): Hessenberg columns per column in the cycle, [m, 2m): keep W (still running)
-  HIPCHECK(ctx, Vb.alloc(vstride * (R + 1)));
-  HIPCHECK(ctx, Wb.alloc(vstride));
-  HIPCHECK(ctx, hdev.alloc((int64_t)(R + 2) * m));
-  HIPCHECK(ctx, ydev.alloc((int64_t)R * m));
-  HIPCHECK(ctx, cdev.alloc(2 * m));
-  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
-  double *V = Vb, *W = Wb;
-  auto v = [&](int k) { return V + (int64_t)k * vstride; };
-  std::vector<GmresColumn> col(m);
-  for (auto &q : col) q.init(R);
-  std::vector<double> hcol((size_t)(R + 2) * m), yhost((size_t)R * m), ycol(R);
-  int32_t active[MULTI_MAX], cflags[2 * MULTI_MAX];
-  MultiCoef coef;
-  const int GE = grid_for(n * m);
-
-  // b -= A x; v0 = M^-1 b; def0 = |v0| per column
-  DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B));
-  DDMCHECK(combined_apply_multi_impl(ctx, prec, m, v(0), B));
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, v(0), v(0), hdev));
-  DDMCHECK(ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m));
-  int nactive = 0;
-  for (int c = 0; c < m; ++c) {
-    col[c].norm = col[c].def0 = std::sqrt(hcol[c]);
-    res[c].def0 = col[c].def0;
-    if (hist_host) hist_host[c] = col[c].def0;
-    const Defect0 d = classify_initial_defect(col[c].def0);
-    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: initial defect is NaN in column %d", c);
-    active[c] = d == Defect0::Go ? 1 : 0;
-    if (!active[c]) res[c].converged = 1;
-    nactive += active[c];
-  }
-  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = DDM_OK, j = 0;
-  while (j < maxit && nactive > 0 && !rc) {
-    for (int c = 0; c < m; ++c) {
-      GmresColumn &q = col[c];
-      q.cnt = 0;
-      coef.a[c] = active[c] ? 1.0 / q.norm : 0.0;
-      if (active[c]) q.start_cycle();
-    }
-    hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)v(0), v(0));
-    int i = 0;
-    for (; i < R && j < maxit && nactive > 0; ++i, ++j) {
-      rc = op_apply_multi(ctx, op, m, v(i), v(i + 1));                      // v[i+1] = A v[i] (temporary)
-      if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, W, v(i + 1));   // w = M^-1 A v[i]
-      if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, fused, V, vstride, W, hdev);
-      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2) * m); // the one read-back of the iteration
-      if (rc) break;
-      for (int c = 0; c < m && !rc; ++c) {
-        coef.a[c] = 0.0;
-        if (!active[c]) continue;
-        const double wnorm = col[c].take_column(i, hcol.data() + c, (size_t)m);
-        if (std::fabs(wnorm) < 1e-80)
-          rc = fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: breakdown in GMRes - |w| == 0.0 after %d iterations (column %d)", j, c);
-        coef.a[c] = 1.0 / wnorm;
-      }
-      if (rc) break;
-      hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)W, v(i + 1));
-      bool changed = false;
-      for (int c = 0; c < m; ++c) {
-        if (!active[c]) continue;
-        GmresColumn &q = col[c];
-        q.rotate(i);
-        res[c].iterations = j + 1;
-        if (hist_host) hist_host[(int64_t)(j + 1) * m + c] = q.norm;
-        if (!(q.norm == q.norm)) {
-          rc = fail(ctx, DDM_ENUMERIC, "ddm_gmres_solve_multi: defect is NaN in iteration %d (column %d)", j + 1, c);
-          break;
-        }
-        if (q.norm < q.def0 * reduction || q.norm < 1e-30) {
-          res[c].converged = 1;
-          active[c] = 0;
-          nactive -= 1;
-          changed = true;
-        }
-      }
-      if (rc) break;
-      if (changed) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
-      if (rc) break;
-    }
-    if (rc) break;
-    // update(w, i, H, s, v) per column: solve its triangular system of cnt_c unknowns; W_c = sum_k y_k v[k]; X_c += W_c
-    std::fill(yhost.begin(), yhost.end(), 0.0);
-    for (int c = 0; c < m; ++c) {
-      GmresColumn &q = col[c];
-      cflags[c] = q.cnt;
-      cflags[m + c] = active[c];
-      q.back_substitute(ycol.data());
-      for (int a = 0; a < q.cnt; ++a) yhost[(size_t)a * m + c] = ycol[a];
-    }
-    rc = ddm_memcpy_h2d(ctx, ydev, yhost.data(), sizeof(double) * (size_t)i * m);
-    if (!rc) rc = ddm_memcpy_h2d(ctx, cdev, cflags, sizeof(int32_t) * (size_t)(2 * m));
-    if (rc) break;
-    {
-      ScopedTimer t(ctx, "GMRES/update");
-      hipLaunchKernelGGL(k_gmres_update_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)cdev, (const int32_t *)(cdev + m), (const double *)ydev,
-                         (const double *)V, vstride, W, X);
-    }
-    if (nactive > 0 && j < maxit) { // restart: b -= A w (w = 0 in the columns that are done); v0 = M^-1 b
-      rc = op_applyscaleadd_multi(ctx, op, m, -1.0, W, B);
-      if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, v(0), B);
-      if (!rc) rc = dot_multi_device(ctx, n, op->owner, m, v(0), v(0), hdev);
-      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m);
-      for (int c = 0; c < m && !rc; ++c)
-        if (active[c]) col[c].norm = std::sqrt(hcol[c]);
-    }
-  }
-  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_gmres_solve_multi");
-  double elapsed = 0.0;
-  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
-  for (int c = 0; c < m; ++c) {
-    res[c].elapsed_s = elapsed;
-    if (col[c].def0 >= 1e-30) res[c].reduction = col[c].norm / col[c].def0;
-  }
-  return rc;
-}
-
-// ---- flexible restarted GMRES ------------------------------------------------------------------------------------------------------
-// dune-istl RestartedFlexibleGMResSolver::apply ([solver] type = restartedflexiblegmressolver; DUNE 2.10 solvers.hh, not in the
-// snapshot -- the algorithm is written out in include/ddm_hip.h and restated in tests/fgmres_reference.py): RIGHT preconditioning
-// with the preconditioned directions z_i = M^-1 v_i kept next to the Krylov basis, so that the solution update x += sum_k y_k z_k
-// needs no further preconditioner apply and M^-1 may be a different operator in every iteration; modified Gram-Schmidt and the Givens
-// rotations of ddm_gmres_solve (the same GmresColumn); the monitored quantity |s_{i+1}| estimates the norm of the TRUE defect
-// b - A x.  Two bases: V with min(restart, maxit) + 1 and Z with min(restart, maxit) vectors, and one work vector.
-
-// what the two bases and the work block need against the free device memory: DDM_ENOTIMPL before anything is allocated
-static int fgmres_memory_check(ddm_ctx *ctx, const char *what, int R, int64_t n, int m)
-{
-  size_t free_b = 0, total_b = 0;
-  HIPCHECK(ctx, hipMemGetInfo(&free_b, &total_b));
-  const double need = (2.0 * (double)R + 2.0) * (double)(std::max<int64_t>(n, 1) * m) * sizeof(double);
-  if (need > (double)free_b)
-    return fail(ctx, DDM_ENOTIMPL, "%s: the two bases of %d + 1 and %d blocks of %lld x %d doubles and the work block need %.0f bytes, %zu are free", what, R, R,
-                (long long)n, m, need, free_b);
-  return DDM_OK;
-}
-
-extern "C" int ddm_fgmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, int restart,
-                                double *hist_host, ddm_solve_result *res)
-{
-  if (!ctx || !op || !prec || !x || !b || !res || x == b || maxit < 0 || restart < 1) return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve: bad arguments");
-  DDMCHECK(local_status_check(ctx, prec->schwarz));
-  const int64_t n = op->n, stride = std::max<int64_t>(n, 1);
-  const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations
-  const int G = grid_for(n);
-  DDMCHECK(fgmres_memory_check(ctx, "ddm_fgmres_solve", R, n, 1));
-  solve_result_reset(res);
-  dbuf<double> V, Z, w, hdev;
-  HIPCHECK(ctx, V.alloc(stride * (R + 1)));
-  HIPCHECK(ctx, Z.alloc(stride * R));
-  HIPCHECK(ctx, w.alloc(n));
-  HIPCHECK(ctx, hdev.alloc(R + 2));
-  StreamDrain drain{ctx}; // (declared after the buffers: from here on every return waits for the stream before they are released)
-  auto v = [&](int k) { return V + (size_t)k * (size_t)stride; };
-  auto z = [&](int k) { return Z + (size_t)k * (size_t)stride; };
-  const size_t bytes = sizeof(double) * (size_t)n;
-  std::vector<double> hcol(R + 2), y(R);
-  GmresColumn q;
-  q.init(R);
-  double nn = 0.0;
-  int rc = ddm_op_applyscaleadd(ctx, op, -1.0, x, b); // b -= A x
-  if (!rc) rc = dot_device(ctx, n, op->owner, b, b, hdev);
-  if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
-  if (rc) return rc;
-  q.norm = std::sqrt(nn); // beta = ||b||: the true defect norm
-  const double def0 = q.norm;
-  res->def0 = def0;
-  if (hist_host) hist_host[0] = def0;
-  if (const Defect0 d = classify_initial_defect(def0); d != Defect0::Go) {
-    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: initial defect is NaN");
-    res->converged = 1;
-    return DDM_OK;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  int j = 0;
-  bool conv = false;
-  while (j < maxit && !conv && !rc) {
-    HIPCHECK(ctx, hipMemcpyAsync(v(0), b, bytes, hipMemcpyDeviceToDevice, ctx->stream)); // v0 = b / beta
-    hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / q.norm, v(0));
-    q.start_cycle();
-    int i = 0;
-    for (; i < R && j < maxit && !conv; ++i, ++j) {
-      rc = ddm_combined_apply(ctx, prec, z(i), v(i));   // z_i = M^-1 v_i, kept
-      if (!rc) rc = ddm_op_apply(ctx, op, z(i), w);     // w = A z_i
-      for (int k = 0; k <= i && !rc; ++k) {             // modified Gram-Schmidt
-        rc = dot_device(ctx, n, op->owner, v(k), w, hdev + k);
-        hipLaunchKernelGGL(k_axpy_negdev, dim3(G), dim3(WG), 0, ctx->stream, n, hdev + k, v(k), w);
-      }
-      if (!rc) rc = dot_device(ctx, n, op->owner, w, w, hdev + i + 1);
-      if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2));
-      if (rc) break;
-      const double wnorm = q.take_column(i, hcol.data(), 1);
-      if (std::fabs(wnorm) < 1e-80) {
-        rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: breakdown in GMRes - |w| == 0.0 after %d iterations", j);
-        break;
-      }
-      HIPCHECK(ctx, hipMemcpyAsync(v(i + 1), w, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-      hipLaunchKernelGGL(k_scal, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0 / wnorm, v(i + 1));
-      const double norm = q.rotate(i);
-      res->iterations = j + 1;
-      if (hist_host) hist_host[j + 1] = norm;
-      if (!(norm == norm)) {
-        rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve: defect is NaN in iteration %d", j + 1);
-        break;
-      }
-      if (norm < def0 * reduction || norm < 1e-30) conv = true;
-    }
-    if (rc) break;
-    // solve the triangular system; w = sum_k y_k z_k; x += w (no preconditioner apply: the z_k were kept)
-    q.back_substitute(y.data());
-    HIPCHECK(ctx, hipMemsetAsync(w, 0, bytes, ctx->stream));
-    for (int a = 0; a < i; ++a) hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, y[a], (const double *)z(a), w);
-    hipLaunchKernelGGL(k_axpy, dim3(G), dim3(WG), 0, ctx->stream, n, 1.0, (const double *)w, x);
-    if (!conv && j < maxit) { // restart: b -= A w; beta = ||b||
-      rc = ddm_op_applyscaleadd(ctx, op, -1.0, w, b);
-      if (!rc) rc = dot_device(ctx, n, op->owner, b, b, hdev);
-      if (!rc) rc = ddm_memcpy_d2h(ctx, &nn, hdev, sizeof(double));
-      q.norm = std::sqrt(nn);
-    }
-  }
-  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_fgmres_solve");
-  rc = krylov_finish(ctx, prec, rc, t0, &res->elapsed_s);
-  res->converged = conv ? 1 : 0;
-  res->reduction = q.norm / def0;
-  return rc;
-}
-
-// ---- flexible restarted GMRES for m right-hand sides ---------------------------------------------------------------------------------
-// Every column is what ddm_fgmres_solve computes on it, under the rules of ddm_gmres_solve_multi: aligned restart cycles, columns
-// frozen by mask, one read-back of the fresh Hessenberg entries per iteration, one all-reduce of m doubles per orthogonalisation step
-// (gmres_mgs_multi).  The cycle end is k_gmres_update_multi pointed at Z (W = sum_k y_k z_k; X += W), one block operator apply
-// T = A W into the basis block that the next cycle overwrites anyway, and k_defect_norm_multi (B -= T and the partial sums of the
-// new defect norms in one pass; frozen columns of B untouched).
 
 // B -= T in the columns of ctx->mactive; out (m device doubles) = owner-masked <B_c, B_c>, summed over the ranks
 static int fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *T, double *B, double *out)
@@ -861,25 +691,21 @@ extern "C" int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const
   return ddm_memcpy_d2h(ctx, norm2_host, out, sizeof(double) * (size_t)m);
 }
 
-extern "C" int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
-                                      int restart, double *hist_host, ddm_solve_result *res)
+// the loop for m right-hand sides; what: the exported function's name, for messages
+static int gmres_loop_multi(ddm_ctx *ctx, const char *what, bool flexible, ddm_op *op, ddm_combined *prec, int m, double *X, double *B, double reduction,
+                            int maxit, int restart, double *hist_host, ddm_solve_result *res)
 {
-  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
-    return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve_multi: bad arguments");
-  DDMCHECK(multi_check(ctx, nrhs, "ddm_fgmres_solve_multi"));
-  DDMCHECK(local_status_check(ctx, prec->schwarz));
-  const int m = nrhs;
   const int64_t n = op->n;
   const int64_t vstride = std::max<int64_t>(n, 1) * m;
   const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis block beyond that
-  DDMCHECK(fgmres_memory_check(ctx, "ddm_fgmres_solve_multi", R, n, m));
+  DDMCHECK(gmres_memory_check(ctx, what, (flexible ? 2 : 1) * (int64_t)R + 2, n, m));
   const bool fused = gmres_multi_fused_env();
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
   dbuf<double> Vb, Zb, Wb, hdev, ydev;
   dbuf<int32_t> cdev; // [0, m): Hessenberg columns per column in the cycle, [m, 2m): keep W (still running)
   HIPCHECK(ctx, Vb.alloc(vstride * (R + 1)));
-  HIPCHECK(ctx, Zb.alloc(vstride * R));
+  if (flexible) HIPCHECK(ctx, Zb.alloc(vstride * R));
   HIPCHECK(ctx, Wb.alloc(vstride));
   HIPCHECK(ctx, hdev.alloc((int64_t)(R + 2) * m));
   HIPCHECK(ctx, ydev.alloc((int64_t)R * m));
@@ -891,84 +717,64 @@ extern "C" int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *pr
   std::vector<GmresColumn> col(m);
   for (auto &q : col) q.init(R);
   std::vector<double> hcol((size_t)(R + 2) * m), yhost((size_t)R * m), ycol(R);
-  int32_t active[MULTI_MAX], cflags[2 * MULTI_MAX];
+  int32_t cflags[2 * MULTI_MAX];
   MultiCoef coef;
+  MultiFrame f{ctx, what, m, reduction, hist_host, res};
   const int GE = grid_for(n * m);
-  // the basis is written through the mask only: a frozen column's entries, which the preconditioner still reads, start as zeros
-  HIPCHECK(ctx, hipMemsetAsync(V, 0, sizeof(double) * (size_t)(vstride * (R + 1)), ctx->stream));
+  // flexible: the basis is written through the mask only: a frozen column's entries, which the preconditioner still reads, start as zeros
+  if (flexible) HIPCHECK(ctx, hipMemsetAsync(V, 0, sizeof(double) * (size_t)(vstride * (R + 1)), ctx->stream));
 
-  // b -= A x; def0 = |b| per column
+  // b -= A x, then the norm the first cycle starts from, per column: left v0 = M^-1 b and |v0|, flexible |b|
   DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B));
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, hdev));
+  if (!flexible) DDMCHECK(combined_apply_multi_impl(ctx, prec, m, v(0), B));
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, flexible ? B : v(0), flexible ? B : v(0), hdev));
   DDMCHECK(ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m));
-  int nactive = 0;
-  for (int c = 0; c < m; ++c) {
-    col[c].norm = col[c].def0 = std::sqrt(hcol[c]);
-    res[c].def0 = col[c].def0;
-    if (hist_host) hist_host[c] = col[c].def0;
-    const Defect0 d = classify_initial_defect(col[c].def0);
-    if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: initial defect is NaN in column %d", c);
-    active[c] = d == Defect0::Go ? 1 : 0;
-    if (!active[c]) res[c].converged = 1;
-    nactive += active[c];
-  }
-  DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m));
+  DDMCHECK(multi_start(f, hcol.data()));
+  for (int c = 0; c < m; ++c) col[c].norm = res[c].def0;
   const auto t0 = std::chrono::steady_clock::now();
   int rc = DDM_OK, j = 0;
-  while (j < maxit && nactive > 0 && !rc) {
+  while (j < maxit && f.nactive > 0 && !rc) {
     for (int c = 0; c < m; ++c) {
       GmresColumn &q = col[c];
       q.cnt = 0;
-      coef.a[c] = active[c] ? 1.0 / q.norm : 0.0;
-      if (active[c]) q.start_cycle();
+      coef.a[c] = f.active[c] ? 1.0 / q.norm : 0.0;
+      if (f.active[c]) q.start_cycle();
     }
-    hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)B, v(0)); // v0 = b / beta
+    // v0 = (left: M^-1 b, in place; flexible: b) / norm
+    hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)(flexible ? B : v(0)), v(0));
     int i = 0;
-    for (; i < R && j < maxit && nactive > 0; ++i, ++j) {
-      rc = combined_apply_multi_impl(ctx, prec, m, z(i), v(i));            // z_i = M^-1 v_i, kept
-      if (!rc) rc = op_apply_multi(ctx, op, m, z(i), W);                    // w = A z_i
+    for (; i < R && j < maxit && f.nactive > 0; ++i, ++j) {
+      if (flexible) {
+        rc = combined_apply_multi_impl(ctx, prec, m, z(i), v(i));             // z_i = M^-1 v_i, kept
+        if (!rc) rc = op_apply_multi(ctx, op, m, z(i), W);                    // w = A z_i
+      } else {
+        rc = op_apply_multi(ctx, op, m, v(i), v(i + 1));                      // v[i+1] = A v[i] (temporary)
+        if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, W, v(i + 1));   // w = M^-1 A v[i]
+      }
       if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, fused, V, vstride, W, hdev);
       if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2) * m); // the one read-back of the iteration
       if (rc) break;
       for (int c = 0; c < m && !rc; ++c) {
         coef.a[c] = 0.0;
-        if (!active[c]) continue;
+        if (!f.active[c]) continue;
         const double wnorm = col[c].take_column(i, hcol.data() + c, (size_t)m);
-        if (std::fabs(wnorm) < 1e-80)
-          rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: breakdown in GMRes - |w| == 0.0 after %d iterations (column %d)", j, c);
+        if (std::fabs(wnorm) < 1e-80) rc = fail(ctx, DDM_ENUMERIC, "%s: breakdown in GMRes - |w| == 0.0 after %d iterations (column %d)", what, j, c);
         coef.a[c] = 1.0 / wnorm;
       }
       if (rc) break;
       hipLaunchKernelGGL(k_scale_into_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, coef, (const double *)W, v(i + 1));
-      bool changed = false;
-      for (int c = 0; c < m; ++c) {
-        if (!active[c]) continue;
-        GmresColumn &q = col[c];
-        q.rotate(i);
-        res[c].iterations = j + 1;
-        if (hist_host) hist_host[(int64_t)(j + 1) * m + c] = q.norm;
-        if (!(q.norm == q.norm)) {
-          rc = fail(ctx, DDM_ENUMERIC, "ddm_fgmres_solve_multi: defect is NaN in iteration %d (column %d)", j + 1, c);
-          break;
-        }
-        if (q.norm < q.def0 * reduction || q.norm < 1e-30) {
-          res[c].converged = 1;
-          active[c] = 0;
-          nactive -= 1;
-          changed = true;
-        }
-      }
-      if (rc) break;
-      if (changed) rc = ddm_memcpy_h2d(ctx, ctx->mactive, active, sizeof(int32_t) * (size_t)m);
+      for (int c = 0; c < m && !rc; ++c)
+        if (f.active[c]) rc = multi_record(f, c, j + 1, col[c].rotate(i));
+      if (!rc) rc = multi_upload_mask(f);
       if (rc) break;
     }
     if (rc) break;
-    // per column: solve its triangular system of cnt_c unknowns; W_c = sum_k y_k z_k; X_c += W_c
+    // update(w, i, H, s, v) per column: solve its triangular system of cnt_c unknowns; W_c = sum_k y_k u_k (u = v or z); X_c += W_c
     std::fill(yhost.begin(), yhost.end(), 0.0);
     for (int c = 0; c < m; ++c) {
       GmresColumn &q = col[c];
       cflags[c] = q.cnt;
-      cflags[m + c] = active[c];
+      cflags[m + c] = f.active[c];
       q.back_substitute(ycol.data());
       for (int a = 0; a < q.cnt; ++a) yhost[(size_t)a * m + c] = ycol[a];
     }
@@ -978,22 +784,41 @@ extern "C" int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *pr
     {
       ScopedTimer t(ctx, "GMRES/update");
       hipLaunchKernelGGL(k_gmres_update_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)cdev, (const int32_t *)(cdev + m), (const double *)ydev,
-                         (const double *)Z, vstride, W, X);
+                         (const double *)(flexible ? Z : V), vstride, W, X);
     }
-    if (nactive > 0 && j < maxit) { // restart: t = A w into v0 (overwritten by the next cycle); b -= t and beta = |b| in the running columns
-      rc = op_apply_multi(ctx, op, m, W, v(0));
-      if (!rc) rc = fgmres_defect_multi(ctx, op, m, v(0), B, hdev);
+    if (f.nactive > 0 && j < maxit) { // restart: the defect and the norm of the next cycle in the running columns
+      if (flexible) {
+        rc = op_apply_multi(ctx, op, m, W, v(0));                             // t = A w into v0 (overwritten by the next cycle)
+        if (!rc) rc = fgmres_defect_multi(ctx, op, m, v(0), B, hdev);         // b -= t and |b|
+      } else {
+        rc = op_applyscaleadd_multi(ctx, op, m, -1.0, W, B);                  // b -= A w (w = 0 in the columns that are done)
+        if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, v(0), B);       // v0 = M^-1 b
+        if (!rc) rc = dot_multi_device(ctx, n, op->owner, m, v(0), v(0), hdev);
+      }
       if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)m);
       for (int c = 0; c < m && !rc; ++c)
-        if (active[c]) col[c].norm = std::sqrt(hcol[c]);
+        if (f.active[c]) col[c].norm = std::sqrt(hcol[c]);
     }
   }
-  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in ddm_fgmres_solve_multi");
-  double elapsed = 0.0;
-  rc = krylov_finish(ctx, prec, rc, t0, &elapsed);
-  for (int c = 0; c < m; ++c) {
-    res[c].elapsed_s = elapsed;
-    if (col[c].def0 >= 1e-30) res[c].reduction = col[c].norm / col[c].def0;
-  }
-  return rc;
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in %s", what);
+  return multi_finish(f, prec, rc, t0);
+}
+
+extern "C" int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                                     int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
+    return fail(ctx, DDM_EINVAL, "ddm_gmres_solve_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_gmres_solve_multi"));
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  return gmres_loop_multi(ctx, "ddm_gmres_solve_multi", false, op, prec, nrhs, X, B, reduction, maxit, restart, hist_host, res);
+}
+extern "C" int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                                      int restart, double *hist_host, ddm_solve_result *res)
+{
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0 || restart < 1)
+    return fail(ctx, DDM_EINVAL, "ddm_fgmres_solve_multi: bad arguments");
+  DDMCHECK(multi_check(ctx, nrhs, "ddm_fgmres_solve_multi"));
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  return gmres_loop_multi(ctx, "ddm_fgmres_solve_multi", true, op, prec, nrhs, X, B, reduction, maxit, restart, hist_host, res);
 }

@@ -208,52 +208,43 @@ protected:
   }
 };
 
-// [solver] type = restartedgmressolver (default of TwoLevelSchwarzSolver, dune/ddm/twolevel_schwarz.hh:121-130)
-template <class X>
-class HipRestartedGMResSolver : public HipKrylovSolverBase<X> {
+// Restarted GMRES, left-preconditioned or flexible: the two solvers below are this class with the two C functions they call
+template <class X, decltype(&ddm_gmres_solve) SOLVE, decltype(&ddm_gmres_solve_multi) SOLVE_BLOCK>
+class HipRestartedGMResSolverBase : public HipKrylovSolverBase<X> {
 public:
-  HipRestartedGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int restart, int maxit, int verbose = 0)
+  HipRestartedGMResSolverBase(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int restart, int maxit, int verbose = 0)
       : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), restart_(restart) {}
-  HipRestartedGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
-      : HipRestartedGMResSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
-
-  using HipKrylovSolverBase<X>::apply;
+  HipRestartedGMResSolverBase(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
+      : HipRestartedGMResSolverBase(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
 
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
   {
-    return ddm_gmres_solve(ctx, o, p, x, b, reduction, this->maxit_, restart_, nullptr, r);
+    return SOLVE(ctx, o, p, x, b, reduction, this->maxit_, restart_, nullptr, r);
   }
   int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
   {
-    return ddm_gmres_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, nullptr, r);
+    return SOLVE_BLOCK(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, nullptr, r);
   }
   int restart_;
+};
+
+// [solver] type = restartedgmressolver (default of TwoLevelSchwarzSolver, dune/ddm/twolevel_schwarz.hh:121-130)
+template <class X>
+class HipRestartedGMResSolver : public HipRestartedGMResSolverBase<X, &ddm_gmres_solve, &ddm_gmres_solve_multi> {
+public:
+  using HipRestartedGMResSolverBase<X, &ddm_gmres_solve, &ddm_gmres_solve_multi>::HipRestartedGMResSolverBase; // both constructors
+  using HipKrylovSolverBase<X>::apply;
 };
 
 // [solver] type = restartedflexiblegmressolver: dune-istl RestartedFlexibleGMResSolver::apply -- right-preconditioned, the TRUE defect is
 // monitored (as in HipCGSolver), and the preconditioner may change between iterations (ddm_schwarz_set_multi_precision); twice the
 // basis memory of HipRestartedGMResSolver
 template <class X>
-class HipRestartedFlexibleGMResSolver : public HipKrylovSolverBase<X> {
+class HipRestartedFlexibleGMResSolver : public HipRestartedGMResSolverBase<X, &ddm_fgmres_solve, &ddm_fgmres_solve_multi> {
 public:
-  HipRestartedFlexibleGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int restart, int maxit, int verbose = 0)
-      : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), restart_(restart) {}
-  HipRestartedFlexibleGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
-      : HipRestartedFlexibleGMResSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
-
+  using HipRestartedGMResSolverBase<X, &ddm_fgmres_solve, &ddm_fgmres_solve_multi>::HipRestartedGMResSolverBase; // both constructors
   using HipKrylovSolverBase<X>::apply;
-
-protected:
-  int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
-  {
-    return ddm_fgmres_solve(ctx, o, p, x, b, reduction, this->maxit_, restart_, nullptr, r);
-  }
-  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
-  {
-    return ddm_fgmres_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, nullptr, r);
-  }
-  int restart_;
 };
 
 // [solver] type = bicgstabsolver: dune-istl BiCGSTABSolver::apply

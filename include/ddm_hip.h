@@ -414,6 +414,7 @@ int ddm_cg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double
  * monitored norm is that of the preconditioned defect): [solver] type = restartedgmressolver,
  * examples/poisson.ini:12-17; default of dune/ddm/twolevel_schwarz.hh:121-130.  Needed for the
  * non-symmetric preconditioners (restricted Schwarz, multiplicative combination) and operators.
+ * Errors and memory as ddm_fgmres_solve below, with ONE basis: min(restart, maxit) + 1 vectors plus one work vector.
  * hist_host (may be NULL): maxit+1 doubles. */
 int ddm_gmres_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit,
                     int restart, double *hist_host, ddm_solve_result *res);

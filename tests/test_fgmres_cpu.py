@@ -41,6 +41,8 @@ def test_fgmres_rejects_bad_arguments_without_a_device(ddm, nrhs, maxit, restart
     assert "ddm_fgmres_solve_multi" in lib.ddm_last_error(None).decode()
     assert lib.ddm_fgmres_solve(None, None, None, None, None, 1e-10, maxit, restart, None, res) == ddm.DDM_EINVAL
     assert "ddm_fgmres_solve:" in lib.ddm_last_error(None).decode()
+    assert lib.ddm_gmres_solve(None, None, None, None, None, 1e-10, maxit, restart, None, res) == ddm.DDM_EINVAL   # the same checks as its siblings
+    assert "ddm_gmres_solve:" in lib.ddm_last_error(None).decode()
     assert lib.ddm_schwarz_set_multi_precision(None, 1) == ddm.DDM_EINVAL
     assert lib.ddm_fgmres_defect_multi(None, None, nrhs, None, None, None, 1, None) == ddm.DDM_EINVAL
 

@@ -204,7 +204,8 @@ def test_column0_matches_oracle(ddm, key):
 
 def test_errors_are_host_side_refusals(ddm):
     """A set local-solve status word, a NaN right-hand side and a basis larger than the device's memory: all refused by the host
-    before or between launches; the context works afterwards."""
+    before or between launches; the context works afterwards.  Then ddm_gmres_solve on one column: bad arguments (restart 0, maxit -1,
+    x == b, a null x), the status word and a basis larger than the free memory are refused in the same way."""
     import torch
     cfg, dec, tl = _make(ddm, "b")
     lib, h = tl.ctx.lib, tl.ctx.h
@@ -245,6 +246,39 @@ def test_errors_are_host_side_refusals(ddm):
     assert torch.cuda.mem_get_info()[0] >= free_before - (64 << 20)             # nothing of that size was allocated
     rc, msg, X2, _ = raw(Bh, MAXIT, 6)                                          # the context is still usable
     assert rc == ddm.DDM_OK and torch.equal(X2, X), msg
+
+    # ddm_gmres_solve on column 0 refuses the same things: DDM_EINVAL before any device work (a poisoned x stays poisoned, b stays the
+    # right-hand side), a set status word on entry, a basis larger than the free device memory
+    b0 = tl.to_device(Bh[:, 0].copy())
+    b1 = b0.clone()
+    x1 = torch.full_like(b1, 123.456)
+    poison = x1.clone()
+
+    def single(xp, bp, maxit, restart):
+        rc = lib.ddm_gmres_solve(h, tl.op.h, tl.prec.h, xp, bp, 1e-10, maxit, restart, None, res)
+        tl.ctx.sync()
+        return rc, lib.ddm_last_error(h).decode()
+
+    for args in [(x1.data_ptr(), b1.data_ptr(), 50, 0), (x1.data_ptr(), b1.data_ptr(), -1, 6), (x1.data_ptr(), x1.data_ptr(), 50, 6), (None, b1.data_ptr(), 50, 6)]:
+        rc, msg = single(*args)
+        assert rc == ddm.DDM_EINVAL and "ddm_gmres_solve:" in msg, (args, rc, msg)
+    assert torch.equal(x1, poison) and torch.equal(b1, b0)
+    assert lib.ddm_ilu0_set_status(F, 1) == ddm.DDM_OK
+    try:
+        assert single(x1.data_ptr(), b1.data_ptr(), 50, 6)[0] == ddm.DDM_ENUMERIC
+        assert torch.equal(x1, poison) and torch.equal(b1, b0)                  # refused on entry: b is still the right-hand side
+    finally:
+        assert lib.ddm_ilu0_set_status(F, 0) == ddm.DDM_OK
+    free = torch.cuda.mem_get_info()[0]
+    big1 = int(free // (n_o * 8)) + 1                                           # (big1 + 2) vectors of n_o doubles exceed the free memory
+    if big1 < 2**31 - 8:
+        rc, msg = single(x1.data_ptr(), b1.data_ptr(), big1, big1)
+        assert rc == ddm.DDM_ENOTIMPL and "bytes" in msg and "ddm_gmres_solve:" in msg and str((big1 + 2) * n_o * 8) in msg, msg
+        assert torch.cuda.mem_get_info()[0] >= free - (64 << 20)               # nothing of that size was allocated
+        assert torch.equal(x1, poison) and torch.equal(b1, b0)
+    x1.zero_()
+    rc, msg = single(x1.data_ptr(), b1.data_ptr(), MAXIT, 6)                    # a normal solve afterwards converges
+    assert rc == ddm.DDM_OK and res[0].converged == 1 and res[0].reduction <= 1e-10, msg
     tl.prec.check_status()
     tl.ctx.close()
 
