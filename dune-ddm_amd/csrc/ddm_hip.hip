@@ -30,7 +30,9 @@
 #include "trsv_pipe.hpp"        // pipe engine of the ILU(0) solve: kernels and host schedule.  Needs host_vec.hpp.
 #include "trsv_box.hpp"         // box engine of the ILU(0) solve: kernels and host schedule.  Needs nothing.
 #include "sparse_chol_host.hpp" // namespace chol: host sparse Cholesky / LU (ordering, symbolic, numeric).  Needs nothing.
-#include "sn_chol.hpp"          // namespace sn: supernodal factor on the device (pulls in sn_chol_host.hpp, sn_solve1.hpp).  Needs device_buffer.hpp, sparse_chol_host.hpp.
+#include "sn_chol.hpp"          // namespace sn: supernodal factor on the device, factorisation and block-solve kernels (pulls in sn_chol_host.hpp).  Needs device_buffer.hpp, sparse_chol_host.hpp.
+#include "sn_solve1.hpp"        // namespace sn: its single-vector solve kernels, TopPlan, ChainDev.  Needs sn_chol.hpp.
+#include "sn_factor.hpp"        // namespace sn: its host driver: Factor, build, factorize, reserve, solve.  Needs sn_chol.hpp, sn_solve1.hpp.
 #include "synth_host.hpp"       // namespace synth: Q1 matrix rows on the host.  Needs nothing.
 
 using namespace ddm;
@@ -38,7 +40,14 @@ using namespace ddm;
 // ---- the objects of include/ddm_hip.h --------------------------------------------------------------
 #include "context.hpp"          // ddm_ctx, fail and the *CHECK macros, grid sizes, upload, timers, RCCL plumbing, all-reduce, ddm_ctx_* / malloc / memcpy / timing.  Needs the building blocks.
 #include "csr.hpp"              // ddm_csr, host_threads, row blocks, tiled row order, csr_adopt, products up to ddm_csr_mm.  Needs context.hpp.
-#include "local_solver.hpp"     // ddm_ilu0: ILU(0) and direct factors, their solve engines, ddm_ilu0_* / ddm_chol_* / ddm_direct_*.  Needs csr.hpp, trsv_*.hpp, sn_chol.hpp.
+#include "local_factor.hpp"     // ddm_ilu0 and its engine parts, SolveKey / GraphCache, engine choice, join of the background build.  Needs csr.hpp, trsv_*.hpp, sn_factor.hpp.
+#include "tri_levels.hpp"       // sliced-ELL level schedules of ILU(0): build_schedule, enqueue_tri, enqueue_multi_levels(_f32).  Needs local_factor.hpp.
+#include "tri_csr.hpp"          // CSR level schedules of the host direct factor: supernodes, build_csr_schedule, enqueue_tri_csr, enqueue_multi_levels_csr.  Needs local_factor.hpp.
+#include "engine_xcd2.hpp"      // xcd2 engine: build_xcd_schedule, enqueue_xcd2.  Needs local_factor.hpp.
+#include "engine_pipe.hpp"      // pipe engine: build_pipe_schedule, enqueue_pipe.  Needs local_factor.hpp, trsv_pipe.hpp.
+#include "engine_box.hpp"       // box engine: build_box_engine, enqueue_box, ddm_ilu0_box_check.  Needs local_factor.hpp, trsv_box.hpp.
+#include "local_solve.hpp"      // the solves: ilu0_enqueue, graph capture, ilu0_solve_epilogue, ilu0_solve_multi_ld, ddm_ilu0_solve*.  Needs tri_*.hpp, engine_*.hpp.
+#include "local_solver.hpp"     // creation: ilu0_create_impl, direct_create_impl, ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*.  Needs local_solve.hpp.
 #include "geneo.hpp"            // ddm_geneo_basis (pulls in dense_host.hpp, geneo_kernels.hpp).  Needs csr.hpp, local_solver.hpp.
 #include "halo.hpp"             // ddm_halo: single-vector and m-column exchange over one RCCL wire function.  Needs context.hpp.
 #include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp.

@@ -1,4 +1,4 @@
-// GenEO coarse-basis builder on the device (included by ddm_hip.hip after csr.hpp and local_solver.hpp; C ABI: ddm_geneo_basis in include/ddm_hip.h).
+// GenEO coarse-basis builder on the device (included by ddm_hip.hip after csr.hpp and the local solver, local_factor.hpp .. local_solver.hpp; C ABI: ddm_geneo_basis in include/ddm_hip.h).
 //
 // Reference: GenEOCoarseSpace::setup_geneo_impl (dune/ddm/coarsespaces/coarse_spaces.hh:319-331): C = D B_neu D
 // (detail::scale_matrix_with_pou, :74-96), the lowest nev eigenpairs of A_neu x = lambda C x (solve_gevp ->

@@ -3,7 +3,7 @@
 // object's single-vector apply is followed by its apply to m columns (the ddm_*_multi entry points).  Block vectors are row-major
 // n x m (entry (i, c) at i * m + c), 1 <= m <= MULTI_MAX; every object keeps its own block scratch, allocated on first use for the
 // widest m seen so far.  The single-vector applies are NOT the block applies at m = 1: they use the fused epilogue of the pipe engine
-// and the all-reduce a scalar can ride on (coarse_allreduce); the headline number depends on them.  Needs halo.hpp, local_solver.hpp.
+// and the all-reduce a scalar can ride on (coarse_allreduce); the headline number depends on them.  Needs halo.hpp and the local solver (local_factor.hpp .. local_solver.hpp).
 #pragma once
 
 // ---- reductions --------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // Single-vector solves with the device supernodal factor (sn_chol.hpp): the local solve of SchwarzPreconditioner::apply with a
-// sparse direct subdomain solver (dune/ddm/schwarz.hh:85-92,133: `type = cholmod | umfpack`).  Included by sn_chol.hpp.
+// sparse direct subdomain solver (dune/ddm/schwarz.hh:85-92,133: `type = cholmod | umfpack`).  Needs sn_chol.hpp (Meta, the constants);
+// the host driver that launches these kernels is sn_factor.hpp.
 //
 // One right-hand side has no work for the matrix cores: every kernel here is a gather / dot-product kernel on the panels,
 // bounded by the HBM stream of the panels (8 bytes per entry and sweep) and, in practice, by the number of dependent steps: the

@@ -101,6 +101,42 @@ def test_ilu0_factor_and_solve(ddm, torch_cuda, trsv_mode, monkeypatch):
     ctx.close()
 
 
+def test_ilu0_graph_caches_follow_their_arguments(ddm, torch_cuda):
+    """Both solve entry points replay a captured graph when they are called again with the same arguments and capture a new one when
+    an argument changes (here: the right-hand side buffer; the single-precision switch).  A replay of the wrong graph would return
+    the other call's result, or leave the NaN fill."""
+    from dune_ddm_amd import synth
+    torch = torch_cuda
+    ctx = ddm.torch_context(0)
+    grid = synth.StructuredPoisson((14, 12, 11), (1, 1, 1), synth.islands_kappa((13, 11, 10), 1e4, 4, 2))
+    M = grid.subdomain(0).A
+    n = M.shape[0]
+    F = ddm.Ilu0(ctx, ddm.CsrMatrix(ctx, M))
+    rng = np.random.default_rng(2)
+    d, d2 = _dev(torch, rng.standard_normal(n)), _dev(torch, rng.standard_normal(n))
+    x = torch.empty(n, dtype=torch.float64, device="cuda")
+    got = []
+    for rhs in (d, d2, d):
+        x.fill_(float("nan"))
+        F.solve(rhs, x)
+        ctx.sync()
+        got.append(x.clone())
+    assert all(bool(torch.isfinite(g).all()) for g in got)
+    assert torch.equal(got[0], got[2]) and not torch.equal(got[0], got[1])
+    D = _dev(torch, rng.standard_normal((n, 4)))
+    X = torch.empty_like(D)
+    got = []
+    for f32 in (False, True, False):
+        X.fill_(float("nan"))
+        F.solve_multi(D, X, single_precision=f32)
+        ctx.sync()
+        got.append(X.clone())
+    assert all(bool(torch.isfinite(g).all()) for g in got)
+    assert torch.equal(got[0], got[2]) and not torch.equal(got[0], got[1])
+    assert F.status() == 0
+    ctx.close()
+
+
 def _build(ddm, N, P, overlap=2, pou_type="distance", shrink=0, kappa=None, neumann=False):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
