@@ -162,6 +162,7 @@ SYMBOLS = {
     "ddm_galerkin_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_combined_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_cg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_cg_solve_queue": (_I32, [_P, _P, _P, _I64, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_gmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
@@ -725,6 +726,23 @@ def cg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreco
     the defects).  Returns (list of m SolveResult, history): history is (iters + 1) x m with iters the largest iteration count; the
     entries of a column after it converged are NaN (its history stops there)."""
     return _solve_multi(ctx, ctx.lib.ddm_cg_solve_multi, op, prec, X, B, reduction, maxit, (), history)
+
+
+def cg_solve_queue(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, width, reduction=1e-10, maxit=1000, history=True):
+    """Any number of right-hand sides through a CG block of ``width`` slots (ddm_cg_solve_queue): a slot whose column has stopped takes
+    the next pending column, so the block stays full until the queue is empty.  X, B: (n, ncols) row-major device tensors; X holds the
+    initial guesses and receives the solutions, B is not modified.  Returns (list of ncols SolveResult, history): history is
+    (iters + 1) x ncols with iters the largest iteration count, row k of column j being that column's defect after its own k-th
+    iteration (NaN after its last one)."""
+    ncols = _ncols(X, B)
+    res = (SolveResult * max(ncols, 1))()
+    hist = np.full((maxit + 1, max(ncols, 1)), np.nan) if history and maxit >= 0 else None
+    ctx.check(ctx.lib.ddm_cg_solve_queue(ctx.h, op.h, prec.h, ncols, int(width), _ptr(X), _ptr(B), float(reduction), int(maxit), _hp(hist), res))
+    out = [res[c] for c in range(ncols)]
+    if not history:
+        return out, None
+    iters = max([r.iterations for r in out] + [0])
+    return out, hist[:iters + 1, :ncols]
 
 
 def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,

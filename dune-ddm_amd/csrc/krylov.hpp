@@ -1,5 +1,6 @@
 // The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES and BiCGSTAB for one right-hand side; CG and restarted GMRES
-// for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods).  Restarted GMRES is one algorithm
+// for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods); CG for any number of right-hand
+// sides queued through a block of fixed width (ddm_cg_solve_queue).  Restarted GMRES is one algorithm
 // with two variants, left-preconditioned and flexible (right-preconditioned, the preconditioned directions kept): one loop per vector
 // count (gmres_loop, gmres_loop_multi) behind the four entry points ddm_gmres_solve, ddm_fgmres_solve, ddm_gmres_solve_multi and
 // ddm_fgmres_solve_multi.  All drivers share the frame around the loop (solve_result_reset, classify_initial_defect, krylov_finish), the
@@ -46,6 +47,7 @@ struct MultiFrame {
   double def[MULTI_MAX];
   int nactive = 0;
   bool changed = false; // active[] differs from ctx->mactive
+  const int64_t *column = nullptr; // queue driver: column[c] = the caller's column that slot c holds (messages name it); null: c itself
 };
 // The initial defects (norm2[c]: the squared norm of column c): def0 and the first history row; a column that needs no iteration is
 // converged and masked out from the start; the mask goes to the device.
@@ -70,7 +72,7 @@ static int multi_record(MultiFrame &f, int c, int it, double def)
   f.def[c] = def;
   f.res[c].iterations = it;
   if (f.hist_host) f.hist_host[(int64_t)it * f.m + c] = def;
-  if (!(def == def)) return fail(f.ctx, DDM_ENUMERIC, "%s: defect is NaN in iteration %d (column %d)", f.what, it, c);
+  if (!(def == def)) return fail(f.ctx, DDM_ENUMERIC, "%s: defect is NaN in iteration %d (column %lld)", f.what, it, (long long)(f.column ? f.column[c] : c));
   if (def < f.res[c].def0 * f.reduction || def < 1e-30) {
     f.res[c].converged = 1;
     f.active[c] = 0;
@@ -540,6 +542,21 @@ extern "C" int ddm_bicgstab_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   return rc;
 }
 
+// B -= T in the columns of ctx->mactive; out (m device doubles) = owner-masked <B_c, B_c>, summed over the ranks (the restart of the
+// flexible GMRES block loop and the initial defect of the slots that ddm_cg_solve_queue refills)
+static int defect_norm_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *T, double *B, double *out)
+{
+  const int64_t n = op->n;
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  for_column_groups(m, [&](int c0, int cb) {
+    DDM_MULTI_CB_DISPATCH(k_defect_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
+                          (const uint8_t *)op->owner, T, B, ctx->mpartial);
+  });
+  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
+  HIPCHECK(ctx, hipGetLastError());
+  return ctx_allreduce(ctx, out, m, "defect norms");
+}
+
 // ---- CG for m right-hand sides ---------------------------------------------------------------------------------------------------------
 // m independent CGSolver::apply recurrences (the loop of ddm_cg_solve per column).  A column whose defect passed the test is frozen by
 // the device-side mask ctx->mactive: its x, defect, scalars and history stop changing while the other columns go on.  Per iteration
@@ -598,6 +615,136 @@ extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   return multi_finish(f, prec, rc, t0);
 }
 
+// ---- CG for any number of right-hand sides through a block of fixed width ------------------------------------------------------------
+// ncols columns queue for the `width` slots of one block loop: the loop of ddm_cg_solve_multi (cg_multi_step, MultiFrame, the mask)
+// with a slot -> column table beside it.  Every column is what ddm_cg_solve_multi computes on it -- its own def0, stop test, iteration
+// counter and maxit.  X and B are the caller's n x ncols blocks; the recurrences run in n x width work blocks (x, defect, p, q), so B
+// is only read.  After the defects of an iteration are read, at the iteration boundary:
+//   store   every slot whose column stopped (converged, or maxit reached) scatters its x into X[:, column] (k_column_store_multi);
+//   refill  the slots freed in this iteration take the next columns of the queue, in ascending slot order, in one launch of
+//           k_column_load_multi (x = X[:, j], defect = B[:, j], p = 0, rholast = 1: the slot's next direction is p = beta * 0 + q = q);
+//   defect  one block operator apply T = A x and k_defect_norm_multi (defect -= T and its norms) under a mask of the refilled slots
+//           only: the running slots' defects are not touched.  A refilled column with def0 < 1e-30 (or maxit = 0) is finished at
+//           once and its slot refilled again at the same boundary (at most ncols passes); then the loop mask is restored.
+// With the queue empty a freed slot is frozen as in ddm_cg_solve_multi.  Every step is the "not first" step of cg_multi_step: a fresh
+// slot has p = 0 and a finite beta, so no step is special and the slots need not be aligned.  A NaN ends the call with DDM_ENUMERIC:
+// the columns stored before keep their results, X[:, j] of the others is as on entry.
+extern "C" int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
+                                  int maxit, double *hist_host, ddm_solve_result *res)
+{
+  const char *what = "ddm_cg_solve_queue";
+  if (width < 1 || width > MULTI_MAX) return fail(ctx, DDM_EINVAL, "%s: width = %d outside [1, %d]", what, width, MULTI_MAX);
+  if (ncols < 1) return fail(ctx, DDM_EINVAL, "%s: ncols = %lld, at least one column is needed", what, (long long)ncols);
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0) return fail(ctx, DDM_EINVAL, "%s: bad arguments", what);
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int w = width;
+  const int64_t n = op->n;
+  for (int64_t j = 0; j < ncols; ++j) solve_result_reset(&res[j]);
+  DDMCHECK(ctx_multi_scratch(ctx));
+  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, w, {{prec->mp, n}, {prec->mq, n}}));   // directions p, q
+  HIPCHECK(ctx, reserve_cols<double>(prec->mqueue_cols, w, {{prec->mxw, n}, {prec->mbw, n}})); // the slots' x and defect
+  if (!prec->mqueue_tab) HIPCHECK(ctx, prec->mqueue_tab.alloc(2 * MULTI_MAX));
+  StreamDrain drain{ctx}; // every return waits for the kernels that read the caller's blocks
+  double *P = prec->mp, *Q = prec->mq, *XW = prec->mxw, *BW = prec->mbw;
+  int64_t *tabdev = prec->mqueue_tab; // (slot, column) pairs of one load or store launch
+  if (n > 0) // a slot that never holds a column stays zero
+    for (double *blk : {P, XW, BW}) HIPCHECK(ctx, hipMemsetAsync(blk, 0, sizeof(double) * (size_t)(n * w), ctx->stream));
+  double *bbdev = ctx->mscal + 5 * MULTI_MAX;
+  double bb[MULTI_MAX];
+  ddm_solve_result sres[MULTI_MAX]; // the slots' results: MultiFrame works on these, a stored column's entry is copied to res
+  int64_t column[MULTI_MAX], tab[2 * MULTI_MAX];
+  int32_t mask[MULTI_MAX];
+  for (int s = 0; s < w; ++s) solve_result_reset(&sres[s]), column[s] = -1;
+  MultiFrame f{ctx, what, w, reduction, nullptr, sres};
+  f.column = column;
+  std::fill(f.active, f.active + w, 0);
+  int64_t next = 0; // head of the queue
+  auto hist = [&](int64_t j, int it, double def) {
+    if (hist_host) hist_host[(int64_t)it * ncols + j] = def;
+  };
+  auto upload_table = [&](int npairs) { return ddm_memcpy_h2d(ctx, tabdev, tab, sizeof(int64_t) * 2 * (size_t)npairs); };
+  // slot s is done with its column: the result entry goes to the caller (x has been stored, or never changed)
+  auto release = [&](int s) {
+    ddm_solve_result &r = res[column[s]] = sres[s];
+    if (r.def0 >= 1e-30) r.reduction = f.def[s] / r.def0;
+    column[s] = -1;
+  };
+  // the free slots take the next columns of the queue; leaves the loop mask on the device
+  auto refill = [&]() -> int {
+    for (int64_t pass = 0; pass < ncols && next < ncols; ++pass) {
+      int nload = 0;
+      std::fill(mask, mask + w, 0);
+      for (int s = 0; s < w && next < ncols; ++s) {
+        if (column[s] >= 0) continue;
+        tab[2 * nload] = s, tab[2 * nload + 1] = column[s] = next++;
+        mask[s] = 1;
+        ++nload;
+      }
+      if (nload == 0) break;
+      DDMCHECK(upload_table(nload));
+      hipLaunchKernelGGL(k_column_load_multi, dim3(grid_for(n * nload)), dim3(WG), 0, ctx->stream, n, w, nload, (const int64_t *)tabdev, ncols, (const double *)X,
+                         (const double *)B, XW, BW, P, ctx->mscal);
+      HIPCHECK(ctx, hipGetLastError());
+      DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, mask, sizeof(int32_t) * (size_t)w)); // the defect pass writes the loaded slots only
+      DDMCHECK(op_apply_multi(ctx, op, w, XW, Q));                                     // t = A x (q is free between two iterations)
+      DDMCHECK(defect_norm_multi(ctx, op, w, Q, BW, bbdev));                         // prec.pre(x, b); b -= t; <b, b>
+      DDMCHECK(ddm_memcpy_d2h(ctx, bb, bbdev, sizeof(double) * (size_t)w));
+      for (int k = 0; k < nload; ++k) {
+        const int s = (int)tab[2 * k];
+        solve_result_reset(&sres[s]);
+        const double def0 = f.def[s] = std::sqrt(bb[s]);
+        sres[s].def0 = def0;
+        hist(column[s], 0, def0);
+        const Defect0 d = classify_initial_defect(def0);
+        if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "%s: initial defect is NaN in column %lld", what, (long long)column[s]);
+        if (d == Defect0::Zero) sres[s].converged = 1;
+        if (d == Defect0::Zero || maxit == 0) { // needs no iteration, or gets none: x stays as it is in X
+          release(s);
+          continue;
+        }
+        f.active[s] = 1;
+        f.nactive += 1;
+      }
+    }
+    f.changed = true;
+    return multi_upload_mask(f);
+  };
+  int rc = refill();
+  (void)hipStreamSynchronize(ctx->stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  while (f.nactive > 0 && !rc) {
+    rc = cg_multi_step(ctx, op, prec, w, false, XW, BW, P, Q);
+    if (!rc) rc = ddm_memcpy_d2h(ctx, bb, bbdev, sizeof(double) * (size_t)w); // the defects are tested every iteration
+    int nstore = 0;
+    for (int s = 0; s < w && !rc; ++s) {
+      if (!f.active[s]) continue;
+      const int it = sres[s].iterations + 1;
+      rc = multi_record(f, s, it, std::sqrt(bb[s]));
+      hist(column[s], it, f.def[s]);
+      if (!rc && f.active[s] && it >= maxit) { // out of iterations: leaves its slot unconverged
+        f.active[s] = 0;
+        f.nactive -= 1;
+        f.changed = true;
+      }
+      if (!rc && !f.active[s]) tab[2 * nstore] = s, tab[2 * nstore + 1] = column[s], ++nstore;
+    }
+    if (rc) break;
+    if (nstore > 0) {
+      rc = upload_table(nstore);
+      if (rc) break;
+      hipLaunchKernelGGL(k_column_store_multi, dim3(grid_for(n * nstore)), dim3(WG), 0, ctx->stream, n, w, nstore, (const int64_t *)tabdev, ncols, (const double *)XW, X);
+      if (hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in %s", what);
+      if (rc) break;
+      for (int k = 0; k < nstore; ++k) release((int)tab[2 * k]);
+    }
+    rc = nstore > 0 && next < ncols ? refill() : multi_upload_mask(f);
+  }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in %s", what);
+  rc = multi_finish(f, prec, rc, t0); // (drains the stream; the elapsed time of the call lands in the slots' entries)
+  for (int64_t j = 0; j < ncols; ++j) res[j].elapsed_s = sres[0].elapsed_s;
+  return rc;
+}
+
 // ---- restarted GMRES for m right-hand sides, left-preconditioned and flexible ------------------------
 // Every column is what gmres_loop computes on it (the same variant, modified Gram-Schmidt in the order k = 0..i, its own GmresColumn),
 // while the operator, the preconditioner and the orthogonalisation sweep run once for all columns.  Restart cycles are aligned.  A
@@ -651,19 +798,6 @@ static bool gmres_multi_fused_env()
   return e && e[0] == '1';
 }
 
-// B -= T in the columns of ctx->mactive; out (m device doubles) = owner-masked <B_c, B_c>, summed over the ranks
-static int fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int m, const double *T, double *B, double *out)
-{
-  const int64_t n = op->n;
-  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
-  for_column_groups(m, [&](int c0, int cb) {
-    DDM_MULTI_CB_DISPATCH(k_defect_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
-                          (const uint8_t *)op->owner, T, B, ctx->mpartial);
-  });
-  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
-  HIPCHECK(ctx, hipGetLastError());
-  return ctx_allreduce(ctx, out, m, "defect norms");
-}
 // The restart step on its own, for tests: B -= T in the columns with active_host[c] != 0, norm2_host[c] = <B_c, B_c> of every column
 // afterwards.  fused != 0: k_defect_norm_multi; fused == 0: the kernels it replaces (k_axpy_negdev_multi with unit coefficients, then
 // the block dot of ddm_dot_multi).  Synchronous.
@@ -678,7 +812,7 @@ extern "C" int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const
   DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active_host, sizeof(int32_t) * (size_t)m));
   double *out = ctx->mscal + 6 * MULTI_MAX;
   if (fused) {
-    DDMCHECK(fgmres_defect_multi(ctx, op, m, T, B, out));
+    DDMCHECK(defect_norm_multi(ctx, op, m, T, B, out));
   } else {
     dbuf<double> one;
     HIPCHECK(ctx, one.alloc(m));
@@ -789,7 +923,7 @@ static int gmres_loop_multi(ddm_ctx *ctx, const char *what, bool flexible, ddm_o
     if (f.nactive > 0 && j < maxit) { // restart: the defect and the norm of the next cycle in the running columns
       if (flexible) {
         rc = op_apply_multi(ctx, op, m, W, v(0));                             // t = A w into v0 (overwritten by the next cycle)
-        if (!rc) rc = fgmres_defect_multi(ctx, op, m, v(0), B, hdev);         // b -= t and |b|
+        if (!rc) rc = defect_norm_multi(ctx, op, m, v(0), B, hdev);         // b -= t and |b|
       } else {
         rc = op_applyscaleadd_multi(ctx, op, m, -1.0, W, B);                  // b -= A w (w = 0 in the columns that are done)
         if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, v(0), B);       // v0 = M^-1 b

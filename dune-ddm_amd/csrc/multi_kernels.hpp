@@ -268,6 +268,39 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, i
   }
 }
 
+// ---- queued CG (ddm_cg_solve_queue, csrc/krylov.hpp): columns of the caller's n x ncols blocks enter and leave the slots of the n x m work blocks ----
+// tab: nload (slot, column) pairs, tab[2k] = slot < m and tab[2k + 1] = column < ncols.  One thread per (row, pair) entry, the pair
+// index running fastest (consecutive lanes = consecutive table entries of one row).
+// Load: x_slot = X[:, column], b_slot = B[:, column], p_slot = 0 and rholast_slot = 1 (scal as in k_cg_beta_multi): the slot's next
+// beta = rho / 1 is finite and its next direction p = beta * 0 + q is q, the first CG direction of the new column.
+__global__ void k_column_load_multi(int64_t n, int m, int nload, const int64_t *__restrict__ tab, int64_t ncols, const double *__restrict__ Xc,
+                                    const double *__restrict__ Bc, double *__restrict__ x, double *__restrict__ b, double *__restrict__ p,
+                                    double *__restrict__ scal)
+{
+  const int64_t gid = blockIdx.x * (int64_t)WG + threadIdx.x;
+  if (gid < nload) scal[tab[2 * gid]] = 1.0;
+  const int64_t total = n * nload;
+  for (int64_t t = gid; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t i = t / nload;
+    const int k = (int)(t - i * nload);
+    const int64_t o = i * m + tab[2 * k], src = i * ncols + tab[2 * k + 1];
+    x[o] = Xc[src];
+    b[o] = Bc[src];
+    p[o] = 0.0;
+  }
+}
+// Store: X[:, column] = x_slot for the nstore pairs of tab
+__global__ void k_column_store_multi(int64_t n, int m, int nstore, const int64_t *__restrict__ tab, int64_t ncols, const double *__restrict__ x,
+                                     double *__restrict__ Xc)
+{
+  const int64_t total = n * nstore;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t i = t / nstore;
+    const int k = (int)(t - i * nstore);
+    Xc[i * ncols + tab[2 * k + 1]] = x[i * m + tab[2 * k]];
+  }
+}
+
 // ---- restarted GMRES vector work (ddm_gmres_solve_multi, csrc/krylov.hpp) -----------------------------------------------------------------------------
 // per-column host scalars of one launch, passed by value (no upload, no synchronisation)
 struct MultiCoef {

@@ -524,7 +524,9 @@ struct ddm_combined {
   bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
   bool overlap = false; // ... and the coarse chain runs on a side stream beside the local solve (measured slower: off by default)
   dbuf<double> mdnext, mp, mq; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
-  int mcols = 0, mcg_cols = 0;
+  dbuf<double> mxw, mbw;       // ddm_cg_solve_queue: the slots' x and defect blocks (mqueue_cols)
+  dbuf<int64_t> mqueue_tab;    // ... and its table of (slot, column) pairs, 2 * MULTI_MAX entries
+  int mcols = 0, mcg_cols = 0, mqueue_cols = 0;
 };
 extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)
 {

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, cg_solve, cg_solve_multi, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
+               SchwarzPreconditioner, cg_solve, cg_solve_multi, cg_solve_queue, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
 
@@ -295,19 +295,10 @@ class TwoLevelSchwarz:
         res, hist = cg_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, fixed_iterations, history)
         return res, hist, x
 
-    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100):
-        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver" /
-        "restartedflexiblegmressolver", m independent (flexible) restarted GMRES solves with aligned restart cycles
-        (ddm_gmres_solve_multi / ddm_fgmres_solve_multi), each column as ``solve`` would run it.
-        B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
-        (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
-        if solver not in self.SOLVERS_MULTI:
-            raise NotImplementedError("solver type '" + str(solver) + "' (of the four device solvers " + ", ".join(self.SOLVERS)
-                                      + ", all but bicgstabsolver are available for several right-hand sides)")
+    def _blocks(self, B, X0):
+        """device copies of the right-hand sides and the initial guesses (zero without X0) as (n_o, m) row-major blocks"""
         torch = self.torch
         n_o = self.rl.n_o
-        if B is None:
-            B = np.asarray(self.rl.b, dtype=np.float64).reshape(n_o, 1)
 
         def block(a):
             t = a.to(self.dev, torch.float64) if isinstance(a, torch.Tensor) else self.to_device(np.asarray(a, dtype=np.float64))
@@ -319,12 +310,41 @@ class TwoLevelSchwarz:
         X = torch.zeros_like(Bd) if X0 is None else block(X0)
         if X.shape != Bd.shape:
             raise ValueError(f"X0 {tuple(X.shape)} and B {tuple(Bd.shape)} differ")
+        return Bd, X
+
+    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100):
+        """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver" /
+        "restartedflexiblegmressolver", m independent (flexible) restarted GMRES solves with aligned restart cycles
+        (ddm_gmres_solve_multi / ddm_fgmres_solve_multi), each column as ``solve`` would run it.
+        B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
+        (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
+        if solver not in self.SOLVERS_MULTI:
+            raise NotImplementedError("solver type '" + str(solver) + "' (of the four device solvers " + ", ".join(self.SOLVERS)
+                                      + ", all but bicgstabsolver are available for several right-hand sides)")
+        n_o = self.rl.n_o
+        if B is None:
+            B = np.asarray(self.rl.b, dtype=np.float64).reshape(n_o, 1)
+        Bd, X = self._blocks(B, X0)
         if solver == "restartedgmressolver":
             res, hist = gmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
         elif solver == "restartedflexiblegmressolver":
             res, hist = fgmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
         else:
             res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
+        return res, hist, X
+
+    def solve_many(self, B, width=8, reduction=1e-10, maxit=1000, history=True, X0=None):
+        """Any number M of right-hand sides, M independent CG solves through one block loop of ``width`` <= 32 slots
+        (ddm_cg_solve_queue): a slot whose column has stopped takes the next pending column, so no slot idles while columns wait.  Each
+        column is what ``solve_multi`` computes on it.  B, X0: (n_o, M) arrays or tensors, M may be smaller than ``width``.  Returns
+        (list of M SolveResult, (iters + 1) x M history -- row k of column j: its defect after its own k-th iteration -- or None, X as an
+        (n_o, M) device tensor)."""
+        if not 1 <= int(width) <= 32:
+            raise ValueError(f"width = {width} outside [1, 32]")
+        if int(maxit) < 0:
+            raise ValueError(f"maxit = {maxit} is negative")
+        Bd, X = self._blocks(B, X0)
+        res, hist = cg_solve_queue(self.ctx, self.op, self.prec, X, Bd, int(width), reduction, maxit, history)
         return res, hist, X
 
 

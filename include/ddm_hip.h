@@ -487,6 +487,20 @@ int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X,
  * defect and when a local solve gave up (ddm_ilu0_peek_status), as ddm_cg_solve. */
 int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                        double *hist_host, ddm_solve_result *res);
+/* Any number of right-hand sides through a CG block of fixed width: ncols >= 1 columns queue for the 1 <= width <= 32 slots of one block
+ * loop (ncols may be smaller than width; DDM_EINVAL outside these ranges).  When a slot's column stops, its solution is written out and
+ * the next pending column takes the slot at the iteration boundary, so the block stays full until the queue is empty.
+ *   X, B: DEVICE blocks, n x ncols row-major (entry (i, j) at i * ncols + j).  X: initial guesses on entry, solutions on exit.  B is NOT
+ *     modified: the defects live in the width-wide work block of the preconditioner object.
+ *   Column j is what ddm_cg_solve_multi computes on it: its own def0, stop test (def < reduction def0 or def < 1e-30; def0 < 1e-30:
+ *     converged with 0 iterations), iteration counter and maxit.  A column that reaches maxit leaves its slot with converged = 0, and its x
+ *     is still written to X.
+ *   hist_host (may be NULL): (maxit + 1) x ncols row-major, entry (k, j) = the defect of column j after ITS OWN k-th iteration, for
+ *     k <= res[j].iterations (later entries are not written).  res: ncols entries; elapsed_s is that of the whole call in every entry.
+ *   DDM_ENUMERIC on a NaN defect (the message names the column) and when a local solve gave up, as ddm_cg_solve_multi: the columns
+ *     stored before keep their results, X[:, j] of every other column is as on entry and its res entry is reset. */
+int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
+                       int maxit, double *hist_host, ddm_solve_result *res);
 /* nrhs INDEPENDENT dune-istl RestartedGMResSolver::apply recurrences in one loop (the loop of ddm_gmres_solve per column: left
  * preconditioning, modified Gram-Schmidt in the order k = 0..i, the same Givens rotations, the monitored norm is that of the
  * preconditioned defect; not a block-Krylov method).  X, B, hist_host ((maxit + 1) x nrhs, entries after a column's last iteration are
