@@ -137,6 +137,7 @@ SYMBOLS = {
     "ddm_galerkin_destroy": (None, [_P]),
     "ddm_galerkin_apply": (_I32, [_P, _P, _P, _P]),
     "ddm_galerkin_products": (_I32, [_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P]),
+    "ddm_galerkin_debug_chain": (_I32, [_P, _P, _P, _I32, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     "ddm_geneo_params_default": (_I32, [ctypes.POINTER(GeneoParams)]),
     "ddm_geneo_basis": (_I32, [_P, _P, _P, _I64, _P, _P, _P, ctypes.POINTER(GeneoParams), _I64, _P, _P, _P, ctypes.POINTER(GeneoInfo)]),
     "ddm_msgfem_basis": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, ctypes.POINTER(GeneoParams), _I64, _P, _P, _P, ctypes.POINTER(GeneoInfo)]),
@@ -654,6 +655,19 @@ class GalerkinPreconditioner:
 
     def apply_multi(self, X, D):
         self.ctx.check(self.ctx.lib.ddm_galerkin_apply_multi(self.ctx.h, self.h, _ncols(X, D), _ptr(X), _ptr(D)))
+
+    def debug_chain(self, d_ovlp, K, spread_grid=0):
+        """diagnostic: the coarse chain alone on an overlapping device defect, with the full-grid basis passes (spread_grid 0) or the
+        spread ones on that many one-wave workgroups; returns device tensors (chunk partials, coarse defect, prolonged correction)"""
+        import torch
+        npart = ctypes.c_int64(0)
+        self.ctx.check(self.ctx.lib.ddm_galerkin_debug_chain(self.ctx.h, self.h, None, int(spread_grid), None, None, None, ctypes.byref(npart)))
+        partial = torch.empty(max(npart.value, 1), dtype=torch.float64, device=d_ovlp.device)
+        d0 = torch.empty(max(int(K), 1), dtype=torch.float64, device=d_ovlp.device)
+        xov = torch.empty_like(d_ovlp)
+        self.ctx.check(self.ctx.lib.ddm_galerkin_debug_chain(self.ctx.h, self.h, _ptr(d_ovlp), int(spread_grid), _ptr(partial), _ptr(d0), _ptr(xov),
+                                                             ctypes.byref(npart)))
+        return partial[:npart.value], d0[:int(K)], xov
 
 
 def galerkin_products(ctx: Context, A_dir: CsrMatrix, left, right, row0, row1):

@@ -332,6 +332,25 @@ extern "C" int ddm_ctx_rccl_size(ddm_ctx *ctx, int *count)
     const ncclResult_t r_ = (call);                                                                                            \
     if (r_ != ncclSuccess) return fail(ctx, DDM_ECOMM, "%s failed: %s", #call, ctx->nccl.GetErrorString ? ctx->nccl.GetErrorString(r_) : "?"); \
   } while (0)
+// the side stream (and its fork / join events), created on first use: non-blocking, at the DEFAULT priority.  (A stream of the lowest
+// priority was measured and loses: with that queue active every kernel boundary of the main stream costs some 40 us more, 5.5 ms per
+// iteration of the headline workload against 4.7 ms with this stream and 5.2 ms on one stream -- DESIGN.md section 4.)
+static int ctx_side_stream(ddm_ctx *ctx)
+{
+  if (ctx->side) return DDM_OK;
+  hipStream_t s = nullptr;
+  HIPCHECK(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  hipError_t e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    ctx->ev_fork = nullptr;
+    (void)hipStreamDestroy(s);
+    return fail(ctx, DDM_EHIP, "side stream: hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
+  }
+  ctx->side = s; // (set last: ddm_ctx_destroy releases the three together)
+  return DDM_OK;
+}
 // in-place sum over all ranks of n doubles at a device pointer, enqueued on the context's stream
 static int ctx_allreduce(ddm_ctx *ctx, double *buf, int64_t n, const char *what)
 {

@@ -68,8 +68,9 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
 }
 
 static unsigned perm_grid(ddm_ctx *ctx, int64_t npos) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((npos + PERM_TILE - 1) / PERM_TILE, (int64_t)ctx->num_cu * 16)); }
-static void enqueue_pipe(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned *err, unsigned long long *stamps, const double *scale = nullptr,
-                         const double *add = nullptr)
+// add_ready: `add` is being written on another stream; only the output permutation waits for that event, the solve kernel does not
+static hipError_t enqueue_pipe(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned *err, unsigned long long *stamps, const double *scale = nullptr,
+                               const double *add = nullptr, hipEvent_t add_ready = nullptr)
 {
   const PipeEngine &E = *F->pipe;
   PipeParams P;
@@ -90,5 +91,8 @@ static void enqueue_pipe(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, 
   hipLaunchKernelGGL(k_pipe_prologue, dim3(1), dim3(64), 0, ctx->stream, F->xstate, E.queue, E.ngroups * 4);
   if (stamps) hipLaunchKernelGGL((k_trsv_pipe<true>), dim3(E.grid), dim3(64 * (PIPE_NC + PIPE_NL)), PIPE_LDS_BYTES, ctx->stream, P);
   else hipLaunchKernelGGL((k_trsv_pipe<false>), dim3(E.grid), dim3(64 * (PIPE_NC + PIPE_NL)), PIPE_LDS_BYTES, ctx->stream, P);
+  const hipError_t e = add_ready ? hipStreamWaitEvent(ctx->stream, add_ready, 0) : hipSuccess;
+  if (e != hipSuccess) return e; // (x stays unwritten: the caller fails)
   hipLaunchKernelGGL(k_pipe_permute_out, dim3(perm_grid(ctx, E.nposU)), dim3(PERM_WG), 0, ctx->stream, E.nposU, E.rowU, (const double *)E.xpos, x, scale, add);
+  return hipSuccess;
 }

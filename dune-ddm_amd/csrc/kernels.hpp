@@ -1246,4 +1246,94 @@ __global__ __launch_bounds__(WG) void k_coarse_prolong(int kmax, int64_t ld, con
   }
 }
 
+// ---- the two passes over the basis, spread: for the coarse chain that runs on a side stream BESIDE the single-launch local solve.
+// Workgroups of ONE wave, `w` per CU (the launch decides), persistent over the work items in grid-stride order: every CU carries the
+// same small share of the stream, and a wave needs few enough registers (make resource-usage: at most 80) to fit on a SIMD next to
+// two waves of k_trsv_pipe.  Sixteen loads per lane are in flight.  Same sums in the same order as the full-grid kernels above.
+constexpr int SPREAD_WG = 64;
+// a wave-uniform global pointer in scalar registers: loads through it take the scalar base + 32-bit lane offset form
+typedef const __attribute__((address_space(1))) double *uniform_gptr;
+__device__ __forceinline__ uniform_gptr uniform_global(const double *p)
+{
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (uniform_gptr)(((uint64_t)hi << 32) | lo);
+}
+// one partial per (chunk, j): lane l adds rows r0 + l + 64 t in ascending t, then wave_sum
+__global__ __launch_bounds__(SPREAD_WG) void k_coarse_restrict_spread(int kmax, int64_t ld, const double *__restrict__ basis,
+                                                                       const double *__restrict__ d, const RowChunk *__restrict__ chunks,
+                                                                       double *__restrict__ partial /* [nchunk][kmax] */, int nchunk)
+{
+  const int lane = threadIdx.x;
+  const int64_t nitem = (int64_t)nchunk * kmax; // (item = chunk * kmax + j: the waves that run together share few chunks of d)
+  for (int64_t item = blockIdx.x; item < nitem; item += gridDim.x) {
+    const int ch = (int)(item / kmax), j = (int)(item % kmax);
+    const RowChunk c = chunks[ch];
+    const double *bj = basis + (int64_t)j * ld;
+    double s = 0.0;
+    int64_t r = c.r0 + lane;
+    for (; r + 7 * 64 < c.r1; r += 8 * 64) {
+      double bv[8], dv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) bv[u] = __builtin_nontemporal_load(bj + r + u * 64);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) dv[u] = d[r + u * 64];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += bv[u] * dv[u];
+    }
+    for (; r < c.r1; r += 64) s += bj[r] * d[r];
+    s = wave_sum(s);
+    if (lane == 0) partial[item] = s;
+  }
+}
+// four rows per lane and trip, four basis vectors of each in flight; per row the vectors are added in ascending j
+__global__ __launch_bounds__(SPREAD_WG) void k_coarse_prolong_spread(int kmax, int64_t ld, const double *__restrict__ basis,
+                                                                      const double *__restrict__ x0, const int64_t *__restrict__ coarse_index,
+                                                                      const RowChunk *__restrict__ chunks, double *__restrict__ xov, int nchunk)
+{
+  __shared__ double cj[COARSE_KMAX];
+  const int lane = threadIdx.x;
+  for (int ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const RowChunk c = chunks[ch];
+    __syncthreads(); // cj of the previous chunk is no longer read
+    for (int j = lane; j < kmax; j += SPREAD_WG) {
+      const int64_t gi = coarse_index[(int64_t)c.sub * kmax + j];
+      cj[j] = gi >= 0 ? x0[gi] : 0.0;
+    }
+    __syncthreads();
+    for (int64_t rb = c.r0; rb < c.r1; rb += 4 * SPREAD_WG) { // (uniform trip base + 32-bit lane offsets: scalar-base addressing, few registers)
+      const int nrow = (int)(c.r1 - rb < 4 * SPREAD_WG ? c.r1 - rb : 4 * SPREAD_WG);
+      if (lane >= nrow) continue;
+      unsigned lo[4]; // (rows of the last trip that do not exist: the lane's first row, computed again and not stored)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) lo[q] = (unsigned)(lane + q * SPREAD_WG < nrow ? lane + q * SPREAD_WG : lane);
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      int j = 0;
+#pragma unroll 1
+      for (; j + 4 <= kmax; j += 4) {
+        double bv[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const uniform_gptr bc = uniform_global(basis + (int64_t)(j + u) * ld + rb);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) bv[q][u] = __builtin_nontemporal_load(bc + lo[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) s[q] += cj[j + u] * bv[q][u];
+      }
+      for (; j < kmax; ++j) {
+        const double *bc = basis + (int64_t)j * ld + rb;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += cj[j] * bc[lo[q]];
+      }
+      xov[rb + lo[0]] = s[0];
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+        if (lo[q] != (unsigned)lane) xov[rb + lo[q]] = s[q];
+    }
+  }
+}
+
 } // namespace ddm

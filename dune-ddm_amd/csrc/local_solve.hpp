@@ -59,7 +59,7 @@ static int ilu0_enqueue(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, c
   *folded = F->engine == Engine::Box || F->engine == Engine::Pipe;
   switch (F->engine) {
   case Engine::Box: return enqueue_box(ctx, F, d, x, scale, add, err);
-  case Engine::Pipe: enqueue_pipe(ctx, F, d, x, err, nullptr, scale, add); return DDM_OK;
+  case Engine::Pipe: (void)enqueue_pipe(ctx, F, d, x, err, nullptr, scale, add); return DDM_OK;
   case Engine::Xcd2: enqueue_xcd2(ctx, F, d, x, err, nullptr); return DDM_OK;
   case Engine::Supernodal: enqueue_sn_panel(ctx, F, 1, d, 1, x, 1, F->pd, F->px, err); return DDM_OK;
   case Engine::Levels: break;
@@ -125,7 +125,7 @@ extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, d
   dbuf<unsigned long long> st;
   HIPCHECK(ctx, st.alloc(PIPE_STAMP_WORDS * (nt + 1)));
   HIPCHECK(ctx, hipMemsetAsync(st, 0, sizeof(unsigned long long) * PIPE_STAMP_WORDS * (size_t)(nt + 1), ctx->stream));
-  enqueue_pipe(ctx, F, d, x, F->err, st);
+  (void)enqueue_pipe(ctx, F, d, x, F->err, st);
   int rc = ddm_memcpy_d2h(ctx, out_host, st, (int64_t)sizeof(unsigned long long) * PIPE_STAMP_WORDS * nt);
   if (!rc && meta_host) {
     std::vector<pipe::Task> tasks((size_t)nt);
@@ -138,12 +138,32 @@ extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, d
   return rc;
 }
 
+// whether the settled engine of the factor is pipe (waits for the background builder)
+static int ilu0_is_pipe(ddm_ctx *ctx, ddm_ilu0 *F, bool *yes)
+{
+  *yes = false;
+  if (!F || F->n == 0) return DDM_OK;
+  DDMCHECK(ilu0_prepare_engine(ctx, F));
+  *yes = F->engine == Engine::Pipe;
+  return DDM_OK;
+}
+
 // x = (LU)^-1 d, then optionally x *= scale and x += add (the tail of the Schwarz level: partition of unity of the restricted
 // variant and the coarse correction); the pipe and box engines fold both into their output pass, the others append the two kernels.
-static int ilu0_solve_epilogue(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, const double *scale, const double *add)
+// add_ready (pipe engine only, ilu0_is_pipe): `add` is being written on another stream and is complete when this event fires.  The
+// solve kernel starts without waiting, only the output pass waits -- enqueued directly (three launches), not through the graph cache.
+static int ilu0_solve_epilogue(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, const double *scale, const double *add, hipEvent_t add_ready = nullptr)
 {
   if (F && F->n == 0) return DDM_OK;
   if (!F || !d || !x || d == x) return fail(ctx, DDM_EINVAL, "ddm_ilu0_solve: bad arguments (d and x must not alias)");
+  if (add_ready) {
+    bool pipe_engine = false;
+    DDMCHECK(ilu0_is_pipe(ctx, F, &pipe_engine));
+    if (!pipe_engine || !add) return fail(ctx, DDM_EINVAL, "ddm_ilu0_solve: only the pipe engine joins a side stream in front of its output pass");
+    HIPCHECK(ctx, enqueue_pipe(ctx, F, d, x, F->err, nullptr, scale, add, add_ready));
+    HIPCHECK(ctx, hipGetLastError());
+    return DDM_OK;
+  }
   SolveKey key;
   key.d = d, key.x = x, key.scale = scale, key.add = add;
   if (F->graph.hit(key)) {

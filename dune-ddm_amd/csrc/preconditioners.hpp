@@ -390,16 +390,24 @@ extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, con
 }
 extern "C" void ddm_galerkin_destroy(ddm_galerkin *G) { delete G; }
 // restrict -> all-reduce (a scalar waiting in ctx->piggy rides along) -> A0^-1 d0 -> prolong into G->x_ovlp, on the context's current
-// stream.  `grid`: workgroups of the two passes over the basis (G->nchunk, or fewer when the chain runs beside the local solve).
+// stream.  spread_grid == 0: the full-grid passes over the basis, one workgroup per chunk; spread_grid > 0: the spread ones on that
+// many one-wave workgroups (the chain runs beside the local solve).  Same result bit for bit either way.
 // Not timed here: the callers' "GalerkinPrec/apply" scopes differ.
-static int coarse_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *dov, int grid)
+static int coarse_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *dov, int spread_grid = 0)
 {
-  hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(grid), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk); // :165-167
+  const unsigned sgrid = (unsigned)spread_grid;
+  if (spread_grid > 0)
+    hipLaunchKernelGGL(k_coarse_restrict_spread, dim3(sgrid), dim3(SPREAD_WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk);
+  else
+    hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk); // :165-167
   hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, ctx->stream, (int)G->nsub, (int)G->kmax, G->sub_chunk_ptr, G->partial, G->coarse_index, G->K, G->d0);
   HIPCHECK(ctx, hipGetLastError());
   DDMCHECK(coarse_allreduce(ctx, G->d0, G->K)); // replaces MPI_Gatherv (:170-171): every rank obtains the full coarse defect
   hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((G->K + 3) / 4)), dim3(WG), 0, ctx->stream, G->K, G->a0inv, G->d0, G->x0); // :174-179 (replicated)
-  hipLaunchKernelGGL(k_coarse_prolong, dim3(grid), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk); // :186-188
+  if (spread_grid > 0)
+    hipLaunchKernelGGL(k_coarse_prolong_spread, dim3(sgrid), dim3(SPREAD_WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk);
+  else
+    hipLaunchKernelGGL(k_coarse_prolong, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk); // :186-188
   return DDM_OK;
 }
 // d_ovlp_ready: the overlapping defect (extended + owner values copied to all holders) if the caller already has it -- in the
@@ -413,7 +421,7 @@ static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const d
     DDMCHECK(ddm_halo_exchange(ctx, G->copy, G->d_ovlp));                                                         // :162
     dov = G->d_ovlp;
   }
-  DDMCHECK(coarse_chain(ctx, G, dov, G->nchunk));
+  DDMCHECK(coarse_chain(ctx, G, dov));
   DDMCHECK(ddm_halo_exchange(ctx, G->add, G->x_ovlp)); // :190
   if (acc)
     hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(G->n)), dim3(WG), 0, ctx->stream, G->n, G->ext_map, G->x_ovlp, (const double *)nullptr, x);
@@ -425,6 +433,24 @@ static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const d
 extern "C" int ddm_galerkin_apply(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d)
 {
   return galerkin_apply_impl(ctx, G, x, d, false);
+}
+// Diagnostic (not part of the product path): the coarse chain alone on an overlapping defect the caller supplies (n doubles on the
+// device), with the full-grid basis passes (spread_grid == 0) or the spread ones on spread_grid one-wave workgroups; copies the chunk
+// partials (*npartial = chunks x kmax doubles), the coarse defect (K) and the prolonged correction (n) to the caller's device arrays.
+// All three may be null to query *npartial.
+extern "C" int ddm_galerkin_debug_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *d_ovlp, int spread_grid, double *partial_out, double *d0_out,
+                                        double *x_ovlp_out, int64_t *npartial)
+{
+  if (!ctx || !G || !npartial || spread_grid < 0) return fail(ctx, DDM_EINVAL, "ddm_galerkin_debug_chain: bad arguments");
+  *npartial = (int64_t)G->nchunk * G->kmax;
+  if (!partial_out && !d0_out && !x_ovlp_out) return DDM_OK;
+  if (!d_ovlp || !partial_out || !d0_out || !x_ovlp_out) return fail(ctx, DDM_EINVAL, "ddm_galerkin_debug_chain: bad arguments");
+  DDMCHECK(coarse_chain(ctx, G, d_ovlp, spread_grid));
+  HIPCHECK(ctx, hipMemcpyAsync(partial_out, G->partial, sizeof(double) * (size_t)*npartial, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(d0_out, G->d0, sizeof(double) * (size_t)G->K, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(x_ovlp_out, G->x_ovlp, sizeof(double) * (size_t)G->n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return DDM_OK;
 }
 // ... and for m columns
 static int galerkin_multi_scratch(ddm_ctx *ctx, ddm_galerkin *G, int m)
@@ -514,6 +540,9 @@ extern "C" int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
 }
 
 // ---- CombinedPreconditioner --------------------------------------------------------------------
+// the coarse chain beside the local solve (combined_apply_fused): whether it is on where DDM_OVERLAP_COARSE is unset, and its width
+constexpr bool OVERLAP_DEFAULT = true;
+constexpr int OVERLAP_WAVES_PER_CU = 1; // (measured at 1, 2 and 4, and at half a wave per CU: DESIGN.md section 4)
 struct ddm_combined {
   int mode = 0;
   ddm_op *op = nullptr;
@@ -522,7 +551,8 @@ struct ddm_combined {
   dbuf<double> dnext;
   int64_t n = 0;
   bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
-  bool overlap = false; // ... and the coarse chain runs on a side stream beside the local solve (measured slower: off by default)
+  int overlap = 0;      // ... and the coarse chain runs on a side stream beside the local solve: 0 never, 1 always, 2 where the local engine is pipe
+  int side_grid = 0;    // one-wave workgroups of the chain's two basis passes on the side stream
   dbuf<double> mdnext, mp, mq; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
   dbuf<double> mxw, mbw;       // ddm_cg_solve_queue: the slots' x and defect blocks (mqueue_cols)
   dbuf<int64_t> mqueue_tab;    // ... and its table of (slot, column) pairs, 2 * MULTI_MAX entries
@@ -541,9 +571,11 @@ extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwa
   C->n = schwarz->n_novlp;
   if (mode == 0 && galerkin) {
     const char *f = std::getenv("DDM_FUSE_LEVELS");    // "0": the two levels one after the other (two halo adds: the reference's order of sums)
-    const char *e = std::getenv("DDM_OVERLAP_COARSE"); // "1": coarse chain on a side stream
+    const char *e = std::getenv("DDM_OVERLAP_COARSE"); // "1" / "0": coarse chain on a side stream / not; unset: OVERLAP_DEFAULT, pipe engine only
+    const char *g = std::getenv("DDM_OVERLAP_GRID");   // workgroups of the side stream's basis passes (default OVERLAP_WAVES_PER_CU per CU)
     C->fused = !(f && f[0] == '0') && galerkin->copy == schwarz->copy && galerkin->add == schwarz->add && galerkin->n == schwarz->n && galerkin->n_novlp == schwarz->n_novlp;
-    C->overlap = C->fused && e && e[0] == '1' && (ctx->nranks == 1 || ctx->rccl);
+    if (C->fused && (ctx->nranks == 1 || ctx->rccl)) C->overlap = e ? (e[0] == '1' ? 1 : 0) : (OVERLAP_DEFAULT ? 2 : 0);
+    C->side_grid = g ? std::max(1, std::atoi(g)) : OVERLAP_WAVES_PER_CU * ctx->num_cu;
   }
   if (C->dnext.alloc(C->n) != hipSuccess) return fail(ctx, DDM_EHIP, "combined: allocation failed");
   *out = C.release();
@@ -560,27 +592,29 @@ extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
 // galerkin_preconditioner.hh:190-193 + combined_preconditioner.hh:136-142) -- one extend, one copy-halo, one halo add and one restrict
 // instead of two each; the result differs from the two-pass order by rounding only (measured: 5.54 -> 5.31 ms per iteration at 216^3).
 //   extend + copy-halo -> local solve -> (POU scale) -> R d -> all-reduce -> A0^-1 -> R^T x0 -> x_s += x_c -> halo add -> restrict
-// two_streams (DDM_OVERLAP_COARSE=1; needs the in-library exchange or a single rank): the coarse chain runs on a side stream BESIDE the
-// local solve -- the local solves are latency-bound and leave 85 % of the HBM bandwidth idle, the coarse level is bandwidth-bound.
-// Measured at 216^3 it LOSES: the local solve slows from 3.39 to 4.34 ms (its dependent L2 / HBM round trips queue behind the
-// basis stream), the coarse chain from 0.87 to 2.2 ms, 5.58 ms per iteration against 5.31 -- off by default.
-static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, bool two_streams)
+// two_streams (C->overlap; needs the in-library exchange or a single rank): the coarse chain runs on a low-priority side stream BESIDE
+// the local solve, which is latency-bound and leaves most of the HBM bandwidth idle.  The chain's two passes over the basis are the
+// spread kernels (one-wave workgroups, C->side_grid of them: every CU carries the same small share of the stream and the solve's
+// workgroups stay resident next to them).  With the pipe engine the chain joins between the solve kernel and its output permutation,
+// which applies "x *= pou; x += x_coarse" as on one stream: the same kernels' sums in the same order, the result is bit-identical.
+// The other engines join behind the solve with k_scale + k_axpy (the same operations as separate passes).
+// Measurements, the losing configurations included: DESIGN.md section 4.
+static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d)
 {
   ddm_schwarz *S = C->schwarz;
   ddm_galerkin *G = C->galerkin;
-  if (two_streams && !ctx->side) {
-    HIPCHECK(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-    HIPCHECK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    HIPCHECK(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-  }
+  bool pipe_engine = false;
+  if (C->overlap != 0) DDMCHECK(ilu0_is_pipe(ctx, S->solver, &pipe_engine));
+  const bool two_streams = C->overlap == 1 || (C->overlap == 2 && pipe_engine);
+  if (two_streams) DDMCHECK(ctx_side_stream(ctx));
   {
     ScopedTimer t(ctx, "Schwarz/get defect");
     hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp);
     DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));
   }
-  auto timed_chain = [&](int grid) -> int { // (the timer records on whichever stream the chain is enqueued on)
+  auto timed_chain = [&](int spread_grid) -> int { // (the timer records on whichever stream the chain is enqueued on)
     ScopedTimer t(ctx, "GalerkinPrec/apply");
-    return coarse_chain(ctx, G, S->d_ovlp, grid);
+    return coarse_chain(ctx, G, S->d_ovlp, spread_grid);
   };
   if (two_streams) {
     // inter-rank operations stay totally ordered: copy-halo (main) -> all-reduce (side) -> [join] -> halo add (main)
@@ -588,10 +622,7 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
     hipStream_t main = ctx->stream;
     HIPCHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
     ctx->stream = ctx->side; // the coarse chain is enqueued on the side stream (kernels, RCCL all-reduce, timer)
-    // a small grid: the chain only has to finish within the (latency-bound, ~3 ms) local solve, and a full-rate basis stream would
-    // queue in front of the pipe kernel's dependent L2 / HBM round trips (DDM_OVERLAP_GRID: workgroups, default 64)
-    static const int side_grid = std::getenv("DDM_OVERLAP_GRID") ? std::max(1, std::atoi(std::getenv("DDM_OVERLAP_GRID"))) : 64;
-    const int rc = timed_chain(std::min(G->nchunk, side_grid));
+    const int rc = timed_chain(C->side_grid);
     const hipError_t e = hipEventRecord(ctx->ev_join, ctx->side);
     ctx->stream = main;
     if (rc) return rc;
@@ -599,14 +630,16 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
   }
   const double *pou = S->type == 1 ? S->pou : nullptr;
   // one stream: the coarse chain runs first, so that the local solve's last kernel can also apply "x *= pou; x += x_coarse"
-  if (!two_streams) DDMCHECK(timed_chain(G->nchunk));
+  if (!two_streams) DDMCHECK(timed_chain(0));
+  const bool fold = !two_streams || pipe_engine; // the solve's output pass applies the POU scale and adds the coarse correction
   {
     ScopedTimer t(ctx, "Schwarz/local solve");
-    DDMCHECK(ilu0_solve_epilogue(ctx, S->solver, S->d_ovlp, S->x_ovlp, two_streams ? nullptr : pou, two_streams ? nullptr : (const double *)G->x_ovlp));
+    DDMCHECK(ilu0_solve_epilogue(ctx, S->solver, S->d_ovlp, S->x_ovlp, fold ? pou : nullptr, fold ? (const double *)G->x_ovlp : nullptr,
+                                 two_streams && fold ? ctx->ev_join : nullptr));
   }
   {
     ScopedTimer t(ctx, "Schwarz/add solution");
-    if (two_streams) {
+    if (!fold) {
       if (pou) hipLaunchKernelGGL(k_scale, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, pou, S->x_ovlp);
       HIPCHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
       hipLaunchKernelGGL(k_axpy, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, 1.0, (const double *)G->x_ovlp, S->x_ovlp);
@@ -622,7 +655,7 @@ extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, cons
 {
   ScopedTimer t(ctx, "CombinedPreconditioner/apply");
   DDMCHECK(local_status_check(ctx, C->schwarz));
-  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d, C->overlap);
+  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d);
   // x = 0; precs[0]->apply(x, d)  (:133-134)  -- the restrict kernel overwrites every entry of x
   DDMCHECK(schwarz_apply_impl(ctx, C->schwarz, x, d, false));
   if (!C->galerkin) return DDM_OK;

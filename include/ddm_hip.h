@@ -301,6 +301,12 @@ int ddm_galerkin_apply(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d
  * restricted to the subdomain row range [row0,row1).  Used by the host to assemble R A R^T. */
 int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nleft, const double *left, int64_t nright,
                           const double *right, int64_t row0, int64_t row1, double *out_host);
+/* Diagnostic: the coarse chain (restrict, all-reduce, A0^-1, prolong) alone on an overlapping defect on the device (n doubles), with the
+ * full-grid passes over the basis (spread_grid = 0) or the spread ones on spread_grid one-wave workgroups (what the chain uses beside
+ * the local solve).  Device outputs: the chunk partials (*npartial doubles), the coarse defect (K) and the prolonged correction (n);
+ * all three NULL only queries *npartial.  Synchronous. */
+int ddm_galerkin_debug_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *d_ovlp, int spread_grid, double *partial_out, double *d0_out,
+                             double *x_ovlp_out, int64_t *npartial);
 
 /* ---- GenEO coarse-basis builder ---------------------------------------------------------------
  * GenEOCoarseSpace(A, B, pou, ptree, taskflow, prefix) -> get_basis() (dune/ddm/coarsespaces/coarse_spaces.hh:219-256, 286-331):
