@@ -164,6 +164,7 @@ SYMBOLS = {
     "ddm_combined_apply_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_cg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_cg_solve_queue": (_I32, [_P, _P, _P, _I64, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_bicgstab_solve_queue": (_I32, [_P, _P, _P, _I64, _I32, _P, _P, _D, _I32, _P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(SolveResult)]),
     "ddm_gmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
@@ -757,6 +758,24 @@ def cg_solve_queue(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreco
         return out, None
     iters = max([r.iterations for r in out] + [0])
     return out, hist[:iters + 1, :ncols]
+
+
+def bicgstab_solve_queue(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, width, reduction=1e-10, maxit=1000, history=True):
+    """Any number of right-hand sides through a BiCGSTAB block of ``width`` slots (ddm_bicgstab_solve_queue): every column is what
+    bicgstab_solve computes on it; a slot whose column has stopped takes the next pending column at the end of the iteration.  X, B:
+    (n, ncols) row-major device tensors; X holds the initial guesses and receives the solutions, B is not modified.  Returns (list of
+    ncols SolveResult, history): history is (halfsteps + 1) x ncols with halfsteps the largest half-step count, row k of column j being
+    that column's defect after its own k-th HALF step (NaN after its last one)."""
+    ncols = _ncols(X, B)
+    res = (SolveResult * max(ncols, 1))()
+    nh = np.zeros(max(ncols, 1), dtype=np.int32)
+    hist = np.full((2 * maxit + 1, max(ncols, 1)), np.nan) if history and maxit >= 0 else None
+    ctx.check(ctx.lib.ddm_bicgstab_solve_queue(ctx.h, op.h, prec.h, ncols, int(width), _ptr(X), _ptr(B), float(reduction), int(maxit), _hp(hist),
+                                               nh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res))
+    out = [res[c] for c in range(ncols)]
+    if not history:
+        return out, None
+    return out, hist[:max(int(nh[:ncols].max(initial=1)), 1), :ncols]
 
 
 def gmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,

@@ -1,6 +1,6 @@
 // The Krylov drivers: CG (begin / steps / defect / solve), restarted GMRES and BiCGSTAB for one right-hand side; CG and restarted GMRES
 // for m right-hand sides at once (m independent recurrences in one loop, not block-Krylov methods); CG for any number of right-hand
-// sides queued through a block of fixed width (ddm_cg_solve_queue).  Restarted GMRES is one algorithm
+// sides queued through a block of fixed width (ddm_cg_solve_queue), and BiCGSTAB likewise (ddm_bicgstab_solve_queue).  Restarted GMRES is one algorithm
 // with two variants, left-preconditioned and flexible (right-preconditioned, the preconditioned directions kept): one loop per vector
 // count (gmres_loop, gmres_loop_multi) behind the four entry points ddm_gmres_solve, ddm_fgmres_solve, ddm_gmres_solve_multi and
 // ddm_fgmres_solve_multi.  All drivers share the frame around the loop (solve_result_reset, classify_initial_defect, krylov_finish), the
@@ -578,7 +578,7 @@ static int cg_multi_step(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int m, bo
   const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
   for_column_groups(m, [&](int c0, int cb) { // x += lambda p; b -= lambda q; <b, b> partials
     DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
-                          (const double *)scal, (const uint8_t *)op->owner, (const double *)P, (const double *)Q, X, B, ctx->mpartial);
+                          (const double *)scal, 2, (const uint8_t *)op->owner, (const double *)P, (const double *)Q, X, B, ctx->mpartial);
   });
   hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + 5 * MULTI_MAX);
   HIPCHECK(ctx, hipGetLastError());
@@ -740,6 +740,269 @@ extern "C" int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
     rc = nstore > 0 && next < ncols ? refill() : multi_upload_mask(f);
   }
   if (!rc && hipGetLastError() != hipSuccess) rc = fail(ctx, DDM_EHIP, "kernel launch failed in %s", what);
+  rc = multi_finish(f, prec, rc, t0); // (drains the stream; the elapsed time of the call lands in the slots' entries)
+  for (int64_t j = 0; j < ncols; ++j) res[j].elapsed_s = sres[0].elapsed_s;
+  return rc;
+}
+
+// ---- BiCGSTAB for any number of right-hand sides through a block of fixed width --------------------------------------------------------
+// ncols columns queue for the `width` slots of one block loop, under the protocol of ddm_cg_solve_queue (MultiFrame, the mask
+// ctx->mactive, the slot -> column table, store / refill at the boundary).  Every column is what ddm_bicgstab_solve computes on it:
+// right-preconditioned, two half steps per iteration, `norm <= def0 * reduction` tested after each, def0 < 1e-30 converged at once,
+// iterations = ceil(half steps / 2), maxit full iterations.  A slot's state is seven vectors (x, r, rt, p, v, y, t: n x width work
+// blocks of the preconditioner object) and three scalars (rho, alpha, omega, on the device); B is only read.
+//   iteration  beta and p = r + beta (p - omega v); y = W^-1 p; v = A y; h = <rt, v>; alpha = rho_new / h; x += alpha y, r -= alpha v
+//              and <r, r>: the host reads <r, r>, h and the rho and omega that beta used in ONE copy, runs the single driver's breakdown
+//              checks on them (|rho| <= 1e-80, |omega| <= 1e-80, |h| < 1e-80) and tests the defect.  A column that passes is masked
+//              out of the second half step: its x, r and scalars do not change.  Then y = W^-1 r; t = A y; <t, t> and <t, r>;
+//              omega = <t, r> / <t, t>, rho = rho_new; x += omega y, r -= omega t with <r, r> and the next rho_new = <rt, r>: the
+//              host reads the defects.
+//   boundary   one per iteration, after the second half step: every slot whose column stopped in either half step or reached maxit is
+//              stored and released; the freed slots take the next columns in ascending slot order (x = X[:, j], r = B[:, j],
+//              p = v = 0, rho = alpha = omega = 1), then under a mask of the loaded slots only r -= A x with its norm, rt = r and
+//              rho_new = <r, r>.  A loaded column with def0 < 1e-30 (or maxit = 0) is finished at once and its slot refilled again
+//              at the same boundary.
+// A fresh slot needs no special first step: with p = v = 0 the direction update, evaluated as the single driver evaluates it
+// (p += (-omega) v; p *= beta; p += r), yields p = r exactly -- the `it < 1` branch of the single driver -- so every step is the
+// general step and the slots need not be aligned.  A column's numbers do not depend on whether it entered at the start or through a
+// refill: both are this one load path.  A breakdown or a NaN in a running column ends the call with DDM_ENUMERIC: the columns stored
+// before keep their results, X[:, j] of the others is as on entry.
+// Vector work per iteration, in passes over n x w doubles (every load and store of a block entry a kernel issues counts 1): the
+// composition of simple kernels (the default) takes 8 + 8 for the first half step and 4 + 6 + 4 for the second: 30.  With
+// DDM_BICGSTAB_QUEUE_FUSED=1 it is direction 4 (p, v, r read, p written), first update with <r, r> 6, <t, t> with <t, r> 2, second
+// update with <r, r> and <rt, r> 7: 19.  h = <rt, v> is the block dot in both (2 more).  Both forms give the same bits (the build
+// does not contract a * b + c).  The composition is the default because it measured faster on MI355X, as for the block GMRES sweep:
+// the kernels that keep the reduction tree of the block dot and skip inactive columns run at a third of the simple kernels' rate
+// (DESIGN.md section 9).
+static bool bicgstab_queue_fused_env() // read once per process
+{
+  static const bool fused = [] {
+    const char *e = std::getenv("DDM_BICGSTAB_QUEUE_FUSED");
+    return e && e[0] == '1';
+  }();
+  return fused;
+}
+extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
+                                        int maxit, double *hist_host, int32_t *nhist, ddm_solve_result *res)
+{
+  const char *what = "ddm_bicgstab_solve_queue";
+  if (width < 1 || width > MULTI_MAX) return fail(ctx, DDM_EINVAL, "%s: width = %d outside [1, %d]", what, width, MULTI_MAX);
+  if (ncols < 1) return fail(ctx, DDM_EINVAL, "%s: ncols = %lld, at least one column is needed", what, (long long)ncols);
+  if (!ctx || !op || !prec || !X || !B || !res || X == B || maxit < 0) return fail(ctx, DDM_EINVAL, "%s: bad arguments", what);
+  DDMCHECK(local_status_check(ctx, prec->schwarz));
+  const int w = width;
+  const int64_t n = op->n;
+  const double EPS = 1e-80;
+  const bool fused = bicgstab_queue_fused_env();
+  for (int64_t j = 0; j < ncols; ++j) solve_result_reset(&res[j]);
+  if (nhist) std::fill(nhist, nhist + ncols, 0);
+  DDMCHECK(ctx_multi_scratch(ctx));
+  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, w, {{prec->mp, n}, {prec->mq, n}}));               // p, t
+  HIPCHECK(ctx, reserve_cols<double>(prec->mqueue_cols, w, {{prec->mxw, n}, {prec->mbw, n}}));           // the slots' x and defect r
+  HIPCHECK(ctx, reserve_cols<double>(prec->mbicg_cols, w, {{prec->mrt, n}, {prec->mv, n}, {prec->my, n}})); // shadow defect, v, y
+  if (!prec->mqueue_tab) HIPCHECK(ctx, prec->mqueue_tab.alloc(2 * MULTI_MAX));
+  StreamDrain drain{ctx}; // every return waits for the kernels that read the caller's blocks
+  double *P = prec->mp, *T = prec->mq, *XW = prec->mxw, *R = prec->mbw, *RT = prec->mrt, *V = prec->mv, *Y = prec->my;
+  int64_t *tabdev = prec->mqueue_tab; // (slot, column) pairs of one load or store launch
+  if (n > 0) // a slot that never holds a column stays zero
+    for (double *blk : {P, XW, R, RT, V}) HIPCHECK(ctx, hipMemsetAsync(blk, 0, sizeof(double) * (size_t)(n * w), ctx->stream));
+  double *scal = ctx->mscal;
+  HIPCHECK(ctx, hipMemsetAsync(scal, 0, sizeof(double) * (size_t)(BICG_SCALARS * MULTI_MAX), ctx->stream));
+  double *half1 = scal + BICG_HALF1 * MULTI_MAX, *half2 = scal + BICG_HALF2 * MULTI_MAX, *loaddev = scal + BICG_LOAD * MULTI_MAX, *ttdev = scal + BICG_TT * MULTI_MAX;
+  const int32_t *active = ctx->mactive;
+  const uint8_t *owner = op->owner;
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS), GE = grid_for(n * w);
+  double rd[4 * MULTI_MAX];
+  ddm_solve_result sres[MULTI_MAX]; // the slots' results; a released column's entry is copied to res
+  int64_t column[MULTI_MAX], tab[2 * MULTI_MAX];
+  int32_t mask[MULTI_MAX], nhalf[MULTI_MAX];
+  for (int s = 0; s < w; ++s) solve_result_reset(&sres[s]), column[s] = -1, nhalf[s] = 0;
+  MultiFrame f{ctx, what, w, reduction, nullptr, sres};
+  f.column = column;
+  std::fill(f.active, f.active + w, 0);
+  int64_t next = 0; // head of the queue
+  auto upload_table = [&](int npairs) { return ddm_memcpy_h2d(ctx, tabdev, tab, sizeof(int64_t) * 2 * (size_t)npairs); };
+  auto launch_ok = [&]() { return hipGetLastError() == hipSuccess ? DDM_OK : fail(ctx, DDM_EHIP, "kernel launch failed in %s", what); };
+  // slot s is done with its column: the result entry goes to the caller (x has been stored, or never changed)
+  auto release = [&](int s) {
+    ddm_solve_result &r = res[column[s]] = sres[s];
+    r.iterations = (nhalf[s] + 1) / 2;
+    if (r.def0 >= 1e-30) r.reduction = f.def[s] / r.def0;
+    if (nhist) nhist[column[s]] = nhalf[s] + 1;
+    column[s] = -1;
+  };
+  // a running slot after a half step: history, NaN, the single driver's stop test; a column that passes leaves the mask
+  auto record = [&](int s, double norm2) -> int {
+    const double def = f.def[s] = std::sqrt(norm2);
+    nhalf[s] += 1;
+    if (hist_host) hist_host[(int64_t)nhalf[s] * ncols + column[s]] = def;
+    if (!(def == def)) return fail(ctx, DDM_ENUMERIC, "%s: defect is NaN after half step %d of column %lld", what, nhalf[s], (long long)column[s]);
+    if (def <= sres[s].def0 * reduction) {
+      sres[s].converged = 1;
+      f.active[s] = 0;
+      f.nactive -= 1;
+      f.changed = true;
+    }
+    return DDM_OK;
+  };
+  // two sums per column from 2 w rows of partials, summed over the ranks in one all-reduce
+  auto finish_pair = [&](double *out, const char *name) -> int {
+    hipLaunchKernelGGL(k_reduce_final_multi, dim3(2 * w), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
+    DDMCHECK(launch_ok());
+    return ctx_allreduce(ctx, out, 2 * w, name);
+  };
+  // the free slots take the next columns of the queue; leaves the loop mask on the device
+  auto refill = [&]() -> int {
+    for (int64_t pass = 0; pass < ncols && next < ncols; ++pass) {
+      int nload = 0;
+      std::fill(mask, mask + w, 0);
+      for (int s = 0; s < w && next < ncols; ++s) {
+        if (column[s] >= 0) continue;
+        tab[2 * nload] = s, tab[2 * nload + 1] = column[s] = next++;
+        mask[s] = 1;
+        ++nload;
+      }
+      if (nload == 0) break;
+      DDMCHECK(upload_table(nload));
+      hipLaunchKernelGGL(k_bicg_column_load_multi, dim3(grid_for(n * nload)), dim3(WG), 0, ctx->stream, n, w, nload, (const int64_t *)tabdev, ncols,
+                         (const double *)X, (const double *)B, XW, R, P, V, scal);
+      DDMCHECK(launch_ok());
+      DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, mask, sizeof(int32_t) * (size_t)w)); // the defect pass writes the loaded slots only
+      DDMCHECK(op_apply_multi(ctx, op, w, XW, T));                                     // t = A x (t is free between two iterations)
+      DDMCHECK(defect_norm_multi(ctx, op, w, T, R, loaddev));                        // r -= t; <r, r>
+      hipLaunchKernelGGL(k_bicg_shadow_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)R, RT, scal); // rt = r; rho_new = <r, r>
+      DDMCHECK(launch_ok());
+      DDMCHECK(ddm_memcpy_d2h(ctx, rd, loaddev, sizeof(double) * (size_t)w));
+      for (int k = 0; k < nload; ++k) {
+        const int s = (int)tab[2 * k];
+        solve_result_reset(&sres[s]);
+        nhalf[s] = 0;
+        const double def0 = f.def[s] = std::sqrt(rd[s]);
+        sres[s].def0 = def0;
+        if (hist_host) hist_host[column[s]] = def0;
+        const Defect0 d = classify_initial_defect(def0);
+        if (d == Defect0::NaN) return fail(ctx, DDM_ENUMERIC, "%s: initial defect is NaN in column %lld", what, (long long)column[s]);
+        if (d == Defect0::Zero) sres[s].converged = 1;
+        if (d == Defect0::Zero || maxit == 0) { // needs no iteration, or gets none: x stays as it is in X
+          release(s);
+          continue;
+        }
+        f.active[s] = 1;
+        f.nactive += 1;
+      }
+    }
+    f.changed = true;
+    return multi_upload_mask(f);
+  };
+  auto axpy = [&](const double *coef, double sign, const double *x, double *y) {
+    hipLaunchKernelGGL(k_axpy_dev_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, coef, sign, x, y);
+  };
+  // first half step; leaves <r, r>, h and the operands of the breakdown checks in half1
+  auto half_step_1 = [&]() -> int {
+    hipLaunchKernelGGL(k_bicg_beta_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal);
+    if (fused) {
+      hipLaunchKernelGGL(k_bicg_direction_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)scal, (const double *)R, (const double *)V, P);
+    } else {
+      axpy(scal + BICG_OMEGA * MULTI_MAX, -1.0, V, P); // p = r + beta (p - omega v)
+      hipLaunchKernelGGL(k_scal_dev_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)(scal + BICG_BETA * MULTI_MAX), P);
+      axpy(nullptr, 1.0, R, P);
+    }
+    DDMCHECK(launch_ok());
+    DDMCHECK(combined_apply_multi_impl(ctx, prec, w, Y, P));          // y = W^-1 p
+    DDMCHECK(op_apply_multi(ctx, op, w, Y, V));                       // v = A y
+    DDMCHECK(dot_multi_device(ctx, n, owner, w, RT, V, half1 + w));   // h = <rt, v>
+    hipLaunchKernelGGL(k_bicg_alpha_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal); // alpha = rho_new / h
+    if (fused) { // x += alpha y; r -= alpha v; <r, r>
+      for_column_groups(w, [&](int c0, int cb) {
+        DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, (const double *)scal, BICG_ALPHA,
+                              owner, (const double *)Y, (const double *)V, XW, R, ctx->mpartial);
+      });
+      hipLaunchKernelGGL(k_reduce_final_multi, dim3(w), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, half1);
+      DDMCHECK(launch_ok());
+      return ctx_allreduce(ctx, half1, w, "defect norms");
+    }
+    axpy(scal + BICG_ALPHA * MULTI_MAX, 1.0, Y, XW);
+    axpy(scal + BICG_ALPHA * MULTI_MAX, -1.0, V, R);
+    DDMCHECK(launch_ok());
+    return dot_multi_device(ctx, n, owner, w, R, R, half1);
+  };
+  // second half step; leaves <r, r> and the next rho_new in half2
+  auto half_step_2 = [&]() -> int {
+    DDMCHECK(combined_apply_multi_impl(ctx, prec, w, Y, R));          // y = W^-1 r
+    DDMCHECK(op_apply_multi(ctx, op, w, Y, T));                       // t = A y
+    if (fused) {
+      for_column_groups(w, [&](int c0, int cb) {
+        DDM_MULTI_CB_DISPATCH(k_dot2_partial_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, owner, (const double *)T,
+                              (const double *)R, ctx->mpartial);
+      });
+      DDMCHECK(finish_pair(ttdev, "scalar products"));
+    } else {
+      DDMCHECK(dot_multi_device(ctx, n, owner, w, T, T, ttdev));
+      DDMCHECK(dot_multi_device(ctx, n, owner, w, T, R, ttdev + w));
+    }
+    hipLaunchKernelGGL(k_bicg_omega_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal); // omega = <t, r> / <t, t>; rho = rho_new
+    if (fused) { // x += omega y; r -= omega t; <r, r> and <rt, r>
+      for_column_groups(w, [&](int c0, int cb) {
+        DDM_MULTI_CB_DISPATCH(k_bicg_half2_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, (const double *)scal, owner,
+                              (const double *)Y, (const double *)T, (const double *)RT, XW, R, ctx->mpartial);
+      });
+      return finish_pair(half2, "defect norms");
+    }
+    axpy(scal + BICG_OMEGA * MULTI_MAX, 1.0, Y, XW);
+    axpy(scal + BICG_OMEGA * MULTI_MAX, -1.0, T, R);
+    DDMCHECK(launch_ok());
+    DDMCHECK(dot_multi_device(ctx, n, owner, w, R, R, half2));
+    // (the block dot writes every column: the rho_new of a slot that sits out this half step is overwritten, and never read again --
+    //  the slot is stored at this boundary)
+    return dot_multi_device(ctx, n, owner, w, RT, R, half2 + w);
+  };
+  int rc = refill();
+  (void)hipStreamSynchronize(ctx->stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  while (f.nactive > 0 && !rc) {
+    rc = half_step_1();
+    if (!rc) rc = ddm_memcpy_d2h(ctx, rd, half1, sizeof(double) * 4 * (size_t)w); // the one read of the half step
+    for (int s = 0; s < w && !rc; ++s) {
+      if (!f.active[s]) continue;
+      const double h = rd[w + s], rho = rd[2 * w + s], omega = rd[3 * w + s];
+      const long long j = (long long)column[s];
+      if (std::fabs(rho) <= EPS) rc = fail(ctx, DDM_ENUMERIC, "%s: breakdown in BiCGSTAB - rho %g <= EPSILON after %d half steps of column %lld", what, rho, nhalf[s], j);
+      else if (std::fabs(omega) <= EPS) rc = fail(ctx, DDM_ENUMERIC, "%s: breakdown in BiCGSTAB - omega %g <= EPSILON after %d half steps of column %lld", what, omega, nhalf[s], j);
+      else if (std::fabs(h) < EPS) rc = fail(ctx, DDM_ENUMERIC, "%s: abs(h) < EPSILON in BiCGSTAB - abort (h %g after %d half steps of column %lld)", what, h, nhalf[s], j);
+      else if (!(rho == rho) || !(omega == omega) || !(h == h))
+        rc = fail(ctx, DDM_ENUMERIC, "%s: %s is NaN after %d half steps of column %lld", what, !(rho == rho) ? "rho" : !(omega == omega) ? "omega" : "h", nhalf[s], j);
+      else rc = record(s, rd[s]);
+    }
+    if (rc) break;
+    if (f.nactive > 0) { // (a column that stopped after the first half step sits out the second)
+      rc = multi_upload_mask(f);
+      if (!rc) rc = half_step_2();
+      if (!rc) rc = ddm_memcpy_d2h(ctx, rd, half2, sizeof(double) * (size_t)w);
+      for (int s = 0; s < w && !rc; ++s) {
+        if (!f.active[s]) continue;
+        rc = record(s, rd[s]);
+        if (!rc && f.active[s] && nhalf[s] >= 2 * maxit) { // out of iterations: leaves its slot unconverged
+          f.active[s] = 0;
+          f.nactive -= 1;
+          f.changed = true;
+        }
+      }
+      if (rc) break;
+    }
+    // the boundary: every slot whose column stopped in this iteration is stored and released, then refilled
+    int nstore = 0;
+    for (int s = 0; s < w; ++s)
+      if (column[s] >= 0 && !f.active[s]) tab[2 * nstore] = s, tab[2 * nstore + 1] = column[s], ++nstore;
+    if (nstore > 0) {
+      rc = upload_table(nstore);
+      if (rc) break;
+      hipLaunchKernelGGL(k_column_store_multi, dim3(grid_for(n * nstore)), dim3(WG), 0, ctx->stream, n, w, nstore, (const int64_t *)tabdev, ncols, (const double *)XW, X);
+      if ((rc = launch_ok())) break;
+      for (int k = 0; k < nstore; ++k) release((int)tab[2 * k]);
+    }
+    rc = nstore > 0 && next < ncols ? refill() : multi_upload_mask(f);
+  }
+  if (!rc) rc = launch_ok();
   rc = multi_finish(f, prec, rc, t0); // (drains the stream; the elapsed time of the call lands in the slots' entries)
   for (int64_t j = 0; j < ncols; ++j) res[j].elapsed_s = sres[0].elapsed_s;
   return rc;

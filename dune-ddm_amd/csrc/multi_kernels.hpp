@@ -234,10 +234,11 @@ __global__ void k_cg_direction_multi(int64_t n, int m, const int32_t *__restrict
   }
 }
 // x += lambda p; b -= lambda q; partial sums of <b, b> for columns [c0, c0 + CB) -- k_cg_update_norm per column (same grid, rows per
-// thread and block_sum).  Columns that are not active are neither read nor written (their partials are 0).
+// thread and block_sum).  Columns that are not active are neither read nor written (their partials are 0).  lambda_c is
+// scal[slot * MULTI_MAX + c]: slot 2 in the CG drivers, the alpha slot in the first half step of the queued BiCGSTAB.
 template <int CB, bool MASKED>
 __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
-                                                             const uint8_t *__restrict__ mask, const double *__restrict__ p, const double *__restrict__ q,
+                                                             int slot, const uint8_t *__restrict__ mask, const double *__restrict__ p, const double *__restrict__ q,
                                                              double *__restrict__ x, double *__restrict__ b, double *__restrict__ partial)
 {
   __shared__ double red[4];
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, i
 #pragma unroll
   for (int u = 0; u < CB; ++u) {
     on[u] = active[c0 + u] != 0;
-    lam[u] = scal[2 * MULTI_MAX + c0 + u];
+    lam[u] = scal[slot * MULTI_MAX + c0 + u];
     s[u] = 0.0;
   }
   for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
@@ -298,6 +299,192 @@ __global__ void k_column_store_multi(int64_t n, int m, int nstore, const int64_t
     const int64_t i = t / nstore;
     const int k = (int)(t - i * nstore);
     Xc[i * ncols + tab[2 * k + 1]] = x[i * m + tab[2 * k]];
+  }
+}
+
+// ---- queued BiCGSTAB (ddm_bicgstab_solve_queue, csrc/krylov.hpp) -----------------------------------------------------------------------
+// Per-column scalars in ctx->mscal, M = MULTI_MAX: [0..M) rho, [M..2M) alpha, [2M..3M) omega, [3M..4M) beta.  The sums the host
+// reads are packed at stride m (the block width), so that one all-reduce and one copy take a group of them:
+//   first half step   [4M..): <r, r>, then h = <rt, v>, then the rho and the omega that the direction update used (4 m doubles)
+//   second half step  [8M..): <r, r>, then rho_new = <rt, r> of the next iteration (2 m doubles)
+//   refill            [10M..): <r, r> of the loaded slots;  [11M..): <t, t>, then <t, r> (2 m doubles)
+constexpr int BICG_RHO = 0, BICG_ALPHA = 1, BICG_OMEGA = 2, BICG_BETA = 3, BICG_HALF1 = 4, BICG_HALF2 = 8, BICG_LOAD = 10, BICG_TT = 11;
+constexpr int BICG_SCALARS = 13; // ... times MULTI_MAX doubles
+
+// beta = (rho_new / rho) (alpha / omega) in the active columns; rho and omega as used go where the host reads them with the first
+// half step's defect (its breakdown checks run on exactly these operands)
+__global__ void k_bicg_beta_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) {
+    const double rho = scal[BICG_RHO * MULTI_MAX + c], omega = scal[BICG_OMEGA * MULTI_MAX + c];
+    const double rho_new = scal[BICG_HALF2 * MULTI_MAX + m + c];
+    scal[BICG_BETA * MULTI_MAX + c] = (rho_new / rho) * (scal[BICG_ALPHA * MULTI_MAX + c] / omega);
+    scal[BICG_HALF1 * MULTI_MAX + 2 * m + c] = rho;
+    scal[BICG_HALF1 * MULTI_MAX + 3 * m + c] = omega;
+  }
+}
+// alpha = rho_new / h
+__global__ void k_bicg_alpha_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) scal[BICG_ALPHA * MULTI_MAX + c] = scal[BICG_HALF2 * MULTI_MAX + m + c] / scal[BICG_HALF1 * MULTI_MAX + m + c];
+}
+// omega = <t, r> / <t, t>; rho = rho_new
+__global__ void k_bicg_omega_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) {
+    scal[BICG_OMEGA * MULTI_MAX + c] = scal[BICG_TT * MULTI_MAX + m + c] / scal[BICG_TT * MULTI_MAX + c];
+    scal[BICG_RHO * MULTI_MAX + c] = scal[BICG_HALF2 * MULTI_MAX + m + c];
+  }
+}
+// p = r + beta (p - omega v) in the active columns, evaluated as the single-vector driver does with three kernels
+// (p += (-omega) v; p *= beta; p += r): with p = v = 0 the result is r exactly, whatever beta and omega are (finite)
+__global__ void k_bicg_direction_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ scal, const double *__restrict__ r,
+                                       const double *__restrict__ v, double *__restrict__ p)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) {
+      double pi = p[t] + -scal[BICG_OMEGA * MULTI_MAX + c] * v[t];
+      pi *= scal[BICG_BETA * MULTI_MAX + c];
+      p[t] = pi + r[t];
+    }
+  }
+}
+// partial sums of <t, t> and <t, r> for columns [c0, c0 + CB) in one pass: the grid, rows per thread and block_sum of
+// k_dot_partial_multi, so both sums are bit-identical to two launches of it.  partial[(q * m + c) * gridDim.x + b], q = 0: <t, t>,
+// q = 1: <t, r>.  Columns that are not active are not read (their partials are 0).
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_dot2_partial_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const uint8_t *__restrict__ mask,
+                                                           const double *__restrict__ t, const double *__restrict__ r, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double stt[CB], str[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    stt[u] = str[u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const int64_t o = i * m + c0;
+#pragma unroll
+      for (int u = 0; u < CB; ++u)
+        if (on[u]) {
+          const double ti = t[o + u];
+          stt[u] += ti * ti;
+          str[u] += ti * r[o + u];
+        }
+    }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double a = block_sum(stt[u], red);
+    const double b = block_sum(str[u], red);
+    if (threadIdx.x == 0) {
+      partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = a;
+      partial[(int64_t)(m + c0 + u) * gridDim.x + blockIdx.x] = b;
+    }
+  }
+}
+// Second half step for columns [c0, c0 + CB): x += omega y; r -= omega t; partial sums of <r, r> and of <rt, r> (the next iteration's
+// rho_new) for the updated r, in one pass.  Vectors and sums are bit-identical to two AXPYs followed by k_dot_partial_multi(r, r) and
+// k_dot_partial_multi(rt, r); the partials are laid out as in k_dot2_partial_multi (q = 0: <r, r>, q = 1: <rt, r>).  Columns that are
+// not active are neither read nor written (their partials are 0).
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_bicg_half2_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
+                                                         const uint8_t *__restrict__ mask, const double *__restrict__ y, const double *__restrict__ t,
+                                                         const double *__restrict__ rt, double *__restrict__ x, double *__restrict__ r,
+                                                         double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double om[CB], srr[CB], srt[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    om[u] = scal[BICG_OMEGA * MULTI_MAX + c0 + u];
+    srr[u] = srt[u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    const int64_t o = i * m + c0;
+    const bool own = !MASKED || mask[i];
+#pragma unroll
+    for (int u = 0; u < CB; ++u)
+      if (on[u]) {
+        x[o + u] += om[u] * y[o + u];
+        const double ri = r[o + u] - om[u] * t[o + u];
+        r[o + u] = ri;
+        if (own) {
+          srr[u] += ri * ri;
+          srt[u] += rt[o + u] * ri;
+        }
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double a = block_sum(srr[u], red);
+    const double b = block_sum(srt[u], red);
+    if (threadIdx.x == 0) {
+      partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = a;
+      partial[(int64_t)(m + c0 + u) * gridDim.x + blockIdx.x] = b;
+    }
+  }
+}
+// Load of a BiCGSTAB slot (tab as in k_column_load_multi): x_slot = X[:, column], r_slot = B[:, column], p_slot = v_slot = 0 and
+// rho = alpha = omega = 1: the slot's next beta is finite and its next direction p = r + beta (0 - omega 0) is r, the first
+// direction of the new column.
+__global__ void k_bicg_column_load_multi(int64_t n, int m, int nload, const int64_t *__restrict__ tab, int64_t ncols, const double *__restrict__ Xc,
+                                         const double *__restrict__ Bc, double *__restrict__ x, double *__restrict__ r, double *__restrict__ p,
+                                         double *__restrict__ v, double *__restrict__ scal)
+{
+  const int64_t gid = blockIdx.x * (int64_t)WG + threadIdx.x;
+  if (gid < nload) {
+    const int64_t s = tab[2 * gid];
+    scal[BICG_RHO * MULTI_MAX + s] = scal[BICG_ALPHA * MULTI_MAX + s] = scal[BICG_OMEGA * MULTI_MAX + s] = 1.0;
+  }
+  const int64_t total = n * nload;
+  for (int64_t t = gid; t < total; t += (int64_t)gridDim.x * WG) {
+    const int64_t i = t / nload;
+    const int k = (int)(t - i * nload);
+    const int64_t o = i * m + tab[2 * k], src = i * ncols + tab[2 * k + 1];
+    x[o] = Xc[src];
+    r[o] = Bc[src];
+    p[o] = 0.0;
+    v[o] = 0.0;
+  }
+}
+// rt = r in the columns of `active` (the slots just loaded, r being their initial defect) and their rho_new = <rt, r> = <r, r>, the
+// sum that the defect pass of the refill has just formed on the grid of the block dot
+__global__ void k_bicg_shadow_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ r, double *__restrict__ rt,
+                                    double *__restrict__ scal)
+{
+  const int64_t gid = blockIdx.x * (int64_t)WG + threadIdx.x;
+  if (gid < m && active[gid]) scal[BICG_HALF2 * MULTI_MAX + m + gid] = scal[BICG_LOAD * MULTI_MAX + gid];
+  const int64_t total = n * m;
+  for (int64_t t = gid; t < total; t += (int64_t)gridDim.x * WG)
+    if (active[t % m]) rt[t] = r[t];
+}
+// the composition of simple kernels (the default; DDM_BICGSTAB_QUEUE_FUSED=1 selects the fused kernels above), one per update: y += sign coef_c x (coef null: 1) and y *= coef_c
+// in the active columns, one thread per block entry
+__global__ void k_axpy_dev_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ coef, double sign,
+                                 const double *__restrict__ x, double *__restrict__ y)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) y[t] += (coef ? sign * coef[c] : sign) * x[t];
+  }
+}
+__global__ void k_scal_dev_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ coef, double *__restrict__ y)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (active[c]) y[t] *= coef[c];
   }
 }
 

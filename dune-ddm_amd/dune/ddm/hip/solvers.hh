@@ -170,12 +170,61 @@ public:
     if (verbose_ > 0) std::printf("=== device block Krylov solve: %zu columns, %.3f s\n", m, m ? r[0].elapsed_s : 0.0);
   }
 
+  // Any number of right-hand sides through a block loop of `width` (1 to 32) slots (HipCGSolver: ddm_cg_solve_queue; HipBiCGSTABSolver:
+  // ddm_bicgstab_solve_queue): a slot whose column has stopped takes the next pending one.  Each column as apply(x[c], b[c], res[c])
+  // with the solver's reduction would run it, except that b is left as it is (the defects live in the device work block).  One upload
+  // of both row-major n x M blocks, one download of x.  A solver without a queued loop (the GMRES solvers: their restart cycles are
+  // aligned) throws Dune::NotImplemented.
+  void apply_queue(std::vector<X>& x, std::vector<X>& b, int width, std::vector<InverseOperatorResult>& res)
+  {
+    const std::size_t m = b.size();
+    if (m < 1 || x.size() != m || width < 1 || width > 32)
+      DUNE_THROW(InvalidStateException, "device Krylov queued apply: at least one column, as many x as b, a width of 1 to 32");
+    const std::size_t n = b[0].N();
+    for (std::size_t c = 0; c < m; ++c)
+      if (b[c].N() != n || x[c].N() != n) DUNE_THROW(InvalidStateException, "device Krylov queued apply: the columns differ in size");
+    auto ctx = cprec->context();
+    ddm_hip::DeviceVector dX(ctx, n * m), dB(ctx, n * m);
+    std::vector<double> hx(n * m), hb(n * m);
+    for (std::size_t c = 0; c < m; ++c) {
+      prec->pre(x[c], b[c]);
+      for (std::size_t i = 0; i < n; ++i) {
+        hx[i * m + c] = x[c][i][0];
+        hb[i * m + c] = b[c][i][0];
+      }
+    }
+    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dX.data(), hx.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dB.data(), hb.data(), (int64_t)(n * m * sizeof(double))), "h2d");
+    std::vector<ddm_solve_result> r(m);
+    ddm_hip::check(ctx->handle(),
+                   solve_queue(ctx->handle(), dop->op_handle(), cprec->handle(n), (int64_t)m, width, dX.data(), dB.data(), reduction_, r.data()),
+                   "device queued Krylov solve");
+    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hx.data(), dX.data(), (int64_t)(n * m * sizeof(double))), "d2h");
+    res.assign(m, InverseOperatorResult{});
+    for (std::size_t c = 0; c < m; ++c) {
+      for (std::size_t i = 0; i < n; ++i) x[c][i][0] = hx[i * m + c];
+      prec->post(x[c]);
+      res[c].clear();
+      res[c].iterations = r[c].iterations;
+      res[c].converged = r[c].converged != 0;
+      res[c].reduction = r[c].reduction;
+      res[c].elapsed = r[c].elapsed_s;
+      res[c].conv_rate = r[c].iterations > 0 ? std::pow(r[c].reduction, 1.0 / r[c].iterations) : 0.0;
+    }
+    if (verbose_ > 0) std::printf("=== device queued Krylov solve: %zu columns through %d slots, %.3f s\n", m, width, r[0].elapsed_s);
+  }
+
 protected:
   virtual int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) = 0;
   // the block loop of the solver on row-major n x m device blocks (r: m entries)
   virtual int solve_block(ddm_ctx*, ddm_op*, ddm_combined*, int, double*, double*, double, ddm_solve_result*)
   {
     DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver, restartedgmressolver and restartedflexiblegmressolver have one)");
+  }
+  // the queued loop of the solver: row-major n x ncols device blocks through `width` slots (r: ncols entries)
+  virtual int solve_queue(ddm_ctx*, ddm_op*, ddm_combined*, int64_t, int, double*, double*, double, ddm_solve_result*)
+  {
+    DUNE_THROW(NotImplemented, "this device Krylov solver has no queued loop for any number of right-hand sides (cgsolver and bicgstabsolver have one)");
   }
   std::shared_ptr<LinearOperator<X, X>> op;
   std::shared_ptr<Preconditioner<X, X>> prec;
@@ -197,49 +246,6 @@ public:
 
   using HipKrylovSolverBase<X>::apply;
 
-  // Any number of right-hand sides through a block loop of `width` (1 to 32) slots (ddm_cg_solve_queue): a slot whose column has
-  // stopped takes the next pending one.  Each column as apply(x[c], b[c], res[c]) with the solver's reduction would run it, except that
-  // b is left as it is (the defects live in the device work block).  One upload of both row-major n x M blocks, one download of x.
-  void apply_queue(std::vector<X>& x, std::vector<X>& b, int width, std::vector<InverseOperatorResult>& res)
-  {
-    const std::size_t m = b.size();
-    if (m < 1 || x.size() != m || width < 1 || width > 32)
-      DUNE_THROW(InvalidStateException, "device Krylov queued apply: at least one column, as many x as b, a width of 1 to 32");
-    const std::size_t n = b[0].N();
-    for (std::size_t c = 0; c < m; ++c)
-      if (b[c].N() != n || x[c].N() != n) DUNE_THROW(InvalidStateException, "device Krylov queued apply: the columns differ in size");
-    auto ctx = this->cprec->context();
-    ddm_hip::DeviceVector dX(ctx, n * m), dB(ctx, n * m);
-    std::vector<double> hx(n * m), hb(n * m);
-    for (std::size_t c = 0; c < m; ++c) {
-      this->prec->pre(x[c], b[c]);
-      for (std::size_t i = 0; i < n; ++i) {
-        hx[i * m + c] = x[c][i][0];
-        hb[i * m + c] = b[c][i][0];
-      }
-    }
-    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dX.data(), hx.data(), (int64_t)(n * m * sizeof(double))), "h2d");
-    ddm_hip::check(ctx->handle(), ddm_memcpy_h2d(ctx->handle(), dB.data(), hb.data(), (int64_t)(n * m * sizeof(double))), "h2d");
-    std::vector<ddm_solve_result> r(m);
-    ddm_hip::check(ctx->handle(),
-                   ddm_cg_solve_queue(ctx->handle(), this->dop->op_handle(), this->cprec->handle(n), (int64_t)m, width, dX.data(), dB.data(), this->reduction_,
-                                      this->maxit_, nullptr, r.data()),
-                   "device queued Krylov solve");
-    ddm_hip::check(ctx->handle(), ddm_memcpy_d2h(ctx->handle(), hx.data(), dX.data(), (int64_t)(n * m * sizeof(double))), "d2h");
-    res.assign(m, InverseOperatorResult{});
-    for (std::size_t c = 0; c < m; ++c) {
-      for (std::size_t i = 0; i < n; ++i) x[c][i][0] = hx[i * m + c];
-      this->prec->post(x[c]);
-      res[c].clear();
-      res[c].iterations = r[c].iterations;
-      res[c].converged = r[c].converged != 0;
-      res[c].reduction = r[c].reduction;
-      res[c].elapsed = r[c].elapsed_s;
-      res[c].conv_rate = r[c].iterations > 0 ? std::pow(r[c].reduction, 1.0 / r[c].iterations) : 0.0;
-    }
-    if (this->verbose_ > 0) std::printf("=== device queued Krylov solve: %zu columns through %d slots, %.3f s\n", m, width, r[0].elapsed_s);
-  }
-
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
   {
@@ -248,6 +254,10 @@ protected:
   int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
   {
     return ddm_cg_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, nullptr, r);
+  }
+  int solve_queue(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int64_t ncols, int width, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_cg_solve_queue(ctx, o, p, ncols, width, X_, B_, reduction, this->maxit_, nullptr, r);
   }
 };
 
@@ -299,12 +309,16 @@ public:
   HipBiCGSTABSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
       : HipBiCGSTABSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("maxit", 1000), cfg.get("verbose", 0)) {}
 
-  using HipKrylovSolverBase<X>::apply; // (the block overload throws Dune::NotImplemented: no block BiCGSTAB loop yet)
+  using HipKrylovSolverBase<X>::apply; // (the block overload throws Dune::NotImplemented: the block BiCGSTAB loop is apply_queue, any M through w slots)
 
 protected:
   int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
   {
     return ddm_bicgstab_solve(ctx, o, p, x, b, reduction, this->maxit_, nullptr, nullptr, r);
+  }
+  int solve_queue(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int64_t ncols, int width, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_bicgstab_solve_queue(ctx, o, p, ncols, width, X_, B_, reduction, this->maxit_, nullptr, nullptr, r);
   }
 };
 

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, cg_solve, cg_solve_multi, cg_solve_queue, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
+               SchwarzPreconditioner, bicgstab_solve_queue, cg_solve, cg_solve_multi, cg_solve_queue, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
 
@@ -273,7 +273,7 @@ class TwoLevelSchwarz:
 
     # -- solve -------------------------------------------------------------------------------
     SOLVERS = ("cgsolver", "restartedgmressolver", "restartedflexiblegmressolver", "bicgstabsolver")
-    SOLVERS_MULTI = SOLVERS[:3]   # (no block BiCGSTAB loop)
+    SOLVERS_MULTI = SOLVERS[:3]   # (the block BiCGSTAB loop is the queued one: solve_many with M <= width)
 
     def solve(self, reduction=1e-10, maxit=1000, fixed_iterations=0, history=True, x0=None, b=None, solver="cgsolver", restart=100):
         """v = 0; solver->apply(v, b, res)  (examples/poisson.cc:318-319).  solver: "cgsolver", "restartedgmressolver",
@@ -333,18 +333,24 @@ class TwoLevelSchwarz:
             res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
         return res, hist, X
 
-    def solve_many(self, B, width=8, reduction=1e-10, maxit=1000, history=True, X0=None):
-        """Any number M of right-hand sides, M independent CG solves through one block loop of ``width`` <= 32 slots
-        (ddm_cg_solve_queue): a slot whose column has stopped takes the next pending column, so no slot idles while columns wait.  Each
-        column is what ``solve_multi`` computes on it.  B, X0: (n_o, M) arrays or tensors, M may be smaller than ``width``.  Returns
-        (list of M SolveResult, (iters + 1) x M history -- row k of column j: its defect after its own k-th iteration -- or None, X as an
-        (n_o, M) device tensor)."""
+    def solve_many(self, B, width=8, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver"):
+        """Any number M of right-hand sides, M independent solves through one block loop of ``width`` <= 32 slots: a slot whose column
+        has stopped takes the next pending column, so no slot idles while columns wait.  solver="cgsolver" (ddm_cg_solve_queue): each
+        column is what ``solve_multi`` computes on it.  solver="bicgstabsolver" (ddm_bicgstab_solve_queue), for the non-symmetric
+        configurations: each column is what ``solve(solver="bicgstabsolver")`` computes on it, and with M <= width this is the block
+        BiCGSTAB solve.  B, X0: (n_o, M) arrays or tensors, M may be smaller than ``width``.  Returns (list of M SolveResult, history or
+        None -- row k of column j: its defect after its own k-th iteration (cgsolver) or half step (bicgstabsolver), NaN after its last
+        --, X as an (n_o, M) device tensor)."""
+        if solver not in ("cgsolver", "bicgstabsolver"):
+            raise NotImplementedError("solver type '" + str(solver) + "' (cgsolver and bicgstabsolver take any number of right-hand sides "
+                                      "through a block of fixed width)")
         if not 1 <= int(width) <= 32:
             raise ValueError(f"width = {width} outside [1, 32]")
         if int(maxit) < 0:
             raise ValueError(f"maxit = {maxit} is negative")
         Bd, X = self._blocks(B, X0)
-        res, hist = cg_solve_queue(self.ctx, self.op, self.prec, X, Bd, int(width), reduction, maxit, history)
+        queue = bicgstab_solve_queue if solver == "bicgstabsolver" else cg_solve_queue
+        res, hist = queue(self.ctx, self.op, self.prec, X, Bd, int(width), reduction, maxit, history)
         return res, hist, X
 
 

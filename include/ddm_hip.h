@@ -507,6 +507,21 @@ int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, d
  *     stored before keep their results, X[:, j] of every other column is as on entry and its res entry is reset. */
 int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
                        int maxit, double *hist_host, ddm_solve_result *res);
+
+/* BiCGSTAB for any number of right-hand sides through a block of fixed width: the queue protocol of ddm_cg_solve_queue over the
+ * recurrence of ddm_bicgstab_solve.  X, B: the caller's row-major n x ncols device blocks (B is only read); width in [1, 32] slots;
+ * res: ncols entries.  Every column is what ddm_bicgstab_solve computes on it (right-preconditioned, two half steps per iteration,
+ * norm <= def0 * reduction tested after each, iterations = ceil(half steps / 2), maxit full iterations per column).  A column that
+ * stops after a first half step sits out the second; there is one boundary per iteration, after the second half step, at which the
+ * stopped columns are stored and the freed slots take the next columns in ascending slot order.  With ncols <= width this is the
+ * plain block solve.  hist_host: (2 maxit + 1) x ncols, row-major, or NULL -- row k of column j is its defect after its own k-th
+ * half step, rows a column never reaches are left as passed; nhist (may be NULL): entries written per column.  A breakdown (the
+ * checks of ddm_bicgstab_solve on rho, omega and h) or a NaN in a running column ends the call with DDM_ENUMERIC, the message naming
+ * the column and the scalar: the columns stored before keep their results, X[:, j] of the others is as on entry.
+ * DDM_BICGSTAB_QUEUE_FUSED (read once per process): 1 selects the fused vector kernels, 0 or unset the composition of simple kernels
+ * (the default: it measured faster); the results are bit-identical. */
+int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
+                             int maxit, double *hist_host, int32_t *nhist, ddm_solve_result *res);
 /* nrhs INDEPENDENT dune-istl RestartedGMResSolver::apply recurrences in one loop (the loop of ddm_gmres_solve per column: left
  * preconditioning, modified Gram-Schmidt in the order k = 0..i, the same Givens rotations, the monitored norm is that of the
  * preconditioned defect; not a block-Krylov method).  X, B, hist_host ((maxit + 1) x nrhs, entries after a column's last iteration are
