@@ -6,37 +6,13 @@
 //        boundary.bin (doubles), ring1.bin / ring2.bin (int64), bdata.bin (2 x #boundary doubles)
 //   out: <space>.bin (k x n doubles) and "lambda <space> <value>" lines
 #include <cstdio>
-#include <fstream>
+#include <cstdlib>
 #include <iostream>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include <dune/istl/bcrsmatrix.hh>
-#include <dune/istl/bvector.hh>
-
-#include <dune/ddm/hip/coarse_spaces.hh>
-
-template <class T>
-static std::vector<T> slurp(const std::string& f)
-{
-  std::ifstream in(f, std::ios::binary | std::ios::ate);
-  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
-  const std::size_t bytes = in.tellg();
-  in.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  in.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
-using Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
-using Mat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
-
-static void dump(const std::string& f, const std::vector<Vec>& vs)
-{
-  std::ofstream out(f, std::ios::binary);
-  for (const auto& v : vs)
-    for (std::size_t i = 0; i < v.N(); ++i) { const double x = v[i][0]; out.write(reinterpret_cast<const char*>(&x), 8); }
-}
+#include "adaptor_fixture.hh"
 
 int main(int argc, char** argv)
 {
@@ -44,14 +20,7 @@ int main(int argc, char** argv)
   const std::string dir = argv[1];
   const int overlap = std::atoi(argv[3]);
   try {
-    auto load = [&](const std::string& pre) {
-      auto rp = slurp<int64_t>(dir + "/" + pre + "_rowptr.bin");
-      auto ci = slurp<int32_t>(dir + "/" + pre + "_col.bin");
-      auto va = slurp<double>(dir + "/" + pre + "_val.bin");
-      const std::size_t n = rp.size() - 1;
-      return std::make_shared<const Mat>(n, n, std::vector<std::size_t>(rp.begin(), rp.end()), std::vector<std::size_t>(ci.begin(), ci.end()), va);
-    };
-    auto A_neu = load("N"), A_dir = load("D"), R1 = load("R1"), R2 = load("R2");
+    std::shared_ptr<const Mat> A_neu = read_csr(dir, "N_"), A_dir = read_csr(dir, "D_"), R1 = read_csr(dir, "R1_"), R2 = read_csr(dir, "R2_");
     auto pou = std::make_shared<const PartitionOfUnity>(slurp<double>(dir + "/pou.bin"));
     const std::size_t n = A_dir->N();
     auto dm = slurp<double>(dir + "/dirichlet.bin"), bm = slurp<double>(dir + "/boundary.bin");
@@ -86,15 +55,15 @@ int main(int argc, char** argv)
     executor.run(taskflow).get();
     std::printf("sizes %zu %zu %zu %zu %zu %zu\n", msgfem->size(), cgeneo->size(), gring->size(), mring->size(), hext->size(), svd->size());
     for (double l : svd->singular_values()) std::printf("lambda svd %.17g\n", l);
-    dump(dir + "/svd.bin", svd->get_basis());
+    write_bin(dir + "/svd.bin", svd->get_basis());
     for (double l : msgfem->eigenvalues()) std::printf("lambda msgfem %.17g\n", l);
     for (double l : gring->eigenvalues()) std::printf("lambda geneo_ring %.17g\n", l);
     for (double l : mring->eigenvalues()) std::printf("lambda msgfem_ring %.17g\n", l);
-    dump(dir + "/msgfem.bin", msgfem->get_basis());
-    dump(dir + "/constraint_geneo.bin", cgeneo->get_basis());
-    dump(dir + "/geneo_ring.bin", gring->get_basis());
-    dump(dir + "/msgfem_ring.bin", mring->get_basis());
-    dump(dir + "/harmonic.bin", hext->get_basis());
+    write_bin(dir + "/msgfem.bin", msgfem->get_basis());
+    write_bin(dir + "/constraint_geneo.bin", cgeneo->get_basis());
+    write_bin(dir + "/geneo_ring.bin", gring->get_basis());
+    write_bin(dir + "/msgfem_ring.bin", mring->get_basis());
+    write_bin(dir + "/harmonic.bin", hext->get_basis());
     // error conventions (coarse_spaces.hh:714-718, :972)
     int caught = 0;
     try {

@@ -11,34 +11,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <iostream>
-#include <memory>
 #include <string>
 #include <vector>
 
-#include <dune/istl/bcrsmatrix.hh>
-#include <dune/istl/bvector.hh>
-#include <dune/istl/owneroverlapcopy.hh>
+#include "adaptor_fixture.hh"   // first: the adaptor headers below expect the dune-istl ones before them
 
-#include <dune/ddm/hip/combined_preconditioner.hh>
-#include <dune/ddm/hip/galerkin_preconditioner.hh>
-#include <dune/ddm/hip/nonoverlapping_operator.hh>
-#include <dune/ddm/hip/schwarz.hh>
-#include <dune/ddm/hip/coarse_spaces.hh>
 #include <dune/ddm/hip/solvers.hh>
-
-template <class T>
-static std::vector<T> slurp(const std::string& f)
-{
-  std::ifstream in(f, std::ios::binary | std::ios::ate);
-  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
-  const std::size_t bytes = in.tellg();
-  in.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  in.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
 
 static std::size_t differing(const double* a, const double* b, std::size_t n)
 {
@@ -52,54 +31,20 @@ int main(int argc, char** argv)
   if (argc < 3) return 2;
   const std::string dir = argv[1];
   const int m = std::atoi(argv[2]);
-  using Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
-  using Mat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
-  using Comm = Dune::OwnerOverlapCopyCommunication<std::size_t, int>;
   try {
-    auto rp64 = slurp<int64_t>(dir + "/rowptr.bin");
-    auto ci32 = slurp<int32_t>(dir + "/col.bin");
-    auto va = slurp<double>(dir + "/val.bin");
-    auto bb = slurp<double>(dir + "/b.bin");
-    auto dm = slurp<unsigned char>(dir + "/dirichlet.bin");
-    auto pw = slurp<double>(dir + "/pou.bin");
-    const std::size_t n = rp64.size() - 1;
-    auto A = std::make_shared<Mat>(n, n, std::vector<std::size_t>(rp64.begin(), rp64.end()), std::vector<std::size_t>(ci32.begin(), ci32.end()), va);
-    auto comm = std::make_shared<Comm>();
-    for (std::size_t i = 0; i < n; ++i) comm->indexSet().v.push_back({i, {i, Dune::OwnerOverlapCopyAttributeSet::owner}});
-
-    Dune::ParameterTree ptree;
-    ptree.sub("schwarz")["type"] = "restricted";
-    ptree.sub("schwarz").sub("subdomain_solver")["type"] = "ilu0";
-    ptree.sub("combined_preconditioner")["mode"] = "multiplicative";
-    ptree.sub("coarse_solver")["type"] = "umfpack";
+    const Problem p = read_problem(dir);
+    const auto bb = slurp<double>(dir + "/b.bin");
+    const std::size_t n = p.n;
+    auto ptree = two_level_ptree("restricted", "ilu0", "multiplicative", "umfpack");
     ptree.sub("solver")["type"] = "restartedflexiblegmressolver";
     ptree.sub("solver")["restart"] = "6";
     ptree.sub("solver")["maxit"] = "500";
     ptree.sub("solver")["reduction"] = "1e-10";
-    auto pou = std::make_shared<PartitionOfUnity>(pw);
-    auto schwarz = std::make_shared<SchwarzPreconditioner<Mat, Vec, Comm>>(A, comm, pou, ptree);
-    tf::Taskflow taskflow("Main taskflow");
-    auto coarse_space = std::make_unique<POUCoarseSpace<Vec>>(pou, taskflow);
-    std::shared_ptr<GalerkinPreconditioner<Vec, Comm>> coarse;
-    auto task = taskflow.emplace([&]() {
-      auto basis = coarse_space->get_basis();
-      for (auto& v : basis)
-        for (std::size_t i = 0; i < n; ++i)
-          if (dm[i]) v[i] = 0.0;   // zero_at_dirichlet (poisson.cc:235-238)
-      coarse = std::make_shared<GalerkinPreconditioner<Vec, Comm>>(*A, basis, comm, ptree, "coarse_solver");
-    });
-    task.name("Build coarse preconditioner").succeed(coarse_space->get_setup_task());
-    tf::Executor executor(1);
-    executor.run(taskflow).get();
-    auto op = std::make_shared<NonOverlappingOperator<Mat, Vec, Vec, Comm>>(A, comm);
-    auto prec = std::make_shared<CombinedPreconditioner<Vec>>(ptree);
-    prec->set_op(op);
-    prec->add(schwarz);
-    prec->add(coarse);
+    const TwoLevel t = build_two_level(p, ptree);
 
     // the factory knows the key and returns the flexible solver; an unknown key still throws, naming the four solvers
     std::shared_ptr<Dune::InverseOperator<Vec, Vec>> made =
-        Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(op), ptree.sub("solver"), std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(prec));
+        Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(t.op), ptree.sub("solver"), std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(t.prec));
     auto solver = std::dynamic_pointer_cast<Dune::HipRestartedFlexibleGMResSolver<Vec>>(made);
     std::printf("factory %d\n", solver ? 1 : 0);
     if (!solver) return 1;
@@ -107,30 +52,20 @@ int main(int argc, char** argv)
     try {
       Dune::ParameterTree other;
       other["type"] = "minressolver";
-      Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(op), other, std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(prec));
+      Dune::getHipSolver<Vec>(std::static_pointer_cast<Dune::LinearOperator<Vec, Vec>>(t.op), other, std::static_pointer_cast<Dune::Preconditioner<Vec, Vec>>(t.prec));
     } catch (Dune::NotImplemented& e) {
       if (std::string(e.what()).find("restartedflexiblegmressolver") != std::string::npos) ++caught;
     }
 
-    // right-hand sides: the problem's, then seeded pseudo-random ones (zero on the Dirichlet rows like the problem's)
-    std::vector<Vec> B(m, Vec(n)), X(m, Vec(n));
-    std::vector<double> hb(n * m), hx(n * m, 0.0);
-    unsigned long long s = 12345;
-    for (int c = 0; c < m; ++c)
-      for (std::size_t i = 0; i < n; ++i) {
-        s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-        const double r = (double)(s >> 11) / 9007199254740992.0 - 0.5;
-        B[c][i] = c == 0 ? bb[i] : (dm[i] ? 0.0 : r);
-        X[c][i] = 0.0;
-        hb[i * m + c] = B[c][i];
-      }
+    std::vector<Vec> B = seeded_columns(p, bb, m), X = zero_columns(n, m);
+    std::vector<double> hb = pack(B), hx(n * m, 0.0);
     const std::vector<Vec> Bsave = B;
 
     // the same device objects through the C ABI
-    auto ctx = prec->context();
+    auto ctx = t.prec->context();
     ddm_ctx* h = ctx->handle();
-    ddm_op* oh = op->op_handle();
-    ddm_combined* ph = prec->handle(n);
+    ddm_op* oh = t.op->op_handle();
+    ddm_combined* ph = t.prec->handle(n);
     bool ok = true;
     {
       Vec x1(n), b1 = Bsave[0];

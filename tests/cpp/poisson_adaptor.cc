@@ -10,104 +10,47 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
-#include <fstream>
 #include <iostream>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include <dune/istl/bcrsmatrix.hh>
-#include <dune/istl/bvector.hh>
-#include <dune/istl/owneroverlapcopy.hh>
+#include "adaptor_fixture.hh"   // first: the adaptor headers below expect the dune-istl ones before them
 
-#include <dune/ddm/hip/combined_preconditioner.hh>
-#include <dune/ddm/hip/galerkin_preconditioner.hh>
-#include <dune/ddm/hip/nonoverlapping_operator.hh>
-#include <dune/ddm/hip/schwarz.hh>
-#include <dune/ddm/hip/coarse_spaces.hh>
 #include <dune/ddm/hip/solvers.hh>
 #include <dune/ddm/hip/rccl_exchange.hh>
-
-template <class T>
-static std::vector<T> slurp(const std::string& f)
-{
-  std::ifstream in(f, std::ios::binary | std::ios::ate);
-  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
-  const std::size_t bytes = in.tellg();
-  in.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  in.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
 
 int main(int argc, char** argv)
 {
   if (argc < 3) return 2;
   const std::string dir = argv[1], mode = argv[2];
-  using Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
-  using Mat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
-  using Comm = Dune::OwnerOverlapCopyCommunication<std::size_t, int>;
   try {
     if (std::getenv("DDM_TEST_RCCL")) {   // the in-library RCCL exchange installed the way a DUNE program would (size-1 communicator, self test)
       auto ctx = ddm_hip::install_rccl_exchange(ddm_hip::make_rccl_id(), 0, 1, 0, /*self_test=*/true);
       std::printf("rccl_exchange installed rank %d of %d\n", ctx->rank, ctx->nranks);
       try { ddm_hip::install_rccl_exchange(ddm_hip::RcclId(), 2, 1); } catch (Dune::InvalidStateException&) { std::printf("rccl_bad_rank_caught\n"); }
     }
-    auto rp64 = slurp<int64_t>(dir + "/rowptr.bin");
-    auto ci32 = slurp<int32_t>(dir + "/col.bin");
-    auto va = slurp<double>(dir + "/val.bin");
-    auto bb = slurp<double>(dir + "/b.bin");
-    auto dm = slurp<unsigned char>(dir + "/dirichlet.bin");
-    auto pw = slurp<double>(dir + "/pou.bin");
-    const std::size_t n = rp64.size() - 1;
-    auto A = std::make_shared<Mat>(n, n, std::vector<std::size_t>(rp64.begin(), rp64.end()), std::vector<std::size_t>(ci32.begin(), ci32.end()), va);
-    auto comm = std::make_shared<Comm>();
-    for (std::size_t i = 0; i < n; ++i) comm->indexSet().v.push_back({i, {i, Dune::OwnerOverlapCopyAttributeSet::owner}});
-
-    Dune::ParameterTree ptree;
-    ptree.sub("schwarz")["type"] = "standard";
-    ptree.sub("schwarz").sub("subdomain_solver")["type"] = mode == "device_cholmod" ? "cholmod" : "ilu0";
-    ptree.sub("combined_preconditioner")["mode"] = mode.rfind("device", 0) == 0 ? "additive" : mode;
-    ptree.sub("coarse_solver")["type"] = mode == "device_cholmod" ? "cholmod" : "umfpack";   // examples/poisson.ini:25-26
-    if (mode.rfind("device", 0) == 0) {
-      // examples/poisson.cc:229-321 with the device-resident pieces
-      auto pou = std::make_shared<PartitionOfUnity>(pw);
-      auto schwarz = std::make_shared<SchwarzPreconditioner<Mat, Vec, Comm>>(A, comm, pou, ptree);
-      tf::Taskflow taskflow("Main taskflow");
-      auto coarse_space = std::make_unique<POUCoarseSpace<Vec>>(pou, taskflow);
-      std::shared_ptr<GalerkinPreconditioner<Vec, Comm>> coarse;
-      auto task = taskflow.emplace([&]() {
-        auto basis = coarse_space->get_basis();
-        for (auto& v : basis)
-          for (std::size_t i = 0; i < n; ++i)
-            if (dm[i]) v[i] = 0.0;   // zero_at_dirichlet (poisson.cc:235-238)
-        coarse = std::make_shared<GalerkinPreconditioner<Vec, Comm>>(*A, basis, comm, ptree, "coarse_solver");
-      });
-      task.name("Build coarse preconditioner").succeed(coarse_space->get_setup_task());
-      tf::Executor executor(1);
-      executor.run(taskflow).get();
-      auto op = std::make_shared<NonOverlappingOperator<Mat, Vec, Vec, Comm>>(A, comm);
-      auto prec = std::make_shared<CombinedPreconditioner<Vec>>(ptree);
-      prec->set_op(op);
-      prec->add(schwarz);
-      prec->add(coarse);
+    const Problem problem = read_problem(dir);
+    const auto& [n, A, comm, dm, pw] = problem;
+    const auto bb = slurp<double>(dir + "/b.bin");
+    const bool device = mode.rfind("device", 0) == 0, cholmod = mode == "device_cholmod";
+    const auto ptree = two_level_ptree("standard", cholmod ? "cholmod" : "ilu0", device ? "additive" : mode, cholmod ? "cholmod" : "umfpack");
+    if (device) {
+      const TwoLevel t = build_two_level(problem, ptree);   // examples/poisson.cc:229-321 with the device-resident pieces
       Dune::ParameterTree solver_subtree;
       solver_subtree["type"] = "cgsolver";
       solver_subtree["reduction"] = "1e-10";
       solver_subtree["maxit"] = "500";
-      auto solver = Dune::getHipSolver<Vec>(op, solver_subtree, prec);
+      auto solver = Dune::getHipSolver<Vec>(t.op, solver_subtree, t.prec);
       Dune::InverseOperatorResult res;
-      Vec v(n), b(n);
-      for (std::size_t i = 0; i < n; ++i) b[i] = bb[i];
+      Vec v(n), b = to_vec(bb);
       v = 0;
       solver->apply(v, b, res);   // poisson.cc:318-319
       std::printf("device_solve iterations %d converged %d reduction %.17g\n", res.iterations, (int)res.converged, res.reduction);
-      std::ofstream out(dir + "/x_device.bin", std::ios::binary);
-      for (std::size_t i = 0; i < n; ++i) { const double xi = v[i][0]; out.write(reinterpret_cast<const char*>(&xi), 8); }
+      write_bin(dir + "/x_device.bin", v);
       // the InverseOperator plugin on its own: exact solve A y = b with the sparse Cholesky, ILU(0) application
       Dune::HipSubdomainSolver<Mat> chol(*A, "cholesky"), ilu(*A, "ilu0");
-      Vec y(n), rhs(n), z(n);
-      for (std::size_t i = 0; i < n; ++i) rhs[i] = bb[i];
+      Vec y(n), rhs = to_vec(bb), z(n);
       Dune::InverseOperatorResult r2;
       chol.apply(y, rhs, r2);
       double rmax = 0, bmax = 0;
@@ -121,7 +64,7 @@ int main(int argc, char** argv)
       std::printf("plugin cholesky_residual %.3e converged %d\n", rmax / bmax, (int)r2.converged);
       int caught = 0;
       try { Dune::HipSubdomainSolver<Mat> bad(*A, "bogus"); } catch (Dune::NotImplemented&) { ++caught; }
-      try { solver_subtree["type"] = "minressolver"; Dune::getHipSolver<Vec>(op, solver_subtree, prec); } catch (Dune::NotImplemented&) { ++caught; }
+      try { solver_subtree["type"] = "minressolver"; Dune::getHipSolver<Vec>(t.op, solver_subtree, t.prec); } catch (Dune::NotImplemented&) { ++caught; }
       std::printf("errors_caught %d\n", caught);
       return 0;
     }

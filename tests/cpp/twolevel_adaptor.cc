@@ -7,48 +7,26 @@
 // Two consecutive solves (the Newton / stationary solver calls apply() once per linear system): both must give the same result.
 #include <cmath>
 #include <cstdio>
-#include <fstream>
 #include <iostream>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include <dune/istl/bcrsmatrix.hh>
-#include <dune/istl/bvector.hh>
-#include <dune/istl/owneroverlapcopy.hh>
+#include "adaptor_fixture.hh"   // first: the adaptor headers below expect the dune-istl ones before them
 
 #include <dune/ddm/hip/twolevel_schwarz.hh>
-
-template <class T>
-static std::vector<T> slurp(const std::string& f)
-{
-  std::ifstream in(f, std::ios::binary | std::ios::ate);
-  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
-  const std::size_t bytes = in.tellg();
-  in.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  in.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
 
 int main(int argc, char** argv)
 {
   if (argc < 5) return 2;
   const std::string dir = argv[1], mode = argv[2], local = argv[3], krylov = argv[4];
-  using Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
-  using Mat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
-  using Comm = Dune::OwnerOverlapCopyCommunication<std::size_t, int>;
   try {
-    auto rp64 = slurp<int64_t>(dir + "/rowptr.bin");
-    auto ci32 = slurp<int32_t>(dir + "/col.bin");
-    auto va = slurp<double>(dir + "/val.bin");
+    auto A = read_csr(dir);
     auto bb = slurp<double>(dir + "/b.bin");
     auto pw = slurp<double>(dir + "/pou.bin");
     auto xy = slurp<double>(dir + "/coords.bin");
-    const std::size_t n = rp64.size() - 1;
-    auto A = std::make_shared<Mat>(n, n, std::vector<std::size_t>(rp64.begin(), rp64.end()), std::vector<std::size_t>(ci32.begin(), ci32.end()), va);
-    auto novlp_comm = std::make_shared<Comm>();
-    for (std::size_t i = 0; i < n; ++i) novlp_comm->indexSet().v.push_back({i, {i, Dune::OwnerOverlapCopyAttributeSet::owner}});
+    const std::size_t n = A->N();
+    auto novlp_comm = one_rank_comm(n);
 
     Dune::ParameterTree ptree;   // examples/convectiondiffusiondg.ini:5-24
     auto& sub = ptree.sub("twolevelschwarz");
@@ -77,19 +55,16 @@ int main(int argc, char** argv)
       try { core.solve(A, z, r, 1e-8); } catch (Dune::InvalidStateException&) { ++caught; }   // before the overlapping objects exist
     }
     // first-call half (:93-128) on one rank: ovlp_comm = novlp_comm's index set, A_ovlp = A, extended template vectors = themselves
-    auto ovlp_comm = std::make_shared<Comm>();
-    for (std::size_t i = 0; i < n; ++i) ovlp_comm->indexSet().v.push_back({i, {i, Dune::OwnerOverlapCopyAttributeSet::owner}});
+    auto ovlp_comm = one_rank_comm(n);
     core.set_overlapping(A, ovlp_comm, std::make_shared<PartitionOfUnity>(pw), templ);
 
     for (int call = 0; call < 2; ++call) {
-      Vec z(n), r(n);
+      Vec z(n), r = to_vec(bb);
       z = 0;
-      for (std::size_t i = 0; i < n; ++i) r[i] = bb[i];
       const auto stat = core.solve(A, z, r, 1e-8);
       std::printf("solve %d iterations %d converged %d reduction %.17g norm_z %.17g novlp_comm_set %d coarse_size %d\n", call, stat.iterations, (int)stat.converged,
                   stat.reduction, core.norm(z), (int)(core.fine->novlp_comm == novlp_comm), core.coarse->coarse_size());
-      std::ofstream out(dir + "/z" + std::to_string(call) + ".bin", std::ios::binary);
-      for (std::size_t i = 0; i < n; ++i) { const double v = z[i][0]; out.write(reinterpret_cast<const char*>(&v), 8); }
+      write_bin(dir + "/z" + std::to_string(call) + ".bin", z);
     }
     // configuration errors surface as in the reference: missing solver key in fine.subdomain_solver / coarse
     try {

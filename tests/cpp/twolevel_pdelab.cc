@@ -4,6 +4,7 @@
 // the overlapping objects, the second only refreshes the matrix values), norm(), the result storage.  Same input files and output
 // format as twolevel_adaptor.cc, whose results it must reproduce bit for bit.
 //   usage: twolevel_pdelab <dir> <mode> <subdomain solver> <krylov>
+#include <array>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -11,23 +12,9 @@
 #include <string>
 #include <vector>
 
-#include <dune/istl/bcrsmatrix.hh>
-#include <dune/istl/bvector.hh>
-#include <dune/istl/owneroverlapcopy.hh>
+#include "adaptor_fixture.hh"   // first: the adaptor headers below expect the dune-istl ones before them
 
 #include <dune/ddm/hip/twolevel_schwarz.hh>
-
-template <class T>
-static std::vector<T> slurp(const std::string& f)
-{
-  std::ifstream in(f, std::ios::binary | std::ios::ate);
-  if (!in) { std::cerr << "cannot open " << f << "\n"; std::exit(2); }
-  const std::size_t bytes = in.tellg();
-  in.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  in.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
 
 struct Space {   // what the stand-in interpolate / make_communication ask of a function space
   std::vector<double> xy;
@@ -39,18 +26,16 @@ int main(int argc, char** argv)
 {
   if (argc < 5) return 2;
   const std::string dir = argv[1], mode = argv[2], local = argv[3], krylov = argv[4];
-  using NVec = Dune::BlockVector<Dune::FieldVector<double, 1>>;
-  using NMat = Dune::BCRSMatrix<Dune::FieldMatrix<double, 1, 1>>;
-  using Vec = Dune::PDELab::mock::Vector<Space, NVec>;
+  using NVec = ::Vec;
+  using NMat = ::Mat;
+  using Vec = Dune::PDELab::mock::Vector<Space, NVec>;   // the PDELab containers around the native ones
   using Mat = Dune::PDELab::mock::Matrix<NMat>;
   try {
-    auto rp64 = slurp<int64_t>(dir + "/rowptr.bin");
-    auto ci32 = slurp<int32_t>(dir + "/col.bin");
-    auto va = slurp<double>(dir + "/val.bin");
     auto bb = slurp<double>(dir + "/b.bin");
     Space gfs{slurp<double>(dir + "/coords.bin")};
-    const std::size_t n = rp64.size() - 1;
-    Mat A(std::make_shared<NMat>(n, n, std::vector<std::size_t>(rp64.begin(), rp64.end()), std::vector<std::size_t>(ci32.begin(), ci32.end()), va));
+    auto native = read_csr(dir);
+    const std::size_t n = native->N();
+    Mat A(native);
 
     Dune::ParameterTree ptree;   // examples/convectiondiffusiondg.ini:5-24
     auto& sub = ptree.sub("twolevelschwarz");

@@ -2,30 +2,22 @@
 signatures on top of the C ABI) compiled against minimal DUNE stand-ins (tests/cpp/mock) and driven like
 examples/poisson.cc drives the reference classes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-
-
-def _build():
-    subprocess.check_call(["make", "-C", CPP], stdout=subprocess.DEVNULL)
-    return os.path.join(CPP, "poisson_adaptor")
+from tests.cpp_harness import build, ddm_symbols_used, dump_csr, dump_one_rank_problem, run
 
 
 def test_adaptors_compile_and_link(ddm):
     ddm.load_library()
-    exe = _build()
-    assert os.path.exists(exe)
+    assert os.path.exists(build("mpi_exchange_check.o"))   # mpi_exchange.hh compiles against the image's MPI headers (-DHAVE_MPI=1)
     # every C-ABI symbol the adaptors use must be exported by the library
-    assert os.path.exists(os.path.join(CPP, "mpi_exchange_check.o"))   # mpi_exchange.hh compiles against the image's MPI headers (-DHAVE_MPI=1)
-    for e in (exe, os.path.join(CPP, "geneo_adaptor"), os.path.join(CPP, "coarse_adaptor"), os.path.join(CPP, "twolevel_adaptor"),
-              os.path.join(CPP, "twolevel_pdelab")):   # (the last one: the PDELab-facing class compiled with HAVE_DUNE_PDELAB=1)
-        out = subprocess.run(["nm", "-D", "--undefined-only", e], capture_output=True, text=True).stdout
-        used = sorted({ln.split()[-1] for ln in out.splitlines() if " ddm_" in ln})
+    for name in ("poisson_adaptor", "geneo_adaptor", "coarse_adaptor", "twolevel_adaptor",
+                 "twolevel_pdelab"):   # (the last one: the PDELab-facing class compiled with HAVE_DUNE_PDELAB=1)
+        exe = build(name)
+        assert os.path.exists(exe)
+        used = ddm_symbols_used(exe)
         assert used and all(u in ddm.SYMBOLS for u in used), [u for u in used if u not in ddm.SYMBOLS]
 
 
@@ -35,18 +27,11 @@ def test_adaptor_cg_matches_oracle(ddm, tmp_path, mode):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
     from tests.oracle_bridge import oracle_solve
-    exe = _build()
+    exe = build("poisson_adaptor")
     dec = build_structured(synth.StructuredPoisson((14, 13, 12), (1, 1, 1)), overlap=1, pou_type="distance")
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
-    sd.b.astype(np.float64).tofile(tmp_path / "b.bin")
-    sd.dirichlet_ovlp.astype(np.uint8).tofile(tmp_path / "dirichlet.bin")
-    sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
-    p = subprocess.run([exe, str(tmp_path), mode], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    dump_one_rank_problem(tmp_path, sd)
+    p = run(exe, tmp_path, mode)
     hist = np.array([float(ln.split()[2]) for ln in p.stdout.splitlines() if ln.startswith("it ")])
     assert "errors_caught 5" in p.stdout          # + the two coarse-solver key errors (galerkin_preconditioner.hh:338-346)
     gs = [ln for ln in p.stdout.splitlines() if ln.startswith("getSolver")][0].split()
@@ -59,13 +44,6 @@ def test_adaptor_cg_matches_oracle(ddm, tmp_path, mode):
     assert (np.abs(hist - ho) <= 1e-8 * ho + 1e-12 * ho[0]).all()
 
 
-def _dump_csr(path, pre, M):
-    M = M.tocsr()
-    np.asarray(M.indptr, dtype=np.int64).tofile(path / f"{pre}_rowptr.bin")
-    np.asarray(M.indices, dtype=np.int32).tofile(path / f"{pre}_col.bin")
-    np.asarray(M.data, dtype=np.float64).tofile(path / f"{pre}_val.bin")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["device", "device_cholmod"])
 def test_adaptor_factory_style_device_solver(ddm, tmp_path, mode):
@@ -76,18 +54,11 @@ def test_adaptor_factory_style_device_solver(ddm, tmp_path, mode):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
     from tests.oracle_bridge import oracle_solve
-    exe = _build()
+    exe = build("poisson_adaptor")
     dec = build_structured(synth.StructuredPoisson((14, 13, 12), (1, 1, 1)), overlap=1, pou_type="distance")
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
-    sd.b.astype(np.float64).tofile(tmp_path / "b.bin")
-    sd.dirichlet_ovlp.astype(np.uint8).tofile(tmp_path / "dirichlet.bin")
-    sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
-    p = subprocess.run([exe, str(tmp_path), mode], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    dump_one_rank_problem(tmp_path, sd)
+    p = run(exe, tmp_path, mode)
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("device_solve")][0].split()
     its, conv = int(line[2]), int(line[4])
     it, convo, hist_o, xo = oracle_solve(dec, reduction=1e-10, maxit=500, coarse="pou", schwarz_type="standard", mode="additive",
@@ -101,8 +72,7 @@ def test_adaptor_factory_style_device_solver(ddm, tmp_path, mode):
         # the same run with the in-library RCCL exchange installed from C++ (dune/ddm/hip/rccl_exchange.hh: id, ncclCommInitRank on a
         # size-1 communicator, reductions routed through ncclAllReduce -- the self-test mode): same iteration count, same bits
         x0 = x.copy()
-        q = subprocess.run([exe, str(tmp_path), mode], capture_output=True, text=True, timeout=300, env=dict(os.environ, DDM_TEST_RCCL="1"))
-        assert q.returncode == 0, q.stdout[-2000:] + q.stderr[-2000:]
+        q = run(exe, tmp_path, mode, env=dict(os.environ, DDM_TEST_RCCL="1"))
         assert "rccl_exchange installed rank 0 of 1" in q.stdout and "rccl_bad_rank_caught" in q.stdout
         line2 = [ln for ln in q.stdout.splitlines() if ln.startswith("device_solve")][0].split()
         assert line2[2] == line[2] and line2[4] == "1"
@@ -117,16 +87,14 @@ def test_geneo_coarse_space_adaptor_matches_oracle(ddm, tmp_path):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
     from oracle import geneo_oracle as go
-    _build()
-    exe = os.path.join(CPP, "geneo_adaptor")
+    exe = build("geneo_adaptor")
     dec = build_structured(synth.StructuredPoisson((25, 25, 25), (2, 2, 2), synth.islands_kappa((24, 24, 24), 1e4, 6, 2)), overlap=2, pou_type="distance", neumann=True)
     sd = dec.subs[5]
-    _dump_csr(tmp_path, "A", sd.A_neu)
-    _dump_csr(tmp_path, "B", sd.B_neu)
+    dump_csr(tmp_path, sd.A_neu, "A_")
+    dump_csr(tmp_path, sd.B_neu, "B_")
     sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
     nev = 4
-    p = subprocess.run([exe, str(tmp_path), str(nev)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    p = run(exe, tmp_path, nev)
     assert f"size {nev} consumed {nev}" in p.stdout and "errors_caught 2" in p.stdout
     lam = np.array([float(ln.split()[1]) for ln in p.stdout.splitlines() if ln.startswith("lambda")])
     vecs, lam_o = go.geneo_basis(sd.A_neu, sd.B_neu, sd.pou, {"nev": nev})
@@ -148,8 +116,7 @@ def test_remaining_coarse_space_adaptors_match_oracle(ddm, tmp_path):
     from dune_ddm_amd.problem import build_structured
     from oracle import coarse_oracle as co
     from oracle import geneo_oracle as go
-    _build()
-    exe = os.path.join(CPP, "coarse_adaptor")
+    exe = build("coarse_adaptor")
     overlap, nev = 2, 4
     grid = synth.StructuredPoisson((29, 27, 25), (2, 2, 2))
     dec = build_structured(grid, overlap=overlap, pou_type="distance", neumann=True, second_region="all")
@@ -161,10 +128,10 @@ def test_remaining_coarse_space_adaptors_match_oracle(ddm, tmp_path):
         return sp.csr_matrix(M)[ring][:, ring].tocsr(), ring
 
     (R1, ring1), (R2, ring2) = ring_of(2 * overlap + 1), ring_of(2 * overlap)
-    _dump_csr(tmp_path, "N", sd.A_neu)
-    _dump_csr(tmp_path, "D", sd.A_dir)
-    _dump_csr(tmp_path, "R1", R1)
-    _dump_csr(tmp_path, "R2", R2)
+    dump_csr(tmp_path, sd.A_neu, "N_")
+    dump_csr(tmp_path, sd.A_dir, "D_")
+    dump_csr(tmp_path, R1, "R1_")
+    dump_csr(tmp_path, R2, "R2_")
     sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
     np.asarray(sd.dirichlet_ovlp, dtype=np.float64).tofile(tmp_path / "dirichlet.bin")
     sd.boundary.astype(np.float64).tofile(tmp_path / "boundary.bin")
@@ -173,8 +140,7 @@ def test_remaining_coarse_space_adaptors_match_oracle(ddm, tmp_path):
     nb = int(sd.boundary.sum())
     bdata = np.array([np.ones(nb), np.sin(np.arange(nb))])
     bdata.tofile(tmp_path / "bdata.bin")
-    p = subprocess.run([exe, str(tmp_path), str(nev), str(overlap)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    p = run(exe, tmp_path, nev, overlap, timeout=600)
     assert f"sizes {nev} {nev} {nev} {nev} 2 5" in p.stdout and "errors_caught 2" in p.stdout
 
     def lam_of(name):
@@ -226,21 +192,16 @@ def test_twolevel_schwarz_solver_adaptor(ddm, tmp_path, cfg):
     from oracle import apply_oracle as ao
     from tests.oracle_bridge import oracle_solve
     mode, local, krylov = cfg
-    _build()
-    exe = os.path.join(CPP, "twolevel_adaptor")
+    exe = build("twolevel_adaptor")
     grid = synth.StructuredDG2D((16, 16), (1, 1))
     dec = build_structured(grid, overlap=1)
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
+    dump_csr(tmp_path, sd.A)
     sd.b.astype(np.float64).tofile(tmp_path / "b.bin")
     sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
     X = grid.dof_coords(sd.glob)
     np.ascontiguousarray(X, dtype=np.float64).tofile(tmp_path / "coords.bin")
-    p = subprocess.run([exe, str(tmp_path), mode, local, krylov], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    p = run(exe, tmp_path, mode, local, krylov)
     assert "errors_caught 2" in p.stdout
     lines = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("solve ")]
     assert len(lines) == 2 and lines[0][2:] == lines[1][2:]                      # second apply(): same result
@@ -263,8 +224,7 @@ def test_twolevel_schwarz_solver_adaptor(ddm, tmp_path, cfg):
     # the overlapping objects, second one refreshing the matrix values, norm(), the result storage -- must reproduce the core's
     # vectors bit for bit (one rank: the partition of unity is 1 everywhere, as in pou.bin).
     assert np.all(sd.pou == 1.0)
-    q = subprocess.run([os.path.join(CPP, "twolevel_pdelab"), str(tmp_path), mode, local, krylov], capture_output=True, text=True, timeout=300)
-    assert q.returncode == 0, q.stdout[-2000:] + q.stderr[-2000:]
+    q = run(build("twolevel_pdelab"), tmp_path, mode, local, krylov)
     pl = [ln.split() for ln in q.stdout.splitlines() if ln.startswith("solve ")]
     assert len(pl) == 2 and pl[0][2:] == pl[1][2:] and pl[0][2:10] == lines[0][2:10], (pl, lines)
     zp0 = np.fromfile(tmp_path / "zp0.bin", dtype=np.float64)

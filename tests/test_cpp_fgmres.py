@@ -1,31 +1,14 @@
 """Dune::HipRestartedFlexibleGMResSolver (dune/ddm/hip/solvers.hh; [solver] type = restartedflexiblegmressolver) compiled against the
-mock DUNE headers (tests/cpp/mock) with the flags of tests/test_cpp_multi_gmres.py: getHipSolver returns it for the new key, and its
+mock DUNE headers (tests/cpp/mock) through tests/cpp/Makefile: getHipSolver returns it for the new key, and its
 single-vector and block applies are bitwise what ddm_fgmres_solve / ddm_fgmres_solve_multi compute on the same device objects."""
-import os
-import subprocess
-
-import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-
-
-def _compile(out_dir):
-    exe = os.path.join(str(out_dir), "fgmres_adaptor")
-    cmd = ["g++", "-std=c++20", "-O2", "-Wall", "-DDUNE_DDM_HAVE_TASKFLOW=1", "-I" + os.path.join(CPP, "mock"), "-I" + os.path.join(ROOT, "dune-ddm_amd"),
-           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(CPP, "fgmres_adaptor.cc"), "-L" + os.path.join(ROOT, "dune-ddm_amd"), "-lddm_hip",
-           "-Wl,-rpath," + os.path.join(ROOT, "dune-ddm_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    return exe
+from tests.cpp_harness import build, ddm_symbols_used, dump_one_rank_problem, run
 
 
 def test_fgmres_adaptor_compiles_and_links(ddm, tmp_path):
     ddm.load_library()
-    exe = _compile(tmp_path)
-    out = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True).stdout
-    used = sorted({ln.split()[-1] for ln in out.splitlines() if " ddm_" in ln})
+    used = ddm_symbols_used(build("fgmres_adaptor"))
     assert "ddm_fgmres_solve" in used and "ddm_fgmres_solve_multi" in used and all(u in ddm.SYMBOLS for u in used), used
 
 
@@ -33,18 +16,12 @@ def test_fgmres_adaptor_compiles_and_links(ddm, tmp_path):
 def test_fgmres_adaptor_matches_the_c_abi_bitwise(ddm, tmp_path):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
-    exe = _compile(tmp_path)
+    exe = build("fgmres_adaptor")
     dec = build_structured(synth.StructuredPoisson((14, 13, 12), (1, 1, 1)), overlap=1, pou_type="distance")
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
-    sd.b.astype(np.float64).tofile(tmp_path / "b.bin")
-    sd.dirichlet_ovlp.astype(np.uint8).tofile(tmp_path / "dirichlet.bin")
-    sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
-    p = subprocess.run([exe, str(tmp_path), "3"], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "factory 1" in p.stdout and "fgmres_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+    dump_one_rank_problem(tmp_path, sd)
+    p = run(exe, tmp_path, 3)
+    assert "factory 1" in p.stdout and "fgmres_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
     single = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("single ")]
     cols = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("col ")]
     assert len(single) == 1 and single[0][1] == single[0][2] and single[0][3:] == ["0", "0"], single

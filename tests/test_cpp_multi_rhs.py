@@ -1,30 +1,13 @@
 """Dune::HipCGSolver's block apply (std::vector<X> of right-hand sides -> ddm_cg_solve_multi) compiled against the mock DUNE headers
-(tests/cpp/mock) with the flags of tests/cpp/Makefile, and run against column-by-column device solves of the same adaptor."""
-import os
-import subprocess
-
-import numpy as np
+(tests/cpp/mock) through tests/cpp/Makefile, and run against column-by-column device solves of the same adaptor."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-
-
-def _compile(out_dir):
-    exe = os.path.join(str(out_dir), "multi_rhs_adaptor")
-    cmd = ["g++", "-std=c++20", "-O2", "-Wall", "-DDUNE_DDM_HAVE_TASKFLOW=1", "-I" + os.path.join(CPP, "mock"), "-I" + os.path.join(ROOT, "dune-ddm_amd"),
-           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(CPP, "multi_rhs_adaptor.cc"), "-L" + os.path.join(ROOT, "dune-ddm_amd"), "-lddm_hip",
-           "-Wl,-rpath," + os.path.join(ROOT, "dune-ddm_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    return exe
+from tests.cpp_harness import build, ddm_symbols_used, dump_one_rank_problem, run
 
 
 def test_block_adaptor_compiles_and_links(ddm, tmp_path):
     ddm.load_library()
-    exe = _compile(tmp_path)
-    out = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True).stdout
-    used = sorted({ln.split()[-1] for ln in out.splitlines() if " ddm_" in ln})
+    used = ddm_symbols_used(build("multi_rhs_adaptor"))
     assert "ddm_cg_solve_multi" in used and all(u in ddm.SYMBOLS for u in used), used
 
 
@@ -32,17 +15,11 @@ def test_block_adaptor_compiles_and_links(ddm, tmp_path):
 def test_block_adaptor_matches_column_solves(ddm, tmp_path):
     from dune_ddm_amd import synth
     from dune_ddm_amd.problem import build_structured
-    exe = _compile(tmp_path)
+    exe = build("multi_rhs_adaptor")
     dec = build_structured(synth.StructuredPoisson((14, 13, 12), (1, 1, 1)), overlap=1, pou_type="distance")
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
-    sd.b.astype(np.float64).tofile(tmp_path / "b.bin")
-    sd.dirichlet_ovlp.astype(np.uint8).tofile(tmp_path / "dirichlet.bin")
-    sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
-    p = subprocess.run([exe, str(tmp_path), "3"], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "block_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+    dump_one_rank_problem(tmp_path, sd)
+    p = run(exe, tmp_path, 3)
+    assert "block_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
     cols = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("col ")]
     assert len(cols) == 3 and all(c[2] == c[3] for c in cols), cols

@@ -1,32 +1,17 @@
 """Dune::HipCGSolver::apply_queue (std::vector<X> of right-hand sides through a block of fixed width -> ddm_cg_solve_queue) compiled
-against the mock DUNE headers (tests/cpp/mock) with the flags of tests/cpp/Makefile, and run against TwoLevelSchwarz.solve_many on the
+against the mock DUNE headers (tests/cpp/mock) through tests/cpp/Makefile, and run against TwoLevelSchwarz.solve_many on the
 same problem and columns."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
+from tests.cpp_harness import build, ddm_symbols_used, dump_one_rank_problem, run
+
 XTOL = 1e-8          # x of a block column against another solve of it (tests/test_gpu_multi_rhs.py)
-
-
-def _compile(out_dir):
-    exe = os.path.join(str(out_dir), "queue_adaptor")
-    cmd = ["g++", "-std=c++20", "-O2", "-Wall", "-DDUNE_DDM_HAVE_TASKFLOW=1", "-I" + os.path.join(CPP, "mock"), "-I" + os.path.join(ROOT, "dune-ddm_amd"),
-           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(CPP, "queue_adaptor.cc"), "-L" + os.path.join(ROOT, "dune-ddm_amd"), "-lddm_hip",
-           "-Wl,-rpath," + os.path.join(ROOT, "dune-ddm_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    return exe
 
 
 def test_queue_adaptor_compiles_and_links(ddm, tmp_path):
     ddm.load_library()
-    exe = _compile(tmp_path)
-    out = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True).stdout
-    used = sorted({ln.split()[-1] for ln in out.splitlines() if " ddm_" in ln})
+    used = ddm_symbols_used(build("queue_adaptor"))
     assert "ddm_cg_solve_queue" in used and all(u in ddm.SYMBOLS for u in used), used
 
 
@@ -38,21 +23,16 @@ def test_queue_adaptor_matches_solve_many(ddm, tmp_path):
     from dune_ddm_amd.problem import build_structured
     from dune_ddm_amd.solver import TwoLevelSchwarz
     M, w = 9, 4
-    exe = _compile(tmp_path)
+    exe = build("queue_adaptor")
     dec = build_structured(synth.StructuredPoisson((14, 13, 12), (1, 1, 1)), overlap=1, pou_type="distance")
     sd = dec.subs[0]
-    A = sd.A.tocsr()
-    np.asarray(A.indptr, dtype=np.int64).tofile(tmp_path / "rowptr.bin")
-    np.asarray(A.indices, dtype=np.int32).tofile(tmp_path / "col.bin")
-    np.asarray(A.data, dtype=np.float64).tofile(tmp_path / "val.bin")
-    sd.dirichlet_ovlp.astype(np.uint8).tofile(tmp_path / "dirichlet.bin")
-    sd.pou.astype(np.float64).tofile(tmp_path / "pou.bin")
+    dump_one_rank_problem(tmp_path, sd, b=False)
     # right-hand sides: the problem's, then seeded random ones that are zero on the Dirichlet rows like the problem's
     R = np.random.default_rng(12345).standard_normal((sd.n, M - 1)) * (sd.dirichlet_ovlp == 0)[:, None]
     B = np.ascontiguousarray(np.concatenate([sd.b.astype(np.float64)[:, None], R], axis=1))
     B.tofile(tmp_path / "rhs.bin")
-    p = subprocess.run([exe, str(tmp_path), str(M), str(w)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "queue_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+    p = run(exe, tmp_path, M, w)
+    assert "queue_ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
     assert "b_unchanged 1" in p.stdout and "errors_caught 2" in p.stdout
     cols = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("col ")]
     assert len(cols) == M
