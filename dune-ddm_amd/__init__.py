@@ -80,6 +80,7 @@ SYMBOLS = {
     "ddm_csr_usmv": (_I32, [_P, _P, _D, _P, _P]),
     "ddm_csr_mm": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_csr_row_order_tiled_host": (_I32, [_I64, _P, _P, _P, _P]),
+    "ddm_dia_build_and_apply_host": (_I32, [_I64, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ddm_ilu0_solve_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_solve_multi_f32": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_create": (_I32, [_P, _P, _I64, _P, _PP]),
@@ -887,6 +888,24 @@ def row_order_tiled_host(block_ptr, A):
     if rc < 0:
         raise ValueError("ddm_csr_row_order_tiled_host: bad arguments")
     return bool(rc), order
+
+
+def dia_build_and_apply_host(A, x):
+    """(y, blocks, counts): the operator's diagonal-row-block layout of a square scipy CSR matrix (sorted indices), applied to x on
+    the host as the device kernel indexes it.  blocks: (nblocks, 4) array of (first row, end row, diagonals; 0 = CSR-stream block,
+    slabs stored: fewer than the diagonals in a symmetric segment); counts: dict(blocks, dia, csr, rows_dia, slots, segments,
+    symmetric_segments).  Host only, no device needed."""
+    lib = load_library()
+    n = A.shape[0]
+    rp, ci, va = _np(A.indptr, np.int64), _np(A.indices, np.int32), _np(A.data, np.float64)
+    x = _np(x, np.float64)
+    y = np.full(n, np.nan)
+    kinds = np.zeros((n + 1, 4), dtype=np.int32)
+    counts = np.zeros(7, dtype=np.int64)
+    rc = lib.ddm_dia_build_and_apply_host(n, _hp(rp), _hp(ci), _hp(va), _hp(x), _hp(y), n + 1, _hp(kinds), _hp(counts))
+    if rc != DDM_OK:
+        raise ValueError("ddm_dia_build_and_apply_host: bad arguments")
+    return y, kinds[:counts[0]], dict(zip(("blocks", "dia", "csr", "rows_dia", "slots", "segments", "symmetric_segments"), counts.tolist()))
 
 
 def blockvec_gram(ctx: Context, sub_ptr, U, V):

@@ -314,3 +314,233 @@ static int csr_mm2_ld(ddm_ctx *ctx, const ddm_csr *A1, const ddm_csr *A2, int nr
   return DDM_OK;
 }
 extern "C" int ddm_csr_mm(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double *X, double *Y) { return csr_mm_ld(ctx, A, nrhs, X, nrhs, Y, nrhs); }
+
+// ---- diagonal row blocks (the layout of k_spmv_dia; ddm_op builds one of its matrix) ---------------------------------------------
+// Rows are split greedily into blocks of at most WG consecutive rows whose entries lie on at most DIA_MAX distinct diagonals.  A
+// block ends early before the row that would exceed the table, and before a row that brings a diagonal in where the matrix
+// decouples (no entry joins the rows before with the rows from there on: a subdomain boundary of a concatenated matrix).
+// A row that cannot join any block (more than DIA_MAX entries, columns not strictly ascending) and blocks whose slabs would be
+// less than half full (irregular rows: a few rows on DIA_MAX diagonals) stay CSR-stream blocks, cut as csr_row_blocks cuts them.
+// The split restarts every DIA_SPLIT_ROWS rows so that it runs on host_threads() workers and does not depend on their number.
+// Consecutive diagonal blocks between two decoupling ends whose offsets together stay within DIA_MAX form a segment on the union
+// table; its slabs are laid out segment-wide, val[slab * rows + row].  A segment keeps only the slabs of the offsets >= 0 when
+// its table is its own mirror image and every entry (r, c) below the diagonal has c inside the segment and a partner (c, r) of
+// the same bits: a(r, r + d), d < 0, is then read as val[slab of -d][r + d].
+constexpr int64_t DIA_SPLIT_ROWS = 256 * WG;
+struct DiaLayout {
+  std::vector<DiaBlock> blk;
+  std::vector<int32_t> stored; // per block: slabs its segment keeps (nd, or the offsets >= 0 of a symmetric segment; 0: CSR-stream)
+  std::vector<int32_t> tab;    // per segment: DIA_MAX offsets, DIA_MAX slab numbers, DIA_MAX row shifts (tails repeat the last entry)
+  hvec<uint32_t> mask;         // per row: bit k set = the row has an entry on diagonal k of its block's table
+  hvec<double> val;            // absent entries 0.0 (loaded, never added)
+  int64_t ndia = 0, ncsr = 0, rows_dia = 0, nseg = 0, nseg_half = 0; // blocks of either kind, rows in diagonal blocks, segments, symmetric ones
+};
+template <class F>
+static void dia_parallel_for(int64_t njobs, F &&job)
+{
+  const unsigned nth = (unsigned)std::max<int64_t>(1, std::min<int64_t>(host_threads(), njobs));
+  std::atomic<int64_t> next{0};
+  auto work = [&]() {
+    for (int64_t j; (j = next.fetch_add(1)) < njobs;) job(j);
+  };
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < nth; ++t) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+}
+static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const double *va, DiaLayout &L)
+{
+  L = DiaLayout();
+  if (n <= 0 || n >= (int64_t)1 << 30) return; // (row + offset is computed in 32 bits)
+  struct Part {
+    std::vector<DiaBlock> blk;
+    std::vector<int32_t> off; // nd offsets per diagonal block, one after the other
+  };
+  const int64_t nparts = (n + DIA_SPLIT_ROWS - 1) / DIA_SPLIT_ROWS;
+  std::vector<Part> parts((size_t)nparts);
+  std::vector<uint8_t> cut((size_t)n, 0); // the matrix decouples before row r (first / last column of the rows: a hint, any value is valid)
+  {
+    std::vector<int32_t> sufmin((size_t)n + 1, INT32_MAX);
+    for (int64_t r = n - 1; r >= 0; --r) sufmin[(size_t)r] = std::min(sufmin[(size_t)r + 1], rp[r + 1] > rp[r] ? ci[rp[r]] : INT32_MAX);
+    int32_t prefmax = -1;
+    for (int64_t r = 0; r < n; ++r) {
+      cut[(size_t)r] = prefmax < r && sufmin[(size_t)r] >= r;
+      if (rp[r + 1] > rp[r]) prefmax = std::max(prefmax, ci[rp[r + 1] - 1]);
+    }
+  }
+  dia_parallel_for(nparts, [&](int64_t p) {
+    Part &P = parts[(size_t)p];
+    const int64_t c0 = p * DIA_SPLIT_ROWS, c1 = std::min(n, c0 + DIA_SPLIT_ROWS);
+    int64_t csr_from = -1;
+    auto flush_csr = [&](int64_t end) {
+      for (int64_t r = csr_from; csr_from >= 0 && r < end;) {
+        int64_t r1 = r;
+        while (r1 < end && r1 - r < WG && rp[r1 + 1] - rp[r] <= SPMV_NNZ) ++r1;
+        if (r1 == r) r1 = r + 1; // long row
+        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, 0, 0, 0, 0});
+        r = r1;
+      }
+      csr_from = -1;
+    };
+    int32_t T[DIA_MAX], R[DIA_MAX], U[2 * DIA_MAX];
+    for (int64_t r = c0; r < c1;) {
+      int nt = 0; // T[0..nt): the block's offsets so far
+      int64_t r1 = r, entries = 0;
+      for (; r1 < c1 && r1 - r < WG; ++r1) {
+        const int64_t z0 = rp[r1], len = rp[r1 + 1] - z0;
+        if (len > DIA_MAX) break;
+        bool ascending = true;
+        for (int64_t j = 0; j < len; ++j) R[j] = (int32_t)(ci[z0 + j] - r1), ascending = ascending && (j == 0 || R[j] > R[j - 1]);
+        const int nu = (int)(std::set_union(T, T + nt, R, R + len, U) - U);
+        if (!ascending || nu > DIA_MAX || (r1 > r && nu > nt && cut[(size_t)r1])) break;
+        std::copy(U, U + nu, T);
+        nt = nu;
+        entries += len;
+      }
+      if (entries > 0 && 2 * entries >= (r1 - r) * nt) {
+        flush_csr(r);
+        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, nt, (int32_t)P.off.size(), cut[(size_t)r] /* a segment starts here */, 0});
+        P.off.insert(P.off.end(), T, T + nt);
+        r = r1;
+      } else {
+        if (csr_from < 0) csr_from = r;
+        r = std::max(r1, r + 1);
+      }
+    }
+    flush_csr(c1);
+  });
+  // segments: runs of diagonal blocks whose tables together stay within DIA_MAX offsets
+  struct Seg {
+    int64_t r0, r1, base = 0;
+    int32_t off[DIA_MAX];
+    int nd = 0, nlow = 0; // nlow > 0: symmetric, the nlow offsets < 0 are not stored
+    std::atomic<bool> full{false};
+    Seg(int64_t a) : r0(a), r1(a) {}
+  };
+  std::deque<Seg> segs;
+  std::vector<int32_t> seg_of;
+  for (Part &P : parts)
+    for (DiaBlock &B : P.blk) {
+      if (B.nd) {
+        const int32_t *off = P.off.data() + B.tab;
+        int32_t U[2 * DIA_MAX];
+        int nu = DIA_MAX + 1;
+        if (!segs.empty() && segs.back().r1 == B.r0 && !B.t0) nu = (int)(std::set_union(segs.back().off, segs.back().off + segs.back().nd, off, off + B.nd, U) - U);
+        if (nu > DIA_MAX) segs.emplace_back(B.r0), nu = B.nd, std::copy(off, off + B.nd, U);
+        std::copy(U, U + nu, segs.back().off);
+        segs.back().nd = nu, segs.back().r1 = B.r1;
+        ++L.ndia, L.rows_dia += B.r1 - B.r0;
+      } else ++L.ncsr;
+      seg_of.push_back(B.nd ? (int32_t)segs.size() - 1 : -1);
+      L.blk.push_back(B);
+    }
+  if (!L.ndia) return; // all CSR: the caller keeps the CSR product
+  for (Seg &S : segs) { // a table that is its own mirror image, else full storage
+    bool mirror = true;
+    for (int k = 0; k < S.nd; ++k) mirror = mirror && S.off[k] == -S.off[S.nd - 1 - k];
+    S.full = !mirror;
+  }
+  dia_parallel_for((int64_t)L.blk.size(), [&](int64_t b) { // every entry below the diagonal has its partner in the segment, bit for bit
+    if (seg_of[(size_t)b] < 0) return;
+    Seg &S = segs[(size_t)seg_of[(size_t)b]];
+    const DiaBlock &B = L.blk[(size_t)b];
+    for (int64_t r = B.r0; r < B.r1 && !S.full; ++r)
+      for (int64_t z = rp[r]; z < rp[r + 1] && ci[z] < r; ++z) {
+        const int64_t c = ci[z];
+        const int32_t *row = ci + rp[c], *end = ci + rp[c + 1], *hit = std::lower_bound(row, end, (int32_t)r);
+        if (c < S.r0 || hit == end || *hit != r || std::memcmp(va + (hit - ci), va + z, sizeof(double))) {
+          S.full = true;
+          break;
+        }
+      }
+  });
+  int64_t slots = 0;
+  L.nseg = (int64_t)segs.size();
+  for (Seg &S : segs) {
+    if (!S.full)
+      while (S.off[S.nlow] < 0) ++S.nlow;
+    L.nseg_half += S.nlow > 0;
+    S.base = slots;
+    slots += (S.nd - S.nlow) * (S.r1 - S.r0);
+    int32_t rec[3 * DIA_MAX];
+    for (int k = 0; k < DIA_MAX; ++k) {
+      const int q = std::min(k, S.nd - 1);
+      rec[k] = S.off[q];
+      rec[DIA_MAX + k] = q < S.nlow ? S.nd - 1 - q - S.nlow : q - S.nlow; // below the diagonal: the slab of the mirrored offset ...
+      rec[2 * DIA_MAX + k] = q < S.nlow ? S.off[q] : 0;                   // ... at the partner's row
+    }
+    L.tab.insert(L.tab.end(), rec, rec + 3 * DIA_MAX);
+  }
+  L.stored.resize(L.blk.size(), 0);
+  for (size_t b = 0; b < L.blk.size(); ++b) {
+    if (seg_of[b] < 0) continue;
+    const Seg &S = segs[(size_t)seg_of[b]];
+    DiaBlock &B = L.blk[b];
+    B.nd = S.nd, B.tab = seg_of[b] * 3 * DIA_MAX;
+    B.t0 = (int32_t)(B.r0 - S.r0), B.stride = (int32_t)(S.r1 - S.r0);
+    B.base = S.base + B.t0;
+    L.stored[b] = S.nd - S.nlow;
+  }
+  L.mask.resize((size_t)n);
+  L.val.resize((size_t)slots);
+  dia_parallel_for((int64_t)L.blk.size(), [&](int64_t b) {
+    const DiaBlock &B = L.blk[(size_t)b];
+    if (!B.nd) {
+      std::fill(L.mask.begin() + B.r0, L.mask.begin() + B.r1, 0u);
+      return;
+    }
+    const int nlow = B.nd - L.stored[(size_t)b];
+    double *v = L.val.data() + B.base; // (slab 0, row r0)
+    for (int j = 0; j < B.nd - nlow; ++j) std::fill(v + (int64_t)j * B.stride, v + (int64_t)j * B.stride + (B.r1 - B.r0), 0.0);
+    const int32_t *off = L.tab.data() + B.tab;
+    for (int64_t r = B.r0; r < B.r1; ++r) {
+      uint32_t m = 0;
+      int k = 0;
+      for (int64_t z = rp[r]; z < rp[r + 1]; ++z) {
+        while (off[k] < ci[z] - r) ++k; // both ascending; the offset is in the table
+        if (k >= nlow) v[(int64_t)(k - nlow) * B.stride + (r - B.r0)] = va[z];
+        m |= 1u << k;
+      }
+      L.mask[(size_t)r] = m;
+    }
+  });
+}
+// y = A x on the host, indexed as k_spmv_dia indexes (CSR-stream blocks: the row sum in column order)
+static void dia_apply_host(const DiaLayout &L, int64_t n, const int64_t *rp, const int32_t *ci, const double *va, const double *x, double *y)
+{
+  for (const DiaBlock &B : L.blk) {
+    const int nr = B.r1 - B.r0;
+    const int32_t *off = L.tab.data() + B.tab, *slab = off + DIA_MAX, *shift = slab + DIA_MAX;
+    for (int t = 0; t < nr; ++t) {
+      const int r = B.r0 + t;
+      double s = 0.0;
+      if (!B.nd)
+        for (int64_t z = rp[r]; z < rp[r + 1]; ++z) s += va[z] * x[ci[z]];
+      else
+        for (int k = 0; k < B.nd; ++k) {
+          const int64_t at = (int64_t)slab[k] * B.stride + std::min(std::max(B.t0 + t + shift[k], 0), B.stride - 1);
+          const double v = L.val[(size_t)(B.base - B.t0 + at)], xv = x[std::min<int64_t>(std::max<int64_t>(r + off[k], 0), n - 1)];
+          if ((L.mask[(size_t)r] >> k) & 1u) s += v * xv; // (-ffp-contract=off: product rounded, then added)
+        }
+      y[r] = s;
+    }
+  }
+}
+// host-only entry for the CPU tests: builds the layout of a square matrix and applies it on the host.  kinds_out (may be null)
+// receives up to max_blocks (r0, r1, nd, slabs stored) quadruples; counts_out = {blocks, diagonal blocks, CSR-stream blocks, rows in
+// diagonal blocks, value slots, segments, symmetric segments}.  With no diagonal block the operator keeps the CSR product.
+extern "C" int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, const double *x, double *y,
+                                            int64_t max_blocks, int32_t *kinds_out, int64_t *counts_out)
+{
+  if (n < 0 || !rowptr || !x || !y || !counts_out || (rowptr[n] > 0 && (!col || !val))) return DDM_EINVAL;
+  for (int64_t z = 0; z < rowptr[n]; ++z)
+    if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
+  DiaLayout L;
+  dia_build(n, rowptr, col, val, L);
+  dia_apply_host(L, n, rowptr, col, val, x, y);
+  for (size_t b = 0; kinds_out && b < L.blk.size() && (int64_t)b < max_blocks; ++b)
+    kinds_out[4 * b] = L.blk[b].r0, kinds_out[4 * b + 1] = L.blk[b].r1, kinds_out[4 * b + 2] = L.blk[b].nd, kinds_out[4 * b + 3] = L.stored.empty() ? 0 : L.stored[b];
+  const int64_t counts[7] = {(int64_t)L.blk.size(), L.ndia, L.ncsr, L.rows_dia, (int64_t)L.val.size(), L.nseg, L.nseg_half};
+  std::copy(counts, counts + 7, counts_out);
+  return DDM_OK;
+}

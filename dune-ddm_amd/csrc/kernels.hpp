@@ -45,16 +45,12 @@ __device__ __forceinline__ double block_sum(double v, double *lds4)
 // SPMV_NNZ non-zeros; values / column indices are read fully coalesced, the products are staged
 // in LDS and each row is then summed sequentially in column order (deterministic).
 // reference: BCRSMatrix::mv / usmv at nonoverlapping_operator.hh:37,47; spectra.hh:100-105.
+// The rows [r0, r1) of one such block, by one workgroup (prod: SPMV_NNZ doubles of LDS, red: 4).
 template <bool ACC>
-__global__ __launch_bounds__(WG) void k_spmv_stream(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci,
-                                                     const double *__restrict__ va, const int32_t *__restrict__ blk_row,
-                                                     int nblk, const double *__restrict__ x, double *__restrict__ y,
-                                                     double alpha)
+__device__ __forceinline__ void spmv_stream_block(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                  const double *__restrict__ va, int r0, int r1, const double *__restrict__ x,
+                                                  double *__restrict__ y, double alpha, double *prod, double *red)
 {
-  __shared__ double prod[SPMV_NNZ];
-  __shared__ double red[4];
-  const int b = xcd_remap(blockIdx.x, nblk);
-  const int r0 = blk_row[b], r1 = blk_row[b + 1];
   const int64_t z0 = rp[r0], z1 = rp[r1];
   const int64_t nz = z1 - z0;
   if (nz > SPMV_NNZ) { // a single long row: strided partial sums + block reduction
@@ -98,6 +94,80 @@ __global__ __launch_bounds__(WG) void k_spmv_stream(const int64_t *__restrict__ 
     }
     y[r] = ACC ? y[r] + alpha * s : s;
   }
+}
+template <bool ACC>
+__global__ __launch_bounds__(WG) void k_spmv_stream(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                     const double *__restrict__ va, const int32_t *__restrict__ blk_row,
+                                                     int nblk, const double *__restrict__ x, double *__restrict__ y,
+                                                     double alpha)
+{
+  __shared__ double prod[SPMV_NNZ];
+  __shared__ double red[4];
+  const int b = xcd_remap(blockIdx.x, nblk);
+  spmv_stream_block<ACC>(rp, ci, va, blk_row[b], blk_row[b + 1], x, y, alpha, prod, red);
+}
+
+// K1d: the operator product (ddm_op) on diagonal row blocks (layout: dia_build, csr.hpp).  A block of at most WG consecutive rows
+// whose entries lie on at most DIA_MAX distinct diagonals (col - row) stores no column indices.  Consecutive blocks form a segment
+// with one table record in tab (per diagonal k, ascending: the offset, the slab that holds its values, a row shift) and
+// segment-wide value slabs val[slab * rows + row], so a wave reads 512 contiguous bytes per diagonal; a row has a presence mask.
+// A symmetric segment keeps the slabs of the offsets >= 0 only: a diagonal below reads the slab of the mirrored offset at the
+// partner's row (shift = offset), elsewhere shift = 0.  One thread per row: the value and x loads of DIA_CH diagonals are issued
+// before the first use (indices clamped, not branched around), then the present entries are added for ascending k, product
+// rounded before the sum -- the operations of k_spmv_stream in its order, hence the same bits.  Absent entries are skipped (not
+// added as zero), a stored 0.0 is present.  Blocks that fit no diagonal layout (nd == 0) are CSR-stream blocks of the same
+// launch: a uniform branch per workgroup.  4 waves per SIMD: with more the scheduler interleaves loads and uses to save registers.
+constexpr int DIA_MAX = 32;  // diagonals of a block (bits of the mask)
+constexpr int DIA_CH = 16;   // diagonals whose loads are in flight together; DIA_MAX is a multiple
+struct DiaBlock {
+  int64_t base;       // slot of (slab 0, row r0) in val
+  int32_t r0, r1;     // rows
+  int32_t nd, tab;    // diagonals (0: CSR-stream block) and the place of the segment's table in tab
+  int32_t t0, stride; // r0's place in the segment; rows of the segment = distance of two slabs
+};
+__device__ __forceinline__ void dia_load_chunk(const int32_t *__restrict__ p, int (&o)[DIA_CH])
+{
+  const int4 *__restrict__ q = reinterpret_cast<const int4 *>(p);
+  const int4 a = q[0], b = q[1], c = q[2], d = q[3];
+  o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w, o[4] = b.x, o[5] = b.y, o[6] = b.z, o[7] = b.w;
+  o[8] = c.x, o[9] = c.y, o[10] = c.z, o[11] = c.w, o[12] = d.x, o[13] = d.y, o[14] = d.z, o[15] = d.w;
+}
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_spmv_dia(const DiaBlock *__restrict__ blk, int nblk, const int32_t *__restrict__ tab,
+                                                  const uint32_t *__restrict__ mask, const double *__restrict__ val,
+                                                  const int64_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                  const double *__restrict__ va, int n, const double *__restrict__ x,
+                                                  double *__restrict__ y)
+{
+  __shared__ double prod[SPMV_NNZ];
+  __shared__ double red[4];
+  const DiaBlock B = blk[xcd_remap(blockIdx.x, nblk)];
+  if (B.nd == 0) {
+    spmv_stream_block<false>(rp, ci, va, B.r0, B.r1, x, y, 0.0, prod, red);
+    return;
+  }
+  const int nr = B.r1 - B.r0, t = min((int)threadIdx.x, nr - 1), r = B.r0 + t;
+  const uint32_t m = mask[r];
+  const int ts = B.t0 + t;
+  const double *__restrict__ vs = val + (B.base - B.t0);
+  double s = 0.0;
+  for (int k0 = 0; k0 < B.nd; k0 += DIA_CH) {
+    // the chunk's offsets, slab numbers and row shifts in three scalar loads (the tables are DIA_MAX long, the tail repeats the last entry)
+    int off[DIA_CH], slab[DIA_CH], shift[DIA_CH];
+    dia_load_chunk(tab + B.tab + k0, off);
+    dia_load_chunk(tab + B.tab + DIA_MAX + k0, slab);
+    dia_load_chunk(tab + B.tab + 2 * DIA_MAX + k0, shift);
+    double v[DIA_CH], xv[DIA_CH];
+#pragma unroll
+    for (int u = 0; u < DIA_CH; ++u) {
+      v[u] = vs[(int64_t)slab[u] * B.stride + min(max(ts + shift[u], 0), B.stride - 1)];
+      xv[u] = x[min(max(r + off[u], 0), n - 1)];
+    }
+    const uint32_t mk = m >> k0; // (no bit at or above nd is set: the clamped loads past the last diagonal are never added)
+#pragma unroll
+    for (int u = 0; u < DIA_CH; ++u)
+      if ((mk >> u) & 1u) s = __dadd_rn(s, __dmul_rn(v[u], xv[u]));
+  }
+  if ((int)threadIdx.x < nr) y[r] = s;
 }
 
 // ---------------------------------------------------------------------------------------------

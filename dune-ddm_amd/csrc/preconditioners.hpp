@@ -69,7 +69,24 @@ struct ddm_op {
   dbuf<double> tmp;
   dbuf<double> mtmp; // multi-RHS block (mcols columns)
   int mcols = 0;
+  // A on diagonal row blocks (dia_build; k_spmv_dia), or nothing (dia_nblk == 0): then the products are ddm_csr_mv
+  dbuf<DiaBlock> dia_blk;
+  dbuf<int32_t> dia_tab;
+  dbuf<uint32_t> dia_mask;
+  dbuf<double> dia_val;
+  int dia_nblk = 0;
 };
+// y = A x: bit-identical to ddm_csr_mv in either layout
+static int op_mv(ddm_ctx *ctx, const ddm_op *op, const double *x, double *y)
+{
+  if (!op->dia_nblk) return ddm_csr_mv(ctx, op->A, x, y);
+  if (x == y) return fail(ctx, DDM_EINVAL, "operator product: x and y alias");
+  const ddm_csr *A = op->A;
+  hipLaunchKernelGGL(k_spmv_dia, dim3(op->dia_nblk), dim3(WG), 0, ctx->stream, (const DiaBlock *)op->dia_blk, op->dia_nblk, (const int32_t *)op->dia_tab,
+                     (const uint32_t *)op->dia_mask, (const double *)op->dia_val, A->rp, A->ci, A->va, (int)op->n, x, y);
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
 extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out)
 {
   if (!ctx || !A || !out || !owner_mask_host) return fail(ctx, DDM_EINVAL, "ddm_op_create: bad arguments");
@@ -81,6 +98,18 @@ extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add
   op->n = A->nrows;
   int rc = upload(ctx, owner_mask_host, op->n, op->owner);
   if (!rc && op->tmp.alloc(op->n) != hipSuccess) rc = DDM_EHIP;
+  const char *fmt = std::getenv("DDM_SPMV_FORMAT"); // "csr": keep the CSR-stream product (A/B runs, tests)
+  if (!rc && !A->host_only && !(fmt && !std::strcmp(fmt, "csr"))) {
+    DiaLayout L;
+    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L);
+    if (L.ndia) {
+      if (!rc) rc = upload(ctx, L.blk.data(), (int64_t)L.blk.size(), op->dia_blk);
+      if (!rc) rc = upload(ctx, L.tab.data(), (int64_t)L.tab.size(), op->dia_tab);
+      if (!rc) rc = upload(ctx, L.mask.data(), (int64_t)L.mask.size(), op->dia_mask);
+      if (!rc) rc = upload(ctx, L.val.data(), (int64_t)L.val.size(), op->dia_val);
+      op->dia_nblk = (int)L.blk.size();
+    }
+  }
   if (rc) return fail(ctx, rc, "ddm_op_create: allocation failed");
   *out = op.release();
   return DDM_OK;
@@ -89,14 +118,14 @@ extern "C" void ddm_op_destroy(ddm_op *op) { delete op; }
 extern "C" int ddm_op_apply(ddm_ctx *ctx, ddm_op *op, const double *x, double *y)
 {
   ScopedTimer t(ctx, "Operator/apply");
-  DDMCHECK(ddm_csr_mv(ctx, op->A, x, y));           // A->mv(x, y)
+  DDMCHECK(op_mv(ctx, op, x, y));                   // A->mv(x, y)
   return ddm_halo_exchange(ctx, op->halo, y);       // comm->addOwnerCopyToOwnerCopy(y, y)
 }
 extern "C" int ddm_op_applyscaleadd(ddm_ctx *ctx, ddm_op *op, double alpha, const double *x, double *y)
 {
   ScopedTimer t(ctx, "Operator/applyscaleadd");
   // y1 = y; y = 0; usmv; halo; y += y1   (only alpha*A*x is communicated, y is already consistent)
-  DDMCHECK(ddm_csr_mv(ctx, op->A, x, op->tmp));
+  DDMCHECK(op_mv(ctx, op, x, op->tmp));
   DDMCHECK(ddm_halo_exchange(ctx, op->halo, op->tmp));
   hipLaunchKernelGGL(k_axpy, dim3(grid_for(op->n)), dim3(WG), 0, ctx->stream, op->n, alpha, op->tmp, y);
   HIPCHECK(ctx, hipGetLastError());

@@ -112,6 +112,14 @@ int ddm_csr_mm(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double *X, double
  * column offsets most rows share; 16 x 4 x 4 bricks).  order_out[n] is always a permutation of the rows; returns 1 when a grid
  * structure was found, 0 when not (identity), < 0 on bad arguments.  A performance hint only: every row is computed as before. */
 int ddm_csr_row_order_tiled_host(int64_t nblocks, const int64_t *block_ptr, const int64_t *rowptr, const int32_t *col, int32_t *order_out);
+/* Host only (no device needed; for tests): the diagonal-row-block layout that ddm_op_create builds of its matrix (blocks of at most 256
+ * consecutive rows on at most 32 diagonals col - row: offset table, one value slab per diagonal, a presence mask per row; rows that fit
+ * none stay CSR-stream blocks; consecutive blocks with one table form a segment, which keeps only the slabs of the offsets >= 0 when
+ * it is symmetric bit for bit), built for the square matrix given and applied to x on the host with the indexing of the device kernel.
+ * kinds_out (may be NULL) receives (first row, end row, diagonals; 0 = CSR-stream, slabs stored) of the first max_blocks blocks;
+ * counts_out[7] = {blocks, diagonal blocks, CSR-stream blocks, rows in diagonal blocks, value slots, segments, symmetric segments}. */
+int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, const double *x, double *y,
+                                 int64_t max_blocks, int32_t *kinds_out, int64_t *counts_out);
 
 /* ---- local subdomain solver: ILU(0), natural row order ------------------------------------
  * The InverseOperator behind schwarz.hh:57,92,133 for [subdomain_solver] type=loopsolver maxit=1,
