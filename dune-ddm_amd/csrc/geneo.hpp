@@ -1,4 +1,4 @@
-// GenEO coarse-basis builder on the device (included by ddm_hip.hip after csr.hpp and the local solver, local_factor.hpp .. local_solver.hpp; C ABI: ddm_geneo_basis in include/ddm_hip.h).
+// GenEO coarse-basis builder on the device (included by ddm_hip.hip after csr.hpp and the local solver, local_factor.hpp .. local_solver.hpp; pulls in geneo_blocks.hpp, the dense block contractions; C ABI: ddm_geneo_basis in include/ddm_hip.h).
 //
 // Reference: GenEOCoarseSpace::setup_geneo_impl (dune/ddm/coarsespaces/coarse_spaces.hh:319-331): C = D B_neu D
 // (detail::scale_matrix_with_pou, :74-96), the lowest nev eigenpairs of A_neu x = lambda C x (solve_gevp ->
@@ -23,13 +23,37 @@
 // Convergence test per wanted pair, for all subdomains: with the exact T the relative residual of the inverted operator in the
 // A~-norm, sqrt(r^T A~^-1 r) / mu  (r = C~ x - mu A~ x, x^T A~ x = 1) -- the quantity Spectra bounds by tol for its B-norm
 // Lanczos residual (HermEigsBase.h:158-175); with ILU(0) the Euclidean relative residual ||r|| / (mu ||A~ x||).
+//
+// In this file: GeneoProblem (what an entry point asks for), GeneoRun (the state of one run at a fixed block width, one method per
+// phase), geneo_run (the loop above, phase by phase), geneo_basis_impl (threshold mode: a fresh run per doubling), the entry points
+// ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, and before them the harmonic extension the last two iterate with.
 #pragma once
 #include <functional>
 
 #include "dense_host.hpp"
-#include "geneo_kernels.hpp"
+#include "geneo_blocks.hpp"
 
-static constexpr int64_t GENEO_CHUNK_ROWS = 2048;
+// Owners of the C-ABI objects this file creates for itself: a unique_ptr whose deleter is the object's destroy function.
+// out_ptr(owner) stands in for the `T **out` of a create call: the owner takes what the call stored.
+template <auto Destroy>
+struct Destroyer {
+  template <class T>
+  void operator()(T *p) const { Destroy(p); }
+};
+using csr_ptr = std::unique_ptr<ddm_csr, Destroyer<ddm_csr_destroy>>;
+using ilu0_ptr = std::unique_ptr<ddm_ilu0, Destroyer<ddm_ilu0_destroy>>;
+template <class Owner>
+struct OutPtr {
+  Owner &owner;
+  typename Owner::pointer raw = nullptr;
+  ~OutPtr() { owner.reset(raw); }
+  operator typename Owner::pointer *() { return &raw; }
+};
+template <class Owner>
+OutPtr<Owner> out_ptr(Owner &owner)
+{
+  return OutPtr<Owner>{owner};
+}
 
 extern "C" int ddm_geneo_params_default(ddm_geneo_params *p)
 {
@@ -76,116 +100,6 @@ __global__ void k_geneo_random(int64_t n, int m, int64_t ld, unsigned long long 
 // widest block the eigensolver iterates (nev + extra): the dense kernels work in column panels beyond 48 (round 3; the threshold mode
 // of the reference doubles nev up to nev_max, spectra.hh:157-163), the limit is the memory of the six n x 3m blocks
 constexpr int GENEO_MAX_BLOCK = 132;
-struct GeneoWork {
-  ddm_ctx *ctx = nullptr;
-  int64_t n = 0;
-  int nsub = 0, m = 0, p = 0, nchunk = 0;
-  dbuf<GChunk> chunks;
-  dbuf<int32_t> sub_chunk_ptr, sub_of_row;
-  dbuf<double> partial;
-  template <class T>
-  int alloc(dbuf<T> &buf, size_t count)
-  {
-    if (buf.alloc((int64_t)count) != hipSuccess) return fail(ctx, DDM_EHIP, "GenEO: device allocation of %zu bytes failed", sizeof(T) * count);
-    return DDM_OK;
-  }
-  // G[sub] = U^T V per subdomain (pu x pv row-major, nsub matrices).  Blocks wider than the register tiles of the kernel (128 x 80)
-  // are computed in column panels that land in their sub-block of the per-chunk partial matrices.
-  int gram(const double *U, int64_t ldu, int pu, const double *V, int64_t ldv, int pv, double *G)
-  {
-    const int64_t pp = (int64_t)pu * pv;
-    if (pu <= 32 && pv <= 32) {
-      const bool same = U == V && ldu == ldv && pu == pv;
-#define DDM_GRAM_SMALL(SAME, A1, B1) hipLaunchKernelGGL((k_gram_small<SAME, A1, B1>), dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, pu, V, ldv, pv, partial, pp, pv)
-      if (same) {
-        if (pu > 16) DDM_GRAM_SMALL(true, true, true);
-        else DDM_GRAM_SMALL(true, false, false);
-      } else if (pu > 16) {
-        if (pv > 16) DDM_GRAM_SMALL(false, true, true);
-        else DDM_GRAM_SMALL(false, true, false);
-      } else {
-        if (pv > 16) DDM_GRAM_SMALL(false, false, true);
-        else DDM_GRAM_SMALL(false, false, false);
-      }
-#undef DDM_GRAM_SMALL
-    } else if (pu <= 128 && pv <= 80)
-      hipLaunchKernelGGL((k_gram_mfma<2, 5>), dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, pu, V, ldv, pv, partial, pp, pv, 0, 0);
-    else if (pu <= 144 && pv <= 144)
-      hipLaunchKernelGGL((k_gram_mfma<3, 9>), dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, pu, V, ldv, pv, partial, pp, pv, 0, 0);
-    else
-      for (int i0 = 0; i0 < pu; i0 += 128)
-        for (int j0 = 0; j0 < pv; j0 += 80)
-          hipLaunchKernelGGL((k_gram_mfma<2, 5>), dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U + i0, ldu, std::min(128, pu - i0), V + j0, ldv, std::min(80, pv - j0),
-                             partial, pp, pv, i0, j0);
-    hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((nsub * pp + 255) / 256)), dim3(256), 0, ctx->stream, nsub, sub_chunk_ptr, pp, partial, pp, G);
-    HIPCHECK(ctx, hipGetLastError());
-    return DDM_OK;
-  }
-  // G1[sub] = U^T V1, G2[sub] = U^T V2 (p x p each) for products that are symmetric by construction (V1 = A~ U, V2 = C~ U): one pass over
-  // U, upper tiles only -- the entries BELOW the diagonal tiles of G1 / G2 are not defined, the caller mirrors the upper triangle
-  // (gram2_mirror_host).  The partial buffer must hold 2 p p doubles per chunk.  p > 80: two general products.
-  bool gram2_sym(const double *U, int64_t ldu, const double *V1, const double *V2, int64_t ldv, int p, double *G1, double *G2)
-  {
-    const int64_t pp = (int64_t)p * p;
-    if (p > 80) {
-      (void)gram(U, ldu, p, V1, ldv, p, G1);
-      (void)gram(U, ldu, p, V2, ldv, p, G2);
-      return false;
-    }
-    switch ((p + 15) >> 4) {
-    case 1: hipLaunchKernelGGL(k_gram2_sym<1>, dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, V1, V2, ldv, p, partial); break;
-    case 2: hipLaunchKernelGGL(k_gram2_sym<2>, dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, V1, V2, ldv, p, partial); break;
-    case 3: hipLaunchKernelGGL(k_gram2_sym<3>, dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, V1, V2, ldv, p, partial); break;
-    case 4: hipLaunchKernelGGL(k_gram2_sym<4>, dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, V1, V2, ldv, p, partial); break;
-    default: hipLaunchKernelGGL(k_gram2_sym<5>, dim3(nchunk), dim3(256), 0, ctx->stream, chunks, U, ldu, V1, V2, ldv, p, partial); break;
-    }
-    hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((nsub * pp + 255) / 256)), dim3(256), 0, ctx->stream, nsub, sub_chunk_ptr, pp, (const double *)partial, 2 * pp, G1);
-    hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((nsub * pp + 255) / 256)), dim3(256), 0, ctx->stream, nsub, sub_chunk_ptr, pp, (const double *)(partial + pp), 2 * pp, G2);
-    return true;
-  }
-  static void gram2_mirror_host(int p, double *G)
-  {
-    for (int i = 1; i < p; ++i)
-      for (int j = 0; j < i; ++j) G[(size_t)i * p + j] = G[(size_t)j * p + i];
-  }
-  // Out_k[:, 0:q) = (Base_k -) U_k[:, 0:pk) Y[sub]  for k < narr.  Y: nsub matrices pk x q, row-major.  More than 48 output columns
-  // or more than 80 inner columns run as panels: 48 output columns per launch, the inner dimension in pieces of 72 whose products are
-  // added onto the output.
-  int rotate(int narr, const double *const *U, double *const *Out, const double *const *Base, int64_t ldu, int pk, const double *Y, int q, int64_t ldo, int64_t ldb,
-             int gap_from = 1 << 30, int gap = 0)
-  {
-    const int KP = pk <= 80 ? pk : 72;
-    for (int j0 = 0; j0 < q; j0 += 16 * ROT_TQ) {
-      const int qq = std::min(16 * ROT_TQ, q - j0);
-      for (int k0 = 0; k0 < pk; k0 += KP) {
-        const int kk = std::min(KP, pk - k0);
-        RotArgs a;
-        for (int k = 0; k < 3; ++k) {
-          a.U[k] = k < narr ? U[k] + k0 : nullptr;
-          a.Out[k] = k < narr ? Out[k] : nullptr;
-          a.Base[k] = (k < narr && Base) ? Base[k] : nullptr;
-        }
-        const int mode = k0 == 0 ? (Base ? 1 : 0) : (Base ? 2 : 3);
-        const int p4 = (kk + 3) & ~3, q16 = ((qq + 15) >> 4) << 4;
-        const size_t lds = sizeof(double) * ((size_t)p4 * q16 + 4 * 16 * (size_t)(p4 + 1));
-#define DDM_ROTATE(PRE, TQ) hipLaunchKernelGGL((k_rotate_mfma<PRE, TQ>), dim3(nchunk, narr), dim3(256), lds, ctx->stream, chunks, a, ldu, kk, Y, qq, ldo, ldb, gap_from, gap, q, pk, k0, j0, mode)
-        const int tq = q16 >> 4;
-        if (16 * p4 <= 20 * 64) {
-          if (tq == 1) DDM_ROTATE(20, 1);
-          else if (tq == 2) DDM_ROTATE(20, 2);
-          else DDM_ROTATE(20, 3);
-        } else {
-          if (tq == 1) DDM_ROTATE(0, 1);
-          else if (tq == 2) DDM_ROTATE(0, 2);
-          else DDM_ROTATE(0, 3);
-        }
-#undef DDM_ROTATE
-      }
-    }
-    HIPCHECK(ctx, hipGetLastError());
-    return DDM_OK;
-  }
-};
 
 // A~ = A + sigma C~ and C~ = D B D without Dirichlet rows / columns, on the union pattern, as host CSR
 static void build_pencil_host(const ddm_csr *A, const ddm_csr *B, const double *pou, const uint8_t *dir, double sigma, hvec<int64_t> &rpT,
@@ -287,22 +201,17 @@ static bool csr_values_symmetric(const ddm_csr *A)
 // (MsGFEMCoarseSpace): P X = keep_b .* X - A^^-1 G_ib X,  P^T R = keep_b .* R - G_bi A^^-T (interior .* R).
 struct ddm_harmonic {
   int64_t n = 0;
-  ddm_csr *Gib = nullptr, *Gbi = nullptr; // owned
-  ddm_ilu0 *F = nullptr;                  // owned
+  csr_ptr Gib, Gbi;
+  ilu0_ptr F;
   dbuf<double> keep;   // 1 outside the interior (rows the extension leaves alone)
   dbuf<double> keep_b; // 1 on boundary rows only (projection: rows that are neither interior nor boundary are zeroed)
   dbuf<double> isint;  // 1 on interior rows
   dbuf<double> t1, t2; // work blocks (n x tcols)
   int tcols = 0;
   bool symmetric = true;
-  ~ddm_harmonic()
-  {
-    ddm_csr_destroy(Gib);
-    ddm_csr_destroy(Gbi);
-    ddm_ilu0_destroy(F);
-  }
 };
 extern "C" void ddm_harmonic_destroy(ddm_harmonic *H) { delete H; }
+using harmonic_ptr = std::unique_ptr<ddm_harmonic, Destroyer<ddm_harmonic_destroy>>;
 // cls[i]: 0 = interior, 1 = boundary, anything else = neither (its values count as zero in the right-hand side, :109-118)
 static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, const uint8_t *cls, bool want_transpose, ddm_harmonic **out)
 {
@@ -347,17 +256,17 @@ static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks,
       }
     }
   }
-  ddm_harmonic *H = new ddm_harmonic;
+  harmonic_ptr H(new ddm_harmonic);
   H->n = n;
-  ddm_csr *Ahat = nullptr;
-  int rc = ddm_csr_create(ctx, n, n, rpI.data(), ciI.data(), vaI.data(), &Ahat);
+  csr_ptr Ahat;
+  int rc = ddm_csr_create(ctx, n, n, rpI.data(), ciI.data(), vaI.data(), out_ptr(Ahat));
   if (!rc) {
-    H->symmetric = csr_values_symmetric(Ahat);
-    rc = direct_create_impl(ctx, Ahat, nblocks, block_ptr, H->symmetric ? 0 : 1, 0.0, /*setup_use=*/true, &H->F);
+    H->symmetric = csr_values_symmetric(Ahat.get());
+    rc = direct_create_impl(ctx, Ahat.get(), nblocks, block_ptr, H->symmetric ? 0 : 1, 0.0, /*setup_use=*/true, out_ptr(H->F));
   }
-  ddm_csr_destroy(Ahat);
-  if (!rc) rc = ddm_csr_create(ctx, n, n, rpG.data(), ciG.data(), vaG.data(), &H->Gib);
-  if (!rc && want_transpose) rc = ddm_csr_create(ctx, n, n, rpT.data(), ciT.data(), vaT.data(), &H->Gbi);
+  Ahat.reset();
+  if (!rc) rc = ddm_csr_create(ctx, n, n, rpG.data(), ciG.data(), vaG.data(), out_ptr(H->Gib));
+  if (!rc && want_transpose) rc = ddm_csr_create(ctx, n, n, rpT.data(), ciT.data(), vaT.data(), out_ptr(H->Gbi));
   if (!rc) {
     std::vector<double> k0((size_t)n), k1((size_t)n), k2((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
@@ -369,19 +278,16 @@ static int harmonic_create_impl(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks,
     if (!rc) rc = upload(ctx, k1.data(), n, H->keep_b);
     if (!rc) rc = upload(ctx, k2.data(), n, H->isint);
   }
-  if (rc) {
-    ddm_harmonic_destroy(H);
-    return rc;
-  }
-  *out = H;
+  if (rc) return rc;
+  *out = H.release();
   return DDM_OK;
 }
 // X <- keep .* X - A^^-1 G_ib X  (keep = rows outside the interior, or boundary rows only)
 static int harmonic_apply(ddm_ctx *ctx, ddm_harmonic *H, int m, double *X, int64_t ldx, bool boundary_only)
 {
   HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
-  DDMCHECK(csr_mm_ld(ctx, H->Gib, m, X, ldx, H->t1, m));
-  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));
+  DDMCHECK(csr_mm_ld(ctx, H->Gib.get(), m, X, ldx, H->t1, m));
+  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t1, m, H->t2, m));
   hipLaunchKernelGGL(k_geneo_project, dim3((unsigned)((H->n * (int64_t)m + 255) / 256)), dim3(256), 0, ctx->stream, H->n, m, boundary_only ? H->keep_b : H->keep,
                      (const double *)H->t2, (int64_t)m, X, ldx);
   HIPCHECK(ctx, hipGetLastError());
@@ -393,8 +299,8 @@ static int harmonic_apply_transposed(ddm_ctx *ctx, ddm_harmonic *H, int m, doubl
   HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
   const unsigned g = (unsigned)((H->n * (int64_t)m + 255) / 256);
   hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(g), dim3(256), 0, ctx->stream, H->n, m, H->isint, (const double *)R, ldr, H->t1, (int64_t)m);
-  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));
-  DDMCHECK(csr_mm_ld(ctx, H->Gbi, m, H->t2, m, H->t1, m));
+  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t1, m, H->t2, m));
+  DDMCHECK(csr_mm_ld(ctx, H->Gbi.get(), m, H->t2, m, H->t1, m));
   hipLaunchKernelGGL(k_geneo_project, dim3(g), dim3(256), 0, ctx->stream, H->n, m, H->keep_b, (const double *)H->t1, (int64_t)m, R, ldr);
   HIPCHECK(ctx, hipGetLastError());
   return DDM_OK;
@@ -425,211 +331,225 @@ extern "C" int ddm_harmonic_extend(ddm_ctx *ctx, ddm_harmonic *H, int nrhs, doub
   return DDM_OK;
 }
 
-static int geneo_run(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, int64_t nsub, const int64_t *sub_ptr, const double *pou_host,
-                     const uint8_t *dirichlet_host, const ddm_geneo_params &P, int nev, double *basis_dev /* nev x n */, double *eig_host /* nsub x nev */,
-                     ddm_geneo_info *info, ddm_harmonic *con = nullptr /* iterate in the a-harmonic subspace */, const double *pou_pencil_host = nullptr,
-                     const std::function<int(int, const double *, int64_t, double *, int64_t)> *op_C = nullptr /* replaces the product with C~ */)
-{
-  const int64_t n = A_neu->nrows;
-  const int m = nev + std::max(P.extra, 1);
-  const int p = 3 * m;
-  if (m > GENEO_MAX_BLOCK) return fail(ctx, DDM_ENOTIMPL, "GenEO: nev + extra = %d exceeds %d vectors per subdomain", m, GENEO_MAX_BLOCK);
-  for (int64_t s = 0; s < nsub; ++s)
-    if (sub_ptr[s + 1] - sub_ptr[s] < 3 * (int64_t)m) return fail(ctx, DDM_EINVAL, "GenEO: subdomain %lld has fewer than 3 (nev + extra) = %d rows", (long long)s, 3 * m);
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-  // "auto": whether the sparse direct factor of A~ is affordable at all is estimated on a helper thread from the first separator of the
-  // largest block of A_neu's pattern (the pencil's pattern, or a superset of B_neu's), while the pencil is being assembled
-  struct Joiner { // (an early error return must not leave a helper thread running on this frame's variables)
-    std::thread &t;
-    ~Joiner()
+// Y = Op X on row-major blocks: (columns, X, ldx, Y, ldy)
+using BlockOp = std::function<int(int, const double *, int64_t, double *, int64_t)>;
+
+// What the eigensolver is asked for: ddm_geneo_basis, ddm_msgfem_basis and ddm_svd_basis fill it.
+struct GeneoProblem {
+  const char *who = "";                     // the entry point, for its messages
+  const ddm_csr *A = nullptr, *B = nullptr; // A x = lambda (D B D) x; only the host arrays are read
+  int64_t nsub = 0;
+  const int64_t *sub_ptr = nullptr;
+  const double *pou = nullptr;         // D of the finalisation v <- D v, and of the pencil unless pou_pencil is given
+  const uint8_t *dirichlet = nullptr;  // optional: rows / columns taken out of C~, zeroed in the basis
+  ddm_harmonic *con = nullptr;         // optional: iterate in the a-harmonic subspace
+  const double *pou_pencil = nullptr;  // optional: D of the pencil
+  const BlockOp *op_C = nullptr;       // optional: replaces the product with C~
+};
+
+static double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// One run of the block eigensolver at a fixed block width: everything its phases share.  geneo_run calls the phases in order.
+struct GeneoRun {
+  struct Helper { // a helper thread that an early error return cannot leave running
+    std::thread t;
+    void join()
     {
       if (t.joinable()) t.join();
     }
+    ~Helper() { join(); }
   };
+  static constexpr double tau = 1e-11; // rank tolerance of the Rayleigh-Ritz step
+  ddm_ctx *const ctx;
+  const GeneoProblem &Q;
+  const ddm_geneo_params &P;
+  const int64_t n, nsub;
+  const int nev, m, p, q2; // block width m = nev + extra, p = 3 m columns of S = [X | W | P], q2 = 2 m: the fused rotation [X_new | P_new]
+  const int64_t ld;
+  const unsigned gnm;
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  double t_pencil = 0.0, t_upload = 0.0, t_direct = 0.0, t_prec = 0.0, t_setup = 0.0; // ends of the setup intervals, seconds after t_begin
+  // ORDER OF THE MEMBERS BELOW = reverse order of destruction, on every return path.  The two helper threads are declared last, so
+  // they are joined first: the probe reads Q.A and writes probe_flops, the ILU(0) build reads At's host arrays and writes T_ilu,
+  // rc_ilu and err_ilu.  Then the buffers go, then the preconditioner(s), then At, whose deleter (ddm_csr_destroy) joins the upload
+  // thread that fills the device arrays of At AND of C -- which is why C is declared before At and outlives it.
+  csr_ptr C, At;      // the pencil: C~ (values only, on At's pattern) and A~ = A + sigma C~
+  ilu0_ptr T, T_ilu;  // the chosen preconditioner; the speculative ILU(0) until the choice is made
   double probe_flops = 0.0;
-  std::thread probe_thread;
-  Joiner probe_joiner{probe_thread};
-  if (P.preconditioner == 0 && P.max_direct_flops > 0.0 && nsub > 1 && !std::getenv("DDM_DIRECT_ENGINE"))
-    probe_thread = std::thread([&]() { probe_flops = sn_probe_largest_block(A_neu->h_rp.data(), A_neu->h_ci.data(), nsub, sub_ptr, false); });
+  int rc_ilu = DDM_OK;
+  std::string err_ilu;
+  int direct = 0; // T is the sparse direct factor of A~
+  bool prec_f32 = false;
+  int refresh_period = 0, orth_passes = 0;
+  GeneoWork W;
+  dbuf<double> S[2], AS[2], CS[2], R, maskd, poud; // double-buffered [X | W | P] and its products, residual block, Dirichlet mask, POU
+  dbuf<double> gA, gC, gmm[5], svec[2], Yd, mud;
+  std::vector<double> hA, hC, hY, hmu, h_rr, h_rw, h_aa;
+  std::vector<double> dscale; // column scaling of S = [X | W | P] folded into the projected problem
+  int cur = 0, rank_min = 0;
+  double worst = 0.0;
+  Helper probe_thread, ilu_thread;
+
+  GeneoRun(ddm_ctx *c, const GeneoProblem &q, const ddm_geneo_params &par, int nev_)
+      : ctx(c), Q(q), P(par), n(q.A->nrows), nsub(q.nsub), nev(nev_), m(nev_ + std::max(par.extra, 1)), p(3 * m), q2(2 * m), ld(p),
+        gnm((unsigned)((n * (int64_t)m + 255) / 256)), rank_min(p)
+  {
+  }
+  // A~ X and C~ X of the same m-column block in one pass (the two matrices share their pattern: build_pencil_host)
+  int apply_AC(const double *X, double *YA, double *YC)
+  {
+    if (!Q.op_C) return csr_mm2_ld(ctx, At.get(), C.get(), m, X, ld, YA, YC, ld);
+    DDMCHECK(csr_mm_ld(ctx, At.get(), m, X, ld, YA, ld));
+    return (*Q.op_C)(m, X, ld, YC, ld);
+  }
+
   // ---- pencil ----
-  hvec<int64_t> rpT;
-  hvec<int32_t> ciT;
-  hvec<double> vaT, vaC;
-  build_pencil_host(A_neu, B_neu, pou_pencil_host ? pou_pencil_host : pou_host, dirichlet_host, P.shift, rpT, ciT, vaT, vaC);
-  const double t_pencil = since(t_begin);
-  struct Owned {
-    ddm_csr *At = nullptr, *C = nullptr;
-    ddm_ilu0 *T = nullptr;
-    ~Owned()
-    {
-      ddm_ilu0_destroy(T);
-      ddm_csr_destroy(At); // (joins the upload thread that also fills C)
-      ddm_csr_destroy(C);
-    }
-  } own;
-  // the host arrays move into At; its device copy and the values of C~ (same pattern, device only) are uploaded by a helper thread
-  // while this one factorises / analyses on the host
-  own.At = csr_adopt(ctx, n, std::move(rpT), std::move(ciT), std::move(vaT), std::move(vaC), &own.C, nsub, sub_ptr);
-  const double t_upload = since(t_begin);
-  // A~ X and C~ X of the same block in one pass (the two matrices share their pattern: build_pencil_host)
-  auto apply_AC = [&](int mm, const double *X, int64_t ldx, double *YA, double *YC, int64_t ldy) -> int {
-    if (!op_C) return csr_mm2_ld(ctx, own.At, own.C, mm, X, ldx, YA, YC, ldy);
-    DDMCHECK(csr_mm_ld(ctx, own.At, mm, X, ldx, YA, ldy));
-    return (*op_C)(mm, X, ldx, YC, ldy);
-  };
+  void assemble_pencil()
+  {
+    // "auto": whether the sparse direct factor of A~ is affordable at all is estimated on a helper thread from the first separator of the
+    // largest block of A's pattern (the pencil's pattern, or a superset of B's), while the pencil is being assembled
+    if (P.preconditioner == 0 && P.max_direct_flops > 0.0 && nsub > 1 && !std::getenv("DDM_DIRECT_ENGINE"))
+      probe_thread.t = std::thread([this]() { probe_flops = sn_probe_largest_block(Q.A->h_rp.data(), Q.A->h_ci.data(), nsub, Q.sub_ptr, false); });
+    hvec<int64_t> rpT;
+    hvec<int32_t> ciT;
+    hvec<double> vaT, vaC;
+    build_pencil_host(Q.A, Q.B, Q.pou_pencil ? Q.pou_pencil : Q.pou, Q.dirichlet, P.shift, rpT, ciT, vaT, vaC);
+    t_pencil = seconds_since(t_begin);
+    // the host arrays move into At; its device copy and the values of C~ (same pattern, device only) are uploaded by a helper thread
+    // while this one factorises / analyses on the host
+    At.reset(csr_adopt(ctx, n, std::move(rpT), std::move(ciT), std::move(vaT), std::move(vaC), out_ptr(C), nsub, Q.sub_ptr));
+    t_upload = seconds_since(t_begin);
+  }
+
   // ---- preconditioner ----
   // "auto": the ILU(0) factorisation starts on a helper thread while this one orders and analyses for the sparse direct factor
   // (at the headline size the analysis ends in "too expensive" after 0.9 s and the ILU(0) setup takes 2.3 s); whichever is not
   // needed is dropped
-  int direct = 0;
-  ddm_ilu0 *T_ilu = nullptr;
-  int rc_ilu = DDM_OK;
-  std::string err_ilu;
-  std::thread ilu_thread;
-  Joiner ilu_joiner{ilu_thread};
-  auto start_ilu = [&]() {
-    ilu_thread = std::thread([&]() {
-      (void)hipSetDevice(ctx->device);
-      rc_ilu = ilu0_create_impl(ctx, own.At, nsub, sub_ptr, /*multi_rhs_only=*/true, &T_ilu);
-      if (rc_ilu) err_ilu = last_error_of_this_thread();
-    });
-  };
-  if (P.preconditioner != 2) start_ilu();
-  int rc_direct = DDM_OK;
-  std::string why_not;
-  if (probe_thread.joinable()) probe_thread.join();
-  if (P.preconditioner == 0 && probe_flops > 4.0 * P.max_direct_flops) { // declined by the early probe: no second analysis
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "sparse direct solver: the factorisation needs about %.1g flops (estimate from the first separator of the largest block; limit %.3g)",
-                  probe_flops, P.max_direct_flops);
-    why_not = buf;
-    rc_direct = DDM_ENOTIMPL;
-  } else if (P.preconditioner != 1) {
-    rc_direct = direct_create_impl(ctx, own.At, nsub, sub_ptr, 0, P.preconditioner == 2 ? 0.0 : P.max_direct_flops, /*setup_use=*/true, &own.T);
-    if (rc_direct == DDM_OK) direct = 1;
-    else why_not = last_error_of_this_thread();
-  }
-  const double t_direct = since(t_begin);
-  if (ilu_thread.joinable()) ilu_thread.join();
-  if (direct) {
-    ddm_ilu0_destroy(T_ilu); // (speculative work, not needed)
-  } else {
-    if (P.preconditioner != 1 && (P.preconditioner == 2 || (rc_direct != DDM_ENOTIMPL && rc_direct != DDM_ENUMERIC))) {
-      ddm_ilu0_destroy(T_ilu);
-      return fail(ctx, rc_direct, "%s", why_not.c_str());
-    }
-    if (P.preconditioner != 1 && P.verbose) std::fprintf(stderr, "[ddm geneo] sparse Cholesky not used (%s): ILU(0) preconditioner\n", why_not.c_str());
-    if (rc_ilu) return fail(ctx, rc_ilu, "%s", err_ilu.c_str());
-    own.T = T_ilu;
-  }
-  // ILU(0) as the preconditioner of the block iteration: single-precision sweeps (the iteration only needs a fixed search direction
-  // W = T r; eigenpairs and residuals are computed in double).  DDM_GENEO_ILU_F64=1 keeps the sweeps in double.
-  const bool prec_f32 = !direct && !std::getenv("DDM_GENEO_ILU_F64");
-  const int refresh_period = std::getenv("DDM_GENEO_REFRESH") ? std::max(1, std::atoi(std::getenv("DDM_GENEO_REFRESH"))) : (direct ? 2 : 8);
-  // W <- W - X (A~X)^T W before the Rayleigh-Ritz step: twice with the exact T (W = A~^-1 r lies almost in span X near convergence: on
-  // the elasticity pencil one pass gave 68-81 block iterations in two of eight runs, none 133 in one, against 12-18 -- measured before the products of P were refreshed, see below), once with
-  // ILU(0) (216^3: the same 109 iterations and residuals with two, one or no pass; 5.6 / 5.2 / 4.9 s).  DDM_GENEO_ORTH_PASSES overrides.
-  const int orth_passes = std::getenv("DDM_GENEO_ORTH_PASSES") ? std::max(0, std::atoi(std::getenv("DDM_GENEO_ORTH_PASSES"))) : (direct ? 2 : 1);
-  const double t_prec = since(t_begin);
-  DDMCHECK(csr_wait_upload(ctx, own.At));
-  const double t_setup = since(t_begin);
-  if (P.verbose)
-    std::fprintf(stderr, "[ddm geneo] setup: pencil %.2f s, sparse direct attempt %.2f s (%s), rest of the ILU(0) setup (helper thread) %.2f s, rest of the matrix upload (helper thread) %.2f s\n",
-                 t_pencil, t_direct - t_upload, direct ? "used" : "declined", t_prec - t_direct, t_setup - t_prec);
-  // ---- work space ----
-  GeneoWork W;
-  W.ctx = ctx;
-  W.n = n;
-  W.nsub = (int)nsub;
-  W.m = m;
-  W.p = p;
-  std::vector<GChunk> chunks;
-  std::vector<int32_t> scp((size_t)nsub + 1, 0), sor((size_t)n);
-  for (int64_t s = 0; s < nsub; ++s) {
-    for (int64_t r = sub_ptr[s]; r < sub_ptr[s + 1]; r += GENEO_CHUNK_ROWS) chunks.push_back(GChunk{r, std::min(r + GENEO_CHUNK_ROWS, sub_ptr[s + 1]), (int32_t)s, 0});
-    scp[(size_t)s + 1] = (int32_t)chunks.size();
-    for (int64_t r = sub_ptr[s]; r < sub_ptr[s + 1]; ++r) sor[(size_t)r] = (int32_t)s;
-  }
-  W.nchunk = (int)chunks.size();
-  DDMCHECK(W.alloc(W.chunks, chunks.size()));
-  DDMCHECK(W.alloc(W.sub_chunk_ptr, scp.size()));
-  DDMCHECK(W.alloc(W.sub_of_row, (size_t)n));
-  DDMCHECK(W.alloc(W.partial, (size_t)W.nchunk * p * p * 2)); // (two products per chunk: gram2_sym)
-  HIPCHECK(ctx, hipMemcpy(W.chunks, chunks.data(), sizeof(GChunk) * chunks.size(), hipMemcpyHostToDevice));
-  HIPCHECK(ctx, hipMemcpy(W.sub_chunk_ptr, scp.data(), sizeof(int32_t) * scp.size(), hipMemcpyHostToDevice));
-  HIPCHECK(ctx, hipMemcpy(W.sub_of_row, sor.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  dbuf<double> S[2], AS[2], CS[2], R, maskd, poud;
-  for (int b = 0; b < 2; ++b) {
-    DDMCHECK(W.alloc(S[b], (size_t)n * p));
-    DDMCHECK(W.alloc(AS[b], (size_t)n * p));
-    DDMCHECK(W.alloc(CS[b], (size_t)n * p));
-    HIPCHECK(ctx, hipMemsetAsync(S[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
-    HIPCHECK(ctx, hipMemsetAsync(AS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
-    HIPCHECK(ctx, hipMemsetAsync(CS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
-  }
-  DDMCHECK(W.alloc(R, (size_t)n * m));
-  DDMCHECK(W.alloc(maskd, (size_t)n));
-  DDMCHECK(W.alloc(poud, (size_t)n));
+  int choose_preconditioner()
   {
-    std::vector<double> mk((size_t)n);
-    for (int64_t i = 0; i < n; ++i) mk[(size_t)i] = (dirichlet_host && dirichlet_host[i]) ? 0.0 : 1.0;
-    HIPCHECK(ctx, hipMemcpy(maskd, mk.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(ctx, hipMemcpy(poud, pou_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  }
-  dbuf<double> gA, gC, gmm[5], svec[2], Yd, mud;
-  DDMCHECK(W.alloc(gA, (size_t)nsub * p * p));
-  DDMCHECK(W.alloc(gC, (size_t)nsub * p * p));
-  for (int k = 0; k < 5; ++k) DDMCHECK(W.alloc(gmm[k], (size_t)nsub * m * m));
-  for (int k = 0; k < 2; ++k) DDMCHECK(W.alloc(svec[k], (size_t)nsub * m));
-  const int q2 = 2 * m; // fused rotation: [X_new | P_new]
-  DDMCHECK(W.alloc(Yd, (size_t)nsub * p * q2));
-  DDMCHECK(W.alloc(mud, (size_t)nsub * m));
-  std::vector<double> hA((size_t)nsub * p * p), hC((size_t)nsub * p * p), hY((size_t)nsub * p * q2), hmu((size_t)nsub * m);
-  std::vector<double> h_rr((size_t)nsub * m * m), h_rw((size_t)nsub * m * m), h_aa((size_t)nsub * m * m);
-  std::vector<double> dscale((size_t)nsub * p, 1.0); // column scaling of S = [X | W | P] folded into the projected problem
-  const unsigned gnm = (unsigned)((n * (int64_t)m + 255) / 256);
-  const int64_t ld = p;
-  // ---- initial block: random on the free DoFs, Rayleigh-Ritz on span X ----
-  hipLaunchKernelGGL(k_geneo_random, dim3(gnm), dim3(256), 0, ctx->stream, n, m, ld, 0x5DEECE66Dull + (unsigned long long)P.seed, maskd, S[0]);
-  if (con) DDMCHECK(harmonic_apply(ctx, con, m, S[0], ld, true));
-  DDMCHECK(apply_AC(m, S[0], ld, AS[0], CS[0], ld));
-  int cur = 0, it = 0, converged = 0, rank_min = p;
-  double worst = 0.0;
-  const double tau = 1e-11;
-  bool have_residual = false;
-  std::vector<int> rcs((size_t)nsub, 0);
-  const auto t_iter = std::chrono::steady_clock::now();
-  for (it = 0; it <= P.maxit; ++it) {
-    if (it > 0) {
-      // R = C X - mu A~ X ; column norms ; W = T R
-      hipLaunchKernelGGL(k_geneo_residual, dim3(gnm), dim3(256), 0, ctx->stream, n, m, W.sub_of_row, mud, AS[cur], ld, CS[cur], ld, R, (int64_t)m);
-      if (con) DDMCHECK(harmonic_apply_transposed(ctx, con, m, R, m)); // residual of the constrained problem: P^T r
-      DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
-      HIPCHECK(ctx, hipMemcpyAsync(h_rr.data(), gmm[0], sizeof(double) * h_rr.size(), hipMemcpyDeviceToHost, ctx->stream));
-      // (W = T r with the residual columns as they are: their scaling is folded into the projected problem below, like W's and P's)
-      double *Wb = S[cur] + m, *AWb = AS[cur] + m, *CWb = CS[cur] + m;
-      DDMCHECK(ilu0_solve_multi_ld(ctx, own.T, m, R, m, Wb, ld, prec_f32));
-      DDMCHECK(W.gram(R, m, m, Wb, ld, m, gmm[1]));   // r^T T r per column (diagonal)
-      HIPCHECK(ctx, hipMemcpyAsync(h_rw.data(), gmm[1], sizeof(double) * h_rw.size(), hipMemcpyDeviceToHost, ctx->stream));
-      if (con) DDMCHECK(harmonic_apply(ctx, con, m, Wb, ld, true));    // W = P T P^T r stays in the subspace
-      DDMCHECK(W.gram(AS[cur], ld, m, AS[cur], ld, m, gmm[2]));
-      HIPCHECK(ctx, hipMemcpyAsync(h_aa.data(), gmm[2], sizeof(double) * h_aa.size(), hipMemcpyDeviceToHost, ctx->stream));
-      // W <- W - X (A~X)^T W   (orth_passes times), then A~-normalise the columns of W
-      for (int pass = 0; pass < orth_passes; ++pass) {
-        DDMCHECK(W.gram(AS[cur], ld, m, Wb, ld, m, gmm[3]));
-        const double *Ux[1] = {S[cur]};
-        double *Ox[1] = {Wb};
-        const double *Bx[1] = {Wb};
-        DDMCHECK(W.rotate(1, Ux, Ox, Bx, ld, m, gmm[3], m, ld, ld));
-      }
-      DDMCHECK(apply_AC(m, Wb, ld, AWb, CWb, ld)); // both products of W in one pass over it
-      // A~-normalisation of the columns of W and P (zero columns stay zero): the blocks themselves are NOT rescaled (six passes over
-      // n x m blocks per iteration in round 2) -- the diagonal scaling D is applied where it is cheap: to the p x p Gram matrices
-      // (D G D) and to the rows of the Ritz coefficients (S D) Y = S (D Y), on the host; the norms W^T A~ W, P^T A~ P are the diagonal
-      // of the unscaled S^T A~ S that is computed below anyway (two separate m x m products until round 3)
-      have_residual = true;
+    if (P.preconditioner != 2)
+      ilu_thread.t = std::thread([this]() {
+        (void)hipSetDevice(ctx->device);
+        rc_ilu = ilu0_create_impl(ctx, At.get(), nsub, Q.sub_ptr, /*multi_rhs_only=*/true, out_ptr(T_ilu));
+        if (rc_ilu) err_ilu = last_error_of_this_thread();
+      });
+    int rc_direct = DDM_OK;
+    std::string why_not;
+    probe_thread.join();
+    if (P.preconditioner == 0 && probe_flops > 4.0 * P.max_direct_flops) { // declined by the early probe: no second analysis
+      char buf[256];
+      std::snprintf(buf, sizeof buf, "sparse direct solver: the factorisation needs about %.1g flops (estimate from the first separator of the largest block; limit %.3g)",
+                    probe_flops, P.max_direct_flops);
+      why_not = buf;
+      rc_direct = DDM_ENOTIMPL;
+    } else if (P.preconditioner != 1) {
+      rc_direct = direct_create_impl(ctx, At.get(), nsub, Q.sub_ptr, 0, P.preconditioner == 2 ? 0.0 : P.max_direct_flops, /*setup_use=*/true, out_ptr(T));
+      if (rc_direct == DDM_OK) direct = 1;
+      else why_not = last_error_of_this_thread();
     }
+    t_direct = seconds_since(t_begin);
+    ilu_thread.join();
+    if (direct) {
+      T_ilu.reset(); // (speculative work, not needed)
+    } else {
+      if (P.preconditioner != 1 && (P.preconditioner == 2 || (rc_direct != DDM_ENOTIMPL && rc_direct != DDM_ENUMERIC))) return fail(ctx, rc_direct, "%s", why_not.c_str());
+      if (P.preconditioner != 1 && P.verbose) std::fprintf(stderr, "[ddm geneo] sparse Cholesky not used (%s): ILU(0) preconditioner\n", why_not.c_str());
+      if (rc_ilu) return fail(ctx, rc_ilu, "%s", err_ilu.c_str());
+      T = std::move(T_ilu);
+    }
+    // ILU(0) as the preconditioner of the block iteration: single-precision sweeps (the iteration only needs a fixed search direction
+    // W = T r; eigenpairs and residuals are computed in double).  DDM_GENEO_ILU_F64=1 keeps the sweeps in double.
+    prec_f32 = !direct && !std::getenv("DDM_GENEO_ILU_F64");
+    refresh_period = std::getenv("DDM_GENEO_REFRESH") ? std::max(1, std::atoi(std::getenv("DDM_GENEO_REFRESH"))) : (direct ? 2 : 8);
+    // W <- W - X (A~X)^T W before the Rayleigh-Ritz step: twice with the exact T (W = A~^-1 r lies almost in span X near convergence: on
+    // the elasticity pencil one pass gave 68-81 block iterations in two of eight runs, none 133 in one, against 12-18 -- measured before the products of P were refreshed, see below), once with
+    // ILU(0) (216^3: the same 109 iterations and residuals with two, one or no pass; 5.6 / 5.2 / 4.9 s).  DDM_GENEO_ORTH_PASSES overrides.
+    orth_passes = std::getenv("DDM_GENEO_ORTH_PASSES") ? std::max(0, std::atoi(std::getenv("DDM_GENEO_ORTH_PASSES"))) : (direct ? 2 : 1);
+    t_prec = seconds_since(t_begin);
+    DDMCHECK(csr_wait_upload(ctx, At.get()));
+    t_setup = seconds_since(t_begin);
+    if (P.verbose)
+      std::fprintf(stderr, "[ddm geneo] setup: pencil %.2f s, sparse direct attempt %.2f s (%s), rest of the ILU(0) setup (helper thread) %.2f s, rest of the matrix upload (helper thread) %.2f s\n",
+                   t_pencil, t_direct - t_upload, direct ? "used" : "declined", t_prec - t_direct, t_setup - t_prec);
+    return DDM_OK;
+  }
+
+  // ---- work space ----
+  int allocate()
+  {
+    DDMCHECK(W.setup(ctx, nsub, Q.sub_ptr, (size_t)p * p * 2, /*rows_to_sub=*/true)); // (two products per chunk: gram2_sym)
+    for (int b = 0; b < 2; ++b) {
+      DDMCHECK(W.alloc(S[b], (size_t)n * p));
+      DDMCHECK(W.alloc(AS[b], (size_t)n * p));
+      DDMCHECK(W.alloc(CS[b], (size_t)n * p));
+      HIPCHECK(ctx, hipMemsetAsync(S[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
+      HIPCHECK(ctx, hipMemsetAsync(AS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
+      HIPCHECK(ctx, hipMemsetAsync(CS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
+    }
+    DDMCHECK(W.alloc(R, (size_t)n * m));
+    DDMCHECK(W.alloc(maskd, (size_t)n));
+    DDMCHECK(W.alloc(poud, (size_t)n));
+    {
+      std::vector<double> mk((size_t)n);
+      for (int64_t i = 0; i < n; ++i) mk[(size_t)i] = (Q.dirichlet && Q.dirichlet[i]) ? 0.0 : 1.0;
+      HIPCHECK(ctx, hipMemcpy(maskd, mk.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+      HIPCHECK(ctx, hipMemcpy(poud, Q.pou, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    DDMCHECK(W.alloc(gA, (size_t)nsub * p * p));
+    DDMCHECK(W.alloc(gC, (size_t)nsub * p * p));
+    for (int k = 0; k < 5; ++k) DDMCHECK(W.alloc(gmm[k], (size_t)nsub * m * m));
+    for (int k = 0; k < 2; ++k) DDMCHECK(W.alloc(svec[k], (size_t)nsub * m));
+    DDMCHECK(W.alloc(Yd, (size_t)nsub * p * q2));
+    DDMCHECK(W.alloc(mud, (size_t)nsub * m));
+    for (auto *h : {&hA, &hC}) h->resize((size_t)nsub * p * p);
+    for (auto *h : {&h_rr, &h_rw, &h_aa}) h->resize((size_t)nsub * m * m);
+    hY.resize((size_t)nsub * p * q2);
+    hmu.resize((size_t)nsub * m);
+    dscale.assign((size_t)nsub * p, 1.0);
+    return DDM_OK;
+  }
+
+  // ---- initial block: random on the free DoFs (the first pass of the loop is then a Rayleigh-Ritz step on span X alone) ----
+  int start_block()
+  {
+    hipLaunchKernelGGL(k_geneo_random, dim3(gnm), dim3(256), 0, ctx->stream, n, m, ld, 0x5DEECE66Dull + (unsigned long long)P.seed, maskd, S[0]);
+    if (Q.con) DDMCHECK(harmonic_apply(ctx, Q.con, m, S[0], ld, true));
+    return apply_AC(S[0], AS[0], CS[0]);
+  }
+
+  // ---- search directions: R = C X - mu A~ X ; column norms ; W = T R, orthogonalised against X, and its products ----
+  int search_directions()
+  {
+    hipLaunchKernelGGL(k_geneo_residual, dim3(gnm), dim3(256), 0, ctx->stream, n, m, W.sub_of_row, mud, AS[cur], ld, CS[cur], ld, R, (int64_t)m);
+    if (Q.con) DDMCHECK(harmonic_apply_transposed(ctx, Q.con, m, R, m)); // residual of the constrained problem: P^T r
+    DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
+    HIPCHECK(ctx, hipMemcpyAsync(h_rr.data(), gmm[0], sizeof(double) * h_rr.size(), hipMemcpyDeviceToHost, ctx->stream));
+    // (W = T r with the residual columns as they are: their scaling is folded into the projected problem below, like W's and P's)
+    double *Wb = S[cur] + m, *AWb = AS[cur] + m, *CWb = CS[cur] + m;
+    DDMCHECK(ilu0_solve_multi_ld(ctx, T.get(), m, R, m, Wb, ld, prec_f32));
+    DDMCHECK(W.gram(R, m, m, Wb, ld, m, gmm[1])); // r^T T r per column (diagonal)
+    HIPCHECK(ctx, hipMemcpyAsync(h_rw.data(), gmm[1], sizeof(double) * h_rw.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (Q.con) DDMCHECK(harmonic_apply(ctx, Q.con, m, Wb, ld, true)); // W = P T P^T r stays in the subspace
+    DDMCHECK(W.gram(AS[cur], ld, m, AS[cur], ld, m, gmm[2]));
+    HIPCHECK(ctx, hipMemcpyAsync(h_aa.data(), gmm[2], sizeof(double) * h_aa.size(), hipMemcpyDeviceToHost, ctx->stream));
+    // W <- W - X (A~X)^T W   (orth_passes times), then A~-normalise the columns of W
+    for (int pass = 0; pass < orth_passes; ++pass) {
+      DDMCHECK(W.gram(AS[cur], ld, m, Wb, ld, m, gmm[3]));
+      const double *Ux[1] = {S[cur]};
+      double *Ox[1] = {Wb};
+      const double *Bx[1] = {Wb};
+      DDMCHECK(W.rotate(1, Ux, Ox, Bx, ld, m, gmm[3], m, ld, ld));
+    }
+    // A~-normalisation of the columns of W and P (zero columns stay zero): the blocks themselves are NOT rescaled (six passes over
+    // n x m blocks per iteration in round 2) -- the diagonal scaling D is applied where it is cheap: to the p x p Gram matrices
+    // (D G D) and to the rows of the Ritz coefficients (S D) Y = S (D Y), on the host; the norms W^T A~ W, P^T A~ P are the diagonal
+    // of the unscaled S^T A~ S that is computed next anyway (two separate m x m products until round 3)
+    return apply_AC(Wb, AWb, CWb); // both products of W in one pass over it
+  }
+
+  // ---- projected problem: S^T (A~ S) and S^T (C~ S) per subdomain, on the host when this returns ----
+  int projected_problem()
+  {
     const bool upper_only = W.gram2_sym(S[cur], ld, AS[cur], CS[cur], ld, p, gA, gC);
     HIPCHECK(ctx, hipGetLastError());
     HIPCHECK(ctx, hipMemcpyAsync(hA.data(), gA, sizeof(double) * hA.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -640,151 +560,191 @@ static int geneo_run(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, i
         GeneoWork::gram2_mirror_host(p, hA.data() + (size_t)s * p * p);
         GeneoWork::gram2_mirror_host(p, hC.data() + (size_t)s * p * p);
       }
-    if (have_residual) { // residuals of the block that entered this iteration (its Ritz values are still in hmu)
-      worst = 0.0;
-      int64_t nconv_cols = 0;
-      int lead_min = nev; // converged columns in front of the first unconverged one, minimum over the subdomains
-      for (int64_t s = 0; s < nsub; ++s) {
-        int lead = 0;
-        bool leading = true;
-        for (int j = 0; j < nev; ++j) {
-          const size_t dj = ((size_t)s * m + j) * m + j;
-          const double rn = std::sqrt(std::max(h_rr[dj], 0.0)), mu = std::fabs(hmu[(size_t)s * m + j]);
-          const double res = direct ? std::sqrt(std::fabs(h_rw[dj])) / std::max(mu, 1e-300) // sqrt(r^T T r) / mu
-                                    : rn / std::max(mu * std::sqrt(std::max(h_aa[dj], 0.0)), 1e-300);
-          worst = std::max(worst, res);
-          if (res < P.tolerance) {
-            ++nconv_cols;
-            if (leading) ++lead;
-          } else
-            leading = false;
-        }
-        lead_min = std::min(lead_min, lead);
+    return DDM_OK;
+  }
+
+  // ---- residual test: the residuals of the block that entered this iteration (its Ritz values are still in hmu); true = converged ----
+  bool residual_test(int it)
+  {
+    worst = 0.0;
+    int64_t nconv_cols = 0;
+    int lead_min = nev; // converged columns in front of the first unconverged one, minimum over the subdomains
+    for (int64_t s = 0; s < nsub; ++s) {
+      int lead = 0;
+      bool leading = true;
+      for (int j = 0; j < nev; ++j) {
+        const size_t dj = ((size_t)s * m + j) * m + j;
+        const double rn = std::sqrt(std::max(h_rr[dj], 0.0)), mu = std::fabs(hmu[(size_t)s * m + j]);
+        const double res = direct ? std::sqrt(std::fabs(h_rw[dj])) / std::max(mu, 1e-300) // sqrt(r^T T r) / mu
+                                  : rn / std::max(mu * std::sqrt(std::max(h_aa[dj], 0.0)), 1e-300);
+        worst = std::max(worst, res);
+        if (res < P.tolerance) {
+          ++nconv_cols;
+          if (leading) ++lead;
+        } else
+          leading = false;
       }
-      if (P.verbose)
-        std::fprintf(stderr, "[ddm geneo] it %3d  worst residual %.3e  rank >= %d  lambda_min(sub 0) %.6g  converged columns %lld of %lld, leading (min over subdomains) %d\n", it, worst,
-                     rank_min, 1.0 / hmu[0] - P.shift, (long long)nconv_cols, (long long)(nsub * nev), lead_min);
-      if (worst < P.tolerance) {
+      lead_min = std::min(lead_min, lead);
+    }
+    if (P.verbose)
+      std::fprintf(stderr, "[ddm geneo] it %3d  worst residual %.3e  rank >= %d  lambda_min(sub 0) %.6g  converged columns %lld of %lld, leading (min over subdomains) %d\n", it, worst,
+                   rank_min, 1.0 / hmu[0] - P.shift, (long long)nconv_cols, (long long)(nsub * nev), lead_min);
+    return worst < P.tolerance;
+  }
+
+  // ---- Rayleigh-Ritz per subdomain on host threads, the column scaling folded in (with_wp: the W and P columns are there) ----
+  int rayleigh_ritz(bool with_wp)
+  {
+    const int nth = (int)std::min<int64_t>(nsub, host_threads());
+    std::vector<std::thread> th;
+    std::vector<int> ranks((size_t)nsub, 0);
+    for (int t = 0; t < nth; ++t)
+      th.emplace_back([&, t]() {
+        std::vector<double> Y1((size_t)p * m);
+        for (int64_t s = t; s < nsub; s += nth) {
+          double *d = dscale.data() + (size_t)s * p;
+          for (int i = 0; i < p; ++i) d[i] = 1.0;
+          if (with_wp)
+            for (int j = 0; j < m; ++j) {
+              const double gw = hA[(size_t)s * p * p + (size_t)(m + j) * p + (m + j)], gp = hA[(size_t)s * p * p + (size_t)(2 * m + j) * p + (2 * m + j)];
+              d[m + j] = gw > 1e-300 ? 1.0 / std::sqrt(gw) : 0.0;
+              d[2 * m + j] = gp > 1e-300 ? 1.0 / std::sqrt(gp) : 0.0;
+            }
+          double *gAs = hA.data() + (size_t)s * p * p, *gCs = hC.data() + (size_t)s * p * p;
+          for (int i = 0; i < p; ++i)
+            for (int j = 0; j < p; ++j) {
+              gAs[(size_t)i * p + j] *= d[i] * d[j];
+              gCs[(size_t)i * p + j] *= d[i] * d[j];
+            }
+          const int r = dense::rayleigh_ritz(p, gAs, gCs, m, tau, hmu.data() + (size_t)s * m, Y1.data());
+          ranks[(size_t)s] = r;
+          if (r < m) continue;
+          double *Y = hY.data() + (size_t)s * p * q2; // [Y | Y with the X rows zeroed]: X_new = S Y, P_new = [W P] Y_{W,P}
+          for (int i = 0; i < p; ++i)
+            for (int j = 0; j < m; ++j) {
+              const double y = d[i] * Y1[(size_t)i * m + j];
+              Y[(size_t)i * q2 + j] = y;
+              Y[(size_t)i * q2 + m + j] = i < m ? 0.0 : y;
+            }
+        }
+      });
+    for (auto &t : th) t.join();
+    rank_min = p;
+    for (int64_t s = 0; s < nsub; ++s) {
+      if (ranks[(size_t)s] < m) return fail(ctx, DDM_ENUMERIC, "GenEO: Rayleigh-Ritz failed in subdomain %lld (rank %d of the block basis)", (long long)s, ranks[(size_t)s]);
+      rank_min = std::min(rank_min, ranks[(size_t)s]);
+    }
+    return DDM_OK;
+  }
+
+  // ---- rotation: [X | . | P] of the other buffer <- S [Y | Y_wp]: two column blocks of one rotation (q = 2m, written with a gap of m columns) ----
+  int rotate_blocks()
+  {
+    HIPCHECK(ctx, hipMemcpyAsync(Yd, hY.data(), sizeof(double) * hY.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(mud, hmu.data(), sizeof(double) * hmu.size(), hipMemcpyHostToDevice, ctx->stream));
+    const int nxt = cur ^ 1;
+    const double *U3[3] = {S[cur], AS[cur], CS[cur]};
+    double *O3[3] = {S[nxt], AS[nxt], CS[nxt]};
+    // first m output columns -> X slot, the other m -> P slot (the W slot in between is overwritten by the next preconditioner solve)
+    DDMCHECK(W.rotate(3, U3, O3, nullptr, ld, p, Yd, q2, ld, ld, /*gap_from=*/m, /*gap=*/m));
+    cur = nxt;
+    return DDM_OK;
+  }
+
+  // ---- refresh A~X, C X from X and A~P, C P from P: the products are carried along by the rotations and drift.  With the exact T every
+  // second iteration: W and P shrink geometrically there (their scaling lives in the projected problem, the blocks are not
+  // renormalised), the Ritz coefficients of such columns are large, and products of P that are never recomputed went wrong often
+  // enough to matter -- on the elasticity pencil 12-18 block iterations in most runs but 36-120 or no convergence within 400 in
+  // about one run of seven (the device factor's atomics make every run round differently); with P refreshed as well: 12-16 in 28
+  // of 28 runs, refreshing X alone does not help (tools/geneo_variability.sh).  With ILU(0) every eighth iteration, as before.
+  int refresh()
+  {
+    if (Q.con) DDMCHECK(harmonic_apply(ctx, Q.con, m, S[cur], ld, true));
+    DDMCHECK(apply_AC(S[cur], AS[cur], CS[cur]));
+    return apply_AC(S[cur] + 2 * m, AS[cur] + 2 * m, CS[cur] + 2 * m);
+  }
+
+  // ---- output: eigenvalues lambda = 1 / mu - sigma, finalised basis (nev x n on the device) ----
+  int output(double *basis_dev, double *eig_host)
+  {
+    for (int64_t s = 0; s < nsub; ++s)
+      for (int j = 0; j < nev; ++j) eig_host[(size_t)s * nev + j] = 1.0 / hmu[(size_t)s * m + j] - P.shift;
+    hipLaunchKernelGGL(k_geneo_copy_cols, dim3(gnm), dim3(256), 0, ctx->stream, n, m, (const double *)S[cur], ld, R, (int64_t)m);
+    if (!P.raw) hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, poud, R, (int64_t)m); // v <- D v
+    DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
+    hipLaunchKernelGGL(k_geneo_invsqrt_diag, dim3((unsigned)((nsub * m + 255) / 256)), dim3(256), 0, ctx->stream, (int)nsub, m, gmm[0], svec[0]); // 1 / ||D v||_2  (raw: 1 / ||v||_2)
+    hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, maskd, R, (int64_t)m);      // zero_at_dirichlet
+    hipLaunchKernelGGL(k_geneo_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, nev, W.sub_of_row, svec[0], m, R, (int64_t)m, basis_dev);
+    HIPCHECK(ctx, hipGetLastError());
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return DDM_OK;
+  }
+};
+
+// The LOBPCG loop of the head of this file at block width nev + extra: basis_dev is nev x n, eig_host nsub x nev.
+static int geneo_run(ddm_ctx *ctx, const GeneoProblem &Q, const ddm_geneo_params &P, int nev, double *basis_dev, double *eig_host, ddm_geneo_info *info)
+{
+  const int m = nev + std::max(P.extra, 1);
+  if (m > GENEO_MAX_BLOCK) return fail(ctx, DDM_ENOTIMPL, "GenEO: nev + extra = %d exceeds %d vectors per subdomain", m, GENEO_MAX_BLOCK);
+  for (int64_t s = 0; s < Q.nsub; ++s)
+    if (Q.sub_ptr[s + 1] - Q.sub_ptr[s] < 3 * (int64_t)m) return fail(ctx, DDM_EINVAL, "GenEO: subdomain %lld has fewer than 3 (nev + extra) = %d rows", (long long)s, 3 * m);
+  GeneoRun G(ctx, Q, P, nev);
+  G.assemble_pencil();
+  DDMCHECK(G.choose_preconditioner());
+  DDMCHECK(G.allocate());
+  DDMCHECK(G.start_block());
+  int it = 0, converged = 0;
+  const auto t_iter = std::chrono::steady_clock::now();
+  for (it = 0; it <= P.maxit; ++it) {
+    if (it > 0) DDMCHECK(G.search_directions());
+    DDMCHECK(G.projected_problem());
+    if (it > 0) {
+      if (G.residual_test(it)) {
         converged = 1;
         break;
       }
       if (it == P.maxit) break;
     }
-    // Rayleigh-Ritz per subdomain on the host
-    {
-      const unsigned hw = host_threads();
-      const int nth = (int)std::min<int64_t>(nsub, hw);
-      std::vector<std::thread> th;
-      std::vector<int> ranks((size_t)nsub, 0);
-      for (int t = 0; t < nth; ++t)
-        th.emplace_back([&, t]() {
-          std::vector<double> Y1((size_t)p * m);
-          for (int64_t s = t; s < nsub; s += nth) {
-            double *d = dscale.data() + (size_t)s * p;
-            for (int i = 0; i < p; ++i) d[i] = 1.0;
-            if (have_residual)
-              for (int j = 0; j < m; ++j) {
-                const double gw = hA[(size_t)s * p * p + (size_t)(m + j) * p + (m + j)], gp = hA[(size_t)s * p * p + (size_t)(2 * m + j) * p + (2 * m + j)];
-                d[m + j] = gw > 1e-300 ? 1.0 / std::sqrt(gw) : 0.0;
-                d[2 * m + j] = gp > 1e-300 ? 1.0 / std::sqrt(gp) : 0.0;
-              }
-            double *gAs = hA.data() + (size_t)s * p * p, *gCs = hC.data() + (size_t)s * p * p;
-            for (int i = 0; i < p; ++i)
-              for (int j = 0; j < p; ++j) {
-                gAs[(size_t)i * p + j] *= d[i] * d[j];
-                gCs[(size_t)i * p + j] *= d[i] * d[j];
-              }
-            const int r = dense::rayleigh_ritz(p, gAs, gCs, m, tau, hmu.data() + (size_t)s * m, Y1.data());
-            ranks[(size_t)s] = r;
-            rcs[(size_t)s] = r < m ? 1 : 0;
-            if (r < m) continue;
-            double *Y = hY.data() + (size_t)s * p * q2; // [Y | Y with the X rows zeroed]: X_new = S Y, P_new = [W P] Y_{W,P}
-            for (int i = 0; i < p; ++i)
-              for (int j = 0; j < m; ++j) {
-                const double y = d[i] * Y1[(size_t)i * m + j];
-                Y[(size_t)i * q2 + j] = y;
-                Y[(size_t)i * q2 + m + j] = i < m ? 0.0 : y;
-              }
-          }
-        });
-      for (auto &t : th) t.join();
-      rank_min = p;
-      for (int64_t s = 0; s < nsub; ++s) {
-        if (rcs[(size_t)s]) return fail(ctx, DDM_ENUMERIC, "GenEO: Rayleigh-Ritz failed in subdomain %lld (rank %d of the block basis)", (long long)s, ranks[(size_t)s]);
-        rank_min = std::min(rank_min, ranks[(size_t)s]);
-      }
-    }
-    HIPCHECK(ctx, hipMemcpyAsync(Yd, hY.data(), sizeof(double) * hY.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(mud, hmu.data(), sizeof(double) * hmu.size(), hipMemcpyHostToDevice, ctx->stream));
-    // [X | . | P] of the other buffer <- S [Y | Y_wp]: two column blocks of one rotation (q = 2m, written with a gap of m columns)
-    {
-      const int nxt = cur ^ 1;
-      const double *U3[3] = {S[cur], AS[cur], CS[cur]};
-      double *O3[3] = {S[nxt], AS[nxt], CS[nxt]};
-      // first m output columns -> X slot, the other m -> P slot (the W slot in between is overwritten by the next preconditioner solve)
-      DDMCHECK(W.rotate(3, U3, O3, nullptr, ld, p, Yd, q2, ld, ld, /*gap_from=*/m, /*gap=*/m));
-      cur = nxt;
-    }
-    // Refresh A~X, C X from X and A~P, C P from P: the products are carried along by the rotations and drift.  With the exact T every
-    // second iteration: W and P shrink geometrically there (their scaling lives in the projected problem, the blocks are not
-    // renormalised), the Ritz coefficients of such columns are large, and products of P that are never recomputed went wrong often
-    // enough to matter -- on the elasticity pencil 12-18 block iterations in most runs but 36-120 or no convergence within 400 in
-    // about one run of seven (the device factor's atomics make every run round differently); with P refreshed as well: 12-16 in 28
-    // of 28 runs, refreshing X alone does not help (tools/geneo_variability.sh).  With ILU(0) every eighth iteration, as before.
-    if (it > 0 && it % refresh_period == 0) {
-      if (con) DDMCHECK(harmonic_apply(ctx, con, m, S[cur], ld, true));
-      DDMCHECK(apply_AC(m, S[cur], ld, AS[cur], CS[cur], ld));
-      DDMCHECK(apply_AC(m, S[cur] + 2 * m, ld, AS[cur] + 2 * m, CS[cur] + 2 * m, ld));
-    }
+    DDMCHECK(G.rayleigh_ritz(/*with_wp=*/it > 0));
+    DDMCHECK(G.rotate_blocks());
+    if (it > 0 && it % G.refresh_period == 0) DDMCHECK(G.refresh());
   }
-  const double t_loop = since(t_iter);
-  // ---- output: eigenvalues, finalised basis ----
-  for (int64_t s = 0; s < nsub; ++s)
-    for (int j = 0; j < nev; ++j) eig_host[(size_t)s * nev + j] = 1.0 / hmu[(size_t)s * m + j] - P.shift;
-  hipLaunchKernelGGL(k_geneo_copy_cols, dim3(gnm), dim3(256), 0, ctx->stream, n, m, (const double *)S[cur], ld, R, (int64_t)m);
-  if (!P.raw) hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, poud, R, (int64_t)m); // v <- D v
-  DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
-  hipLaunchKernelGGL(k_geneo_invsqrt_diag, dim3((unsigned)((nsub * m + 255) / 256)), dim3(256), 0, ctx->stream, (int)nsub, m, gmm[0], svec[0]); // 1 / ||D v||_2  (raw: 1 / ||v||_2)
-  hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, maskd, R, (int64_t)m);      // zero_at_dirichlet
-  hipLaunchKernelGGL(k_geneo_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, nev, W.sub_of_row, svec[0], m, R, (int64_t)m, basis_dev);
-  HIPCHECK(ctx, hipGetLastError());
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const double t_loop = seconds_since(t_iter);
+  DDMCHECK(G.output(basis_dev, eig_host));
   if (info) {
     info->iterations = it;
     info->converged = converged;
-    info->used_direct = direct;
-    info->worst_residual = worst;
-    info->setup_s = t_setup;
+    info->used_direct = G.direct;
+    info->worst_residual = G.worst;
+    info->setup_s = G.t_setup;
     info->iterate_s = t_loop;
     info->nev = nev;
-    info->direct_flops = direct ? ilu0_direct_flops(own.T) : 0.0;
+    info->direct_flops = G.direct ? ilu0_direct_flops(G.T.get()) : 0.0;
   }
   return DDM_OK;
 }
 
-static int geneo_basis_impl(ddm_ctx *ctx, const char *who, const ddm_csr *A_neu, const ddm_csr *B_neu, int64_t nsub, const int64_t *sub_ptr, const double *pou_host,
-                            const uint8_t *dirichlet_host, const ddm_geneo_params *params, int64_t kmax, double *basis_host, int32_t *nconv,
-                            double *eigenvalues_host, ddm_geneo_info *info, ddm_harmonic *con, const double *pou_pencil_host,
-                            const std::function<int(int, const double *, int64_t, double *, int64_t)> *op_C = nullptr)
+static int geneo_basis_impl(ddm_ctx *ctx, const GeneoProblem &Q, const ddm_geneo_params *params, int64_t kmax, double *basis_host, int32_t *nconv, double *eigenvalues_host,
+                            ddm_geneo_info *info)
 {
-  if (!ctx || !A_neu || !B_neu || !sub_ptr || !pou_host || !params || !basis_host || !nconv || !eigenvalues_host || nsub < 1)
-    return fail(ctx, DDM_EINVAL, "%s: bad arguments", who);
-  if (A_neu->nrows != A_neu->ncols || B_neu->nrows != A_neu->nrows || B_neu->ncols != A_neu->ncols)
+  const int64_t nsub = Q.nsub;
+  if (!ctx || !Q.A || !Q.B || !Q.sub_ptr || !Q.pou || !params || !basis_host || !nconv || !eigenvalues_host || nsub < 1) return fail(ctx, DDM_EINVAL, "%s: bad arguments", Q.who);
+  if (Q.A->nrows != Q.A->ncols || Q.B->nrows != Q.A->nrows || Q.B->ncols != Q.A->ncols)
     return fail(ctx, DDM_EINVAL, "The matrix and the partition of unity must have the same size"); // coarse_spaces.hh:323
-  if (sub_ptr[0] != 0 || sub_ptr[nsub] != A_neu->nrows) return fail(ctx, DDM_EINVAL, "sub_ptr does not cover the matrix");
+  if (Q.sub_ptr[0] != 0 || Q.sub_ptr[nsub] != Q.A->nrows) return fail(ctx, DDM_EINVAL, "sub_ptr does not cover the matrix");
   const ddm_geneo_params &P = *params;
-  if (P.nev < 1 || P.extra < 1 || !(P.tolerance > 0.0)) return fail(ctx, DDM_EINVAL, "%s: bad eigensolver parameters", who);
-  const int64_t n = A_neu->nrows;
+  if (P.nev < 1 || P.extra < 1 || !(P.tolerance > 0.0)) return fail(ctx, DDM_EINVAL, "%s: bad eigensolver parameters", Q.who);
+  const int64_t n = Q.A->nrows;
   int nev = P.nev;
   // threshold mode of spectra_gevp_op (eigensolvers/spectra.hh:157-163, 186-189): keep the eigenvalues below the threshold (at least
   // one), double nev until the largest computed one exceeds it or nev >= nev_max
   for (;;) {
-    if (nev > kmax) return fail(ctx, DDM_EINVAL, "%s: kmax = %lld is smaller than nev = %d", who, (long long)kmax, nev);
+    if (nev > kmax) return fail(ctx, DDM_EINVAL, "%s: kmax = %lld is smaller than nev = %d", Q.who, (long long)kmax, nev);
     dbuf<double> basis_dev;
     HIPCHECK(ctx, basis_dev.alloc(nev * std::max<int64_t>(n, 1)));
     std::vector<double> eig((size_t)nsub * nev);
-    int rc = geneo_run(ctx, A_neu, B_neu, nsub, sub_ptr, pou_host, dirichlet_host, P, nev, basis_dev, eig.data(), info, con, pou_pencil_host, op_C);
-    if (!rc && hipMemcpy(basis_host, basis_dev, sizeof(double) * (size_t)nev * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, DDM_EHIP, "%s: basis download failed", who);
+    int rc = geneo_run(ctx, Q, P, nev, basis_dev, eig.data(), info);
+    if (!rc && hipMemcpy(basis_host, basis_dev, sizeof(double) * (size_t)nev * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, DDM_EHIP, "%s: basis download failed", Q.who);
     if (rc) return rc;
     bool done = true;
     if (P.threshold > 0.0) {
@@ -815,8 +775,20 @@ extern "C" int ddm_geneo_basis(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr
                                const uint8_t *dirichlet_host, const ddm_geneo_params *params, int64_t kmax, double *basis_host, int32_t *nconv,
                                double *eigenvalues_host, ddm_geneo_info *info)
 {
-  return geneo_basis_impl(ctx, "ddm_geneo_basis", A_neu, B_neu, nsub, sub_ptr, pou_host, dirichlet_host, params, kmax, basis_host, nconv, eigenvalues_host, info, nullptr,
-                          nullptr);
+  const GeneoProblem Q{"ddm_geneo_basis", A_neu, B_neu, nsub, sub_ptr, pou_host, dirichlet_host};
+  return geneo_basis_impl(ctx, Q, params, kmax, basis_host, nconv, eigenvalues_host, info);
+}
+
+// Rows as MsGFEM (coarse_spaces.hh:722-740) and the SVD space (:1293-1309) sort them: cls = 0 interior, 1 subdomain boundary, 2 global
+// Dirichlet; pou_int = the partition of unity on the interior rows, zero elsewhere
+static void classify_rows(int64_t n, const uint8_t *dirichlet, const uint8_t *boundary, const double *pou, std::vector<uint8_t> &cls, std::vector<double> &pou_int)
+{
+  cls.resize((size_t)n);
+  pou_int.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    cls[(size_t)i] = (dirichlet && dirichlet[i]) ? 2 : boundary[i] ? 1 : 0;
+    pou_int[(size_t)i] = cls[(size_t)i] == 0 ? pou[i] : 0.0;
+  }
 }
 
 // MsGFEMCoarseSpace::setup_msgfem_impl (coarse_spaces.hh:712-826).  The reference assembles the saddle-point pencil
@@ -833,22 +805,14 @@ extern "C" int ddm_msgfem_basis(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_cs
 {
   if (!ctx || !A_neu || !A_dir || !sub_ptr || !pou_host || !boundary_host || !params || nsub < 1) return fail(ctx, DDM_EINVAL, "ddm_msgfem_basis: bad arguments");
   if (A_dir->nrows != A_neu->nrows || A_dir->ncols != A_dir->nrows) return fail(ctx, DDM_EINVAL, "The two matrices must have the same size"); // :714
-  const int64_t n = A_dir->nrows;
-  std::vector<uint8_t> cls((size_t)n);
-  std::vector<double> pou_int((size_t)n);
-  for (int64_t i = 0; i < n; ++i) { // :722-740
-    cls[(size_t)i] = (dirichlet_host && dirichlet_host[i]) ? 2 : boundary_host[i] ? 1 : 0;
-    pou_int[(size_t)i] = cls[(size_t)i] == 0 ? pou_host[i] : 0.0; // the right-hand side has interior x interior entries only (:801-811)
-  }
-  ddm_harmonic *H = nullptr;
-  DDMCHECK(harmonic_create_impl(ctx, A_dir, nsub, sub_ptr, cls.data(), true, &H));
-  int rc = DDM_OK;
-  if (!H->symmetric) rc = fail(ctx, DDM_ENOTIMPL, "ddm_msgfem_basis: the interior block of A_dir is not symmetric");
-  if (!rc)
-    rc = geneo_basis_impl(ctx, "ddm_msgfem_basis", A_neu, A_neu, nsub, sub_ptr, pou_host, dirichlet_host, params, kmax, basis_host, nconv, eigenvalues_host, info, H,
-                          pou_int.data());
-  ddm_harmonic_destroy(H);
-  return rc;
+  std::vector<uint8_t> cls;
+  std::vector<double> pou_int; // the right-hand side has interior x interior entries only (:801-811)
+  classify_rows(A_dir->nrows, dirichlet_host, boundary_host, pou_host, cls, pou_int);
+  harmonic_ptr H;
+  DDMCHECK(harmonic_create_impl(ctx, A_dir, nsub, sub_ptr, cls.data(), true, out_ptr(H)));
+  if (!H->symmetric) return fail(ctx, DDM_ENOTIMPL, "ddm_msgfem_basis: the interior block of A_dir is not symmetric");
+  const GeneoProblem Q{"ddm_msgfem_basis", A_neu, A_neu, nsub, sub_ptr, pou_host, dirichlet_host, H.get(), pou_int.data()};
+  return geneo_basis_impl(ctx, Q, params, kmax, basis_host, nconv, eigenvalues_host, info);
 }
 
 // SVDCoarseSpace (coarse_spaces.hh:1268-1407): the leading left singular vectors of T = D A_ii^-1 A_{i,Gamma} (interior x subdomain
@@ -864,41 +828,31 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
     return fail(ctx, DDM_EINVAL, "ddm_svd_basis: bad arguments");
   if (A_dir->nrows != A_dir->ncols || sub_ptr[0] != 0 || sub_ptr[nsub] != A_dir->nrows) return fail(ctx, DDM_EINVAL, "ddm_svd_basis: sub_ptr does not cover the matrix");
   const int64_t n = A_dir->nrows;
-  std::vector<uint8_t> cls((size_t)n), notint((size_t)n);
-  std::vector<double> pou_int((size_t)n), ones((size_t)n, 1.0);
-  for (int64_t i = 0; i < n; ++i) { // :1293-1309
-    cls[(size_t)i] = (dirichlet_host && dirichlet_host[i]) ? 2 : boundary_host[i] ? 1 : 0;
-    notint[(size_t)i] = cls[(size_t)i] != 0;
-    pou_int[(size_t)i] = cls[(size_t)i] == 0 ? pou_host[i] : 0.0;
-  }
-  ddm_harmonic *H = nullptr;
-  DDMCHECK(harmonic_create_impl(ctx, A_dir, nsub, sub_ptr, cls.data(), true, &H));
-  struct Guard {
-    ddm_harmonic *H;
-    ddm_csr *I = nullptr;
-    dbuf<double> d;
-    ~Guard()
-    {
-      ddm_harmonic_destroy(H);
-      ddm_csr_destroy(I);
-    }
-  } g{H};
+  std::vector<uint8_t> cls, notint((size_t)n);
+  std::vector<double> pou_int, ones((size_t)n, 1.0);
+  classify_rows(n, dirichlet_host, boundary_host, pou_host, cls, pou_int);
+  for (int64_t i = 0; i < n; ++i) notint[(size_t)i] = cls[(size_t)i] != 0;
+  harmonic_ptr Hown;
+  DDMCHECK(harmonic_create_impl(ctx, A_dir, nsub, sub_ptr, cls.data(), true, out_ptr(Hown)));
+  ddm_harmonic *const H = Hown.get();
   if (!H->symmetric) return fail(ctx, DDM_ENOTIMPL, "ddm_svd_basis: the interior block of A_dir is not symmetric");
   std::vector<int64_t> rp((size_t)n + 1);
   std::vector<int32_t> ci((size_t)n);
   for (int64_t i = 0; i <= n; ++i) rp[(size_t)i] = i;
   for (int64_t i = 0; i < n; ++i) ci[(size_t)i] = (int32_t)i;
-  DDMCHECK(ddm_csr_create(ctx, n, n, rp.data(), ci.data(), ones.data(), &g.I));
-  DDMCHECK(upload(ctx, pou_int.data(), n, g.d));
-  const std::function<int(int, const double *, int64_t, double *, int64_t)> op = [&](int m, const double *X, int64_t ldx, double *Y, int64_t ldy) -> int {
+  csr_ptr I;
+  dbuf<double> d;
+  DDMCHECK(ddm_csr_create(ctx, n, n, rp.data(), ci.data(), ones.data(), out_ptr(I)));
+  DDMCHECK(upload(ctx, pou_int.data(), n, d));
+  const BlockOp op = [&](int m, const double *X, int64_t ldx, double *Y, int64_t ldy) -> int {
     HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
     const unsigned gr = (unsigned)((n * (int64_t)m + 255) / 256);
-    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)g.d, X, ldx, H->t1, (int64_t)m); // D x
-    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t1, m, H->t2, m));                                                                 // A_ii^-T
-    DDMCHECK(csr_mm_ld(ctx, H->Gbi, m, H->t2, m, H->t1, m));                                                                         // A_{i,Gamma}^T
-    DDMCHECK(csr_mm_ld(ctx, H->Gib, m, H->t1, m, H->t2, m));                                                                         // A_{i,Gamma}
-    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F, m, H->t2, m, H->t1, m));                                                                 // A_ii^-1
-    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)g.d, (const double *)H->t1, (int64_t)m, Y, ldy); // D
+    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)d, X, ldx, H->t1, (int64_t)m); // D x
+    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t1, m, H->t2, m));                                                          // A_ii^-T
+    DDMCHECK(csr_mm_ld(ctx, H->Gbi.get(), m, H->t2, m, H->t1, m));                                                                  // A_{i,Gamma}^T
+    DDMCHECK(csr_mm_ld(ctx, H->Gib.get(), m, H->t1, m, H->t2, m));                                                                  // A_{i,Gamma}
+    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t2, m, H->t1, m));                                                          // A_ii^-1
+    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)d, (const double *)H->t1, (int64_t)m, Y, ldy); // D
     HIPCHECK(ctx, hipGetLastError());
     return DDM_OK;
   };
@@ -913,76 +867,8 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   P.raw = mult_pou ? 0 : 1; // :1403: finalize_eigenvectors only with mult_pou
   std::vector<int32_t> nconv((size_t)nsub);
   std::vector<double> eig((size_t)nsub * n_vectors);
-  DDMCHECK(geneo_basis_impl(ctx, "ddm_svd_basis", g.I, g.I, nsub, sub_ptr, pou_host, notint.data(), &P, n_vectors, basis_host, nconv.data(), eig.data(), info, nullptr,
-                            ones.data(), &op));
+  const GeneoProblem Q{"ddm_svd_basis", I.get(), I.get(), nsub, sub_ptr, pou_host, notint.data(), nullptr, ones.data(), &op};
+  DDMCHECK(geneo_basis_impl(ctx, Q, &P, n_vectors, basis_host, nconv.data(), eig.data(), info));
   for (size_t k = 0; k < eig.size(); ++k) singular_values_host[k] = 1.0 / std::sqrt(std::max(eig[k], 1e-300)); // mu = sigma^2 = 1 / lambda
   return DDM_OK;
-}
-
-// ---- the two dense block kernels on their own (parity tests against an FP64 host reference; also usable by callers that keep
-//      their block vectors on the device) ------------------------------------------------------------------------------------
-static int blockvec_setup(ddm_ctx *ctx, GeneoWork &W, int64_t nsub, const int64_t *sub_ptr, int pmax_sq)
-{
-  W.ctx = ctx;
-  W.nsub = (int)nsub;
-  W.n = sub_ptr[nsub];
-  std::vector<GChunk> chunks;
-  std::vector<int32_t> scp((size_t)nsub + 1, 0);
-  for (int64_t s = 0; s < nsub; ++s) {
-    for (int64_t r = sub_ptr[s]; r < sub_ptr[s + 1]; r += GENEO_CHUNK_ROWS) chunks.push_back(GChunk{r, std::min(r + GENEO_CHUNK_ROWS, sub_ptr[s + 1]), (int32_t)s, 0});
-    scp[(size_t)s + 1] = (int32_t)chunks.size();
-  }
-  W.nchunk = (int)chunks.size();
-  DDMCHECK(W.alloc(W.chunks, chunks.size()));
-  DDMCHECK(W.alloc(W.sub_chunk_ptr, scp.size()));
-  DDMCHECK(W.alloc(W.partial, (size_t)std::max(W.nchunk, 1) * (size_t)pmax_sq));
-  HIPCHECK(ctx, hipMemcpy(W.chunks, chunks.data(), sizeof(GChunk) * chunks.size(), hipMemcpyHostToDevice));
-  HIPCHECK(ctx, hipMemcpy(W.sub_chunk_ptr, scp.data(), sizeof(int32_t) * scp.size(), hipMemcpyHostToDevice));
-  return DDM_OK;
-}
-extern "C" int ddm_blockvec_gram(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, const double *U, int64_t ldu, int pu, const double *V, int64_t ldv,
-                                 int pv, double *G_host)
-{
-  if (!ctx || !sub_ptr || !U || !V || !G_host || nsub < 1 || pu < 1 || pv < 1 || ldu < pu || ldv < pv) return fail(ctx, DDM_EINVAL, "ddm_blockvec_gram: bad arguments");
-  GeneoWork W;
-  DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, pu * pv));
-  dbuf<double> G;
-  DDMCHECK(W.alloc(G, (size_t)nsub * pu * pv));
-  DDMCHECK(W.gram(U, ldu, pu, V, ldv, pv, G));
-  return ddm_memcpy_d2h(ctx, G_host, G, (int64_t)sizeof(double) * nsub * pu * pv);
-}
-extern "C" int ddm_blockvec_gram2_sym(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, const double *U, int64_t ldu, const double *V1, const double *V2, int64_t ldv, int p,
-                                      double *G1_host, double *G2_host)
-{
-  if (!ctx || !sub_ptr || !U || !V1 || !V2 || !G1_host || !G2_host || nsub < 1 || p < 1 || ldu < p || ldv < p) return fail(ctx, DDM_EINVAL, "ddm_blockvec_gram2_sym: bad arguments");
-  GeneoWork W;
-  DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, 2 * p * p));
-  dbuf<double> G;
-  DDMCHECK(W.alloc(G, (size_t)nsub * p * p * 2));
-  const bool upper_only = W.gram2_sym(U, ldu, V1, V2, ldv, p, G, G + (size_t)nsub * p * p);
-  HIPCHECK(ctx, hipGetLastError());
-  DDMCHECK(ddm_memcpy_d2h(ctx, G1_host, G, (int64_t)sizeof(double) * nsub * p * p));
-  DDMCHECK(ddm_memcpy_d2h(ctx, G2_host, G + (size_t)nsub * p * p, (int64_t)sizeof(double) * nsub * p * p));
-  if (upper_only)
-    for (int64_t s = 0; s < nsub; ++s) {
-      GeneoWork::gram2_mirror_host(p, G1_host + (size_t)s * p * p);
-      GeneoWork::gram2_mirror_host(p, G2_host + (size_t)s * p * p);
-    }
-  return DDM_OK;
-}
-extern "C" int ddm_blockvec_rotate(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, const double *U, int64_t ldu, int p, const double *Y_host, int q,
-                                   const double *Base, int64_t ldb, double *Out, int64_t ldo)
-{
-  if (!ctx || !sub_ptr || !U || !Y_host || !Out || nsub < 1 || p < 1 || q < 1 || ldu < p || ldo < q || (Base && ldb < q) || U == Out)
-    return fail(ctx, DDM_EINVAL, "ddm_blockvec_rotate: bad arguments");
-  GeneoWork W;
-  DDMCHECK(blockvec_setup(ctx, W, nsub, sub_ptr, 1));
-  dbuf<double> Y;
-  DDMCHECK(W.alloc(Y, (size_t)nsub * p * q));
-  DDMCHECK(ddm_memcpy_h2d(ctx, Y, Y_host, (int64_t)sizeof(double) * nsub * p * q));
-  const double *Ux[1] = {U};
-  double *Ox[1] = {Out};
-  const double *Bx[1] = {Base};
-  DDMCHECK(W.rotate(1, Ux, Ox, Base ? Bx : nullptr, ldu, p, Y, q, ldo, ldb));
-  return ddm_ctx_sync(ctx);
 }

@@ -290,6 +290,25 @@ def test_geneo_cache_blocked_row_order_is_bit_identical(ddm, monkeypatch):
         assert np.array_equal(i0["eigenvalues"][s], i1["eigenvalues"][s])
 
 
+def test_geneo_two_runs_on_one_context_are_bit_identical(ddm):
+    """Every ddm_geneo_basis call builds its own pencil, preconditioner and work space: nothing of one run may reach the next.  Two
+    consecutive calls on ONE context (ILU(0) preconditioner: no atomics on the path) must give the same bytes -- basis, eigenvalues,
+    iteration count."""
+    from dune_ddm_amd import synth
+    from dune_ddm_amd.geneo import geneo_basis
+    from dune_ddm_amd.problem import build_structured
+    from dune_ddm_amd.solver import TwoLevelSchwarz
+    dec = build_structured(synth.StructuredPoisson((17, 15, 13), (2, 2, 1)), overlap=2, pou_type="distance", neumann=True)
+    tl = TwoLevelSchwarz(dec, coarse="none")
+    (b0, i0), (b1, i1) = (geneo_basis(tl, nev=3, preconditioner="ilu0", return_info=True) for _ in range(2))
+    assert i0["converged"] and i1["converged"] and not i0["used_direct"] and not i1["used_direct"]
+    assert i0["iterations"] == i1["iterations"]
+    for s in b0:
+        assert np.array_equal(b0[s], b1[s])
+        assert np.array_equal(i0["eigenvalues"][s], i1["eigenvalues"][s])
+    tl.ctx.close()
+
+
 def test_host_only_matrix_objects(ddm):
     """ddm_csr_create_host: the GenEO inputs A_neu / B_neu are read on the host only; such an object must be refused (DDM_EINVAL with a
     message, not a fault) by every entry point that would touch device arrays."""
