@@ -81,6 +81,7 @@ SYMBOLS = {
     "ddm_csr_mm": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_csr_row_order_tiled_host": (_I32, [_I64, _P, _P, _P, _P]),
     "ddm_dia_build_and_apply_host": (_I32, [_I64, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "ddm_dia_windows_host": (_I32, [_I64, _P, _P, _P, _I64, _P, _I64, _P, _P]),
     "ddm_ilu0_solve_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_solve_multi_f32": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_create": (_I32, [_P, _P, _I64, _P, _PP]),
@@ -906,6 +907,23 @@ def dia_build_and_apply_host(A, x):
     if rc != DDM_OK:
         raise ValueError("ddm_dia_build_and_apply_host: bad arguments")
     return y, kinds[:counts[0]], dict(zip(("blocks", "dia", "csr", "rows_dia", "slots", "segments", "symmetric_segments"), counts.tolist()))
+
+
+def dia_windows_host(A):
+    """(segments, capacity): the x windows of the same layout.  segments: one dict(staged, window, runs) per segment, runs a list of
+    (first offset, doubles, window position); capacity: the doubles the windows of a staged segment may take.  Host only."""
+    lib = load_library()
+    n = A.shape[0]
+    rp, ci, va = _np(A.indptr, np.int64), _np(A.indices, np.int32), _np(A.data, np.float64)
+    max_segs, max_runs = n + 1, 32 * (n + 1)
+    segs = np.zeros((max_segs, 4), dtype=np.int32)
+    runs = np.zeros((max_runs, 3), dtype=np.int32)
+    counts = np.zeros(4, dtype=np.int64)
+    rc = lib.ddm_dia_windows_host(n, _hp(rp), _hp(ci), _hp(va), max_segs, _hp(segs), max_runs, _hp(runs), _hp(counts))
+    if rc != DDM_OK:
+        raise ValueError("ddm_dia_windows_host: bad arguments")
+    out = [dict(staged=bool(s[0]), window=int(s[2]), runs=[tuple(r) for r in runs[s[3]:s[3] + s[1]].tolist()]) for s in segs[:counts[0]]]
+    return out, int(counts[2])
 
 
 def blockvec_gram(ctx: Context, sub_ptr, U, V):

@@ -326,11 +326,25 @@ extern "C" int ddm_csr_mm(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double
 // table; its slabs are laid out segment-wide, val[slab * rows + row].  A segment keeps only the slabs of the offsets >= 0 when
 // its table is its own mirror image and every entry (r, c) below the diagonal has c inside the segment and a partner (c, r) of
 // the same bits: a(r, r + d), d < 0, is then read as val[slab of -d][r + d].
+// x windows: the ascending offsets of a segment are grouped into runs, offset k joining the run of k - 1 when off[k] - off[k-1] <= WG
+// (joining costs that many doubles of window, a new run costs WG).  A block reads, per run with first offset f and last offset l,
+// the WG + (l - f) consecutive doubles x[r0 + f ...] (clamped to the vector): its window; the windows lie back to back, thread t
+// finds x[r + off[k]] at lds_pos[k] + t.  A segment whose windows fit DIA_WIN doubles is staged: its blocks load the windows into
+// LDS once instead of one x load per diagonal and row (stage_x = false, DDM_SPMV_STAGE_X=0: no segment is).
 constexpr int64_t DIA_SPLIT_ROWS = 256 * WG;
+struct DiaRun {
+  int32_t first, len, start; // first offset, window doubles WG + (last - first), window position
+};
+struct DiaSegWindows {
+  bool staged = false;
+  int32_t window = 0; // doubles of all runs
+  std::vector<DiaRun> runs;
+};
 struct DiaLayout {
   std::vector<DiaBlock> blk;
   std::vector<int32_t> stored; // per block: slabs its segment keeps (nd, or the offsets >= 0 of a symmetric segment; 0: CSR-stream)
-  std::vector<int32_t> tab;    // per segment: DIA_MAX offsets, DIA_MAX slab numbers, DIA_MAX row shifts (tails repeat the last entry)
+  std::vector<int32_t> tab;    // per segment: a record of DIA_REC ints (kernels.hpp: DIA_TAB_*; tails of the rows repeat the last entry)
+  std::vector<DiaSegWindows> win; // per segment: the runs of its offset table (all of them, staged or not)
   hvec<uint32_t> mask;         // per row: bit k set = the row has an entry on diagonal k of its block's table
   hvec<double> val;            // absent entries 0.0 (loaded, never added)
   int64_t ndia = 0, ncsr = 0, rows_dia = 0, nseg = 0, nseg_half = 0; // blocks of either kind, rows in diagonal blocks, segments, symmetric ones
@@ -348,7 +362,13 @@ static void dia_parallel_for(int64_t njobs, F &&job)
   work();
   for (auto &t : th) t.join();
 }
-static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const double *va, DiaLayout &L)
+// DDM_SPMV_STAGE_X=0 (read where the layout is built: ddm_op_create, the host entries): no segment stages x (A/B runs, tests)
+static bool dia_stage_x_from_env()
+{
+  const char *e = std::getenv("DDM_SPMV_STAGE_X");
+  return !(e && !std::strcmp(e, "0"));
+}
+static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const double *va, DiaLayout &L, bool stage_x = true)
 {
   L = DiaLayout();
   if (n <= 0 || n >= (int64_t)1 << 30) return; // (row + offset is computed in 32 bits)
@@ -462,21 +482,39 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
     L.nseg_half += S.nlow > 0;
     S.base = slots;
     slots += (S.nd - S.nlow) * (S.r1 - S.r0);
-    int32_t rec[3 * DIA_MAX];
+    DiaSegWindows Wd;
+    int32_t pos[DIA_MAX];
+    for (int k = 0; k < S.nd; ++k) {
+      if (k == 0 || S.off[k] - S.off[k - 1] > WG) Wd.runs.push_back(DiaRun{S.off[k], WG, Wd.window}), Wd.window += WG;
+      else Wd.runs.back().len += S.off[k] - S.off[k - 1], Wd.window += S.off[k] - S.off[k - 1];
+      pos[k] = Wd.runs.back().start + (S.off[k] - Wd.runs.back().first);
+    }
+    // (a staged block computes r0 + first + i, i < len, in 32 bits)
+    Wd.staged = stage_x && Wd.window <= DIA_WIN && n <= ((int64_t)1 << 30) - WG;
+    int32_t rec[DIA_REC] = {};
     for (int k = 0; k < DIA_MAX; ++k) {
       const int q = std::min(k, S.nd - 1);
-      rec[k] = S.off[q];
-      rec[DIA_MAX + k] = q < S.nlow ? S.nd - 1 - q - S.nlow : q - S.nlow; // below the diagonal: the slab of the mirrored offset ...
-      rec[2 * DIA_MAX + k] = q < S.nlow ? S.off[q] : 0;                   // ... at the partner's row
+      rec[DIA_TAB_OFF + k] = S.off[q];
+      rec[DIA_TAB_SLAB + k] = q < S.nlow ? S.nd - 1 - q - S.nlow : q - S.nlow; // below the diagonal: the slab of the mirrored offset ...
+      rec[DIA_TAB_SHIFT + k] = q < S.nlow ? S.off[q] : 0;                      // ... at the partner's row
+      rec[DIA_TAB_POS + k] = Wd.staged ? pos[q] : 0;
     }
-    L.tab.insert(L.tab.end(), rec, rec + 3 * DIA_MAX);
+    rec[DIA_TAB_STAGED] = Wd.staged;
+    for (int j = 0; j < DIA_RUNS; ++j) rec[DIA_TAB_RSTART + j] = DIA_WIN; // (a run that is not there starts behind every window)
+    if (Wd.staged) { // (at most DIA_RUNS runs fit DIA_WIN doubles: each owns at least WG)
+      rec[DIA_TAB_NRUNS] = (int32_t)Wd.runs.size(), rec[DIA_TAB_WINDOW] = Wd.window;
+      for (size_t j = 0; j < Wd.runs.size(); ++j)
+        rec[DIA_TAB_RFIRST + j] = Wd.runs[j].first, rec[DIA_TAB_RLEN + j] = Wd.runs[j].len, rec[DIA_TAB_RSTART + j] = Wd.runs[j].start;
+    }
+    L.tab.insert(L.tab.end(), rec, rec + DIA_REC);
+    L.win.push_back(std::move(Wd));
   }
   L.stored.resize(L.blk.size(), 0);
   for (size_t b = 0; b < L.blk.size(); ++b) {
     if (seg_of[b] < 0) continue;
     const Seg &S = segs[(size_t)seg_of[b]];
     DiaBlock &B = L.blk[b];
-    B.nd = S.nd, B.tab = seg_of[b] * 3 * DIA_MAX;
+    B.nd = S.nd, B.tab = seg_of[b] * DIA_REC;
     B.t0 = (int32_t)(B.r0 - S.r0), B.stride = (int32_t)(S.r1 - S.r0);
     B.base = S.base + B.t0;
     L.stored[b] = S.nd - S.nlow;
@@ -492,7 +530,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
     const int nlow = B.nd - L.stored[(size_t)b];
     double *v = L.val.data() + B.base; // (slab 0, row r0)
     for (int j = 0; j < B.nd - nlow; ++j) std::fill(v + (int64_t)j * B.stride, v + (int64_t)j * B.stride + (B.r1 - B.r0), 0.0);
-    const int32_t *off = L.tab.data() + B.tab;
+    const int32_t *off = L.tab.data() + B.tab + DIA_TAB_OFF;
     for (int64_t r = B.r0; r < B.r1; ++r) {
       uint32_t m = 0;
       int k = 0;
@@ -508,9 +546,17 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
 // y = A x on the host, indexed as k_spmv_dia indexes (CSR-stream blocks: the row sum in column order)
 static void dia_apply_host(const DiaLayout &L, int64_t n, const int64_t *rp, const int32_t *ci, const double *va, const double *x, double *y)
 {
+  std::vector<double> win((size_t)DIA_WIN);
   for (const DiaBlock &B : L.blk) {
     const int nr = B.r1 - B.r0;
-    const int32_t *off = L.tab.data() + B.tab, *slab = off + DIA_MAX, *shift = slab + DIA_MAX;
+    const int32_t *rec = L.tab.data() + B.tab, *off = rec + DIA_TAB_OFF, *slab = rec + DIA_TAB_SLAB, *shift = rec + DIA_TAB_SHIFT, *pos = rec + DIA_TAB_POS;
+    const bool staged = B.nd && rec[DIA_TAB_STAGED];
+    if (staged) { // the block's x windows, as the kernel loads them into LDS (every element written before any is read)
+      std::fill(win.begin(), win.end(), std::numeric_limits<double>::quiet_NaN());
+      for (int j = 0; j < rec[DIA_TAB_NRUNS]; ++j)
+        for (int i = 0; i < rec[DIA_TAB_RLEN + j]; ++i)
+          win.at((size_t)(rec[DIA_TAB_RSTART + j] + i)) = x[std::min<int64_t>(std::max<int64_t>((int64_t)B.r0 + rec[DIA_TAB_RFIRST + j] + i, 0), n - 1)];
+    }
     for (int t = 0; t < nr; ++t) {
       const int r = B.r0 + t;
       double s = 0.0;
@@ -519,7 +565,8 @@ static void dia_apply_host(const DiaLayout &L, int64_t n, const int64_t *rp, con
       else
         for (int k = 0; k < B.nd; ++k) {
           const int64_t at = (int64_t)slab[k] * B.stride + std::min(std::max(B.t0 + t + shift[k], 0), B.stride - 1);
-          const double v = L.val[(size_t)(B.base - B.t0 + at)], xv = x[std::min<int64_t>(std::max<int64_t>(r + off[k], 0), n - 1)];
+          const double v = L.val[(size_t)(B.base - B.t0 + at)];
+          const double xv = staged ? win.at((size_t)(pos[k] + t)) : x[std::min<int64_t>(std::max<int64_t>(r + off[k], 0), n - 1)];
           if ((L.mask[(size_t)r] >> k) & 1u) s += v * xv; // (-ffp-contract=off: product rounded, then added)
         }
       y[r] = s;
@@ -536,11 +583,37 @@ extern "C" int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, co
   for (int64_t z = 0; z < rowptr[n]; ++z)
     if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
   DiaLayout L;
-  dia_build(n, rowptr, col, val, L);
+  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env());
   dia_apply_host(L, n, rowptr, col, val, x, y);
   for (size_t b = 0; kinds_out && b < L.blk.size() && (int64_t)b < max_blocks; ++b)
     kinds_out[4 * b] = L.blk[b].r0, kinds_out[4 * b + 1] = L.blk[b].r1, kinds_out[4 * b + 2] = L.blk[b].nd, kinds_out[4 * b + 3] = L.stored.empty() ? 0 : L.stored[b];
   const int64_t counts[7] = {(int64_t)L.blk.size(), L.ndia, L.ncsr, L.rows_dia, (int64_t)L.val.size(), L.nseg, L.nseg_half};
   std::copy(counts, counts + 7, counts_out);
+  return DDM_OK;
+}
+// host-only entry for the CPU tests: the x windows of the same layout (DDM_SPMV_STAGE_X as above).  segs_out receives, for the first
+// max_segments segments, (staged, runs, window doubles, place of the first run in runs_out); runs_out (first offset, doubles, window
+// position) of the first max_runs runs, segment after segment; counts_out = {segments, runs of all segments, DIA_WIN: the doubles a
+// staged segment's windows may take, WG}.
+extern "C" int ddm_dia_windows_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t max_segments, int32_t *segs_out,
+                                    int64_t max_runs, int32_t *runs_out, int64_t *counts_out)
+{
+  if (n < 0 || !rowptr || !counts_out || (rowptr[n] > 0 && (!col || !val)) || (max_segments > 0 && !segs_out) || (max_runs > 0 && !runs_out)) return DDM_EINVAL;
+  for (int64_t z = 0; z < rowptr[n]; ++z)
+    if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
+  DiaLayout L;
+  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env());
+  int64_t nruns = 0;
+  for (size_t s = 0; s < L.win.size(); ++s) {
+    const DiaSegWindows &W = L.win[s];
+    if ((int64_t)s < max_segments)
+      segs_out[4 * s] = W.staged, segs_out[4 * s + 1] = (int32_t)W.runs.size(), segs_out[4 * s + 2] = W.window, segs_out[4 * s + 3] = (int32_t)nruns;
+    for (const DiaRun &R : W.runs) {
+      if (nruns < max_runs) runs_out[3 * nruns] = R.first, runs_out[3 * nruns + 1] = R.len, runs_out[3 * nruns + 2] = R.start;
+      ++nruns;
+    }
+  }
+  const int64_t counts[4] = {(int64_t)L.win.size(), nruns, DIA_WIN, WG};
+  std::copy(counts, counts + 4, counts_out);
   return DDM_OK;
 }

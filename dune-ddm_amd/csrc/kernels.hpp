@@ -11,6 +11,7 @@ namespace ddm {
 constexpr int WG = 256;          // 4 waves of 64
 constexpr int SPMV_NNZ = 2048;   // non-zeros staged in LDS per workgroup (16 KiB of products)
 constexpr int RED_MAX_BLOCKS = 1024;
+constexpr int RED_TRIPS = 4;     // grid-stride trips of k_dot_partial whose loads are issued together
 
 // bijective XCD-aware remap (cdna_hip_programming.md T1): consecutive work items of one XCD
 // become contiguous, so each XCD's L2 sees one contiguous slab of the matrix / x vector.
@@ -117,8 +118,25 @@ __global__ __launch_bounds__(WG) void k_spmv_stream(const int64_t *__restrict__ 
 // rounded before the sum -- the operations of k_spmv_stream in its order, hence the same bits.  Absent entries are skipped (not
 // added as zero), a stored 0.0 is present.  Blocks that fit no diagonal layout (nd == 0) are CSR-stream blocks of the same
 // launch: a uniform branch per workgroup.  4 waves per SIMD: with more the scheduler interleaves loads and uses to save registers.
+// Build: 87 VGPRs, 74 SGPRs, 0 scratch, 16 416 B LDS.
 constexpr int DIA_MAX = 32;  // diagonals of a block (bits of the mask)
 constexpr int DIA_CH = 16;   // diagonals whose loads are in flight together; DIA_MAX is a multiple
+// Staged blocks (a flag of the segment's record; a third uniform branch): the x entries a block of WG rows reads on neighbouring
+// diagonals overlap -- on a 108-wide box the 27 offsets are three runs of span 218 -- so the workgroup loads each run's window
+// x[r0 + first ... + WG + span) once, coalesced, into the LDS array the CSR-stream branch owns (DIA_WIN doubles; 1 422 of them at
+// 216^3), and thread t reads x[r + off[k]] at win[lds_pos[k] + t]: 28 value + 6 window loads per thread instead of 27 + 27, all
+// issued before the one barrier, and the address unit (busy 85 % of the kernel's time before) handles 21 wavefront loads fewer per
+// 55.  Same products in the same order, so the same bits; window elements outside the vector are clamped (loaded, never added).
+// Segments whose windows exceed DIA_WIN keep the body above.
+constexpr int DIA_WIN = SPMV_NNZ;      // doubles of x windows a staged block may hold: the prod array
+constexpr int DIA_RUNS = DIA_WIN / WG; // runs of a staged segment at most: every run owns at least WG doubles
+// a segment's record in tab: four rows of DIA_MAX (offset, slab, row shift, window position of thread 0), then the staged flag,
+// the run count and the doubles of all windows, then three rows of DIA_RUNS (first offset, doubles, window position of each run)
+constexpr int DIA_TAB_OFF = 0, DIA_TAB_SLAB = DIA_MAX, DIA_TAB_SHIFT = 2 * DIA_MAX, DIA_TAB_POS = 3 * DIA_MAX;
+constexpr int DIA_TAB_STAGED = 4 * DIA_MAX, DIA_TAB_NRUNS = DIA_TAB_STAGED + 1, DIA_TAB_WINDOW = DIA_TAB_STAGED + 2;
+constexpr int DIA_TAB_RFIRST = DIA_TAB_STAGED + 4, DIA_TAB_RLEN = DIA_TAB_RFIRST + DIA_RUNS, DIA_TAB_RSTART = DIA_TAB_RLEN + DIA_RUNS;
+constexpr int DIA_REC = (DIA_TAB_RSTART + DIA_RUNS + 15) / 16 * 16;
+static_assert(DIA_RUNS == 8 && DIA_TAB_RFIRST % 4 == 0, "the run rows are read as two int4 each");
 struct DiaBlock {
   int64_t base;       // slot of (slab 0, row r0) in val
   int32_t r0, r1;     // rows
@@ -150,6 +168,66 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   const int ts = B.t0 + t;
   const double *__restrict__ vs = val + (B.base - B.t0);
   double s = 0.0;
+  const int32_t *__restrict__ rec = tab + B.tab;
+  if (rec[DIA_TAB_STAGED]) {
+    // values first (groups of four behind a uniform test, so that 27 diagonals cost 28 loads)
+    double v[DIA_MAX];
+#pragma unroll
+    for (int k0 = 0; k0 < DIA_MAX; k0 += DIA_CH)
+      if (k0 < B.nd) {
+        int slab[DIA_CH], shift[DIA_CH];
+        dia_load_chunk(rec + DIA_TAB_SLAB + k0, slab);
+        dia_load_chunk(rec + DIA_TAB_SHIFT + k0, shift);
+#pragma unroll
+        for (int g = 0; g < DIA_CH; g += 4)
+          if (k0 + g < B.nd) {
+#pragma unroll
+            for (int u = g; u < g + 4; ++u) v[k0 + u] = vs[(int64_t)slab[u] * B.stride + min(max(ts + shift[u], 0), B.stride - 1)];
+          }
+      }
+    // the windows: element e of the LDS array belongs to the last run that starts at or before e, and is x[r0 + first + (e - start)].
+    // A run is at least WG long, so the WG elements of one trip lie in at most two runs: which two is a scalar computation.
+    const int4 *__restrict__ rq = reinterpret_cast<const int4 *>(rec + DIA_TAB_RFIRST);
+    const int4 f0 = rq[0], f1 = rq[1], s0 = rq[4], s1 = rq[5];
+    const int rfirst[DIA_RUNS] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w}, rstart[DIA_RUNS] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const int nwin = rec[DIA_TAB_WINDOW];
+    double xw[DIA_RUNS];
+#pragma unroll
+    for (int u = 0; u < DIA_RUNS; ++u)
+      if (u * WG < nwin) {
+        int d0 = rfirst[0] - rstart[0], d1 = d0, split = DIA_WIN;
+#pragma unroll
+        for (int j = DIA_RUNS - 1; j >= 1; --j)
+          if (rstart[j] > u * WG) split = rstart[j], d1 = rfirst[j] - rstart[j];
+#pragma unroll
+        for (int j = 1; j < DIA_RUNS; ++j)
+          if (rstart[j] <= u * WG) d0 = rfirst[j] - rstart[j];
+        const int e = u * WG + (int)threadIdx.x;
+        xw[u] = x[min(max(B.r0 + e + (e < split ? d0 : d1), 0), n - 1)];
+      }
+#pragma unroll
+    for (int u = 0; u < DIA_RUNS; ++u)
+      if (u * WG < nwin && u * WG + (int)threadIdx.x < nwin) prod[u * WG + threadIdx.x] = xw[u];
+    __syncthreads();
+#pragma unroll
+    for (int k0 = 0; k0 < DIA_MAX; k0 += DIA_CH)
+      if (k0 < B.nd) {
+        int pos[DIA_CH];
+        dia_load_chunk(rec + DIA_TAB_POS + k0, pos);
+#pragma unroll
+        for (int g = 0; g < DIA_CH; g += 4)
+          if (k0 + g < B.nd) {
+            double w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = prod[pos[g + u] + t];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+              if ((m >> (k0 + g + u)) & 1u) s = __dadd_rn(s, __dmul_rn(v[k0 + g + u], w[u]));
+          }
+      }
+    if ((int)threadIdx.x < nr) y[r] = s;
+    return;
+  }
   for (int k0 = 0; k0 < B.nd; k0 += DIA_CH) {
     // the chunk's offsets, slab numbers and row shifts in three scalar loads (the tables are DIA_MAX long, the tail repeats the last entry)
     int off[DIA_CH], slab[DIA_CH], shift[DIA_CH];
@@ -1150,7 +1228,18 @@ __global__ __launch_bounds__(WG) void k_dot_partial(int64_t n, const uint8_t *__
 {
   __shared__ double red[4];
   double s = 0.0;
-  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+  const int64_t step = (int64_t)gridDim.x * WG;
+  int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x;
+  for (; i + (RED_TRIPS - 1) * step < n; i += RED_TRIPS * step) { // the loads of RED_TRIPS trips in flight, added in trip order
+    double a[RED_TRIPS], b[RED_TRIPS];
+    bool own[RED_TRIPS];
+#pragma unroll
+    for (int u = 0; u < RED_TRIPS; ++u) a[u] = x[i + u * step], b[u] = y[i + u * step], own[u] = !MASKED || mask[i + u * step];
+#pragma unroll
+    for (int u = 0; u < RED_TRIPS; ++u)
+      if (own[u]) s += a[u] * b[u];
+  }
+  for (; i < n; i += step)
     if (!MASKED || mask[i]) s += x[i] * y[i];
   s = block_sum(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;

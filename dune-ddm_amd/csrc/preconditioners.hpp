@@ -101,7 +101,7 @@ extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add
   const char *fmt = std::getenv("DDM_SPMV_FORMAT"); // "csr": keep the CSR-stream product (A/B runs, tests)
   if (!rc && !A->host_only && !(fmt && !std::strcmp(fmt, "csr"))) {
     DiaLayout L;
-    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L);
+    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L, dia_stage_x_from_env()); // DDM_SPMV_STAGE_X=0: no x windows in LDS
     if (L.ndia) {
       if (!rc) rc = upload(ctx, L.blk.data(), (int64_t)L.blk.size(), op->dia_blk);
       if (!rc) rc = upload(ctx, L.tab.data(), (int64_t)L.tab.size(), op->dia_tab);

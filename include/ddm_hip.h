@@ -120,6 +120,14 @@ int ddm_csr_row_order_tiled_host(int64_t nblocks, const int64_t *block_ptr, cons
  * counts_out[7] = {blocks, diagonal blocks, CSR-stream blocks, rows in diagonal blocks, value slots, segments, symmetric segments}. */
 int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, const double *x, double *y,
                                  int64_t max_blocks, int32_t *kinds_out, int64_t *counts_out);
+/* Host only (for tests): the x windows of the same layout.  The ascending offsets of a segment form runs (an offset joins the run of
+ * the one before when they are at most 256 apart); a block reads one window of 256 + (last - first offset) consecutive doubles of x
+ * per run, and a segment whose windows fit the capacity is staged: its blocks load the windows into LDS once (none is with
+ * DDM_SPMV_STAGE_X=0 in the environment, which ddm_op_create reads as well).  segs_out: (staged, runs, window doubles, place of the
+ * first run in runs_out) of the first max_segments segments; runs_out: (first offset, doubles, window position) of the first max_runs
+ * runs, segment after segment; counts_out[4] = {segments, runs, capacity in doubles, rows of a full block}. */
+int ddm_dia_windows_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t max_segments, int32_t *segs_out,
+                         int64_t max_runs, int32_t *runs_out, int64_t *counts_out);
 
 /* ---- local subdomain solver: ILU(0), natural row order ------------------------------------
  * The InverseOperator behind schwarz.hh:57,92,133 for [subdomain_solver] type=loopsolver maxit=1,

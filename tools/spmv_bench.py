@@ -45,7 +45,8 @@ def timed(f):
 
 ms = timed(lambda: A.mv(x, y))
 ms_op = timed(lambda: op.apply(x, yo))
-print(f"operator apply ({os.environ.get('DDM_SPMV_FORMAT', 'diagonal blocks')}) {ms_op:.4f} ms  bit-equal to CsrMatrix.mv: {torch.equal(y.view(torch.int64), yo.view(torch.int64))}")
+staged = "x windows in LDS" if os.environ.get("DDM_SPMV_STAGE_X") != "0" else "x per diagonal (DDM_SPMV_STAGE_X=0)"
+print(f"operator apply ({os.environ.get('DDM_SPMV_FORMAT', 'diagonal blocks, ' + staged)}) {ms_op:.4f} ms bit-equal to CsrMatrix.mv: {torch.equal(y.view(torch.int64), yo.view(torch.int64))}")
 ref = M @ x.cpu().numpy()
 err = np.abs(y.cpu().numpy() - ref).max() / np.abs(ref).max()
 print(f"spmv {ms:.4f} ms  {12.0 * M.nnz / ms / 1e6:.1f} GB/s (12 B per non-zero)  max rel dev vs scipy {err:.2e}")
