@@ -171,6 +171,9 @@ SYMBOLS = {
     "ddm_fgmres_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fgmres_defect_multi": (_I32, [_P, _P, _I32, _P, _P, _P, _I32, _P]),
+    "ddm_fcg_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_fcg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_fcg_orth_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
@@ -811,6 +814,40 @@ def fgmres_defect_multi(ctx: Context, op: NonOverlappingOperator, active, T, B, 
     r = np.zeros(max(m, 1), dtype=np.float64)
     ctx.check(ctx.lib.ddm_fgmres_defect_multi(ctx.h, op.h, m, _hp(act), _ptr(T), _ptr(B), 1 if fused else 0, _hp(r)))
     return r[:m]
+
+
+def fcg_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, mmax=10, complete=False,
+              history=True):
+    """dune-istl RestartedFCGSolver::apply ([solver] type = restartedfcgsolver) or, with complete=True, CompleteFCGSolver::apply
+    (completefcgsolver): flexible CG for a symmetric positive definite operator with a preconditioner that is not symmetric or not
+    fixed; mmax + 1 slots of stored directions; the history holds the TRUE defect norm (ddm_fcg_solve)."""
+    res = SolveResult()
+    hist = np.zeros(maxit + 1, dtype=np.float64) if history else None
+    ctx.check(ctx.lib.ddm_fcg_solve(ctx.h, op.h, prec.h, _ptr(x), _ptr(b), float(reduction), int(maxit), int(mmax), 1 if complete else 0, _hp(hist),
+                                    ctypes.byref(res)))
+    return res, (hist[:res.iterations + 1] if history else None)
+
+
+def fcg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, mmax=10, complete=False,
+                    history=True):
+    """m independent flexible CG recurrences at once (ddm_fcg_solve_multi); all columns share the slot index.  Arguments and return
+    value as gmres_solve_multi."""
+    return _solve_multi(ctx, ctx.lib.ddm_fcg_solve_multi, op, prec, X, B, reduction, maxit, (int(mmax), 1 if complete else 0), history)
+
+
+def fcg_orth_multi(ctx: Context, op: NonOverlappingOperator, active, AD, DS, g, W, fused=True):
+    """one orthogonalisation of ddm_fcg_solve_multi on its own: W (n x m, device, overwritten in the columns with active[c] != 0) against
+    the nslots stored blocks DS / AD (nslots x n x m device tensors, or None with nslots = 0), g: nslots x m host array of <d_k, Ad_k>;
+    returns the nslots x m coefficients <Ad_k, W> / g_k (ddm_fcg_orth_multi)"""
+    m = _ncols(W, W)
+    act = _np(active, np.int32)
+    gh = np.ascontiguousarray(np.asarray(g, dtype=np.float64).reshape(-1, m))
+    nslots = gh.shape[0]
+    assert act.shape == (m,) and (nslots == 0 or (tuple(AD.shape) == tuple(DS.shape) == (nslots,) + tuple(W.shape)))
+    coef = np.zeros((max(nslots, 1), m), dtype=np.float64)
+    ctx.check(ctx.lib.ddm_fcg_orth_multi(ctx.h, op.h, m, nslots, _hp(act), _ptr(AD) if nslots else None, _ptr(DS) if nslots else None,
+                                         _hp(gh) if nslots else None, _ptr(W), 1 if fused else 0, _hp(coef)))
+    return coef[:nslots]
 
 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,

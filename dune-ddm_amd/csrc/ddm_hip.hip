@@ -52,7 +52,7 @@ using namespace ddm;
 #include "geneo.hpp"            // GeneoProblem, GeneoRun, ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, ddm_harmonic (pulls in dense_host.hpp and geneo_blocks.hpp: GeneoWork over geneo_kernels.hpp, ddm_blockvec_*).  Needs csr.hpp, local_solver.hpp.
 #include "halo.hpp"             // ddm_halo: single-vector and m-column exchange over one RCCL wire function.  Needs context.hpp.
 #include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp.
-#include "krylov.hpp"           // CG (begin / steps / defect / solve), GMRES, BiCGSTAB, block CG, block GMRES.  Needs preconditioners.hpp.
+#include "krylov.hpp"           // CG (begin / steps / defect / solve), GMRES, BiCGSTAB, flexible CG, block CG, block GMRES, block flexible CG.  Needs preconditioners.hpp.
 
 // ---- dense host helpers exposed for the CPU tests (host logic of the GenEO Rayleigh-Ritz step) -------------------------
 extern "C" int ddm_dense_sym_eig_host(int n, double *V, double *w) { return dense::sym_eig(n, V, w) ? DDM_OK : DDM_ENUMERIC; }

@@ -1298,6 +1298,92 @@ __global__ void k_cg_direction(int64_t n, const double *__restrict__ scal, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// Flexible CG (ddm_fcg_solve, csrc/krylov.hpp): the orthogonalisation of a fresh direction d against stored slots.
+// The stored vectors of a launch, passed by value: vector j of the set is base + buf[j] * stride.
+constexpr int FCG_SET_MAX = 16;  // entries of one FcgSet (k_fcg_coef, k_fcg_orth and their block forms take that many per launch)
+constexpr int FCG_SG1 = 8;       // slots one pass of k_fcg_project takes (one accumulator each)
+struct FcgSet {
+  int32_t n;
+  int32_t buf[FCG_SET_MAX];
+};
+// Projection: the owner-masked partial sums of <Ad_j, d> for the set.n <= FCG_SG1 stored images of the set in ONE pass over d; the
+// grid, rows per thread, summation order and block_sum of k_dot_partial, so each sum is bit-identical to dot_device(Ad_j, d).
+// partial[(j0 + j) * gridDim.x + b]
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_fcg_project(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ AD, int64_t stride, FcgSet set,
+                                                     int j0, const double *__restrict__ d, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double s[FCG_SG1];
+  const double *a[FCG_SG1];
+#pragma unroll
+  for (int j = 0; j < FCG_SG1; ++j) {
+    s[j] = 0.0;
+    a[j] = AD + (int64_t)set.buf[j < set.n ? j : 0] * stride; // (past the set: a valid address that is never loaded)
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const double di = d[i];
+      double ai[FCG_SG1];
+#pragma unroll
+      for (int j = 0; j < FCG_SG1; ++j) ai[j] = j < set.n ? a[j][i] : 0.0; // every load of the row is issued before the first use
+#pragma unroll
+      for (int j = 0; j < FCG_SG1; ++j) s[j] += ai[j] * di;
+    }
+#pragma unroll
+  for (int j = 0; j < FCG_SG1; ++j) {
+    const double t = block_sum(s[j], red);
+    if (threadIdx.x == 0 && j < set.n) partial[(int64_t)(j0 + j) * gridDim.x + blockIdx.x] = t;
+  }
+}
+// coef[j0 + j] = num[j0 + j] / g[set.buf[j]]: the Gram-Schmidt coefficients <Ad_k, d> / <d_k, Ad_k>, formed on the device
+__global__ void k_fcg_coef(FcgSet set, int j0, const double *__restrict__ num, const double *__restrict__ g, double *__restrict__ coef)
+{
+  const int j = threadIdx.x;
+  if (j < set.n) coef[j0 + j] = num[j0 + j] / g[set.buf[j]];
+}
+// Update: d -= sum_j coef[j0 + j] d_j in one read-modify-write of d, the terms in the order of the set: per entry the operations of
+// set.n launches of k_axpy_negdev, so d is bit-identical to them (the build does not contract a * b + c)
+__global__ __launch_bounds__(WG) void k_fcg_orth(int64_t n, const double *__restrict__ D, int64_t stride, FcgSet set, int j0, const double *__restrict__ coef,
+                                                  double *__restrict__ d)
+{
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    double w = d[i];
+    for (int j = 0; j < set.n; ++j) w -= coef[j0 + j] * D[(int64_t)set.buf[j] * stride + i];
+    d[i] = w;
+  }
+}
+// the owner-masked partial sums of <d, Ad> (partial[b]) and <d, b> (partial[gridDim.x + b]) in one pass over d; each in the summation
+// order of k_dot_partial
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_fcg_dots(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ d, const double *__restrict__ Ad,
+                                                  const double *__restrict__ b, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double sg = 0.0, sb = 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const double di = d[i];
+      sg += di * Ad[i];
+      sb += di * b[i];
+    }
+  sg = block_sum(sg, red);
+  sb = block_sum(sb, red);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = sg;
+    partial[gridDim.x + blockIdx.x] = sb;
+  }
+}
+// g_s = <d, Ad> into its slot and the step alpha = <d, b> / g_s into scal[2], where k_cg_update_norm reads it; dots: the two sums of
+// k_fcg_dots.  g_s == 0 makes the step NaN whatever <d, b> is, so that the driver's NaN test on the defect reports the breakdown.
+__global__ void k_fcg_alpha(const double *__restrict__ dots, double *__restrict__ gslot, double *__restrict__ scal)
+{
+  const double g = dots[0];
+  gslot[0] = g;
+  scal[2] = g == 0.0 ? __builtin_nan("") : dots[1] / g;
+}
+
+// ---------------------------------------------------------------------------------------------
 // K6 coarse restriction d0[(s,j)] = <r_j^s, d_ovlp^s>  (galerkin_preconditioner.hh:165-167):
 // a tall-skinny GEMV.  Work item = (chunk of rows inside one subdomain); wave w of the
 // workgroup handles vectors w, w+4, ...; lanes stride the rows (coalesced).

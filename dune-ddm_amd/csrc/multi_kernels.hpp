@@ -632,4 +632,122 @@ __global__ __launch_bounds__(WG) void k_defect_norm_multi(int64_t n, int m, int 
   }
 }
 
+// ---- flexible CG (ddm_fcg_solve_multi, csrc/krylov.hpp): the orthogonalisation of a fresh direction block against stored slots ---------
+constexpr int FCG_SG = 4; // slots one pass of k_fcg_project_multi takes: FCG_SG x CB accumulators
+// Projection for columns [c0, c0 + CB): the owner-masked partial sums of <Ad_j, d> for the set.n <= FCG_SG stored image blocks of the
+// set (block j at AD + set.buf[j] * stride) in ONE pass over the block d.  The grid, the rows per thread and block_sum are those of
+// k_dot_partial_multi, so every sum is bit-identical to dot_multi_device(Ad_j, d) -- in every column, frozen ones included, as there.
+// partial[((j0 + j) * m + c) * gridDim.x + b]
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_fcg_project_multi(int64_t n, int m, int c0, const uint8_t *__restrict__ mask, const double *__restrict__ AD,
+                                                          int64_t stride, FcgSet set, int j0, const double *__restrict__ d, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double s[FCG_SG][CB];
+  const double *a[FCG_SG];
+#pragma unroll
+  for (int j = 0; j < FCG_SG; ++j) {
+    a[j] = AD + (int64_t)set.buf[j < set.n ? j : 0] * stride; // (past the set: a valid address that is never loaded)
+#pragma unroll
+    for (int u = 0; u < CB; ++u) s[j][u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const int64_t o = i * m + c0;
+      double di[CB];
+#pragma unroll
+      for (int u = 0; u < CB; ++u) di[u] = d[o + u];
+#pragma unroll
+      for (int j = 0; j < FCG_SG; ++j)
+        if (j < set.n) { // (uniform over the grid)
+          double ai[CB];
+#pragma unroll
+          for (int u = 0; u < CB; ++u) ai[u] = a[j][o + u];
+#pragma unroll
+          for (int u = 0; u < CB; ++u) s[j][u] += ai[u] * di[u];
+        }
+    }
+#pragma unroll
+  for (int j = 0; j < FCG_SG; ++j)
+#pragma unroll
+    for (int u = 0; u < CB; ++u) {
+      const double t = block_sum(s[j][u], red);
+      if (threadIdx.x == 0 && j < set.n) partial[((int64_t)(j0 + j) * m + c0 + u) * gridDim.x + blockIdx.x] = t;
+    }
+}
+// coef[(j0 + j) * m + c] = num[(j0 + j) * m + c] / g[set.buf[j] * m + c] in the active columns, 0 in the others (their coefficients are
+// never applied): the Gram-Schmidt coefficients <Ad_k, d> / <d_k, Ad_k>, formed on the device.  One thread per (j, c).
+__global__ void k_fcg_coef_multi(int m, const int32_t *__restrict__ active, FcgSet set, int j0, const double *__restrict__ num, const double *__restrict__ g,
+                                 double *__restrict__ coef)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= set.n * m) return;
+  const int j = t / m, c = t - j * m;
+  coef[(int64_t)(j0 + j) * m + c] = active[c] ? num[(int64_t)(j0 + j) * m + c] / g[(int64_t)set.buf[j] * m + c] : 0.0;
+}
+// Update: d -= sum_j coef_j d_j in the active columns, in one read-modify-write of the block d, the terms in the order of the set: per
+// entry the operations of set.n launches of k_axpy_negdev_multi, so d is bit-identical to them (the build does not contract
+// a * b + c).  A column that is not active is neither read nor written.  One thread per block entry.
+__global__ __launch_bounds__(WG) void k_fcg_orth_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ D, int64_t stride,
+                                                       FcgSet set, int j0, const double *__restrict__ coef, double *__restrict__ d)
+{
+  const int64_t total = n * m;
+  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
+    const int c = (int)(t % m);
+    if (!active[c]) continue;
+    double w = d[t];
+    for (int j = 0; j < set.n; ++j) w -= coef[(int64_t)(j0 + j) * m + c] * D[(int64_t)set.buf[j] * stride + t];
+    d[t] = w;
+  }
+}
+// the owner-masked partial sums of <d, Ad> and <d, b> for columns [c0, c0 + CB) in one pass over d, each in the summation order of
+// k_dot_partial_multi; laid out as in k_dot2_partial_multi: partial[(q * m + c) * gridDim.x + b], q = 0: <d, Ad>, q = 1: <d, b>.
+// Columns that are not active are not read (their partials are 0).
+template <int CB, bool MASKED>
+__global__ __launch_bounds__(WG) void k_fcg_dots_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const uint8_t *__restrict__ mask,
+                                                       const double *__restrict__ d, const double *__restrict__ Ad, const double *__restrict__ b,
+                                                       double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  double sg[CB], sb[CB];
+  bool on[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    on[u] = active[c0 + u] != 0;
+    sg[u] = sb[u] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
+    if (!MASKED || mask[i]) {
+      const int64_t o = i * m + c0;
+#pragma unroll
+      for (int u = 0; u < CB; ++u)
+        if (on[u]) {
+          const double di = d[o + u];
+          sg[u] += di * Ad[o + u];
+          sb[u] += di * b[o + u];
+        }
+    }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const double x = block_sum(sg[u], red);
+    const double y = block_sum(sb[u], red);
+    if (threadIdx.x == 0) {
+      partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = x;
+      partial[(int64_t)(m + c0 + u) * gridDim.x + blockIdx.x] = y;
+    }
+  }
+}
+// per active column: g_s = <d, Ad> into its slot (gslot: m doubles) and the step alpha = <d, b> / g_s into the lambda row of scal,
+// where k_cg_update_norm_multi reads it; dots: the 2 m sums of k_fcg_dots_multi.  g_s == 0 makes the step NaN (see k_fcg_alpha).
+__global__ void k_fcg_alpha_multi(int m, const int32_t *__restrict__ active, const double *__restrict__ dots, double *__restrict__ gslot,
+                                  double *__restrict__ scal)
+{
+  const int c = threadIdx.x;
+  if (c < m && active[c]) {
+    const double g = dots[c];
+    gslot[c] = g;
+    scal[2 * MULTI_MAX + c] = g == 0.0 ? __builtin_nan("") : dots[m + c] / g;
+  }
+}
+
 } // namespace ddm

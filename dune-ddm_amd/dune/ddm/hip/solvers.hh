@@ -127,7 +127,7 @@ public:
   }
 
   // Several right-hand sides at once: x.size() independent solves (1 to 32 columns) in one device loop (HipCGSolver: ddm_cg_solve_multi;
-  // HipRestartedGMResSolver: ddm_gmres_solve_multi; HipRestartedFlexibleGMResSolver: ddm_fgmres_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
+  // HipRestartedGMResSolver: ddm_gmres_solve_multi; HipRestartedFlexibleGMResSolver: ddm_fgmres_solve_multi; HipRestartedFCGSolver / HipCompleteFCGSolver: ddm_fcg_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
   // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  A solver without a block
   // loop (HipBiCGSTABSolver) throws Dune::NotImplemented.
   void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
@@ -219,7 +219,7 @@ protected:
   // the block loop of the solver on row-major n x m device blocks (r: m entries)
   virtual int solve_block(ddm_ctx*, ddm_op*, ddm_combined*, int, double*, double*, double, ddm_solve_result*)
   {
-    DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver, restartedgmressolver and restartedflexiblegmressolver have one)");
+    DUNE_THROW(NotImplemented, "this device Krylov solver has no loop for several right-hand sides (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver and completefcgsolver have one)");
   }
   // the queued loop of the solver: row-major n x ncols device blocks through `width` slots (r: ncols entries)
   virtual int solve_queue(ddm_ctx*, ddm_op*, ddm_combined*, int64_t, int, double*, double*, double, ddm_solve_result*)
@@ -300,6 +300,45 @@ public:
   using HipKrylovSolverBase<X>::apply;
 };
 
+// Flexible CG, restarted or complete: the two solvers below are this class with the variant flag of ddm_fcg_solve / ddm_fcg_solve_multi.
+// For a symmetric positive definite operator with a preconditioner that is not symmetric (restricted Schwarz, the multiplicative
+// combination) or not fixed (ddm_schwarz_set_multi_precision); the TRUE defect is tested; 2 (mmax + 1) vectors per column.
+template <class X, int COMPLETE>
+class HipFCGSolverBase : public HipKrylovSolverBase<X> {
+public:
+  HipFCGSolverBase(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int maxit, int verbose = 0, int mmax = 10)
+      : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), mmax_(mmax) {}
+  HipFCGSolverBase(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
+      : HipFCGSolverBase(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("maxit", 1000), cfg.get("verbose", 0), cfg.get("mmax", 10)) {}
+
+protected:
+  int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_fcg_solve(ctx, o, p, x, b, reduction, this->maxit_, mmax_, COMPLETE, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_fcg_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, mmax_, COMPLETE, nullptr, r);
+  }
+  int mmax_;
+};
+
+// [solver] type = restartedfcgsolver: dune-istl RestartedFCGSolver::apply (mmax: the slots kept, default 10)
+template <class X>
+class HipRestartedFCGSolver : public HipFCGSolverBase<X, 0> {
+public:
+  using HipFCGSolverBase<X, 0>::HipFCGSolverBase; // both constructors
+  using HipKrylovSolverBase<X>::apply;            // (apply_queue throws Dune::NotImplemented: there is no queued flexible CG loop)
+};
+
+// [solver] type = completefcgsolver: dune-istl CompleteFCGSolver::apply -- the window keeps the stale higher slots after a wrap
+template <class X>
+class HipCompleteFCGSolver : public HipFCGSolverBase<X, 1> {
+public:
+  using HipFCGSolverBase<X, 1>::HipFCGSolverBase; // both constructors
+  using HipKrylovSolverBase<X>::apply;
+};
+
 // [solver] type = bicgstabsolver: dune-istl BiCGSTABSolver::apply
 template <class X>
 class HipBiCGSTABSolver : public HipKrylovSolverBase<X> {
@@ -330,8 +369,10 @@ std::shared_ptr<InverseOperator<X, X>> getHipSolver(std::shared_ptr<LinearOperat
   if (type == "cgsolver") return std::make_shared<HipCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "restartedgmressolver") return std::make_shared<HipRestartedGMResSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "restartedflexiblegmressolver") return std::make_shared<HipRestartedFlexibleGMResSolver<X>>(std::move(op), std::move(prec), cfg);
+  if (type == "restartedfcgsolver") return std::make_shared<HipRestartedFCGSolver<X>>(std::move(op), std::move(prec), cfg);
+  if (type == "completefcgsolver") return std::make_shared<HipCompleteFCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "bicgstabsolver") return std::make_shared<HipBiCGSTABSolver<X>>(std::move(op), std::move(prec), cfg);
-  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, bicgstabsolver)");
+  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver, completefcgsolver, bicgstabsolver)");
 }
 
 }  // namespace Dune

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
-               SchwarzPreconditioner, bicgstab_solve_queue, cg_solve, cg_solve_multi, cg_solve_queue, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
+               SchwarzPreconditioner, bicgstab_solve_queue, cg_solve, cg_solve_multi, cg_solve_queue, fcg_solve, fcg_solve_multi, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
 
@@ -272,12 +272,13 @@ class TwoLevelSchwarz:
         return cache[dst][src]
 
     # -- solve -------------------------------------------------------------------------------
-    SOLVERS = ("cgsolver", "restartedgmressolver", "restartedflexiblegmressolver", "bicgstabsolver")
-    SOLVERS_MULTI = SOLVERS[:3]   # (the block BiCGSTAB loop is the queued one: solve_many with M <= width)
+    SOLVERS = ("cgsolver", "restartedgmressolver", "restartedflexiblegmressolver", "restartedfcgsolver", "completefcgsolver", "bicgstabsolver")
+    SOLVERS_MULTI = SOLVERS[:5]   # (the block BiCGSTAB loop is the queued one: solve_many with M <= width)
 
-    def solve(self, reduction=1e-10, maxit=1000, fixed_iterations=0, history=True, x0=None, b=None, solver="cgsolver", restart=100):
+    def solve(self, reduction=1e-10, maxit=1000, fixed_iterations=0, history=True, x0=None, b=None, solver="cgsolver", restart=100, mmax=10):
         """v = 0; solver->apply(v, b, res)  (examples/poisson.cc:318-319).  solver: "cgsolver", "restartedgmressolver",
-        "restartedflexiblegmressolver" or "bicgstabsolver" (the [solver] type keys of dune-istl's solver factory).  Returns (res, hist, x)."""
+        "restartedflexiblegmressolver", "restartedfcgsolver", "completefcgsolver" (flexible CG with mmax + 1 slots) or "bicgstabsolver"
+        (the [solver] type keys of dune-istl's solver factory).  Returns (res, hist, x)."""
         if solver not in self.SOLVERS:
             raise NotImplementedError("solver type '" + str(solver) + "' (" + ", ".join(self.SOLVERS[:-1]) + " and " + self.SOLVERS[-1]
                                       + " are available on the device)")
@@ -285,6 +286,9 @@ class TwoLevelSchwarz:
         bd = self.to_device(self.rl.b if b is None else b)
         if solver == "restartedflexiblegmressolver":
             res, hist = fgmres_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, restart, history)
+            return res, hist, x
+        if solver in ("restartedfcgsolver", "completefcgsolver"):
+            res, hist = fcg_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, mmax, solver == "completefcgsolver", history)
             return res, hist, x
         if solver == "restartedgmressolver":
             res, hist = gmres_solve(self.ctx, self.op, self.prec, x, bd, reduction, maxit, restart, history)
@@ -312,14 +316,15 @@ class TwoLevelSchwarz:
             raise ValueError(f"X0 {tuple(X.shape)} and B {tuple(Bd.shape)} differ")
         return Bd, X
 
-    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100):
+    def solve_multi(self, B=None, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver", restart=100, mmax=10):
         """m right-hand sides at once: m independent CG solves (ddm_cg_solve_multi) or, with solver="restartedgmressolver" /
         "restartedflexiblegmressolver", m independent (flexible) restarted GMRES solves with aligned restart cycles
-        (ddm_gmres_solve_multi / ddm_fgmres_solve_multi), each column as ``solve`` would run it.
+        (ddm_gmres_solve_multi / ddm_fgmres_solve_multi), or, with "restartedfcgsolver" / "completefcgsolver", m independent flexible CG
+        solves that share the slot index (ddm_fcg_solve_multi), each column as ``solve`` would run it.
         B, X0: (n_o, m) arrays or tensors (B=None: the problem's right-hand side as one column).  Returns (list of m SolveResult,
         (iters + 1) x m history or None, X as an (n_o, m) device tensor)."""
         if solver not in self.SOLVERS_MULTI:
-            raise NotImplementedError("solver type '" + str(solver) + "' (of the four device solvers " + ", ".join(self.SOLVERS)
+            raise NotImplementedError("solver type '" + str(solver) + "' (of the six device solvers " + ", ".join(self.SOLVERS)
                                       + ", all but bicgstabsolver are available for several right-hand sides)")
         n_o = self.rl.n_o
         if B is None:
@@ -329,6 +334,8 @@ class TwoLevelSchwarz:
             res, hist = gmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
         elif solver == "restartedflexiblegmressolver":
             res, hist = fgmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, history)
+        elif solver in ("restartedfcgsolver", "completefcgsolver"):
+            res, hist = fcg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, mmax, solver == "completefcgsolver", history)
         else:
             res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
         return res, hist, X
@@ -399,7 +406,7 @@ class TwoLevelSchwarzSolver:
         """solve A z = r to the given reduction (twolevel_schwarz.hh:84-169); returns (SolveResult, history, z)"""
         sol = dict(self.ptree.get("solver", {"type": "restartedgmressolver", "restart": 30, "maxit": 1000}))   # :146-153
         res, hist, z = self.tl.solve(reduction=reduction, maxit=int(sol.get("maxit", 1000)), solver=sol.get("type", "restartedgmressolver"),
-                                     restart=int(sol.get("restart", 30)), b=b)
+                                     restart=int(sol.get("restart", 30)), mmax=int(sol.get("mmax", 10)), b=b)
         self.tl.prec.check_status()
         self.result = res                                                                              # LinearResultStorage (:170-174)
         return res, hist, z

@@ -581,6 +581,49 @@ int ddm_fgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrh
 int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const int32_t *active_host, const double *T, double *B, int fused,
                             double *norm2_host);
 
+/* ---- flexible CG ---------------------------------------------------------------------------------------------------------------
+ * dune-istl RestartedFCGSolver::apply (complete = 0; [solver] type = restartedfcgsolver) and CompleteFCGSolver::apply (complete != 0;
+ * completefcgsolver), DUNE 2.10 solvers.hh, not in the reference snapshot, restated here: CG for a symmetric positive definite
+ * operator with a preconditioner that is not symmetric or not fixed.  Like CG it tests the TRUE defect; it keeps 2 (mmax + 1) vectors.
+ * Slots 0 .. mmax hold a direction d_s, its image Ad_s and g_s = <d_s, Ad_s>; dots and norms are those of ddm_dot / ddm_norm.
+ *   1. b -= A x; def0 = ||b||; hist_host[0] = def0; def0 < 1e-30: converged with 0 iterations, x untouched.
+ *   2. i = 1 (global iteration), s = 0 (slot), klimit = 0; while i <= maxit and not stopped:
+ *        while s <= mmax, i <= maxit and not stopped:
+ *          d_s = M^-1 b (ddm_combined_apply);
+ *          J = {0 .. s - 1} (restarted) or {k < klimit, k != s}, then if (klimit <= s) ++klimit (complete);
+ *          c_k = <Ad_k, d_s> / g_k for every k in J, ALL from the unmodified d_s (classical Gram-Schmidt); d_s -= c_k d_k, k ascending;
+ *          Ad_s = A d_s; g_s = <d_s, Ad_s>; alpha = <d_s, b> / g_s; x += alpha d_s; b -= alpha Ad_s; def = ||b||; hist_host[i] = def;
+ *          stop when def < reduction def0 or def < 1e-30; ++i; ++s.
+ *        end of a pass: slot 0 <-> slot mmax (d, Ad, g) and s = 1 (restarted); s = 0 and klimit = mmax + 1 (complete).
+ *   3. res->iterations = i - 1, res->reduction = def / def0.
+ * The orthogonalisation is two kernels around ONE all-reduce of the |J| numerators: a projection that reads d_s once per 8 slots and
+ * gives every <Ad_k, d_s> bit-identical to ddm_dot, and one read-modify-write of d_s.  alpha and g_s stay on the device; the host reads
+ * one squared defect per iteration.
+ * DDM_EINVAL (before any device work) for NULL pointers, x == b, mmax < 1 or maxit < 0; DDM_ENUMERIC for g_s == 0 or a NaN defect
+ * (g_s == 0 turns the defect into NaN, one message covers both) and when a local solve gave up (ddm_ilu0_peek_status on entry,
+ * ddm_ilu0_status at the end).  Memory: 2 (min(mmax, maxit) + 1) vectors, allocated per call and freed on every return path;
+ * DDM_ENOTIMPL (the byte count is in the message) before anything is allocated when they exceed the free device memory.
+ * hist_host (may be NULL): maxit + 1 doubles. */
+int ddm_fcg_solve(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, double reduction, int maxit, int mmax, int complete,
+                  double *hist_host, ddm_solve_result *res);
+/* nrhs INDEPENDENT ddm_fcg_solve recurrences in one loop (not a block-Krylov method).  All columns share the slot index s and the
+ * window J, which do not depend on data; a column stops on its own test and is then frozen by mask: no kernel writes its x, its column
+ * of B, its g or its history afterwards.  Per iteration: one all-reduce of |J| x nrhs numerators (projection: one pass over d_s per
+ * 4 slots, every sum bit-identical to ddm_dot_multi), one of 2 nrhs (<d, Ad> and <d, b>, one pass), one of nrhs defect norms, and one
+ * read-back of nrhs doubles.  X, B, hist_host ((maxit + 1) x nrhs) and res (nrhs entries) as in ddm_cg_solve_multi; errors and memory
+ * (2 (min(mmax, maxit) + 1) blocks of n x nrhs doubles) as in ddm_fcg_solve, DDM_EINVAL also for nrhs outside 1..32.  With
+ * ddm_schwarz_set_multi_precision(S, 1) the local solves run in single precision; the test is still on the true defect. */
+int ddm_fcg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit, int mmax,
+                        int complete, double *hist_host, ddm_solve_result *res);
+/* One orthogonalisation of ddm_fcg_solve_multi on its own (for tests): the n x nrhs block W against nslots >= 0 stored slots -- DS the
+ * directions and AD their images, nslots consecutive n x nrhs blocks each, g_host[k * nrhs + c] = <d_k, Ad_k>.  In the columns with
+ * active_host[c] != 0: W -= sum_k coef_k d_k with coef_k = <Ad_k, W> / g_k, every coefficient from the W passed in, the terms in
+ * ascending k; the other columns of W are not written.  coef_host (nslots x nrhs) receives the coefficients (0 in the other columns).
+ * fused != 0: the projection and update kernels the driver uses; fused == 0: the composition they replace (the block dot of
+ * ddm_dot_multi per slot on the unmodified W, then one AXPY per slot); the results are bit-identical.  Synchronous. */
+int ddm_fcg_orth_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, int nslots, const int32_t *active_host, const double *AD, const double *DS,
+                       const double *g_host, double *W, int fused, double *coef_host);
+
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,
  * dune/ddm/schwarz.hh:178-181).  Times are HIP-event milliseconds accumulated on the stream. */

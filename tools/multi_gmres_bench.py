@@ -7,14 +7,18 @@ consistent vectors.  For every m of --m the same m right-hand sides are solved (
 once; the sequential time of m columns is the sum over the first m).  Prints a table and one JSON line: RHS-iterations per second of
 both, their ratio, and the per-iteration breakdown of a --profile-iters run with the library's event timers (local solve, coarse level,
 operator, orthogonalisation; the single-vector loop has no orthogonalisation timer: its share is the rest of the wall time).
---solver restartedflexiblegmressolver measures ddm_fgmres_solve_multi / ddm_fgmres_solve instead.  Every row also carries the largest
+--solver restartedflexiblegmressolver measures ddm_fgmres_solve_multi / ddm_fgmres_solve instead; restartedfcgsolver and
+completefcgsolver measure flexible CG with --mmax + 1 slots (ddm_fcg_solve_multi / ddm_fcg_solve), cgsolver the block CG they are
+compared with (ddm_cg_solve_multi / ddm_cg_solve).  The CG family needs a symmetric positive definite operator: --problem poisson (Q1
+Poisson --cells^3, 8 subdomains, ILU(0), restricted Schwarz, POU coarse space, additive, to 1e-10; restricted Schwarz is not symmetric,
+so cgsolver is there for its cost per iteration, not for its convergence).  Every row also carries the largest
 reported and the largest recomputed true reduction ||b - A x|| / ||b|| of its columns and the bytes of the Krylov bases.
 --fused-reps R > 0 adds, at m = 8, R timed repetitions of a --profile-iters long block run with the fused Gram-Schmidt kernel and R
 with DDM_GMRES_MULTI_FUSED=0 (median and spread of both).
 
 The measurement runs in a child process under `timeout -k 10 --step-timeout`; the parent only starts it and passes its exit code on.
 
-    python tools/multi_gmres_bench.py [--problem dg|elasticity] [--m 1,4,8,16] [--fused-reps 5]
+    python tools/multi_gmres_bench.py [--problem dg|elasticity|poisson] [--solver ...] [--mmax 3] [--m 1,4,8,16] [--fused-reps 5]
 """
 from __future__ import annotations
 
@@ -38,16 +42,46 @@ def log(*a):
     print("[multi_gmres_bench]", *a, file=sys.stderr, flush=True)
 
 
+FCG = ("restartedfcgsolver", "completefcgsolver")
+
+
+def solver_name(args):
+    if args.solver in FCG:
+        return f"{'restarted' if args.solver == FCG[0] else 'complete'} flexible CG(mmax = {args.mmax})"
+    if args.solver == "cgsolver":
+        return "CG"
+    return ("flexible GMRES" if args.solver == "restartedflexiblegmressolver" else "GMRES") + f"({args.restart})"
+
+
+def krylov_blocks(args):
+    """n x m blocks the driver keeps next to x and b"""
+    if args.solver in FCG:
+        return 2 * (min(args.mmax, args.maxit) + 1)
+    if args.solver == "cgsolver":
+        return 2
+    return (2 if args.solver == "restartedflexiblegmressolver" else 1) * min(args.restart, args.maxit) + 2
+
+
 def build(args):
     from dune_ddm_amd import synth
     from dune_ddm_amd.geneo import geneo_basis
     from dune_ddm_amd.problem import build_structured
     from dune_ddm_amd.solver import TwoLevelSchwarz
+    if args.problem == "poisson":
+        cells = args.cells or 128
+        grid = synth.StructuredPoisson((cells, cells, cells), (2, 2, 2))
+        dec = build_structured(grid, overlap=2, pou_type="distance")
+        cfg = dict(schwarz_type="restricted", mode="additive", reduction=1e-10)
+        tl = TwoLevelSchwarz(dec, coarse="pou", schwarz_type=cfg["schwarz_type"], mode=cfg["mode"])
+        tl.schwarz.wait_setup()
+        tl.ctx.sync()
+        return dec, tl, cfg, f"Q1 Poisson {cells}^3 = {grid.nglobal} DoF, 8 subdomains (overlap 2), ILU(0), restricted, POU coarse space, additive, {solver_name(args)} to 1e-10"
     if args.problem == "dg":
-        grid = synth.StructuredDG2D((args.cells, args.cells), (4, 2))
+        cells = args.cells or 512
+        grid = synth.StructuredDG2D((cells, cells), (4, 2))
         dec = build_structured(grid, overlap=2, neumann=True)
         cfg = dict(schwarz_type="standard", mode="additive", reduction=1e-8, tol=1e-5, nev=args.nev, local="umfpack")
-        workload = f"Q1-DG convection-diffusion {args.cells}^2 cells = {grid.nglobal} DoF, 8 subdomains (overlap 2), umfpack, GenEO nev {args.nev}, additive"
+        workload = f"Q1-DG convection-diffusion {cells}^2 cells = {grid.nglobal} DoF, 8 subdomains (overlap 2), umfpack, GenEO nev {args.nev}, additive"
     else:
         grid = synth.StructuredElasticity(refine=args.refine, parts=8)
         dec = build_structured(grid, overlap=1, neumann=True, second_region="all")
@@ -58,8 +92,7 @@ def build(args):
     tl.rebuild_combined(cfg["mode"])
     tl.schwarz.wait_setup()
     tl.ctx.sync()
-    name = "flexible GMRES" if args.solver == "restartedflexiblegmressolver" else "GMRES"
-    return dec, tl, cfg, workload + f", {name}({args.restart}) to {cfg['reduction']:g}"
+    return dec, tl, cfg, workload + f", {solver_name(args)} to {cfg['reduction']:g}"
 
 
 def timers_per_iteration(tl, iters):
@@ -71,12 +104,13 @@ def worker(args):
     ge.import_package()
     import torch
     ms_ = sorted({int(v) for v in args.m.split(",")})
+    if args.solver in FCG:
+        TIMERS["orthogonalisation"] = "FCG/orthogonalisation"
     assert all(1 <= m <= 32 for m in ms_)
     t0 = time.perf_counter()
     dec, tl, cfg, workload = build(args)
     log(f"setup {time.perf_counter() - t0:.1f} s, n_o = {tl.rl.n_o}, local engine {tl.schwarz.engine()}")
-    kw = dict(solver=args.solver, restart=args.restart)
-    flexible = args.solver == "restartedflexiblegmressolver"
+    kw = dict(solver=args.solver, restart=args.restart, mmax=args.mmax)
 
     def true_reductions(X, B0):
         """||b - A x|| / ||b|| per column, recomputed"""
@@ -129,7 +163,7 @@ def worker(args):
                "rhs_iterations_per_s": sum(its) / el, "sequential_rhs_iterations_per_s": sum(seq_its) / seq_el,
                "ms_per_block_iteration_by_timer": prof, "reported_reduction_max": max(float(r.reduction) for r in res),
                "true_reduction_max": float(np.max(true_red)),
-               "basis_bytes": ((2 if flexible else 1) * min(args.restart, args.maxit) + 2) * int(tl.rl.n_o) * m * 8}
+               "basis_bytes": krylov_blocks(args) * int(tl.rl.n_o) * m * 8}
         row["ratio"] = row["rhs_iterations_per_s"] / row["sequential_rhs_iterations_per_s"]
         rows.append(row)
         del X
@@ -168,22 +202,25 @@ def worker(args):
         print(f"m = {r['m']}: reported reduction (max over the columns) {r['reported_reduction_max']:.3e}, recomputed true reduction {r['true_reduction_max']:.3e}, "
               f"basis and work blocks {r['basis_bytes'] / 2**20:.1f} MiB")
     out = {"workload": workload, "solver": args.solver, "problem": args.problem, "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "restart": args.restart,
-           "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows, "fused_vs_unfused_m8": fused,
-           "what": "rhs_iterations_per_s = sum of the columns' GMRES iterations / wall time of the solve; sequential = the same columns solved one by one "
-                   "with ddm_gmres_solve; *_by_timer: ms per (block) iteration of a run of profile_iters iterations (reduction 0) with the event timers on"}
+           "mmax": args.mmax if args.solver in FCG else None, "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows, "fused_vs_unfused_m8": fused,
+           "what": "rhs_iterations_per_s = sum of the columns' iterations / wall time of the solve; sequential = the same columns solved one by one "
+                   "with the single-vector driver; *_by_timer: ms per (block) iteration of a run of profile_iters iterations (reduction 0) with the event timers on"}
     print(json.dumps(out))
     tl.ctx.close()
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--problem", default="dg", choices=["dg", "elasticity"])
-    ap.add_argument("--cells", type=int, default=512)
+    ap.add_argument("--problem", default="dg", choices=["dg", "elasticity", "poisson"])
+    ap.add_argument("--cells", type=int, default=None, help="cells per direction (default: dg 512, poisson 128)")
     ap.add_argument("--refine", type=int, default=1)
     ap.add_argument("--nev", type=int, default=16)
     ap.add_argument("--restart", type=int, default=100)
-    ap.add_argument("--solver", default="restartedgmressolver", choices=["restartedgmressolver", "restartedflexiblegmressolver"],
-                    help="restartedflexiblegmressolver: ddm_fgmres_solve(_multi), right-preconditioned, two bases")
+    ap.add_argument("--solver", default="restartedgmressolver",
+                    choices=["restartedgmressolver", "restartedflexiblegmressolver", "restartedfcgsolver", "completefcgsolver", "cgsolver"],
+                    help="restartedflexiblegmressolver: ddm_fgmres_solve(_multi), right-preconditioned, two bases; restartedfcgsolver / completefcgsolver: "
+                         "ddm_fcg_solve(_multi) with --mmax; cgsolver: ddm_cg_solve(_multi)")
+    ap.add_argument("--mmax", type=int, default=10, help="flexible CG: slots 0 .. mmax")
     ap.add_argument("--m", default="1,4,8,16", help="block widths, comma separated (each <= 32)")
     ap.add_argument("--maxit", type=int, default=1000)
     ap.add_argument("--profile-iters", type=int, default=20, help="iterations of the timer runs")
