@@ -91,6 +91,10 @@ def test_ilu0_factor_and_solve(ddm, torch_cuda, trsv_mode, monkeypatch):
     xo = np.zeros(M.shape[0])
     ref.apply(xo, d)
     assert _relerr(xd.cpu().numpy(), xo) < RTOL_VEC
+    # every engine sums a row in ascending column order, each product rounded before it is subtracted -- the oracle's sequential
+    # solve bit for bit (at most 13 entries per triangle row here: no level takes the few-wide-rows branch of the level engine;
+    # tests/test_gpu_trsv_shapes.py holds xcd2 and levels to this on the shapes their kernels branch on)
+    assert np.array_equal(xd.cpu().numpy(), xo)
     assert F.num_levels(False) > 1 and F.num_levels(True) > 1
     with pytest.raises(ddm.DdmError):
         F.solve(dd, dd)                                    # aliasing is rejected
