@@ -454,7 +454,7 @@ static int multi_check(ddm_ctx *ctx, int m, const char *what)
 static int ctx_multi_scratch(ddm_ctx *ctx)
 {
   if (ctx->mscal) return DDM_OK;
-  HIPCHECK(ctx, ctx->mpartial.alloc((int64_t)RED_MAX_BLOCKS * MULTI_MAX * 2)); // (two sums per column in one pass: k_dot2_partial_multi, k_bicg_half2_multi)
+  HIPCHECK(ctx, ctx->mpartial.alloc((int64_t)RED_MAX_BLOCKS * MULTI_MAX * 2)); // (two sums per column in one pass: k_fcg_dots_multi)
   HIPCHECK(ctx, ctx->mactive.alloc(MULTI_MAX));
   HIPCHECK(ctx, ctx->mscal.alloc(std::max(8, BICG_SCALARS) * MULTI_MAX)); // (CG: 6 rows, the scratch of ddm_dot_multi: row 6; queued BiCGSTAB: 13)
   return DDM_OK;

@@ -769,21 +769,10 @@ extern "C" int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
 // general step and the slots need not be aligned.  A column's numbers do not depend on whether it entered at the start or through a
 // refill: both are this one load path.  A breakdown or a NaN in a running column ends the call with DDM_ENUMERIC: the columns stored
 // before keep their results, X[:, j] of the others is as on entry.
-// Vector work per iteration, in passes over n x w doubles (every load and store of a block entry a kernel issues counts 1): the
-// composition of simple kernels (the default) takes 8 + 8 for the first half step and 4 + 6 + 4 for the second: 30.  With
-// DDM_BICGSTAB_QUEUE_FUSED=1 it is direction 4 (p, v, r read, p written), first update with <r, r> 6, <t, t> with <t, r> 2, second
-// update with <r, r> and <rt, r> 7: 19.  h = <rt, v> is the block dot in both (2 more).  Both forms give the same bits (the build
-// does not contract a * b + c).  The composition is the default because it measured faster on MI355X, as for the block GMRES sweep:
-// the kernels that keep the reduction tree of the block dot and skip inactive columns run at a third of the simple kernels' rate
+// Vector work per iteration, in passes over n x w doubles (every load and store of a block entry a kernel issues counts 1): one
+// simple kernel per update and one block dot per sum, 8 + 8 for the first half step and 4 + 6 + 4 for the second: 30, plus the block
+// dot for h = <rt, v> (2 more).  A form with fused update-and-sum kernels (19 passes) was measured slower on MI355X and removed
 // (DESIGN.md section 9).
-static bool bicgstab_queue_fused_env() // read once per process
-{
-  static const bool fused = [] {
-    const char *e = std::getenv("DDM_BICGSTAB_QUEUE_FUSED");
-    return e && e[0] == '1';
-  }();
-  return fused;
-}
 extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
                                         int maxit, double *hist_host, int32_t *nhist, ddm_solve_result *res)
 {
@@ -795,7 +784,6 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
   const int w = width;
   const int64_t n = op->n;
   const double EPS = 1e-80;
-  const bool fused = bicgstab_queue_fused_env();
   for (int64_t j = 0; j < ncols; ++j) solve_result_reset(&res[j]);
   if (nhist) std::fill(nhist, nhist + ncols, 0);
   DDMCHECK(ctx_multi_scratch(ctx));
@@ -813,7 +801,7 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
   double *half1 = scal + BICG_HALF1 * MULTI_MAX, *half2 = scal + BICG_HALF2 * MULTI_MAX, *loaddev = scal + BICG_LOAD * MULTI_MAX, *ttdev = scal + BICG_TT * MULTI_MAX;
   const int32_t *active = ctx->mactive;
   const uint8_t *owner = op->owner;
-  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS), GE = grid_for(n * w);
+  const int GE = grid_for(n * w);
   double rd[4 * MULTI_MAX];
   ddm_solve_result sres[MULTI_MAX]; // the slots' results; a released column's entry is copied to res
   int64_t column[MULTI_MAX], tab[2 * MULTI_MAX];
@@ -846,12 +834,6 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
       f.changed = true;
     }
     return DDM_OK;
-  };
-  // two sums per column from 2 w rows of partials, summed over the ranks in one all-reduce
-  auto finish_pair = [&](double *out, const char *name) -> int {
-    hipLaunchKernelGGL(k_reduce_final_multi, dim3(2 * w), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
-    DDMCHECK(launch_ok());
-    return ctx_allreduce(ctx, out, 2 * w, name);
   };
   // the free slots take the next columns of the queue; leaves the loop mask on the device
   auto refill = [&]() -> int {
@@ -902,28 +884,15 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
   // first half step; leaves <r, r>, h and the operands of the breakdown checks in half1
   auto half_step_1 = [&]() -> int {
     hipLaunchKernelGGL(k_bicg_beta_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal);
-    if (fused) {
-      hipLaunchKernelGGL(k_bicg_direction_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)scal, (const double *)R, (const double *)V, P);
-    } else {
-      axpy(scal + BICG_OMEGA * MULTI_MAX, -1.0, V, P); // p = r + beta (p - omega v)
-      hipLaunchKernelGGL(k_scal_dev_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)(scal + BICG_BETA * MULTI_MAX), P);
-      axpy(nullptr, 1.0, R, P);
-    }
+    axpy(scal + BICG_OMEGA * MULTI_MAX, -1.0, V, P); // p = r + beta (p - omega v)
+    hipLaunchKernelGGL(k_scal_dev_multi, dim3(GE), dim3(WG), 0, ctx->stream, n, w, active, (const double *)(scal + BICG_BETA * MULTI_MAX), P);
+    axpy(nullptr, 1.0, R, P);
     DDMCHECK(launch_ok());
     DDMCHECK(combined_apply_multi_impl(ctx, prec, w, Y, P));          // y = W^-1 p
     DDMCHECK(op_apply_multi(ctx, op, w, Y, V));                       // v = A y
     DDMCHECK(dot_multi_device(ctx, n, owner, w, RT, V, half1 + w));   // h = <rt, v>
     hipLaunchKernelGGL(k_bicg_alpha_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal); // alpha = rho_new / h
-    if (fused) { // x += alpha y; r -= alpha v; <r, r>
-      for_column_groups(w, [&](int c0, int cb) {
-        DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, (const double *)scal, BICG_ALPHA,
-                              owner, (const double *)Y, (const double *)V, XW, R, ctx->mpartial);
-      });
-      hipLaunchKernelGGL(k_reduce_final_multi, dim3(w), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, half1);
-      DDMCHECK(launch_ok());
-      return ctx_allreduce(ctx, half1, w, "defect norms");
-    }
-    axpy(scal + BICG_ALPHA * MULTI_MAX, 1.0, Y, XW);
+    axpy(scal + BICG_ALPHA * MULTI_MAX, 1.0, Y, XW); // x += alpha y; r -= alpha v; <r, r>
     axpy(scal + BICG_ALPHA * MULTI_MAX, -1.0, V, R);
     DDMCHECK(launch_ok());
     return dot_multi_device(ctx, n, owner, w, R, R, half1);
@@ -932,25 +901,10 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
   auto half_step_2 = [&]() -> int {
     DDMCHECK(combined_apply_multi_impl(ctx, prec, w, Y, R));          // y = W^-1 r
     DDMCHECK(op_apply_multi(ctx, op, w, Y, T));                       // t = A y
-    if (fused) {
-      for_column_groups(w, [&](int c0, int cb) {
-        DDM_MULTI_CB_DISPATCH(k_dot2_partial_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, owner, (const double *)T,
-                              (const double *)R, ctx->mpartial);
-      });
-      DDMCHECK(finish_pair(ttdev, "scalar products"));
-    } else {
-      DDMCHECK(dot_multi_device(ctx, n, owner, w, T, T, ttdev));
-      DDMCHECK(dot_multi_device(ctx, n, owner, w, T, R, ttdev + w));
-    }
+    DDMCHECK(dot_multi_device(ctx, n, owner, w, T, T, ttdev));
+    DDMCHECK(dot_multi_device(ctx, n, owner, w, T, R, ttdev + w));
     hipLaunchKernelGGL(k_bicg_omega_multi, dim3(1), dim3(64), 0, ctx->stream, w, active, scal); // omega = <t, r> / <t, t>; rho = rho_new
-    if (fused) { // x += omega y; r -= omega t; <r, r> and <rt, r>
-      for_column_groups(w, [&](int c0, int cb) {
-        DDM_MULTI_CB_DISPATCH(k_bicg_half2_multi, owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, w, c0, active, (const double *)scal, owner,
-                              (const double *)Y, (const double *)T, (const double *)RT, XW, R, ctx->mpartial);
-      });
-      return finish_pair(half2, "defect norms");
-    }
-    axpy(scal + BICG_OMEGA * MULTI_MAX, 1.0, Y, XW);
+    axpy(scal + BICG_OMEGA * MULTI_MAX, 1.0, Y, XW); // x += omega y; r -= omega t; <r, r> and <rt, r>
     axpy(scal + BICG_OMEGA * MULTI_MAX, -1.0, T, R);
     DDMCHECK(launch_ok());
     DDMCHECK(dot_multi_device(ctx, n, owner, w, R, R, half2));
@@ -1015,9 +969,9 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
 // while the operator, the preconditioner and the orthogonalisation sweep run once for all columns.  Restart cycles are aligned.  A
 // basis is min(restart, maxit) blocks (V: one more) of n x m doubles, row-major.  Per basis block the sweep is one AXPY over the
 // block with the coefficients in device memory, the block dot (one kernel per column group, k_reduce_final_multi) and one all-reduce
-// of m doubles; with DDM_GMRES_MULTI_FUSED=1 the AXPY and the partial sums of the next dot are one kernel (k_mgs_step_multi:
-// bit-identical, 32 instead of 40 bytes per block entry, but measured slower on MI355X -- DESIGN.md section 9).  The host reads the
-// (i + 2) x m fresh Hessenberg entries once per iteration and nothing else synchronises inside an iteration.
+// of m doubles (a kernel that fused the AXPY with the partial sums of the next dot was measured slower on MI355X and removed,
+// DESIGN.md section 9).  The host reads the (i + 2) x m fresh Hessenberg entries once per iteration and nothing else synchronises
+// inside an iteration.
 //
 // Frozen columns: a column that passed its test is masked out (ctx->mactive) of every kernel of the loop; the operator and the
 // preconditioner still run on its (stale) basis entries, whose results nobody reads.  The flexible variant writes V through the mask
@@ -1029,38 +983,20 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
 // pass; frozen columns of B untouched).
 
 // the sweep of iteration i: hdev[k * m + c] = h_{k,i} of column c for k <= i, hdev[(i + 1) * m + c] = <w, w>; w orthogonalised in place
-static int gmres_mgs_multi(ddm_ctx *ctx, ddm_op *op, int m, int i, bool fused, const double *V, int64_t vstride, double *W, double *hdev)
+static int gmres_mgs_multi(ddm_ctx *ctx, ddm_op *op, int m, int i, const double *V, int64_t vstride, double *W, double *hdev)
 {
   ScopedTimer t(ctx, "GMRES/orthogonalisation");
   const int64_t n = op->n;
-  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
   const int32_t *active = ctx->mactive;
   DDMCHECK(dot_multi_device(ctx, n, op->owner, m, V, W, hdev)); // h_0 = <v_0, w>
   for (int k = 0; k <= i; ++k) {
     const double *vk = V + (int64_t)k * vstride;
     const double *z = k < i ? V + (int64_t)(k + 1) * vstride : W; // next dot: <v_{k+1}, w>, or <w, w> at the end
     double *out = hdev + (int64_t)(k + 1) * m;
-    if (!fused) {
-      hipLaunchKernelGGL(k_axpy_negdev_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, active, (const double *)(hdev + (int64_t)k * m), vk, W);
-      DDMCHECK(dot_multi_device(ctx, n, op->owner, m, z, W, out));
-      continue;
-    }
-    for_column_groups(m, [&](int c0, int cb) {
-      DDM_MULTI_CB_DISPATCH(k_mgs_step_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, active,
-                            (const double *)(hdev + (int64_t)k * m), (const uint8_t *)op->owner, vk, z, W, ctx->mpartial);
-    });
-    hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, out);
-    HIPCHECK(ctx, hipGetLastError());
-    DDMCHECK(ctx_allreduce(ctx, out, m, "Gram-Schmidt coefficients"));
+    hipLaunchKernelGGL(k_axpy_negdev_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, active, (const double *)(hdev + (int64_t)k * m), vk, W);
+    DDMCHECK(dot_multi_device(ctx, n, op->owner, m, z, W, out));
   }
   return DDM_OK;
-}
-
-// DDM_GMRES_MULTI_FUSED, read once per solve; the unfused composition is the default (it measured faster)
-static bool gmres_multi_fused_env()
-{
-  const char *e = std::getenv("DDM_GMRES_MULTI_FUSED");
-  return e && e[0] == '1';
 }
 
 // The restart step on its own, for tests: B -= T in the columns with active_host[c] != 0, norm2_host[c] = <B_c, B_c> of every column
@@ -1098,7 +1034,6 @@ static int gmres_loop_multi(ddm_ctx *ctx, const char *what, bool flexible, ddm_o
   const int64_t vstride = std::max<int64_t>(n, 1) * m;
   const int R = std::min(restart, std::max(maxit, 1)); // a cycle never gets longer than maxit iterations: no basis block beyond that
   DDMCHECK(gmres_memory_check(ctx, what, (flexible ? 2 : 1) * (int64_t)R + 2, n, m));
-  const bool fused = gmres_multi_fused_env();
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
   dbuf<double> Vb, Zb, Wb, hdev, ydev;
@@ -1150,7 +1085,7 @@ static int gmres_loop_multi(ddm_ctx *ctx, const char *what, bool flexible, ddm_o
         rc = op_apply_multi(ctx, op, m, v(i), v(i + 1));                      // v[i+1] = A v[i] (temporary)
         if (!rc) rc = combined_apply_multi_impl(ctx, prec, m, W, v(i + 1));   // w = M^-1 A v[i]
       }
-      if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, fused, V, vstride, W, hdev);
+      if (!rc) rc = gmres_mgs_multi(ctx, op, m, i, V, vstride, W, hdev);
       if (!rc) rc = ddm_memcpy_d2h(ctx, hcol.data(), hdev, sizeof(double) * (size_t)(i + 2) * m); // the one read-back of the iteration
       if (rc) break;
       for (int c = 0; c < m && !rc; ++c) {

@@ -235,7 +235,7 @@ __global__ void k_cg_direction_multi(int64_t n, int m, const int32_t *__restrict
 }
 // x += lambda p; b -= lambda q; partial sums of <b, b> for columns [c0, c0 + CB) -- k_cg_update_norm per column (same grid, rows per
 // thread and block_sum).  Columns that are not active are neither read nor written (their partials are 0).  lambda_c is
-// scal[slot * MULTI_MAX + c]: slot 2 in the CG drivers, the alpha slot in the first half step of the queued BiCGSTAB.
+// scal[slot * MULTI_MAX + c]: slot 2 in the CG drivers.
 template <int CB, bool MASKED>
 __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
                                                              int slot, const uint8_t *__restrict__ mask, const double *__restrict__ p, const double *__restrict__ q,
@@ -304,7 +304,7 @@ __global__ void k_column_store_multi(int64_t n, int m, int nstore, const int64_t
 
 // ---- queued BiCGSTAB (ddm_bicgstab_solve_queue, csrc/krylov.hpp) -----------------------------------------------------------------------
 // Per-column scalars in ctx->mscal, M = MULTI_MAX: [0..M) rho, [M..2M) alpha, [2M..3M) omega, [3M..4M) beta.  The sums the host
-// reads are packed at stride m (the block width), so that one all-reduce and one copy take a group of them:
+// reads are packed at stride m (the block width), so that one copy takes a group of them:
 //   first half step   [4M..): <r, r>, then h = <rt, v>, then the rho and the omega that the direction update used (4 m doubles)
 //   second half step  [8M..): <r, r>, then rho_new = <rt, r> of the next iteration (2 m doubles)
 //   refill            [10M..): <r, r> of the loaded slots;  [11M..): <t, t>, then <t, r> (2 m doubles)
@@ -337,101 +337,6 @@ __global__ void k_bicg_omega_multi(int m, const int32_t *__restrict__ active, do
   if (c < m && active[c]) {
     scal[BICG_OMEGA * MULTI_MAX + c] = scal[BICG_TT * MULTI_MAX + m + c] / scal[BICG_TT * MULTI_MAX + c];
     scal[BICG_RHO * MULTI_MAX + c] = scal[BICG_HALF2 * MULTI_MAX + m + c];
-  }
-}
-// p = r + beta (p - omega v) in the active columns, evaluated as the single-vector driver does with three kernels
-// (p += (-omega) v; p *= beta; p += r): with p = v = 0 the result is r exactly, whatever beta and omega are (finite)
-__global__ void k_bicg_direction_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ scal, const double *__restrict__ r,
-                                       const double *__restrict__ v, double *__restrict__ p)
-{
-  const int64_t total = n * m;
-  for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
-    const int c = (int)(t % m);
-    if (active[c]) {
-      double pi = p[t] + -scal[BICG_OMEGA * MULTI_MAX + c] * v[t];
-      pi *= scal[BICG_BETA * MULTI_MAX + c];
-      p[t] = pi + r[t];
-    }
-  }
-}
-// partial sums of <t, t> and <t, r> for columns [c0, c0 + CB) in one pass: the grid, rows per thread and block_sum of
-// k_dot_partial_multi, so both sums are bit-identical to two launches of it.  partial[(q * m + c) * gridDim.x + b], q = 0: <t, t>,
-// q = 1: <t, r>.  Columns that are not active are not read (their partials are 0).
-template <int CB, bool MASKED>
-__global__ __launch_bounds__(WG) void k_dot2_partial_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const uint8_t *__restrict__ mask,
-                                                           const double *__restrict__ t, const double *__restrict__ r, double *__restrict__ partial)
-{
-  __shared__ double red[4];
-  double stt[CB], str[CB];
-  bool on[CB];
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    on[u] = active[c0 + u] != 0;
-    stt[u] = str[u] = 0.0;
-  }
-  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG)
-    if (!MASKED || mask[i]) {
-      const int64_t o = i * m + c0;
-#pragma unroll
-      for (int u = 0; u < CB; ++u)
-        if (on[u]) {
-          const double ti = t[o + u];
-          stt[u] += ti * ti;
-          str[u] += ti * r[o + u];
-        }
-    }
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    const double a = block_sum(stt[u], red);
-    const double b = block_sum(str[u], red);
-    if (threadIdx.x == 0) {
-      partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = a;
-      partial[(int64_t)(m + c0 + u) * gridDim.x + blockIdx.x] = b;
-    }
-  }
-}
-// Second half step for columns [c0, c0 + CB): x += omega y; r -= omega t; partial sums of <r, r> and of <rt, r> (the next iteration's
-// rho_new) for the updated r, in one pass.  Vectors and sums are bit-identical to two AXPYs followed by k_dot_partial_multi(r, r) and
-// k_dot_partial_multi(rt, r); the partials are laid out as in k_dot2_partial_multi (q = 0: <r, r>, q = 1: <rt, r>).  Columns that are
-// not active are neither read nor written (their partials are 0).
-template <int CB, bool MASKED>
-__global__ __launch_bounds__(WG) void k_bicg_half2_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
-                                                         const uint8_t *__restrict__ mask, const double *__restrict__ y, const double *__restrict__ t,
-                                                         const double *__restrict__ rt, double *__restrict__ x, double *__restrict__ r,
-                                                         double *__restrict__ partial)
-{
-  __shared__ double red[4];
-  double om[CB], srr[CB], srt[CB];
-  bool on[CB];
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    on[u] = active[c0 + u] != 0;
-    om[u] = scal[BICG_OMEGA * MULTI_MAX + c0 + u];
-    srr[u] = srt[u] = 0.0;
-  }
-  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
-    const int64_t o = i * m + c0;
-    const bool own = !MASKED || mask[i];
-#pragma unroll
-    for (int u = 0; u < CB; ++u)
-      if (on[u]) {
-        x[o + u] += om[u] * y[o + u];
-        const double ri = r[o + u] - om[u] * t[o + u];
-        r[o + u] = ri;
-        if (own) {
-          srr[u] += ri * ri;
-          srt[u] += rt[o + u] * ri;
-        }
-      }
-  }
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    const double a = block_sum(srr[u], red);
-    const double b = block_sum(srt[u], red);
-    if (threadIdx.x == 0) {
-      partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = a;
-      partial[(int64_t)(m + c0 + u) * gridDim.x + blockIdx.x] = b;
-    }
   }
 }
 // Load of a BiCGSTAB slot (tab as in k_column_load_multi): x_slot = X[:, column], r_slot = B[:, column], p_slot = v_slot = 0 and
@@ -468,8 +373,8 @@ __global__ void k_bicg_shadow_multi(int64_t n, int m, const int32_t *__restrict_
   for (int64_t t = gid; t < total; t += (int64_t)gridDim.x * WG)
     if (active[t % m]) rt[t] = r[t];
 }
-// the composition of simple kernels (the default; DDM_BICGSTAB_QUEUE_FUSED=1 selects the fused kernels above), one per update: y += sign coef_c x (coef null: 1) and y *= coef_c
-// in the active columns, one thread per block entry
+// the vector updates, one simple kernel each: y += sign coef_c x (coef null: 1) and y *= coef_c in the active columns, one thread per
+// block entry
 __global__ void k_axpy_dev_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ coef, double sign,
                                  const double *__restrict__ x, double *__restrict__ y)
 {
@@ -493,52 +398,8 @@ __global__ void k_scal_dev_multi(int64_t n, int m, const int32_t *__restrict__ a
 struct MultiCoef {
   double a[MULTI_MAX];
 };
-// One modified Gram-Schmidt step for columns [c0, c0 + CB): w -= h v with the coefficients h (m device doubles, already summed over
-// the ranks), and in the same pass the owner-masked partial sums of <z, w> for the updated w (z = the next basis block, or z = w for
-// the norm that ends the sweep).  The grid, the rows per thread and block_sum are those of k_dot_partial_multi and the build does not
-// contract a * b + c, so w and the partials are bit-identical to k_axpy_negdev_multi followed by k_dot_partial_multi.  Columns that
-// are not active are neither read nor written (their partials are 0).
-template <int CB, bool MASKED>
-__global__ __launch_bounds__(WG) void k_mgs_step_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ h,
-                                                       const uint8_t *__restrict__ mask, const double *__restrict__ v, const double *z,
-                                                       double *w, double *__restrict__ partial)
-{
-  __shared__ double red[4];
-  double hk[CB], s[CB];
-  bool on[CB];
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    on[u] = active[c0 + u] != 0;
-    hk[u] = h[c0 + u];
-    s[u] = 0.0;
-  }
-  const bool norm = z == w;
-  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
-    const int64_t o = i * m + c0;
-    const bool own = !MASKED || mask[i];
-    double wi[CB], vi[CB], zi[CB];
-#pragma unroll
-    for (int u = 0; u < CB; ++u) { // every load of the row is issued before the first use
-      wi[u] = on[u] ? w[o + u] : 0.0;
-      vi[u] = on[u] ? v[o + u] : 0.0;
-      zi[u] = on[u] && !norm ? z[o + u] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < CB; ++u)
-      if (on[u]) {
-        const double t = wi[u] - hk[u] * vi[u];
-        w[o + u] = t;
-        if (own) s[u] += (norm ? t : zi[u]) * t;
-      }
-  }
-#pragma unroll
-  for (int u = 0; u < CB; ++u) {
-    const double t = block_sum(s[u], red);
-    if (threadIdx.x == 0) partial[(int64_t)(c0 + u) * gridDim.x + blockIdx.x] = t;
-  }
-}
-// the unfused step (the default; DDM_GMRES_MULTI_FUSED=1 selects k_mgs_step_multi): k_axpy_negdev on every active column, one thread
-// per block entry
+// The update of one modified Gram-Schmidt step, w -= h v with the coefficients h (m device doubles, already summed over the ranks):
+// k_axpy_negdev on every active column, one thread per block entry
 __global__ void k_axpy_negdev_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ h, const double *__restrict__ v,
                                     double *__restrict__ w)
 {
@@ -701,7 +562,7 @@ __global__ __launch_bounds__(WG) void k_fcg_orth_multi(int64_t n, int m, const i
   }
 }
 // the owner-masked partial sums of <d, Ad> and <d, b> for columns [c0, c0 + CB) in one pass over d, each in the summation order of
-// k_dot_partial_multi; laid out as in k_dot2_partial_multi: partial[(q * m + c) * gridDim.x + b], q = 0: <d, Ad>, q = 1: <d, b>.
+// k_dot_partial_multi; partial[(q * m + c) * gridDim.x + b] holds block b's sum for column c, q = 0: <d, Ad>, q = 1: <d, b>.
 // Columns that are not active are not read (their partials are 0).
 template <int CB, bool MASKED>
 __global__ __launch_bounds__(WG) void k_fcg_dots_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const uint8_t *__restrict__ mask,

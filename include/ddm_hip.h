@@ -533,9 +533,7 @@ int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t nco
  * plain block solve.  hist_host: (2 maxit + 1) x ncols, row-major, or NULL -- row k of column j is its defect after its own k-th
  * half step, rows a column never reaches are left as passed; nhist (may be NULL): entries written per column.  A breakdown (the
  * checks of ddm_bicgstab_solve on rho, omega and h) or a NaN in a running column ends the call with DDM_ENUMERIC, the message naming
- * the column and the scalar: the columns stored before keep their results, X[:, j] of the others is as on entry.
- * DDM_BICGSTAB_QUEUE_FUSED (read once per process): 1 selects the fused vector kernels, 0 or unset the composition of simple kernels
- * (the default: it measured faster); the results are bit-identical. */
+ * the column and the scalar: the columns stored before keep their results, X[:, j] of the others is as on entry. */
 int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64_t ncols, int width, double *X, double *B, double reduction,
                              int maxit, double *hist_host, int32_t *nhist, ddm_solve_result *res);
 /* nrhs INDEPENDENT dune-istl RestartedGMResSolver::apply recurrences in one loop (the loop of ddm_gmres_solve per column: left
@@ -555,15 +553,14 @@ int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int64
  *     every return path.  When that exceeds the free device memory the call returns DDM_ENOTIMPL (the byte count is in the message)
  *     before it allocates anything.
  *   Host traffic: one read-back per iteration (the (i + 2) x nrhs fresh Hessenberg entries); the dots of one orthogonalisation step
- *     travel as one all-reduce of nrhs doubles.  DDM_GMRES_MULTI_FUSED in the environment (read once per call): 0 (the default) runs every
- *     orthogonalisation step as an AXPY and a separate dot, 1 as one fused kernel; the results are bit-identical. */
+ *     travel as one all-reduce of nrhs doubles. */
 int ddm_gmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                           int restart, double *hist_host, ddm_solve_result *res);
 /* nrhs INDEPENDENT ddm_fgmres_solve recurrences in one loop (flexible restarted GMRES: right preconditioning, the true defect is
  * monitored; not a block-Krylov method), under every rule of ddm_gmres_solve_multi: aligned restart cycles; a column stops on its own
  * test and is then frozen by mask (its x, history, res entry and column of B do not change any more; it is never multiplied by a zero
  * coefficient); one read-back of the (i + 2) x nrhs fresh Hessenberg entries per iteration; one all-reduce of nrhs doubles per
- * orthogonalisation step (DDM_GMRES_MULTI_FUSED as there); DDM_EINVAL before any device work for nrhs outside 1..32, restart < 1,
+ * orthogonalisation step; DDM_EINVAL before any device work for nrhs outside 1..32, restart < 1,
  * maxit < 0, NULL pointers or X == B; DDM_ENUMERIC, naming column and iteration, for a NaN norm or |w| == 0 in an active column and
  * when a local solve gave up.  X, B, hist_host ((maxit + 1) x nrhs) and res as in ddm_cg_solve_multi.
  *   Memory: two bases, min(restart, maxit) + 1 and min(restart, maxit) blocks of n x nrhs doubles, plus one work block -- twice what

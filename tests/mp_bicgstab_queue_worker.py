@@ -1,12 +1,7 @@
-"""Worker of tests/test_gpu_bicgstab_queue.py, two modes.
-
-  ranks            launched by torch.distributed.run (backend gloo): the ranks share cuda:0 and exchange through the alltoall /
-                   allreduce callbacks.  M = 6 right-hand sides through w = 4 BiCGSTAB slots (ddm_bicgstab_solve_queue): the halo blocks
-                   go column by column through the callback, the pairs of sums of one half step in one all-reduce of 2 w doubles.
-                   Rank 0 compares with the same call on a single-rank context and prints BICGSTAB_QUEUE_RANKS_OK <world>.
-  dump <out.npz>   a fresh single process (the environment switch DDM_BICGSTAB_QUEUE_FUSED is read by the library, once, from ITS
-                   environment): queued solves with w = 1, 3, 8, 13 slots and M = w + 2 columns on the two problems of the test,
-                   iterations, histories and solutions written to <out.npz> for a bitwise comparison by the parent."""
+"""Worker of tests/test_gpu_bicgstab_queue.py, launched by torch.distributed.run (backend gloo): the ranks share cuda:0 and exchange
+through the alltoall / allreduce callbacks.  M = 6 right-hand sides through w = 4 BiCGSTAB slots (ddm_bicgstab_solve_queue): the halo
+blocks go column by column through the callback, the sums of one block dot in one all-reduce of w doubles.  Rank 0 compares with the
+same call on a single-rank context and prints BICGSTAB_QUEUE_RANKS_OK <world>.  The test module takes its two problems from here."""
 import os
 import sys
 
@@ -20,7 +15,6 @@ ge.import_package()
 from dune_ddm_amd import synth  # noqa: E402
 from dune_ddm_amd.problem import build_structured  # noqa: E402
 
-DUMP_W = (1, 3, 8, 13)
 RED, MAXIT = 1e-9, 200
 CONFIGS = {
     "poisson": dict(schwarz_type="restricted", mode="multiplicative", subdomain_solver="ilu0"),     # non-symmetric preconditioner
@@ -85,26 +79,5 @@ def ranks():
     dist.destroy_process_group()
 
 
-def dump(path):
-    from dune_ddm_amd.solver import TwoLevelSchwarz
-    out = {}
-    for name, kw in CONFIGS.items():
-        dec = decomposition(name)
-        tl = TwoLevelSchwarz(dec, coarse="pou", **kw)
-        for w in DUMP_W:
-            res, hist, X = tl.solve_many(rhs_block(dec, tl, w + 2, seed=60 + w), width=w, reduction=RED, maxit=MAXIT, solver="bicgstabsolver")
-            assert all(r.converged for r in res), (name, w)
-            out[f"{name}_hist{w}"] = hist
-            out[f"{name}_x{w}"] = X.cpu().numpy()
-            out[f"{name}_it{w}"] = np.array([r.iterations for r in res])
-        tl.prec.check_status()
-        tl.ctx.close()
-    np.savez(path, **out)
-    print("BICGSTAB_QUEUE_DUMP_OK", os.environ.get("DDM_BICGSTAB_QUEUE_FUSED", "(unset)"), flush=True)
-
-
 if __name__ == "__main__":
-    if sys.argv[1] == "ranks":
-        ranks()
-    else:
-        dump(sys.argv[2])
+    ranks()

@@ -1,12 +1,7 @@
-"""Worker of tests/test_gpu_multi_gmres.py, two modes.
-
-  ranks            launched by torch.distributed.run (backend gloo): the ranks share cuda:0 (`levels` engine) and exchange through the
-                   alltoall / allreduce callbacks.  Block GMRES with m = 4 right-hand sides (ddm_gmres_solve_multi): the halo blocks go
-                   column by column through the callback, the Gram-Schmidt coefficients of one step in one all-reduce of m doubles.
-                   Rank 0 compares with the same block solve on a single-rank context and prints MULTI_GMRES_RANKS_OK <world>.
-  dump <out.npz>   a fresh single process (the environment switch DDM_GMRES_MULTI_FUSED is read by the library from ITS environment):
-                   block solves for m = 1, 3, 8, 13 on the restricted multiplicative Poisson configuration, histories and solutions
-                   written to <out.npz> for a bitwise comparison by the parent."""
+"""Worker of tests/test_gpu_multi_gmres.py, launched by torch.distributed.run (backend gloo): the ranks share cuda:0 (`levels` engine)
+and exchange through the alltoall / allreduce callbacks.  Block GMRES with m = 4 right-hand sides (ddm_gmres_solve_multi): the halo
+blocks go column by column through the callback, the Gram-Schmidt coefficients of one step in one all-reduce of m doubles.  Rank 0
+compares with the same block solve on a single-rank context and prints MULTI_GMRES_RANKS_OK <world>."""
 import os
 import sys
 
@@ -20,7 +15,6 @@ ge.import_package()
 from dune_ddm_amd import synth  # noqa: E402
 from dune_ddm_amd.problem import build_structured  # noqa: E402
 
-DUMP_M = (1, 3, 8, 13)
 TOL_REL, TOL_ABS = 1e-7, 1e-11     # |h - h'| <= 1e-7 |r_k| + 1e-11 |r_0| for GMRES histories
 
 
@@ -80,25 +74,5 @@ def ranks():
     dist.destroy_process_group()
 
 
-def dump(path):
-    from dune_ddm_amd.solver import TwoLevelSchwarz
-    dec = build_structured(synth.StructuredPoisson((17, 16, 15), (2, 2, 2)), overlap=2, pou_type="distance")
-    tl = TwoLevelSchwarz(dec, coarse="pou", schwarz_type="restricted", mode="multiplicative")
-    out = {}
-    for m in DUMP_M:
-        res, hist, X = tl.solve_multi(rhs_block(dec, tl, m, seed=40 + m), reduction=1e-10, maxit=200, solver="restartedgmressolver", restart=100)
-        assert all(r.converged for r in res), m
-        out[f"hist{m}"] = hist
-        out[f"x{m}"] = X.cpu().numpy()
-        out[f"it{m}"] = np.array([r.iterations for r in res])
-    tl.prec.check_status()
-    tl.ctx.close()
-    np.savez(path, **out)
-    print("MULTI_GMRES_DUMP_OK", os.environ.get("DDM_GMRES_MULTI_FUSED", "(unset)"), flush=True)
-
-
 if __name__ == "__main__":
-    if sys.argv[1] == "ranks":
-        ranks()
-    else:
-        dump(sys.argv[2])
+    ranks()

@@ -1,10 +1,9 @@
 """-m gpu: restarted GMRES for several right-hand sides at once (ddm_gmres_solve_multi) against ddm_gmres_solve column by column,
-against the CPU oracle, and against itself (independence of the columns, frozen columns, the fused Gram-Schmidt kernel against its
-unfused composition, the exchange paths).
+against the CPU oracle, and against itself (independence of the columns, frozen columns, the exchange paths).
 
 Tolerances are the project's: GMRES histories within 1e-7 |r_k| + 1e-11 |r_0|, x within 1e-8 (ILU(0)) or 1e-7
 (direct local solves) of the largest entry.  Everything that compares the block solver with itself is bitwise: the columns are
-independent recurrences, and the fused kernel keeps the summation order of the kernels it replaces."""
+independent recurrences."""
 import ctypes
 import os
 import subprocess
@@ -91,6 +90,33 @@ def test_columns_match_single_solves(ddm, key):
     tl.ctx.close()
 
 
+@pytest.mark.parametrize("m", [1, 3, 8, 13])
+def test_block_widths_match_single_solves(ddm, m):
+    """The widths the column-group dispatch branches on, m = 1, 3 (2 + 1), 8 and 13 (8 + 4 + 1), on configuration a with m seeded
+    consistent columns: columns 0 and m - 1 against tl.solve(solver="restartedgmressolver") as in test_columns_match_single_solves."""
+    cfg, dec, tl = _make(ddm, "a")
+    Bh = _consistent_block(tl, dec, m, seed=40 + m)
+    res, hist, X, _ = _block_solve(ddm, tl, Bh, cfg["restart"])
+    Xh = X.cpu().numpy()
+    its = [r.iterations for r in res]
+    print("m", m, "block iterations", its)
+    assert len(res) == m and hist.shape == (max(its) + 1, m)
+    for j in sorted({0, m - 1}):
+        r1, h1, x1 = tl.solve(reduction=1e-10, maxit=MAXIT, b=Bh[:, j], solver="restartedgmressolver", restart=cfg["restart"])
+        x1 = x1.cpu().numpy()
+        hj = hist[:res[j].iterations + 1, j]
+        k = min(len(hj), len(h1))
+        print("m", m, "column", j, "iterations", res[j].iterations, r1.iterations, "history deviation / |r_k|", float(np.max(np.abs(hj[:k] - h1[:k]) / h1[:k])),
+              "x deviation", float(np.max(np.abs(Xh[:, j] - x1)) / np.max(np.abs(x1))))
+        assert res[j].iterations == r1.iterations and res[j].converged == r1.converged == 1, (j, res[j].iterations, r1.iterations)
+        assert _hist_close(hj, h1), j
+        assert np.isnan(hist[res[j].iterations + 1:, j]).all()
+        assert np.max(np.abs(Xh[:, j] - x1)) <= cfg["xtol"] * np.max(np.abs(x1)), j
+        assert res[j].reduction <= 1e-10
+    tl.prec.check_status()
+    tl.ctx.close()
+
+
 @pytest.mark.parametrize("key", ["a", "b", "c"])
 def test_columns_are_independent_bit_for_bit(ddm, key):
     """Exact scaling (column 2 = 2 x column 0), permutation of the columns, and a second solve on the same objects: all bitwise."""
@@ -168,23 +194,6 @@ def test_column_frozen_through_restarts(ddm):
                 assert res2[j].converged == 0 and res2[j].iterations == its[early], j
     tl.prec.check_status()
     tl.ctx.close()
-
-
-def test_fused_step_matches_its_composition(tmp_path):
-    """k_mgs_step_multi against "AXPY per column, then the block dot" (DDM_GMRES_MULTI_FUSED=0), each in a fresh process: bit-identical
-    histories and solutions for m = 1, 3 (2 + 1 column groups), 8 and 13 (8 + 4 + 1)."""
-    out = {}
-    for fused in ("1", "0"):
-        path = str(tmp_path / f"fused{fused}.npz")
-        env = dict(os.environ, DDM_GMRES_MULTI_FUSED=fused)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mp_multi_gmres_worker.py"), "dump", path], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0 and "MULTI_GMRES_DUMP_OK " + fused in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
-        out[fused] = np.load(path)
-    for m in (1, 3, 8, 13):
-        assert np.array_equal(out["1"][f"it{m}"], out["0"][f"it{m}"]), m
-        assert np.array_equal(out["1"][f"hist{m}"], out["0"][f"hist{m}"], equal_nan=True), m
-        assert np.array_equal(out["1"][f"x{m}"], out["0"][f"x{m}"]), m
 
 
 @pytest.mark.parametrize("key", ["a", "c"])

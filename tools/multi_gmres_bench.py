@@ -13,12 +13,10 @@ compared with (ddm_cg_solve_multi / ddm_cg_solve).  The CG family needs a symmet
 Poisson --cells^3, 8 subdomains, ILU(0), restricted Schwarz, POU coarse space, additive, to 1e-10; restricted Schwarz is not symmetric,
 so cgsolver is there for its cost per iteration, not for its convergence).  Every row also carries the largest
 reported and the largest recomputed true reduction ||b - A x|| / ||b|| of its columns and the bytes of the Krylov bases.
---fused-reps R > 0 adds, at m = 8, R timed repetitions of a --profile-iters long block run with the fused Gram-Schmidt kernel and R
-with DDM_GMRES_MULTI_FUSED=0 (median and spread of both).
 
 The measurement runs in a child process under `timeout -k 10 --step-timeout`; the parent only starts it and passes its exit code on.
 
-    python tools/multi_gmres_bench.py [--problem dg|elasticity|poisson] [--solver ...] [--mmax 3] [--m 1,4,8,16] [--fused-reps 5]
+    python tools/multi_gmres_bench.py [--problem dg|elasticity|poisson] [--solver ...] [--mmax 3] [--m 1,4,8,16]
 """
 from __future__ import annotations
 
@@ -118,7 +116,7 @@ def worker(args):
         tl.op.apply_multi(X, Y)
         R = B0 - Y
         return np.sqrt(tl.op.dot_multi(R, R) / tl.op.dot_multi(B0, B0))
-    mmax = max(ms_ + ([8] if args.fused_reps > 0 else []))
+    mmax = max(ms_)
     rng = np.random.default_rng(args.seed)
     cols = [np.asarray(tl.rl.b, dtype=np.float64)]
     for _ in range(mmax - 1):
@@ -167,24 +165,6 @@ def worker(args):
         row["ratio"] = row["rhs_iterations_per_s"] / row["sequential_rhs_iterations_per_s"]
         rows.append(row)
         del X
-    fused = None
-    if args.fused_reps > 0:
-        B = Bd[:, :8].contiguous()
-        fused = {"1": [], "0": []}
-        for _ in range(args.fused_reps + 1):                                    # interleaved: drift hits both alike
-            for flag in ("1", "0"):
-                os.environ["DDM_GMRES_MULTI_FUSED"] = flag
-                tl.ctx.timing(True)
-                tl.ctx.timing_reset()
-                res, _, _ = tl.solve_multi(B, reduction=0.0, maxit=P, history=False, **kw)
-                tl.ctx.timing(False)
-                fused[flag].append((1e3 * float(res[0].elapsed_s) / P, tl.ctx.timer(TIMERS["orthogonalisation"])[0] / P))
-        del os.environ["DDM_GMRES_MULTI_FUSED"]                                  # (back to the library's default)
-        fused = {("fused" if k == "1" else "unfused"): {"reps": len(v) - 1, "wall_ms_per_iteration": sorted(w for w, _ in v[1:]),
-                                                         "orthogonalisation_ms_per_iteration": sorted(o for _, o in v[1:])} for k, v in fused.items()}
-        for v in fused.values():                                                 # (the first repetition of each is a warm-up)
-            v["median_wall"] = float(np.median(v["wall_ms_per_iteration"]))
-            v["median_orthogonalisation"] = float(np.median(v["orthogonalisation_ms_per_iteration"]))
     tl.prec.check_status()
 
     hdr = f"{'m':>3} {'block it':>8} {'ms/it':>8} {'RHS-it/s':>10} {'seq RHS-it/s':>12} {'ratio':>6} | " + " ".join(f"{k[:9]:>9}" for k in TIMERS)
@@ -194,15 +174,11 @@ def worker(args):
         p = r["ms_per_block_iteration_by_timer"]
         print(f"{r['m']:>3} {max(r['iterations']):>8} {r['ms_per_block_iteration']:>8.2f} {r['rhs_iterations_per_s']:>10.0f} "
               f"{r['sequential_rhs_iterations_per_s']:>12.0f} {r['ratio']:>6.2f} | " + " ".join(f"{p[k]:>9.3f}" for k in TIMERS))
-    if fused:
-        for k, v in fused.items():
-            print(f"m = 8 {k}: wall {v['median_wall']:.3f} ms/it (min {v['wall_ms_per_iteration'][0]:.3f}, max {v['wall_ms_per_iteration'][-1]:.3f}), "
-                  f"orthogonalisation {v['median_orthogonalisation']:.3f} ms/it over {v['reps']} repetitions of {P} iterations")
     for r in rows:
         print(f"m = {r['m']}: reported reduction (max over the columns) {r['reported_reduction_max']:.3e}, recomputed true reduction {r['true_reduction_max']:.3e}, "
               f"basis and work blocks {r['basis_bytes'] / 2**20:.1f} MiB")
     out = {"workload": workload, "solver": args.solver, "problem": args.problem, "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "restart": args.restart,
-           "mmax": args.mmax if args.solver in FCG else None, "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows, "fused_vs_unfused_m8": fused,
+           "mmax": args.mmax if args.solver in FCG else None, "profile_iters": P, "single_ms_per_iteration_by_timer": single_prof, "rows": rows,
            "what": "rhs_iterations_per_s = sum of the columns' iterations / wall time of the solve; sequential = the same columns solved one by one "
                    "with the single-vector driver; *_by_timer: ms per (block) iteration of a run of profile_iters iterations (reduction 0) with the event timers on"}
     print(json.dumps(out))
@@ -224,7 +200,6 @@ def main():
     ap.add_argument("--m", default="1,4,8,16", help="block widths, comma separated (each <= 32)")
     ap.add_argument("--maxit", type=int, default=1000)
     ap.add_argument("--profile-iters", type=int, default=20, help="iterations of the timer runs")
-    ap.add_argument("--fused-reps", type=int, default=0, help="timed repetitions of the fused / unfused comparison at m = 8 (0 = none)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--step-timeout", type=int, default=540, help="seconds the measuring child process may take")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
