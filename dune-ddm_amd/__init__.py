@@ -174,6 +174,11 @@ SYMBOLS = {
     "ddm_fcg_solve": (_I32, [_P, _P, _P, _P, _P, _D, _I32, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fcg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _I32, _P, ctypes.POINTER(SolveResult)]),
     "ddm_fcg_orth_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
+    "ddm_bcg_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _D, _P, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_bcg_gram_multi": (_I32, [_P, _P, _I32, _P, _P, _P, _P]),
+    "ddm_bcg_update_multi": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "ddm_bcg_direction_multi": (_I32, [_P, _P, _I32, _P, _P, _P]),
+    "ddm_dense_sym_pinv_host": (_I32, [_I32, _P, _D, _P, _P]),
     "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
@@ -848,6 +853,79 @@ def fcg_orth_multi(ctx: Context, op: NonOverlappingOperator, active, AD, DS, g, 
     ctx.check(ctx.lib.ddm_fcg_orth_multi(ctx.h, op.h, m, nslots, _hp(act), _ptr(AD) if nslots else None, _ptr(DS) if nslots else None,
                                          _hp(gh) if nslots else None, _ptr(W), 1 if fused else 0, _hp(coef)))
     return coef[:nslots]
+
+
+# Default rank_tol of block CG (DDM_BCG_RANK_TOL_DEFAULT of include/ddm_hip.h): the relative eigenvalue of the Jacobi-scaled coupling
+# matrix P^T A P below which a direction counts as dependent.  Chosen on the numpy restatement (tests/bcg_reference.py) with the degenerate
+# block of tests/test_bcg_cpu.py (b, random, 2 b, zero, random; golden 12^3 problem, reduction 1e-10) by the gap between the recomputed true
+# reduction and the reported one: every value from 1e-15 to 1e-6 gives the same run (rank 3 in every iteration, iterations 30, 28, 30, 0,
+# 28, gap 4.5e-18); 1e-16 lets rounding noise through as a fourth direction in some iterations, which costs iterations (35, 30, 35, 0, 30;
+# gap 7.7e-17, still converging).  1e-12, the value the algorithm was first run with, sits three decades above the lower edge of that
+# plateau and is confirmed (tests/test_bcg_cpu.py::test_rank_tol_default prints the table).
+BCG_RANK_TOL = 1e-12
+
+
+def bcg_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, rank_tol=BCG_RANK_TOL,
+                    history=True):
+    """Block CG (ddm_bcg_solve_multi): the m columns share ONE search space; operator and preconditioner symmetric positive definite.
+    X, B: (n, m) row-major device tensors (B is overwritten by the defects).  Returns (list of m SolveResult, history, ranks): history
+    is (k_end + 1) x m, every row written for every column (no column is frozen); ranks[k - 1] = rank of the coupling matrix in
+    iteration k = 1 .. k_end.  res[c].iterations = the first iteration at which column c passed its test."""
+    m = _ncols(X, B)
+    res = (SolveResult * max(m, 1))()
+    hist = np.full((maxit + 1, max(m, 1)), np.nan) if maxit >= 0 else None
+    ranks = np.zeros(max(maxit, 0) + 1, dtype=np.int32)
+    ctx.check(ctx.lib.ddm_bcg_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), float(rank_tol), _hp(hist), _hp(ranks), res))
+    out = [res[c] for c in range(m)]
+    k_end = int(np.sum(~np.isnan(hist[:, 0]))) - 1
+    return out, (hist[:k_end + 1, :m] if history else None), ranks[1:k_end + 1].copy()
+
+
+def bcg_gram_multi(ctx: Context, op: NonOverlappingOperator, U, V1, V2=None):
+    """the Gram pass of block CG on its own: returns U^T V1 (m x m) or, with V2, the pair (U^T V1, U^T V2); owner-masked, summed over
+    the ranks (ddm_bcg_gram_multi)"""
+    m = _ncols(U, V1)
+    if V2 is not None:
+        _ncols(U, V2)
+    G = np.full((2 if V2 is not None else 1, m, m), np.nan)       # (every entry must be written)
+    ctx.check(ctx.lib.ddm_bcg_gram_multi(ctx.h, op.h, m, _ptr(U), _ptr(V1), _ptr(V2) if V2 is not None else None, _hp(G)))
+    return (G[0], G[1]) if V2 is not None else G[0]
+
+
+def bcg_update_multi(ctx: Context, op: NonOverlappingOperator, alpha, P, Q, X, R):
+    """the update pass of block CG on its own: X += P alpha, R -= Q alpha (alpha: m x m host array); returns the m squared owner-masked
+    norms of R afterwards (ddm_bcg_update_multi)"""
+    m = _ncols(P, Q)
+    _ncols(X, R)
+    _ncols(P, X)
+    a = _np(alpha, np.float64)
+    assert a.shape == (m, m)
+    r = np.full(m, np.nan)
+    ctx.check(ctx.lib.ddm_bcg_update_multi(ctx.h, op.h, m, _hp(a), _ptr(P), _ptr(Q), _ptr(X), _ptr(R), _hp(r)))
+    return r
+
+
+def bcg_direction_multi(ctx: Context, op: NonOverlappingOperator, beta, Z, P):
+    """the direction pass of block CG on its own: P = Z + P beta in place (beta: m x m host array; ddm_bcg_direction_multi)"""
+    m = _ncols(Z, P)
+    b = _np(beta, np.float64)
+    assert b.shape == (m, m)
+    ctx.check(ctx.lib.ddm_bcg_direction_multi(ctx.h, op.h, m, _hp(b), _ptr(Z), _ptr(P)))
+    ctx.sync()
+
+
+def dense_sym_pinv_host(W, tol=BCG_RANK_TOL):
+    """pseudo-inverse of the symmetrised m x m matrix W as block CG forms it on the host (ddm_dense_sym_pinv_host; no device needed):
+    returns (Wpinv, rank)"""
+    Wc = _np(W, np.float64)
+    m = Wc.shape[0]
+    assert Wc.shape == (m, m)
+    out = np.zeros((m, m), dtype=np.float64)
+    rank = ctypes.c_int(0)
+    rc = load_library().ddm_dense_sym_pinv_host(m, _hp(Wc), float(tol), _hp(out), ctypes.byref(rank))
+    if rc != 0:
+        raise DdmError(rc, load_library().ddm_last_error(None).decode())
+    return out, int(rank.value)
 
 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,

@@ -60,6 +60,12 @@ extern "C" int ddm_dense_rayleigh_ritz_host(int p, const double *gA, const doubl
 {
   return dense::rayleigh_ritz(p, gA, gC, keep, tau, mu, Y);
 }
+// ... and of block CG: the pseudo-inverse of the m x m coupling matrix
+extern "C" int ddm_dense_sym_pinv_host(int m, const double *W, double tol, double *Wpinv, int *rank)
+{
+  if (m < 1 || !W || !Wpinv || !rank || W == Wpinv || !(tol > 0.0 && tol < 1.0)) return fail(nullptr, DDM_EINVAL, "ddm_dense_sym_pinv_host: bad arguments");
+  return dense::sym_pinv(m, W, tol, Wpinv, rank) ? DDM_OK : DDM_ENUMERIC;
+}
 
 // ---- input synthesis on the host (bench.py / tests: the matrices PDELab's assembler hands to the reference) ----------------------
 extern "C" int ddm_synth_q1_matrix(int dim, const int64_t *bshape, const double *ke, const int64_t *eshape, const int64_t *eoff, const double *K,

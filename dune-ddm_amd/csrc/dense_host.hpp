@@ -217,4 +217,37 @@ inline int rayleigh_ritz(int p, const double *gA, const double *gC, int keep, do
   return r;
 }
 
+// Pseudo-inverse of the symmetrised m x m matrix W (row-major) for the coupling of block CG (ddm_bcg_solve_multi): Jacobi scaling
+// d_i = sqrt(|W_ii|) (1 where W_ii == 0), symmetric eigen-decomposition of D^-1 (W + W^T)/2 D^-1, eigenvalues <= tol * lambda_max
+// dropped, the rest inverted, scaled back.  The scaling is what keeps columns of very different size (right-hand sides that converge at
+// different speeds) from being mistaken for dependent ones.  *rank = eigenvalues kept (0: Wpinv = 0, also when lambda_max <= 0).
+// Returns false when W holds a NaN / Inf or the QL iteration does not converge.
+inline bool sym_pinv(int m, const double *W, double tol, double *Wpinv, int *rank)
+{
+  std::vector<double> G((size_t)m * m), d(m), lam(m);
+  for (int i = 0; i < m; ++i) {
+    const double g = std::fabs(W[(size_t)i * m + i]);
+    if (!std::isfinite(g)) return false;
+    d[i] = g > 0.0 ? std::sqrt(g) : 1.0;
+  }
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) {
+      const double s = 0.5 * (W[(size_t)i * m + j] + W[(size_t)j * m + i]);
+      if (!std::isfinite(s)) return false;
+      G[(size_t)i * m + j] = s / d[i] / d[j];
+    }
+  if (!sym_eig(m, G.data(), lam.data())) return false;
+  const double lmax = m > 0 ? lam[m - 1] : 0.0;
+  int first = 0;
+  while (first < m && !(lmax > 0.0 && lam[first] > tol * lmax)) ++first;
+  *rank = m - first;
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) {
+      double s = 0.0;
+      for (int k = first; k < m; ++k) s += G[(size_t)i * m + k] * G[(size_t)j * m + k] / lam[k];
+      Wpinv[(size_t)i * m + j] = s / d[i] / d[j];
+    }
+  return true;
+}
+
 } // namespace dense

@@ -611,4 +611,166 @@ __global__ void k_fcg_alpha_multi(int m, const int32_t *__restrict__ active, con
   }
 }
 
+// ---- block CG (ddm_bcg_solve_multi, csrc/krylov.hpp): the m x m coupling of the columns ------------------------------------------------
+// All three kernels walk the block in tiles of whole rows that one workgroup stages in LDS with contiguous loads (a tile of rows IS a
+// contiguous piece of a row-major block), tile tb = blockIdx.x, blockIdx.x + gridDim.x, ...  No atomics: every sum has one owner and a
+// fixed order, so the results do not change from call to call.  Plain FP64 multiplies and adds (the build does not contract them); the
+// passes are HBM-bound up to m = 32.
+constexpr int BCG_TILE = 1024; // block entries of one staged tile (8 KiB per block)
+
+// Owner-masked Gram products of row-major n x m blocks in ONE pass: G1 = U^T V1 and, with TWO, G2 = U^T V2.
+// A tile is BCG_TILE / mp rows (mp = m rounded up to even; the LDS rows are mp wide, the pad column is zero; rows that are not owned
+// are staged as zeros).  The outputs are cut into NO = (mp / 2)^2 blocks of 2 x 2 entries (x 2 products: 8 accumulators); thread
+// (s, o) owns output block o for the tile rows s, s + NS, ... with NS = WG / NO row slices (threads past NS * NO idle: m = 32 uses
+// all 256 as 256 x 1, m = 8 as 16 x 16).  At the end the NS slices are summed in ascending s through LDS.
+// partial[((p * m + i) * m + j) * gridDim.x + b] = block b's sum for entry (i, j) of product p: the layout k_reduce_final_multi sums.
+template <bool TWO, bool MASKED>
+__global__ __launch_bounds__(WG) void k_bcg_gram_partial(int64_t n, int m, const uint8_t *__restrict__ mask, const double *__restrict__ U,
+                                                         const double *__restrict__ V1, const double *__restrict__ V2, double *__restrict__ partial)
+{
+  __shared__ double lds[3 * BCG_TILE];
+  const int mp = (m + 1) & ~1, hb = mp >> 1, NO = hb * hb, NS = WG / NO, TR = BCG_TILE / mp;
+  double *Ut = lds, *V1t = lds + BCG_TILE, *V2t = lds + 2 * BCG_TILE;
+  const int t = threadIdx.x;
+  const int s = t / NO, o = t - s * NO, oi = o / hb, oj = o - oi * hb;
+  double acc[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+  if (mp != m)
+    for (int r = t; r < TR; r += WG) Ut[r * mp + m] = V1t[r * mp + m] = V2t[r * mp + m] = 0.0; // (no staging loop writes the pad column)
+  const int64_t ntile = (n + TR - 1) / TR;
+  for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+    const int64_t r0 = tb * TR;
+    const int rows = (int)(n - r0 < TR ? n - r0 : TR);
+    __syncthreads(); // the previous tile is no longer read
+    for (int e = t; e < rows * m; e += WG) {
+      const int r = e / m, l = r * mp + (e - r * m);
+      const int64_t g = r0 * m + e;
+      const bool own = !MASKED || mask[r0 + r];
+      Ut[l] = own ? U[g] : 0.0;
+      V1t[l] = own ? V1[g] : 0.0;
+      if (TWO) V2t[l] = own ? V2[g] : 0.0;
+    }
+    __syncthreads();
+    if (s < NS)
+      for (int r = s; r < rows; r += NS) {
+        const double *u = Ut + r * mp + 2 * oi, *v1 = V1t + r * mp + 2 * oj;
+        const double u0 = u[0], u1 = u[1], a0 = v1[0], a1 = v1[1];
+        acc[0] += u0 * a0;
+        acc[1] += u0 * a1;
+        acc[2] += u1 * a0;
+        acc[3] += u1 * a1;
+        if (TWO) {
+          const double *v2 = V2t + r * mp + 2 * oj;
+          const double b0 = v2[0], b1 = v2[1];
+          acc[4] += u0 * b0;
+          acc[5] += u0 * b1;
+          acc[6] += u1 * b0;
+          acc[7] += u1 * b1;
+        }
+      }
+  }
+  __syncthreads(); // the tiles are done with: their LDS takes the accumulators, thread t's at 8 t (t = s * NO + o)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) lds[t * 8 + k] = s < NS ? acc[k] : 0.0;
+  __syncthreads();
+  for (int idx = t; idx < NO * 8; idx += WG) {
+    const int oo = idx >> 3, k = idx & 7;
+    if (!TWO && k >= 4) continue;
+    double sum = 0.0;
+    for (int ss = 0; ss < NS; ++ss) sum += lds[(ss * NO + oo) * 8 + k];
+    const int i = 2 * (oo / hb) + ((k >> 1) & 1), j = 2 * (oo % hb) + (k & 1), p = k >> 2;
+    if (i < m && j < m) partial[((int64_t)(p * m + i) * m + j) * gridDim.x + blockIdx.x] = sum;
+  }
+}
+
+// The tiles of the two update kernels: QR = WG / m rows per quarter, a tile is four quarters (4 QR rows, at most BCG_TILE entries).
+// Thread t < QR m owns entry t of every quarter -- row t / m of the quarter, column c = t % m, the same column in all four, so the
+// coefficient coef[j][c] is read once for four rows.  Global entry of quarter q: g0 + q QR m + t, consecutive over the threads.
+__device__ __forceinline__ void bcg_stage_tile(int64_t g0, int64_t total, int entries, const double *__restrict__ src, double *tile)
+{
+  for (int e = threadIdx.x; e < entries; e += WG) tile[e] = g0 + e < total ? src[g0 + e] : 0.0;
+}
+// X += P alpha; R -= Q alpha (alpha: m x m row-major device doubles, staged in LDS; per entry the m products are summed in ascending j
+// and the sum is then added to x / taken from r); the owner-masked partial sums of the new <R_c, R_c> from the same pass, a column's
+// terms added per thread over the tiles, then over the threads of the column in ascending row: partial[c * gridDim.x + b].
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_bcg_update_norm(int64_t n, int m, const double *__restrict__ alpha, const uint8_t *__restrict__ mask,
+                                                        const double *__restrict__ P, const double *__restrict__ Q, double *__restrict__ X,
+                                                        double *__restrict__ R, double *__restrict__ partial)
+{
+  __shared__ double Pt[BCG_TILE], Qt[BCG_TILE], al[MULTI_MAX * MULTI_MAX], red[WG];
+  const int QR = WG / m, QE = QR * m, TR = 4 * QR;
+  const int t = threadIdx.x, r = t / m, c = t - r * m;
+  const bool on = t < QE;
+  for (int e = t; e < m * m; e += WG) al[e] = alpha[e];
+  double s = 0.0;
+  const int64_t total = n * m, ntile = (n + TR - 1) / TR;
+  for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+    const int64_t r0 = tb * TR, g0 = r0 * m;
+    __syncthreads(); // the previous tile is no longer read (first trip: al is complete)
+    bcg_stage_tile(g0, total, 4 * QE, P, Pt);
+    bcg_stage_tile(g0, total, 4 * QE, Q, Qt);
+    __syncthreads();
+    if (on) {
+      double xs[4] = {0.0, 0.0, 0.0, 0.0}, rs[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < m; ++j) {
+        const double a = al[j * m + c];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          xs[q] += Pt[q * QE + r * m + j] * a;
+          rs[q] += Qt[q * QE + r * m + j] * a;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t g = g0 + q * QE + t;
+        if (g < total) {
+          X[g] += xs[q];
+          const double rn = R[g] - rs[q];
+          R[g] = rn;
+          if (!MASKED || mask[r0 + q * QR + r]) s += rn * rn;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  red[t] = on ? s : 0.0;
+  __syncthreads();
+  if (t < m) {
+    double sum = 0.0;
+    for (int k = 0; k < QR; ++k) sum += red[k * m + t];
+    partial[(int64_t)t * gridDim.x + blockIdx.x] = sum;
+  }
+}
+// P = Z + P beta, in place (beta: m x m row-major device doubles): a row's m outputs need that row's m inputs only, and the tile is
+// staged before any of its entries is written.
+__global__ __launch_bounds__(WG) void k_bcg_direction(int64_t n, int m, const double *__restrict__ beta, const double *__restrict__ Z, double *__restrict__ P)
+{
+  __shared__ double Pt[BCG_TILE], be[MULTI_MAX * MULTI_MAX];
+  const int QR = WG / m, QE = QR * m, TR = 4 * QR;
+  const int t = threadIdx.x, r = t / m, c = t - r * m;
+  for (int e = t; e < m * m; e += WG) be[e] = beta[e];
+  const int64_t total = n * m, ntile = (n + TR - 1) / TR;
+  for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+    const int64_t g0 = tb * TR * m;
+    __syncthreads();
+    bcg_stage_tile(g0, total, 4 * QE, P, Pt);
+    __syncthreads();
+    if (t < QE) {
+      double ps[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < m; ++j) {
+        const double b = be[j * m + c];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ps[q] += Pt[q * QE + r * m + j] * b;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t g = g0 + q * QE + t;
+        if (g < total) P[g] = Z[g] + ps[q];
+      }
+    }
+  }
+}
+
 } // namespace ddm

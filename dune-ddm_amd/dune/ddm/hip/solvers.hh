@@ -128,7 +128,8 @@ public:
 
   // Several right-hand sides at once: x.size() independent solves (1 to 32 columns) in one device loop (HipCGSolver: ddm_cg_solve_multi;
   // HipRestartedGMResSolver: ddm_gmres_solve_multi; HipRestartedFlexibleGMResSolver: ddm_fgmres_solve_multi; HipRestartedFCGSolver / HipCompleteFCGSolver: ddm_fcg_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
-  // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  A solver without a block
+  // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  HipBlockCGSolver is the one
+  // solver whose columns are NOT independent: ddm_bcg_solve_multi, one shared search space.  A solver without a block
   // loop (HipBiCGSTABSolver) throws Dune::NotImplemented.
   void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
   {
@@ -339,6 +340,35 @@ public:
   using HipKrylovSolverBase<X>::apply;
 };
 
+// [solver] type = blockcgsolver: block CG (ddm_bcg_solve_multi), a true block-Krylov method -- the columns of the block apply share ONE
+// search space, so the iteration count falls as columns are added; not a dune-istl solver.  For a symmetric positive definite
+// preconditioner, as HipCGSolver.  rank_tol: relative eigenvalue of the scaled coupling matrix below which a direction counts as
+// dependent.  res[c].iterations is the first iteration at which column c passed its test.  The single-vector apply is the block of
+// width 1 (CG); apply_queue throws Dune::NotImplemented (there is no queued block CG).
+template <class X>
+class HipBlockCGSolver : public HipKrylovSolverBase<X> {
+public:
+  HipBlockCGSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int maxit, int verbose = 0,
+                   double rank_tol = DDM_BCG_RANK_TOL_DEFAULT)
+      : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), rank_tol_(rank_tol) {}
+  HipBlockCGSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
+      : HipBlockCGSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("maxit", 1000), cfg.get("verbose", 0),
+                         cfg.get("rank_tol", DDM_BCG_RANK_TOL_DEFAULT)) {}
+
+  using HipKrylovSolverBase<X>::apply;
+
+protected:
+  int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_bcg_solve_multi(ctx, o, p, 1, x, b, reduction, this->maxit_, rank_tol_, nullptr, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_bcg_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, rank_tol_, nullptr, nullptr, r);
+  }
+  double rank_tol_;
+};
+
 // [solver] type = bicgstabsolver: dune-istl BiCGSTABSolver::apply
 template <class X>
 class HipBiCGSTABSolver : public HipKrylovSolverBase<X> {
@@ -372,7 +402,8 @@ std::shared_ptr<InverseOperator<X, X>> getHipSolver(std::shared_ptr<LinearOperat
   if (type == "restartedfcgsolver") return std::make_shared<HipRestartedFCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "completefcgsolver") return std::make_shared<HipCompleteFCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "bicgstabsolver") return std::make_shared<HipBiCGSTABSolver<X>>(std::move(op), std::move(prec), cfg);
-  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver, completefcgsolver, bicgstabsolver)");
+  if (type == "blockcgsolver") return std::make_shared<HipBlockCGSolver<X>>(std::move(op), std::move(prec), cfg);
+  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver, completefcgsolver, bicgstabsolver, blockcgsolver)");
 }
 
 }  // namespace Dune

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import (CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
+from . import (BCG_RANK_TOL, bcg_solve_multi, CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
                SchwarzPreconditioner, bicgstab_solve_queue, cg_solve, cg_solve_multi, cg_solve_queue, fcg_solve, fcg_solve_multi, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
@@ -339,6 +339,18 @@ class TwoLevelSchwarz:
         else:
             res, hist = cg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, history)
         return res, hist, X
+
+    def solve_block(self, B, reduction=1e-10, maxit=1000, history=True, X0=None, rank_tol=BCG_RANK_TOL):
+        """m right-hand sides through ONE shared search space: block CG (ddm_bcg_solve_multi), a true block-Krylov method -- every
+        column's error is minimised over the span of all columns' Krylov spaces, so it needs fewer iterations than ``solve_multi`` on
+        the same block, the more the harder the operator.  For a symmetric positive definite preconditioner only (standard Schwarz,
+        additive combination), as CG.  Dependent or duplicate columns and zero columns are safe (the m x m coupling is solved with a
+        pseudo-inverse; rank_tol: relative eigenvalue below which a direction counts as dependent).  B, X0: (n_o, m) arrays or tensors,
+        m <= 32.  Returns (list of m SolveResult -- iterations: the first iteration at which the column passed its test --, the
+        (k_end + 1) x m history or None, X as an (n_o, m) device tensor, the k_end ranks of the coupling matrix)."""
+        Bd, X = self._blocks(B, X0)
+        res, hist, ranks = bcg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, rank_tol, history)
+        return res, hist, X, ranks
 
     def solve_many(self, B, width=8, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver"):
         """Any number M of right-hand sides, M independent solves through one block loop of ``width`` <= 32 slots: a slot whose column

@@ -621,6 +621,49 @@ int ddm_fcg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, 
 int ddm_fcg_orth_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, int nslots, const int32_t *active_host, const double *AD, const double *DS,
                        const double *g_host, double *W, int fused, double *coef_host);
 
+/* ---- block CG --------------------------------------------------------------------------------------------------------------------
+ * A TRUE block-Krylov method (O'Leary 1980), unlike every *_multi driver above: the nrhs columns share one search space, each column's
+ * error is minimised over the span of ALL columns' Krylov spaces, so the iteration count falls as nrhs grows.  The operator and the
+ * preconditioner must be symmetric positive definite, as for CG (standard Schwarz with the additive combination; not restricted
+ * Schwarz, not the multiplicative combination); this is not tested.  Blocks are n x nrhs row-major, 1 <= nrhs <= 32; <.,.> is the
+ * owner-masked scalar product summed over the ranks and U^T V the nrhs x nrhs matrix of those products.
+ *   1. R = B - A X (in B); def0_c = ||R_c||; hist row 0.  def0_c < 1e-30: column c is converged with 0 iterations; it STAYS in the
+ *      block (a zero right-hand side gives exactly zero coefficients: its x is not changed).  NaN: DDM_ENUMERIC.
+ *   2. Z = M^-1 R; P = Z.
+ *   3. k = 1 .. maxit, while some column fails its test:
+ *        Q = A P;  W = P^T Q, S = P^T R (one pass over P, Q, R; one all-reduce of 2 nrhs^2 doubles; host read-back 1);
+ *        W^+ = pseudo-inverse of (W + W^T) / 2 on the host (ddm_dense_sym_pinv_host with rank_tol), rank_k = eigenvalues kept;
+ *        alpha = W^+ S;  X += P alpha;  R -= Q alpha;  def_c = ||R_c|| (the norms come from the pass of the two updates);
+ *        Z = M^-1 R;  Q^T Z (one pass; ONE all-reduce of nrhs^2 + nrhs doubles takes it and the squared norms; host read-back 2);
+ *        the test; if some column still fails: beta = -W^+ (Q^T Z);  P = Z + P beta.
+ *   4. Column c passes when def_c < reduction def0_c or def_c < 1e-30.  The loop ends at the first k at which EVERY column passes.  No
+ *      column is frozen: one that has passed goes on being improved.  res[c].iterations = the first k at which c passed (k_end if it
+ *      never did); res[c].converged and res[c].reduction describe the state at the end.  hist_host (may be NULL; (maxit + 1) x nrhs):
+ *      rows 0 .. k_end are written for EVERY column.  rank_hist_host (may be NULL; maxit + 1 int32): entry k = rank_k, entry 0 = 0.
+ * The pseudo-inverse is what makes the method safe with duplicate or dependent right-hand sides, a zero column, and columns that
+ * converge at very different speeds; with nrhs = 1 the algorithm is CG.
+ * DDM_EINVAL (before any device work; the message names the function) for NULL pointers, X == B, nrhs outside 1..32, maxit < 0 or
+ * rank_tol outside (0, 1); DDM_ENUMERIC for a NaN defect (the message names the column), a coupling matrix that is not finite, rank_k = 0
+ * while a column still fails, and when a local solve gave up.  Nothing outlives the call on the device but three n x nrhs work blocks
+ * of the preconditioner object (P and Q are those of ddm_cg_solve_multi); the active-column mask of the other drivers is not used. */
+#define DDM_BCG_RANK_TOL_DEFAULT 1e-12
+int ddm_bcg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                        double rank_tol, double *hist_host, int32_t *rank_hist_host, ddm_solve_result *res);
+/* Its three passes over the blocks on their own (for tests; synchronous; no atomics: two identical calls give identical bits).
+ *   gram:      G_host = [U^T V1 | U^T V2] (nrhs^2 doubles each, row-major; V2 may be NULL: U^T V1 only), owner-masked, all ranks.
+ *   update:    X += P alpha; R -= Q alpha (alpha_host: nrhs x nrhs row-major; per entry the nrhs products are summed in ascending
+ *              index and the sum is then applied); norm2_host[c] = <R_c, R_c> afterwards.  The four blocks must be distinct.
+ *   direction: P = Z + P beta, in place. */
+int ddm_bcg_gram_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *U, const double *V1, const double *V2, double *G_host);
+int ddm_bcg_update_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *alpha_host, const double *P, const double *Q, double *X, double *R,
+                         double *norm2_host);
+int ddm_bcg_direction_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *beta_host, const double *Z, double *P);
+/* host logic of the coupling, exposed for the CPU tests: Wpinv = pseudo-inverse of (W + W^T) / 2 (m x m row-major) -- Jacobi scaling
+ * d_i = sqrt(|W_ii|) (1 where W_ii = 0), symmetric eigen-decomposition of the scaled matrix, eigenvalues <= tol lambda_max dropped,
+ * the rest inverted, scaled back; *rank = eigenvalues kept.  DDM_EINVAL for m < 1, NULL, W == Wpinv, tol outside (0, 1); DDM_ENUMERIC
+ * for an entry that is not finite. */
+int ddm_dense_sym_pinv_host(int m, const double *W, double tol, double *Wpinv, int *rank);
+
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,
  * dune/ddm/schwarz.hh:178-181).  Times are HIP-event milliseconds accumulated on the stream. */
