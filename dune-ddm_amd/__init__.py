@@ -179,6 +179,11 @@ SYMBOLS = {
     "ddm_bcg_update_multi": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "ddm_bcg_direction_multi": (_I32, [_P, _P, _I32, _P, _P, _P]),
     "ddm_dense_sym_pinv_host": (_I32, [_I32, _P, _D, _P, _P]),
+    "ddm_bgmres_solve_multi": (_I32, [_P, _P, _P, _I32, _P, _P, _D, _I32, _I32, _D, _P, _P, ctypes.POINTER(SolveResult)]),
+    "ddm_bgmres_project_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "ddm_bgmres_combine_multi": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "ddm_bgmres_combine_gram_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "ddm_dense_bgmres_factor_host": (_I32, [_I32, _P, _P, _D, _P, _P, _P]),
     "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
@@ -926,6 +931,80 @@ def dense_sym_pinv_host(W, tol=BCG_RANK_TOL):
     if rc != 0:
         raise DdmError(rc, load_library().ddm_last_error(None).decode())
     return out, int(rank.value)
+
+
+# Default rank_tol of block GMRES (DDM_BGMRES_RANK_TOL_DEFAULT of include/ddm_hip.h): the relative eigenvalue of the scaled Gram matrix of
+# a block below which a direction counts as dependent.  Confirmed on the numpy restatement (tests/bgmres_reference.py) with the
+# degenerate block of tests/test_bgmres_cpu.py by the gap between the recomputed and the monitored reduction:
+# tests/test_bgmres_cpu.py::test_rank_tol_default prints the table and states the plateau.
+BGMRES_RANK_TOL = 1e-12
+
+
+def bgmres_solve_multi(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, X, B, reduction=1e-10, maxit=1000, restart=100,
+                       rank_tol=BGMRES_RANK_TOL, history=True):
+    """Block GMRES (ddm_bgmres_solve_multi): the m columns share ONE Krylov space; right preconditioning with a fixed preconditioner,
+    which need not be symmetric.  X, B: (n, m) row-major device tensors (B is overwritten by the defects).  maxit counts block
+    iterations.  Returns (list of m SolveResult, history, widths): history is (k_end + 1) x m, the monitored defects, recomputed at
+    every cycle end; widths[k - 1] = width of the cycle that block iteration k = 1 .. k_end belongs to.  res[c].iterations = the first
+    block iteration at which column c passed its test and stayed passed."""
+    m = _ncols(X, B)
+    res = (SolveResult * max(m, 1))()
+    hist = np.full((maxit + 1, max(m, 1)), np.nan) if maxit >= 0 else None
+    widths = np.zeros(max(maxit, 0) + 1, dtype=np.int32)
+    ctx.check(ctx.lib.ddm_bgmres_solve_multi(ctx.h, op.h, prec.h, m, _ptr(X), _ptr(B), float(reduction), int(maxit), int(restart), float(rank_tol),
+                                             _hp(hist), _hp(widths), res))
+    out = [res[c] for c in range(m)]
+    k_end = int(np.sum(~np.isnan(hist[:, 0]))) - 1
+    return out, (hist[:k_end + 1, :m] if history else None), widths[1:k_end + 1].copy()
+
+
+def bgmres_project_multi(ctx: Context, op: NonOverlappingOperator, V, W):
+    """the projection pass of block GMRES on its own: V a (K, n, p) device tensor of K stored blocks, W (n, p); returns the K matrices
+    V_k^T W as a (K, p, p) array, owner-masked, summed over the ranks (ddm_bgmres_project_multi)"""
+    K, p = int(V.shape[0]), _ncols(W)
+    assert tuple(V.shape[1:]) == tuple(W.shape) and V.is_contiguous()
+    H = np.full((K, p, p), np.nan)                                 # (every entry must be written)
+    ctx.check(ctx.lib.ddm_bgmres_project_multi(ctx.h, op.h, p, K, _ptr(V), _ptr(W), _hp(H)))
+    return H
+
+
+def bgmres_combine_multi(ctx: Context, op: NonOverlappingOperator, mode, V, coef, Out):
+    """the combination pass of block GMRES on its own: Out (n, q) = (mode 0) / += (1) / -= (2) sum_k V[k] coef[k], V a (K, n, pin)
+    device tensor, coef a (K, pin, q) host array (ddm_bgmres_combine_multi)"""
+    K, pin, q = int(V.shape[0]), int(V.shape[2]), _ncols(Out)
+    c = _np(coef, np.float64)
+    assert c.shape == (K, pin, q) and V.is_contiguous() and int(V.shape[1]) == int(Out.shape[0])
+    ctx.check(ctx.lib.ddm_bgmres_combine_multi(ctx.h, op.h, int(mode), pin, q, K, _ptr(V), _hp(c), _ptr(Out)))
+    ctx.sync()
+
+
+def bgmres_combine_gram_multi(ctx: Context, op: NonOverlappingOperator, V, coef, W):
+    """W (n, p) -= sum_k V[k] coef[k] and, from the same pass, W^T W afterwards as a (p, p) array, owner-masked, summed over the ranks
+    (ddm_bgmres_combine_gram_multi)"""
+    K, p = int(V.shape[0]), _ncols(W)
+    c = _np(coef, np.float64)
+    assert c.shape == (K, p, p) and tuple(V.shape[1:]) == tuple(W.shape) and V.is_contiguous()
+    G = np.full((p, p), np.nan)
+    ctx.check(ctx.lib.ddm_bgmres_combine_gram_multi(ctx.h, op.h, p, K, _ptr(V), _hp(c), _ptr(W), _hp(G)))
+    return G
+
+
+def dense_bgmres_factor_host(G, scale2=None, tol=BGMRES_RANK_TOL):
+    """the factor of the p x p Gram matrix of a block as block GMRES forms it on the host (ddm_dense_bgmres_factor_host; no device
+    needed): returns (S (rank, p) with S^T S = G, C (p, rank) with C^T G C = I, rank)"""
+    Gc = _np(G, np.float64)
+    p = Gc.shape[0]
+    assert Gc.shape == (p, p)
+    sc = _np(scale2, np.float64) if scale2 is not None else None
+    assert sc is None or sc.shape == (p,)
+    S = np.zeros((p, p), dtype=np.float64)
+    C = np.zeros((p, p), dtype=np.float64)
+    rank = ctypes.c_int(0)
+    rc = load_library().ddm_dense_bgmres_factor_host(p, _hp(Gc), _hp(sc), float(tol), _hp(S), _hp(C), ctypes.byref(rank))
+    if rc != 0:
+        raise DdmError(rc, load_library().ddm_last_error(None).decode())
+    r = int(rank.value)
+    return S[:r].copy(), C[:, :r].copy(), r
 
 
 def gmres_solve(ctx: Context, op: NonOverlappingOperator, prec: CombinedPreconditioner, x, b, reduction=1e-10, maxit=1000, restart=100,

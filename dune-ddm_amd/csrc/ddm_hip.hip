@@ -66,6 +66,13 @@ extern "C" int ddm_dense_sym_pinv_host(int m, const double *W, double tol, doubl
   if (m < 1 || !W || !Wpinv || !rank || W == Wpinv || !(tol > 0.0 && tol < 1.0)) return fail(nullptr, DDM_EINVAL, "ddm_dense_sym_pinv_host: bad arguments");
   return dense::sym_pinv(m, W, tol, Wpinv, rank) ? DDM_OK : DDM_ENUMERIC;
 }
+// ... and of block GMRES: the factor of the p x p Gram matrix of a block (scale2 may be NULL: the diagonal of G)
+extern "C" int ddm_dense_bgmres_factor_host(int p, const double *G, const double *scale2, double tol, double *S, double *C, int *rank)
+{
+  if (p < 1 || !G || !S || !C || !rank || S == C || G == S || G == C || !(tol > 0.0 && tol < 1.0))
+    return fail(nullptr, DDM_EINVAL, "ddm_dense_bgmres_factor_host: bad arguments");
+  return dense::bgmres_factor(p, G, scale2, tol, S, C, rank) ? DDM_OK : DDM_ENUMERIC;
+}
 
 // ---- input synthesis on the host (bench.py / tests: the matrices PDELab's assembler hands to the reference) ----------------------
 extern "C" int ddm_synth_q1_matrix(int dim, const int64_t *bshape, const double *ke, const int64_t *eshape, const int64_t *eoff, const double *K,

@@ -250,4 +250,119 @@ inline bool sym_pinv(int m, const double *W, double tol, double *Wpinv, int *ran
   return true;
 }
 
+// Factor of a symmetric positive semi-definite p x p Gram matrix G = W^T W (row-major) for block GMRES (ddm_bgmres_solve_multi):
+// S (rank x p) with S^T S = G and C (p x rank) with C^T G C = I, so that W C has orthonormal columns and W = (W C) S.  Jacobi scaling
+// d_c = sqrt(|scale2_c|) (1 where that is 0; scale2 == nullptr: the diagonal of G), eigen-decomposition of D^-1 (G + G^T)/2 D^-1, the
+// eigenvalues above tol * lambda_max kept, largest first: S = Lambda^1/2 U^T D, C = D^-1 U Lambda^-1/2.  A scale2 larger than G's diagonal
+// (the squared column norms of W BEFORE it was orthogonalised) is what lets a column that is rounding noise be seen as such: scaled by
+// its own norm it would be a unit column.  S and C are written as p x p row-major arrays: rows >= rank of S and columns >= rank of C
+// are zero.  Returns false when an entry is not finite or the QL iteration does not converge.
+inline bool bgmres_factor(int p, const double *G, const double *scale2, double tol, double *S, double *C, int *rank)
+{
+  std::vector<double> U((size_t)p * p), d(p), lam(p);
+  for (int i = 0; i < p; ++i) {
+    const double g = std::fabs(scale2 ? scale2[i] : G[(size_t)i * p + i]);
+    if (!std::isfinite(g)) return false;
+    d[i] = g > 0.0 ? std::sqrt(g) : 1.0;
+  }
+  for (int i = 0; i < p; ++i)
+    for (int j = 0; j < p; ++j) {
+      const double s = 0.5 * (G[(size_t)i * p + j] + G[(size_t)j * p + i]);
+      if (!std::isfinite(s)) return false;
+      U[(size_t)i * p + j] = s / d[i] / d[j];
+    }
+  if (!sym_eig(p, U.data(), lam.data())) return false;
+  const double lmax = lam[p - 1];
+  int first = 0;
+  while (first < p && !(lmax > 0.0 && lam[first] > tol * lmax)) ++first;
+  const int r = *rank = p - first;
+  std::fill(S, S + (size_t)p * p, 0.0);
+  std::fill(C, C + (size_t)p * p, 0.0);
+  for (int a = 0; a < r; ++a) {
+    const int k = p - 1 - a; // eigenvalues descending
+    const double sq = std::sqrt(lam[k]);
+    for (int i = 0; i < p; ++i) {
+      S[(size_t)a * p + i] = sq * U[(size_t)i * p + k] * d[i];
+      C[(size_t)i * p + a] = U[(size_t)i * p + k] / sq / d[i];
+    }
+  }
+  return true;
+}
+
+// The least-squares problem of block GMRES, min || E_1 T e_c - Hbar y || for the m columns of T at once, by incremental Householder
+// QR of the block Hessenberg matrix Hbar (block size p).  Column block j arrives as its (j + 2) p entries per column; the reflectors
+// of the earlier columns are applied to it, then p new reflectors remove what lies under its diagonal, and they are applied to the
+// right-hand sides as well.  Every rank runs this on the same all-reduced numbers, in the same order.
+struct BlockHessenberg {
+  int p = 0, m = 0, steps = 0;
+  std::vector<std::vector<double>> col; // column a of R: a + 1 entries (after its reflector)
+  std::vector<std::vector<double>> v;   // reflector of column a: acts on rows a .. a + v[a].size() - 1
+  std::vector<double> tau;
+  std::vector<double> g;                // right-hand sides: rows x m, row-major; rows = (steps + 1) p
+  void start(int p_, int m_, const double *T) // T: p x m
+  {
+    p = p_, m = m_, steps = 0;
+    col.clear(), v.clear(), tau.clear();
+    g.assign(T, T + (size_t)p * m);
+  }
+  static void reflect(const std::vector<double> &u, double t, double *x, size_t stride)
+  {
+    double s = 0.0;
+    for (size_t i = 0; i < u.size(); ++i) s += u[i] * x[i * stride];
+    s *= t;
+    for (size_t i = 0; i < u.size(); ++i) x[i * stride] -= s * u[i];
+  }
+  // block: (steps + 2) p x p row-major = [H_0j; ..; H_jj; S]
+  void add_block(const double *block)
+  {
+    const int rows = (steps + 2) * p;
+    g.resize((size_t)rows * m, 0.0);
+    std::vector<double> x(rows);
+    for (int b = 0; b < p; ++b) {
+      const int a = steps * p + b;
+      for (int i = 0; i < rows; ++i) x[i] = block[(size_t)i * p + b];
+      for (int q = 0; q < a; ++q) reflect(v[q], tau[q], x.data() + q, 1);
+      // the reflector that maps x[a .. rows) onto a multiple of the first unit vector
+      std::vector<double> u(x.begin() + a, x.end());
+      double nrm = 0.0;
+      for (double e : u) nrm += e * e;
+      nrm = std::sqrt(nrm);
+      double t = 0.0;
+      if (nrm > 0.0) {
+        const double alpha = u[0] > 0.0 ? -nrm : nrm;
+        u[0] -= alpha;
+        double uu = 0.0;
+        for (double e : u) uu += e * e;
+        t = uu > 0.0 ? 2.0 / uu : 0.0;
+        x[a] = alpha;
+      }
+      col.emplace_back(x.begin(), x.begin() + a + 1);
+      for (int c = 0; c < m; ++c) reflect(u, t, g.data() + (size_t)a * m + c, (size_t)m);
+      v.push_back(std::move(u));
+      tau.push_back(t);
+    }
+    ++steps;
+  }
+  // the least-squares residual of column c after the blocks added so far
+  double residual(int c) const
+  {
+    double s = 0.0;
+    for (int i = steps * p; i < (steps + 1) * p; ++i) s += g[(size_t)i * m + c] * g[(size_t)i * m + c];
+    return std::sqrt(s);
+  }
+  // Y (steps p x m, row-major): the minimisers; false when a diagonal entry of R is zero
+  bool solve(double *Y) const
+  {
+    const int nn = steps * p;
+    for (int c = 0; c < m; ++c)
+      for (int a = nn - 1; a >= 0; --a) {
+        double t = g[(size_t)a * m + c];
+        for (int b = a + 1; b < nn; ++b) t -= col[b][a] * Y[(size_t)b * m + c];
+        if (col[a][a] == 0.0) return false;
+        Y[(size_t)a * m + c] = t / col[a][a];
+      }
+    return true;
+  }
+};
+
 } // namespace dense

@@ -773,4 +773,166 @@ __global__ __launch_bounds__(WG) void k_bcg_direction(int64_t n, int m, const do
   }
 }
 
+// ---- block GMRES (ddm_bgmres_solve_multi, csrc/krylov.hpp): block classical Gram-Schmidt against the stored basis blocks ----------------
+// Blocks are n x p row-major, 1 <= p <= MULTI_MAX; stored block k starts at V + k * vstride.  As for block CG: LDS-staged tiles of whole
+// rows, tile tb = blockIdx.x, blockIdx.x + gridDim.x, ..., no atomics, plain FP64 multiplies and adds in a fixed order.
+constexpr int BGM_SG = 4; // stored blocks of one group of k_bgmres_project: BGM_SG x 4 accumulators per thread
+
+// Projection: the owner-masked partial sums of V_k^T W (p x p each) for K stored blocks in one launch.  The stored blocks are taken in
+// groups of BGM_SG: for a group the workgroup walks its tiles once, stages the W tile ONCE and the group's V tiles beside it (rows
+// that are not owned as zeros), and thread (s, o) -- the layout of k_bcg_gram_partial -- keeps the 2 x 2 output block o of every
+// block of the group in registers for the tile rows s, s + NS, ...  The slices are summed in ascending s through LDS.
+// partial[(((k * p + i) * p + j) * gridDim.x + b] = workgroup b's sum for entry (i, j) of V_k^T W: the layout k_reduce_final_multi sums.
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_bgmres_project(int64_t n, int p, int K, const uint8_t *__restrict__ mask, const double *__restrict__ V,
+                                                       int64_t vstride, const double *__restrict__ W, double *__restrict__ partial)
+{
+  __shared__ double lds[(BGM_SG + 1) * BCG_TILE];
+  const int mp = (p + 1) & ~1, hb = mp >> 1, NO = hb * hb, NS = WG / NO, TR = BCG_TILE / mp;
+  const int t = threadIdx.x;
+  const int s = t / NO, o = t - s * NO, oi = o / hb, oj = o - oi * hb;
+  const int64_t ntile = (n + TR - 1) / TR;
+  for (int k0 = 0; k0 < K; k0 += BGM_SG) {
+    const int ng = K - k0 < BGM_SG ? K - k0 : BGM_SG;
+    double acc[BGM_SG][4];
+#pragma unroll
+    for (int g = 0; g < BGM_SG; ++g)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[g][k] = 0.0;
+    __syncthreads(); // the sums of the previous group have been read
+    if (mp != p)
+      for (int r = t; r < TR; r += WG)
+#pragma unroll
+        for (int g = 0; g <= BGM_SG; ++g) lds[g * BCG_TILE + r * mp + p] = 0.0; // (no staging loop writes the pad column)
+    for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+      const int64_t r0 = tb * TR;
+      const int rows = (int)(n - r0 < TR ? n - r0 : TR);
+      __syncthreads(); // the previous tile is no longer read
+      for (int e = t; e < rows * p; e += WG) {
+        const int r = e / p, l = r * mp + (e - r * p);
+        const int64_t gi = r0 * p + e;
+        const bool own = !MASKED || mask[r0 + r];
+        lds[l] = own ? W[gi] : 0.0;
+#pragma unroll
+        for (int g = 0; g < BGM_SG; ++g)
+          if (g < ng) lds[(g + 1) * BCG_TILE + l] = own ? V[(int64_t)(k0 + g) * vstride + gi] : 0.0;
+      }
+      __syncthreads();
+      if (s < NS)
+        for (int r = s; r < rows; r += NS) {
+          const double *w = lds + r * mp + 2 * oj;
+          const double w0 = w[0], w1 = w[1];
+#pragma unroll
+          for (int g = 0; g < BGM_SG; ++g)
+            if (g < ng) {
+              const double *v = lds + (g + 1) * BCG_TILE + r * mp + 2 * oi;
+              const double v0 = v[0], v1 = v[1];
+              acc[g][0] += v0 * w0;
+              acc[g][1] += v0 * w1;
+              acc[g][2] += v1 * w0;
+              acc[g][3] += v1 * w1;
+            }
+        }
+    }
+    __syncthreads(); // the tiles are done with: their LDS takes the accumulators, thread t's at 4 BGM_SG t
+#pragma unroll
+    for (int g = 0; g < BGM_SG; ++g)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) lds[t * (4 * BGM_SG) + g * 4 + k] = s < NS ? acc[g][k] : 0.0;
+    __syncthreads();
+    for (int idx = t; idx < NO * 4 * BGM_SG; idx += WG) {
+      const int oo = idx / (4 * BGM_SG), rem = idx - oo * (4 * BGM_SG), g = rem >> 2, k = rem & 3;
+      if (g >= ng) continue;
+      double sum = 0.0;
+      for (int ss = 0; ss < NS; ++ss) sum += lds[(ss * NO + oo) * (4 * BGM_SG) + rem];
+      const int i = 2 * (oo / hb) + (k >> 1), j = 2 * (oo % hb) + (k & 1);
+      if (i < p && j < p) partial[((int64_t)((k0 + g) * p + i) * p + j) * gridDim.x + blockIdx.x] = sum;
+    }
+  }
+}
+
+// Combination: Out (n x q) = (MODE 0) / += (1) / -= (2) sum_k V_k (n x pin) C_k (pin x q), the K coefficient blocks row-major one after
+// the other in device memory (what k_bgmres_project and k_reduce_final_multi leave behind IS that layout).  A tile is
+// TR = min(4 (WG / q), BCG_TILE / pin') rows (pin' = pin rounded up to even); thread t < (WG / q) q owns column c = t % q of the
+// rows t / q + i (WG / q), i < 4, of every tile.  Per stored block the V tile and C_k are staged; per entry the products are summed in
+// ascending k, then ascending row of C_k, and the sum is then applied to Out.  Out must not overlap a stored block.
+// GRAM (MODE 2, pin == q == p): the owner-masked partial sums of Out^T Out (p x p, the new Out) from the same pass, summed as
+// k_bgmres_project sums one block: partial[((i * p + j) * gridDim.x + b].
+template <int MODE, bool GRAM, bool MASKED>
+__global__ __launch_bounds__(WG) void k_bgmres_combine(int64_t n, int pin, int q, int K, const double *__restrict__ V, int64_t vstride,
+                                                       const double *__restrict__ coef, const uint8_t *__restrict__ mask, double *__restrict__ Out,
+                                                       double *__restrict__ partial)
+{
+  __shared__ double Vt[BCG_TILE], Ck[MULTI_MAX * MULTI_MAX], Ot[GRAM ? BCG_TILE : 1];
+  const int QR = WG / q, pe = (pin + 1) & ~1;
+  const int TR = 4 * QR < BCG_TILE / pe ? 4 * QR : BCG_TILE / pe;
+  const int t = threadIdx.x, r = t / q, c = t - r * q;
+  const bool on = r < QR;
+  // (GRAM) the layout of k_bcg_gram_partial on the Out tile
+  const int mp = (q + 1) & ~1, hb = mp >> 1, NO = hb * hb, NS = WG / NO;
+  const int s = t / NO, o = t - s * NO, oi = o / hb, oj = o - oi * hb;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (GRAM && mp != q)
+    for (int rr = t; rr < TR; rr += WG) Ot[rr * mp + q] = 0.0; // (the pad column is never written again)
+  const int64_t ntile = (n + TR - 1) / TR;
+  for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+    const int64_t r0 = tb * TR;
+    const int rows = (int)(n - r0 < TR ? n - r0 : TR);
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < K; ++k) {
+      __syncthreads(); // the previous V tile and C_k (and, GRAM, the previous Out tile) are no longer read
+      const double *vk = V + (int64_t)k * vstride + r0 * pin;
+      for (int e = t; e < rows * pin; e += WG) Vt[e] = vk[e];
+      for (int e = t; e < pin * q; e += WG) Ck[e] = coef[(int64_t)k * pin * q + e];
+      __syncthreads();
+      if (on)
+        for (int j = 0; j < pin; ++j) {
+          const double a = Ck[j * q + c];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int rr = r + i * QR;
+            if (rr < rows) sum[i] += Vt[rr * pin + j] * a;
+          }
+        }
+    }
+    if (on) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rr = r + i * QR;
+        if (rr < rows) {
+          const int64_t g = (r0 + rr) * q + c;
+          const double v = MODE == 0 ? sum[i] : MODE == 1 ? Out[g] + sum[i] : Out[g] - sum[i];
+          Out[g] = v;
+          if (GRAM) Ot[rr * mp + c] = (!MASKED || mask[r0 + rr]) ? v : 0.0;
+        }
+      }
+    }
+    if (GRAM) {
+      __syncthreads();
+      if (s < NS)
+        for (int rr = s; rr < rows; rr += NS) {
+          const double *u = Ot + rr * mp + 2 * oi, *w = Ot + rr * mp + 2 * oj;
+          const double u0 = u[0], u1 = u[1], w0 = w[0], w1 = w[1];
+          acc[0] += u0 * w0;
+          acc[1] += u0 * w1;
+          acc[2] += u1 * w0;
+          acc[3] += u1 * w1;
+        }
+    }
+  }
+  if (GRAM) {
+    __syncthreads(); // the tiles are done with: Vt takes the accumulators, thread t's at 4 t
+#pragma unroll
+    for (int k = 0; k < 4; ++k) Vt[t * 4 + k] = s < NS ? acc[k] : 0.0;
+    __syncthreads();
+    for (int idx = t; idx < NO * 4; idx += WG) {
+      const int oo = idx >> 2, k = idx & 3;
+      double tot = 0.0;
+      for (int ss = 0; ss < NS; ++ss) tot += Vt[(ss * NO + oo) * 4 + k];
+      const int i = 2 * (oo / hb) + (k >> 1), j = 2 * (oo % hb) + (k & 1);
+      if (i < q && j < q) partial[((int64_t)(i * q + j)) * gridDim.x + blockIdx.x] = tot;
+    }
+  }
+}
+
 } // namespace ddm

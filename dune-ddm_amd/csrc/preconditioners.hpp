@@ -586,7 +586,7 @@ struct ddm_combined {
   dbuf<double> mxw, mbw;       // ddm_cg_solve_queue: the slots' x and defect blocks (mqueue_cols)
   dbuf<int64_t> mqueue_tab;    // ... and its table of (slot, column) pairs, 2 * MULTI_MAX entries
   dbuf<double> mrt, mv, my;    // ddm_bicgstab_solve_queue: shadow defect, v and y (mbicg_cols); its x, r, p, t are mxw, mbw, mp, mq
-  dbuf<double> mz;             // ddm_bcg_solve_multi: the preconditioned defect block Z (mbcg_cols); its P and Q are mp, mq
+  dbuf<double> mz;             // ddm_bcg_solve_multi: the preconditioned defect block Z (mbcg_cols); its P and Q are mp, mq.  ddm_bgmres_solve_multi: its Z, U, W
   int mcols = 0, mcg_cols = 0, mqueue_cols = 0, mbicg_cols = 0, mbcg_cols = 0;
 };
 extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)

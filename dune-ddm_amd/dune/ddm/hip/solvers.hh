@@ -129,7 +129,7 @@ public:
   // Several right-hand sides at once: x.size() independent solves (1 to 32 columns) in one device loop (HipCGSolver: ddm_cg_solve_multi;
   // HipRestartedGMResSolver: ddm_gmres_solve_multi; HipRestartedFlexibleGMResSolver: ddm_fgmres_solve_multi; HipRestartedFCGSolver / HipCompleteFCGSolver: ddm_fcg_solve_multi), each column as apply(x[c], b[c], reduction, res[c]) would run it.  One upload and
   // one download of the whole row-major n x m block; b receives what the solver left there (the defects).  HipBlockCGSolver is the one
-  // solver whose columns are NOT independent: ddm_bcg_solve_multi, one shared search space.  A solver without a block
+  // solver whose columns are NOT independent: ddm_bcg_solve_multi, one shared search space; HipBlockGMResSolver likewise (ddm_bgmres_solve_multi).  A solver without a block
   // loop (HipBiCGSTABSolver) throws Dune::NotImplemented.
   void apply(std::vector<X>& x, std::vector<X>& b, double reduction, std::vector<InverseOperatorResult>& res)
   {
@@ -369,6 +369,37 @@ protected:
   double rank_tol_;
 };
 
+// [solver] type = blockgmressolver: block GMRES (ddm_bgmres_solve_multi), the companion of HipBlockCGSolver for a preconditioner or an
+// operator that is not symmetric -- the columns of the block apply share ONE Krylov space; not a dune-istl solver.  Right preconditioning
+// with a fixed preconditioner, the true defect is monitored.  restart: block iterations per cycle (default 30, as HipRestartedGMResSolver); maxit counts block iterations;
+// rank_tol: relative eigenvalue of the scaled Gram matrix of a block below which a direction counts as dependent.  res[c].iterations
+// is the first block iteration at which column c passed its test and stayed passed.  The single-vector apply is the block of width 1
+// (right-preconditioned restarted GMRES); apply_queue throws Dune::NotImplemented (there is no queued block GMRES).
+template <class X>
+class HipBlockGMResSolver : public HipKrylovSolverBase<X> {
+public:
+  HipBlockGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, double reduction, int restart, int maxit,
+                      int verbose = 0, double rank_tol = DDM_BGMRES_RANK_TOL_DEFAULT)
+      : HipKrylovSolverBase<X>(std::move(op), std::move(prec), reduction, maxit, verbose), restart_(restart), rank_tol_(rank_tol) {}
+  HipBlockGMResSolver(std::shared_ptr<LinearOperator<X, X>> op, std::shared_ptr<Preconditioner<X, X>> prec, const ParameterTree& cfg)
+      : HipBlockGMResSolver(std::move(op), std::move(prec), cfg.get("reduction", 1e-8), cfg.get("restart", 30), cfg.get("maxit", 1000),
+                            cfg.get("verbose", 0), cfg.get("rank_tol", DDM_BGMRES_RANK_TOL_DEFAULT)) {}
+
+  using HipKrylovSolverBase<X>::apply;
+
+protected:
+  int solve(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, double* x, double* b, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_bgmres_solve_multi(ctx, o, p, 1, x, b, reduction, this->maxit_, restart_, rank_tol_, nullptr, nullptr, r);
+  }
+  int solve_block(ddm_ctx* ctx, ddm_op* o, ddm_combined* p, int m, double* X_, double* B_, double reduction, ddm_solve_result* r) override
+  {
+    return ddm_bgmres_solve_multi(ctx, o, p, m, X_, B_, reduction, this->maxit_, restart_, rank_tol_, nullptr, nullptr, r);
+  }
+  int restart_;
+  double rank_tol_;
+};
+
 // [solver] type = bicgstabsolver: dune-istl BiCGSTABSolver::apply
 template <class X>
 class HipBiCGSTABSolver : public HipKrylovSolverBase<X> {
@@ -403,7 +434,8 @@ std::shared_ptr<InverseOperator<X, X>> getHipSolver(std::shared_ptr<LinearOperat
   if (type == "completefcgsolver") return std::make_shared<HipCompleteFCGSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "bicgstabsolver") return std::make_shared<HipBiCGSTABSolver<X>>(std::move(op), std::move(prec), cfg);
   if (type == "blockcgsolver") return std::make_shared<HipBlockCGSolver<X>>(std::move(op), std::move(prec), cfg);
-  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver, completefcgsolver, bicgstabsolver, blockcgsolver)");
+  if (type == "blockgmressolver") return std::make_shared<HipBlockGMResSolver<X>>(std::move(op), std::move(prec), cfg);
+  DUNE_THROW(NotImplemented, "solver type '" + type + "' has no device implementation (cgsolver, restartedgmressolver, restartedflexiblegmressolver, restartedfcgsolver, completefcgsolver, bicgstabsolver, blockcgsolver, blockgmressolver)");
 }
 
 }  // namespace Dune

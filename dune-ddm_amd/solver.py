@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import (BCG_RANK_TOL, bcg_solve_multi, CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
+from . import (BCG_RANK_TOL, BGMRES_RANK_TOL, bcg_solve_multi, bgmres_solve_multi, CombinedPreconditioner, Context, torch_context, gmres_solve, bicgstab_solve, CsrMatrix, GalerkinPreconditioner, Halo, NonOverlappingOperator,
                SchwarzPreconditioner, bicgstab_solve_queue, cg_solve, cg_solve_multi, cg_solve_queue, fcg_solve, fcg_solve_multi, fgmres_solve, fgmres_solve_multi, galerkin_products, gmres_solve_multi)
 from .problem import Decomposition, RankLocal
 
@@ -351,6 +351,19 @@ class TwoLevelSchwarz:
         Bd, X = self._blocks(B, X0)
         res, hist, ranks = bcg_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, rank_tol, history)
         return res, hist, X, ranks
+
+    def solve_block_gmres(self, B, reduction=1e-10, maxit=1000, restart=100, history=True, X0=None, rank_tol=BGMRES_RANK_TOL):
+        """m right-hand sides through ONE shared Krylov space: block GMRES (ddm_bgmres_solve_multi), the companion of ``solve_block``
+        for a preconditioner that is not symmetric (restricted Schwarz, the multiplicative combination, a non-symmetric operator).
+        Right preconditioning with a fixed preconditioner; the true defect is monitored and recomputed at every cycle end.  The block is
+        deflated at every cycle start, so dependent, duplicate and zero columns are safe and cost no width (rank_tol: relative
+        eigenvalue below which a direction counts as dependent).  maxit counts block iterations; restart: block iterations per cycle
+        (the basis takes (restart + 1) n_o m doubles).  B, X0: (n_o, m) arrays or tensors, m <= 32.  Returns (list of m SolveResult --
+        iterations: the first block iteration at which the column passed its test and stayed passed --, the (k_end + 1) x m history or
+        None, X as an (n_o, m) device tensor, the k_end cycle widths)."""
+        Bd, X = self._blocks(B, X0)
+        res, hist, widths = bgmres_solve_multi(self.ctx, self.op, self.prec, X, Bd, reduction, maxit, restart, rank_tol, history)
+        return res, hist, X, widths
 
     def solve_many(self, B, width=8, reduction=1e-10, maxit=1000, history=True, X0=None, solver="cgsolver"):
         """Any number M of right-hand sides, M independent solves through one block loop of ``width`` <= 32 slots: a slot whose column

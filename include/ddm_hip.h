@@ -664,6 +664,67 @@ int ddm_bcg_direction_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *be
  * for an entry that is not finite. */
 int ddm_dense_sym_pinv_host(int m, const double *W, double tol, double *Wpinv, int *rank);
 
+/* ---- block GMRES -----------------------------------------------------------------------------------------------------------------
+ * The non-symmetric companion of block CG: right-preconditioned block GMRES with a FIXED preconditioner (any linear map that does not
+ * change within the call: restricted Schwarz, the multiplicative combination, single-precision local solves).  The nrhs columns share
+ * one Krylov space; the true defect is monitored, as by CG and flexible GMRES; the basis is that of ddm_gmres_solve_multi, restart + 1
+ * blocks of n x nrhs doubles (half of the flexible variant's).  Blocks are n x nrhs row-major, 1 <= nrhs <= 32; <.,.> is the
+ * owner-masked scalar product summed over the ranks, U^T V the matrix of those products; maxit counts block iterations.
+ *   1. R = B - A X (in B); def0_c = ||R_c||; hist row 0.  def0_c < 1e-30: column c has converged with 0 iterations and is never
+ *      touched.  NaN: DDM_ENUMERIC naming the column.
+ *   2. Cycle start (deflation).  The running columns are those that have not passed their test.  G = R^T R over the running columns
+ *      (rows and columns of the others zero); on the host (ddm_dense_bgmres_factor_host) scaled with d_c = sqrt(G_cc) (1 where
+ *      G_cc = 0), eigen-decomposition of the scaled matrix, the p eigenvalues above rank_tol lambda_max kept:
+ *      T = Lambda^1/2 U^T D (p x nrhs), C0 = D^-1 U Lambda^-1/2 (nrhs x p); V_0 = R C0 is n x p with orthonormal columns, R = V_0 T.
+ *      The width p is fixed for the cycle; duplicate, dependent and zero columns cost no width.  p = 0 while a column runs: DDM_ENUMERIC.
+ *   3. Step j of the cycle (j < restart, k < maxit; k counts block iterations):
+ *        W = A M^-1 V_j (the block applies at width p);
+ *        H1 = [V_0 .. V_j]^T W;  W -= [V_0 .. V_j] H1;  H2 and a second subtraction the same way (block classical Gram-Schmidt twice);
+ *        G_W = W^T W from the pass of the second subtraction: four passes over the basis, three all-reduces, one host read-back;
+ *        H1 + H2 is column block j of the block Hessenberg matrix; G_W is factored as in 2., but scaled with
+ *        d_c^2 = sum_rows (H1 + H2)^2_{.c} + (G_W)_cc, the squared norm of W_c BEFORE the orthogonalisation (scaled by its own diagonal
+ *        a column of rounding noise would be a unit column and a rank drop would never be seen): S (rank x p) with S^T S = G_W,
+ *        C (p x rank); S, padded with zero rows to p x p, is the sub-diagonal block;
+ *        per running column c the monitored defect is the least-squares residual of min || E_1 T e_c - Hbar y || (incremental Householder
+ *        QR of the block Hessenberg matrix on the host; every rank computes the same numbers from the all-reduced coefficients);
+ *        rank = p: V_{j+1} = W C, the cycle goes on;  rank < p: the space is exhausted -- the step counts and enters the least squares,
+ *        the cycle ends after it.
+ *   4. Cycle end (restart, maxit, exhaustion, or every running column passes): U = [V_0 .. V_{j-1}] Y, Y one column per block column,
+ *      zero for the columns that do not run; Z = M^-1 U; X += Z; R -= A Z; the defect norms are recomputed (one block preconditioner
+ *      apply and one block operator apply at width nrhs per cycle) and overwrite the history row of the cycle's last step.  A column
+ *      that passed on the monitored value but fails on the recomputed one runs again.
+ *   5. Column c passes when def_c < reduction def0_c or def_c < 1e-30.  res[c].iterations = the first block iteration at which c
+ *      passed and stayed passed (the final k otherwise); converged and reduction come from the last recomputed defect.
+ *      hist_host (may be NULL; (maxit + 1) x nrhs): hist[k nrhs + c] = the monitored defect after block iteration k, recomputed at cycle
+ *      ends; a column that does not run repeats its last value, a zero column has zeros throughout.  width_hist_host (may be NULL;
+ *      maxit + 1 int32): entry k = the cycle width p of iteration k, entry 0 = 0.
+ * With nrhs = 1 the algorithm is right-preconditioned restarted GMRES.  At short restarts a single column can need an iteration more
+ * than its independent recurrence.
+ * DDM_EINVAL (before any device work; the message names the function) for NULL pointers, X == B, nrhs outside 1..32, maxit < 0,
+ * restart < 1 or rank_tol outside (0, 1); DDM_ENOTIMPL when the basis does not fit the free device memory; DDM_ENUMERIC for a NaN
+ * defect, coefficients that are not finite, width 0 while a column runs, a singular block Hessenberg matrix, and when a local solve
+ * gave up.  Nothing outlives the call on the device but the three n x nrhs work blocks of block CG in the preconditioner object; the
+ * active-column mask of the other drivers is not used. */
+#define DDM_BGMRES_RANK_TOL_DEFAULT 1e-12
+int ddm_bgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
+                           int restart, double rank_tol, double *hist_host, int32_t *width_hist_host, ddm_solve_result *res);
+/* Its three passes over the blocks on their own (for tests; synchronous; no atomics: two identical calls give identical bits).  V: K
+ * stored blocks of n x p (combine: n x pin) doubles one after the other; 1 <= p, pin, q <= 32, K >= 1.
+ *   project:      H_host (K p^2 doubles, block k row-major) = V_k^T W, owner-masked, all ranks.
+ *   combine:      Out (n x q) = (mode 0) / += (1) / -= (2) sum_k V_k C_k with coef_host = the K blocks C_k (pin x q row-major) one
+ *                 after the other; per entry the products are summed in ascending k, then ascending row of C_k, and the sum is then
+ *                 applied.  Out must not be V.
+ *   combine_gram: W (n x p) -= sum_k V_k C_k and G_host (p^2 doubles) = W^T W afterwards, owner-masked, all ranks, in one pass. */
+int ddm_bgmres_project_multi(ddm_ctx *ctx, ddm_op *op, int p, int K, const double *V, const double *W, double *H_host);
+int ddm_bgmres_combine_multi(ddm_ctx *ctx, ddm_op *op, int mode, int pin, int q, int K, const double *V, const double *coef_host, double *Out);
+int ddm_bgmres_combine_gram_multi(ddm_ctx *ctx, ddm_op *op, int p, int K, const double *V, const double *coef_host, double *W, double *G_host);
+/* host logic of steps 2 and 3, exposed for the CPU tests: the symmetric positive semi-definite p x p matrix G = S^T S with S (rank x p)
+ * and C (p x rank) with C^T G C = I -- scaling d_c = sqrt(|scale2_c|) (1 where 0; scale2 == NULL: the diagonal of G),
+ * eigen-decomposition of D^-1 (G + G^T) / 2 D^-1, the eigenvalues above tol lambda_max kept, largest first.  S and C are p x p
+ * row-major arrays: rows >= rank of S and columns >= rank of C are zero.  DDM_EINVAL for p < 1, NULL, overlapping arrays, tol outside
+ * (0, 1); DDM_ENUMERIC for an entry that is not finite. */
+int ddm_dense_bgmres_factor_host(int p, const double *G, const double *scale2, double tol, double *S, double *C, int *rank);
+
 /* ---- instrumentation ---------------------------------------------------------------------
  * Named event timers mirroring the reference's Logger events ("Schwarz/local solve", ...,
  * dune/ddm/schwarz.hh:178-181).  Times are HIP-event milliseconds accumulated on the stream. */
