@@ -1392,32 +1392,77 @@ struct RowChunk {
   int64_t r0, r1;
   int32_t sub, pad;
 };
+// a wave-uniform global pointer in scalar registers: loads through it take the scalar base + 32-bit lane offset form
+typedef const __attribute__((address_space(1))) double *uniform_gptr;
+__device__ __forceinline__ uniform_gptr uniform_global(const double *p)
+{
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (uniform_gptr)(((uint64_t)hi << 32) | lo);
+}
+// Vectors of one group of a restriction pass: the defect is loaded once per group, not once per vector.  10 is the largest count with
+// which k_coarse_restrict_spread stays within its 80 VGPRs (make resource-usage); the full-grid kernel's waves take five vectors each
+// at the usual 20 (82 VGPRs there, no scratch; about 50 instead of 64 us per launch in the setup's Galerkin products at 216^3).
+constexpr int COARSE_JG = 10, COARSE_JG_FULL = 5;
+// One wave, the JG vectors b0, b0 + vstride, ... over the rows of chunk `c`: out[jj * ostride] = <b_jj, d>.  Per trip of 8 x 64 rows a
+// lane loads its 8 defect values once, then the 8 basis values of each vector (two vectors = 16 loads in flight) and adds
+// s_jj += b * d in ascending row; the rows of an incomplete last trip one by one.  Per (lane, vector) that is rows r0 + l + 64 t in
+// ascending t, then wave_sum: whatever JG, the sums of the one-vector-at-a-time loop (JG = 1) in the same order.
+template <int JG>
+__device__ __forceinline__ void restrict_group(const double *__restrict__ b0, int64_t vstride, const RowChunk c, int lane,
+                                               const double *__restrict__ d, double *__restrict__ out, int ostride)
+{
+  double s[JG];
+#pragma unroll
+  for (int jj = 0; jj < JG; ++jj) s[jj] = 0.0;
+  int64_t rb = c.r0;
+  for (; rb + 8 * 64 <= c.r1; rb += 8 * 64) { // (the wave's trip base: uniform, the lane is a 32-bit offset)
+    const uniform_gptr dc = uniform_global(d + rb);
+    double dv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dv[u] = __builtin_nontemporal_load(dc + (unsigned)(lane + u * 64));
+#pragma unroll
+    for (int p = 0; p < JG; p += 2) {
+      const int nv = p + 1 < JG ? 2 : 1;
+      double bv[2][8];
+#pragma unroll
+      for (int v = 0; v < nv; ++v) {
+        const uniform_gptr bc = uniform_global(b0 + (int64_t)(p + v) * vstride + rb);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) bv[v][u] = __builtin_nontemporal_load(bc + (unsigned)(lane + u * 64));
+      }
+#pragma unroll
+      for (int v = 0; v < nv; ++v)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s[p + v] += bv[v][u] * dv[u];
+      __builtin_amdgcn_sched_barrier(0); // (two vectors' loads in flight, not more: the register budget)
+    }
+  }
+  for (; rb < c.r1; rb += 64) {
+    if (rb + lane >= c.r1) continue;
+    const double dr = __builtin_nontemporal_load(d + rb + lane);
+    const uniform_gptr bc = uniform_global(b0 + rb);
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) s[jj] += bc[(int64_t)jj * vstride + lane] * dr;
+  }
+#pragma unroll
+  for (int jj = 0; jj < JG; ++jj) {
+    const double t = wave_sum(s[jj]);
+    if (lane == 0) out[(int64_t)jj * ostride] = t;
+  }
+}
 __global__ __launch_bounds__(WG) void k_coarse_restrict_partial(int kmax, int64_t ld, const double *__restrict__ basis,
                                                                  const double *__restrict__ d, const RowChunk *__restrict__ chunks,
                                                                  double *__restrict__ partial /* [nchunk][kmax] */, int nchunk)
 {
   // (grid-stride over the chunks: a small grid keeps the kernel's footprint per CU low when it runs beside the local solve)
-  for (int ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-  const RowChunk c = chunks[ch];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int j = w; j < kmax; j += 4) {
-    const double *bj = basis + (int64_t)j * ld;
-    double s = 0.0;
-    // (eight loads of each stream in flight per lane; the products are added in the same order as one by one)
-    int64_t r = c.r0 + lane;
-    for (; r + 7 * 64 < c.r1; r += 8 * 64) {
-      double bv[8], dv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) bv[u] = __builtin_nontemporal_load(bj + r + u * 64);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) dv[u] = d[r + u * 64];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += bv[u] * dv[u];
-    }
-    for (; r < c.r1; r += 64) s += bj[r] * d[r];
-    s = wave_sum(s);
-    if (lane == 0) partial[(int64_t)ch * kmax + j] = s;
-  }
+  for (int ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const RowChunk c = chunks[ch];
+    int j = w; // the wave's vectors w, w + 4, ...: in groups, the rest one by one
+    for (; j + 4 * (COARSE_JG_FULL - 1) < kmax; j += 4 * COARSE_JG_FULL)
+      restrict_group<COARSE_JG_FULL>(basis + (int64_t)j * ld, 4 * ld, c, lane, d, partial + (int64_t)ch * kmax + j, 4);
+    for (; j < kmax; j += 4) restrict_group<1>(basis + (int64_t)j * ld, 4 * ld, c, lane, d, partial + (int64_t)ch * kmax + j, 4);
   }
 }
 // one workgroup: sums the chunk partials of each (subdomain, vector) in chunk order and scatters
@@ -1492,46 +1537,35 @@ __global__ __launch_bounds__(WG) void k_coarse_prolong(int kmax, int64_t ld, con
 }
 
 // ---- the two passes over the basis, spread: for the coarse chain that runs on a side stream BESIDE the single-launch local solve.
-// Workgroups of ONE wave, `w` per CU (the launch decides), persistent over the work items in grid-stride order: every CU carries the
-// same small share of the stream, and a wave needs few enough registers (make resource-usage: at most 80) to fit on a SIMD next to
-// two waves of k_trsv_pipe.  Sixteen loads per lane are in flight.  Same sums in the same order as the full-grid kernels above.
+// Workgroups of ONE wave (how many, the launch decides), persistent over the work items in grid-stride order: the CUs carry a
+// small share of the stream each, and a wave needs few enough registers (at most 80; make resource-usage: 80 the restriction, 66 the
+// prolongation, no scratch) to fit on a SIMD next to two waves of k_trsv_pipe.  128 bytes per lane are in flight.  Same sums in the
+// same order as the full-grid kernels above.
 constexpr int SPREAD_WG = 64;
-// a wave-uniform global pointer in scalar registers: loads through it take the scalar base + 32-bit lane offset form
-typedef const __attribute__((address_space(1))) double *uniform_gptr;
-__device__ __forceinline__ uniform_gptr uniform_global(const double *p)
-{
-  const uint64_t v = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (uniform_gptr)(((uint64_t)hi << 32) | lo);
-}
-// one partial per (chunk, j): lane l adds rows r0 + l + 64 t in ascending t, then wave_sum
+// one partial per (chunk, j), a work item is (chunk, group of COARSE_JG consecutive vectors): restrict_group above
 __global__ __launch_bounds__(SPREAD_WG) void k_coarse_restrict_spread(int kmax, int64_t ld, const double *__restrict__ basis,
                                                                        const double *__restrict__ d, const RowChunk *__restrict__ chunks,
                                                                        double *__restrict__ partial /* [nchunk][kmax] */, int nchunk)
 {
   const int lane = threadIdx.x;
-  const int64_t nitem = (int64_t)nchunk * kmax; // (item = chunk * kmax + j: the waves that run together share few chunks of d)
+  const int nfull = kmax / COARSE_JG, ngroup = nfull + (kmax % COARSE_JG != 0); // (the vectors of a short last group: one by one)
+  const int64_t nitem = (int64_t)nchunk * ngroup; // (item = chunk * ngroup + group: the waves that run together share few chunks of d)
   for (int64_t item = blockIdx.x; item < nitem; item += gridDim.x) {
-    const int ch = (int)(item / kmax), j = (int)(item % kmax);
+    const int ch = (int)(item / ngroup), g = (int)(item % ngroup);
     const RowChunk c = chunks[ch];
-    const double *bj = basis + (int64_t)j * ld;
-    double s = 0.0;
-    int64_t r = c.r0 + lane;
-    for (; r + 7 * 64 < c.r1; r += 8 * 64) {
-      double bv[8], dv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) bv[u] = __builtin_nontemporal_load(bj + r + u * 64);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) dv[u] = d[r + u * 64];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += bv[u] * dv[u];
-    }
-    for (; r < c.r1; r += 64) s += bj[r] * d[r];
-    s = wave_sum(s);
-    if (lane == 0) partial[item] = s;
+    const double *b0 = basis + (int64_t)g * COARSE_JG * ld;
+    double *out = partial + (int64_t)ch * kmax + g * COARSE_JG;
+    if (g < nfull)
+      restrict_group<COARSE_JG>(b0, ld, c, lane, d, out, 1);
+    else
+      for (int j = 0; j < kmax - nfull * COARSE_JG; ++j) restrict_group<1>(b0 + (int64_t)j * ld, ld, c, lane, d, out + j, 1);
   }
 }
-// four rows per lane and trip, four basis vectors of each in flight; per row the vectors are added in ascending j
+// Two neighbouring rows per lane and 16-byte load: a trip is two strips of 128 rows, four basis vectors of each in flight; per row the
+// vectors are added in ascending j.  The basis' leading dimension is a multiple of 64 rows, so that an even row is 16-byte aligned in
+// every vector: a chunk that starts at an odd row has that row taken alone, and so is an odd last row.
+typedef double double2_t __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) double2_t *uniform_gptr2;
 __global__ __launch_bounds__(SPREAD_WG) void k_coarse_prolong_spread(int kmax, int64_t ld, const double *__restrict__ basis,
                                                                       const double *__restrict__ x0, const int64_t *__restrict__ coarse_index,
                                                                       const RowChunk *__restrict__ chunks, double *__restrict__ xov, int nchunk)
@@ -1546,37 +1580,54 @@ __global__ __launch_bounds__(SPREAD_WG) void k_coarse_prolong_spread(int kmax, i
       cj[j] = gi >= 0 ? x0[gi] : 0.0;
     }
     __syncthreads();
-    for (int64_t rb = c.r0; rb < c.r1; rb += 4 * SPREAD_WG) { // (uniform trip base + 32-bit lane offsets: scalar-base addressing, few registers)
-      const int nrow = (int)(c.r1 - rb < 4 * SPREAD_WG ? c.r1 - rb : 4 * SPREAD_WG);
-      if (lane >= nrow) continue;
-      unsigned lo[4]; // (rows of the last trip that do not exist: the lane's first row, computed again and not stored)
+    const int64_t ra = c.r0 + (c.r0 & 1), re = ra + ((c.r1 - ra) & ~(int64_t)1); // the row pairs are [ra, re), ra even
+    {
+      const int64_t rs = lane == 0 && ra != c.r0 ? c.r0 : lane == 1 && re < c.r1 ? re : -1; // the single rows, one lane each
+      if (rs >= 0) {
+        double s = 0.0;
+        for (int j = 0; j < kmax; ++j) s += cj[j] * basis[(int64_t)j * ld + rs];
+        xov[rs] = s;
+      }
+    }
+    for (int64_t rb = ra; rb < re; rb += 4 * SPREAD_WG) { // (uniform trip base + 32-bit lane offsets: scalar-base addressing, few registers)
+      const int npair = (int)(re - rb < 4 * SPREAD_WG ? re - rb : 4 * SPREAD_WG) / 2;
+      if (lane >= npair) continue;
+      unsigned lo[2]; // (a pair of the last trip that does not exist: the lane's first pair, computed again and not stored)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) lo[q] = (unsigned)(lane + q * SPREAD_WG < nrow ? lane + q * SPREAD_WG : lane);
-      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int q = 0; q < 2; ++q) lo[q] = (unsigned)(lane + q * SPREAD_WG < npair ? lane + q * SPREAD_WG : lane);
+      double2_t s[2] = {{0.0, 0.0}, {0.0, 0.0}};
       int j = 0;
 #pragma unroll 1
       for (; j + 4 <= kmax; j += 4) {
-        double bv[4][4];
+        double2_t bv[2][4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const uniform_gptr bc = uniform_global(basis + (int64_t)(j + u) * ld + rb);
+          const uniform_gptr2 bc = (uniform_gptr2)uniform_global(basis + (int64_t)(j + u) * ld + rb);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) bv[q][u] = __builtin_nontemporal_load(bc + lo[q]);
+          for (int q = 0; q < 2; ++q) bv[q][u] = __builtin_nontemporal_load(bc + lo[q]);
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < 2; ++q)
 #pragma unroll
-          for (int u = 0; u < 4; ++u) s[q] += cj[j + u] * bv[q][u];
+          for (int u = 0; u < 4; ++u) {
+            const double cu = cj[j + u];
+            s[q].x += cu * bv[q][u].x;
+            s[q].y += cu * bv[q][u].y;
+          }
       }
       for (; j < kmax; ++j) {
-        const double *bc = basis + (int64_t)j * ld + rb;
+        const double2_t *bc = (const double2_t *)(basis + (int64_t)j * ld + rb);
+        const double cu = cj[j];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += cj[j] * bc[lo[q]];
+        for (int q = 0; q < 2; ++q) {
+          const double2_t b = bc[lo[q]];
+          s[q].x += cu * b.x;
+          s[q].y += cu * b.y;
+        }
       }
-      xov[rb + lo[0]] = s[0];
-#pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (lo[q] != (unsigned)lane) xov[rb + lo[q]] = s[q];
+      double2_t *xo = (double2_t *)(xov + rb);
+      xo[lo[0]] = s[0];
+      if (lo[1] != (unsigned)lane) xo[lo[1]] = s[1];
     }
   }
 }

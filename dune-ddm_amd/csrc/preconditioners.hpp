@@ -571,7 +571,20 @@ extern "C" int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
 // ---- CombinedPreconditioner --------------------------------------------------------------------
 // the coarse chain beside the local solve (combined_apply_fused): whether it is on where DDM_OVERLAP_COARSE is unset, and its width
 constexpr bool OVERLAP_DEFAULT = true;
-constexpr int OVERLAP_WAVES_PER_CU = 1; // (measured at 1, 2 and 4, and at half a wave per CU: DESIGN.md section 4)
+// One-wave workgroups of the side stream's basis passes: OVERLAP_WAVES_PER_16_CU per 16 CUs at up to OVERLAP_KMAX_MEASURED basis
+// vectors per subdomain, in proportion to the vector count beyond that, never more than one per CU (overlap_default_grid).
+// The width is tuned at ONE shape (216^3, 27-point rows, 20 vectors: DESIGN.md section 4, measured at 5, 6, 7, 8, 16 and 32 per 16
+// CUs) and the optimum has a steep side: the narrower the chain, the less it slows the solve beside it, but a chain that outlasts
+// the solve is paid in full (5 per 16 CUs: 4.84 instead of 4.28 ms per iteration).  7 per 16 CUs leaves the chain 0.4 ms of a
+// 3.5 ms solve.  The chain's time grows with vectors x rows, hence the scaling; a local solve that is much cheaper per row than
+// ILU(0) of a 27-point matrix is not covered by it and wants DDM_OVERLAP_GRID.
+constexpr int OVERLAP_WAVES_PER_16_CU = 7, OVERLAP_KMAX_MEASURED = 20;
+static int overlap_default_grid(int num_cu, int64_t kmax)
+{
+  const int64_t k = std::max<int64_t>(kmax, OVERLAP_KMAX_MEASURED);
+  const int64_t g = (OVERLAP_WAVES_PER_16_CU * num_cu * k + 16 * OVERLAP_KMAX_MEASURED - 1) / (16 * OVERLAP_KMAX_MEASURED);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(g, num_cu));
+}
 struct ddm_combined {
   int mode = 0;
   ddm_op *op = nullptr;
@@ -603,10 +616,10 @@ extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwa
   if (mode == 0 && galerkin) {
     const char *f = std::getenv("DDM_FUSE_LEVELS");    // "0": the two levels one after the other (two halo adds: the reference's order of sums)
     const char *e = std::getenv("DDM_OVERLAP_COARSE"); // "1" / "0": coarse chain on a side stream / not; unset: OVERLAP_DEFAULT, pipe engine only
-    const char *g = std::getenv("DDM_OVERLAP_GRID");   // workgroups of the side stream's basis passes (default OVERLAP_WAVES_PER_CU per CU)
+    const char *g = std::getenv("DDM_OVERLAP_GRID");   // workgroups of the side stream's basis passes (default: overlap_default_grid)
     C->fused = !(f && f[0] == '0') && galerkin->copy == schwarz->copy && galerkin->add == schwarz->add && galerkin->n == schwarz->n && galerkin->n_novlp == schwarz->n_novlp;
     if (C->fused && (ctx->nranks == 1 || ctx->rccl)) C->overlap = e ? (e[0] == '1' ? 1 : 0) : (OVERLAP_DEFAULT ? 2 : 0);
-    C->side_grid = g ? std::max(1, std::atoi(g)) : OVERLAP_WAVES_PER_CU * ctx->num_cu;
+    C->side_grid = g ? std::max(1, std::atoi(g)) : overlap_default_grid(ctx->num_cu, galerkin->kmax);
   }
   if (C->dnext.alloc(C->n) != hipSuccess) return fail(ctx, DDM_EHIP, "combined: allocation failed");
   *out = C.release();
@@ -625,8 +638,8 @@ extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
 //   extend + copy-halo -> local solve -> (POU scale) -> R d -> all-reduce -> A0^-1 -> R^T x0 -> x_s += x_c -> halo add -> restrict
 // two_streams (C->overlap; needs the in-library exchange or a single rank): the coarse chain runs on a low-priority side stream BESIDE
 // the local solve, which is latency-bound and leaves most of the HBM bandwidth idle.  The chain's two passes over the basis are the
-// spread kernels (one-wave workgroups, C->side_grid of them: every CU carries the same small share of the stream and the solve's
-// workgroups stay resident next to them).  With the pipe engine the chain joins between the solve kernel and its output permutation,
+// spread kernels (one-wave workgroups, C->side_grid of them, fewer than CUs by default: a wave is small enough for the solve's
+// workgroups to stay resident next to it, and the chain is kept as narrow as still ends inside the solve).  With the pipe engine the chain joins between the solve kernel and its output permutation,
 // which applies "x *= pou; x += x_coarse" as on one stream: the same kernels' sums in the same order, the result is bit-identical.
 // The other engines join behind the solve with k_scale + k_axpy (the same operations as separate passes).
 // Measurements, the losing configurations included: DESIGN.md section 4.
