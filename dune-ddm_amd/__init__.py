@@ -498,7 +498,7 @@ class Ilu0:
         return st.value
 
     def factors(self):
-        out = np.empty(self.A.nnz, dtype=np.float64)
+        out = np.empty(self.nnz, dtype=np.float64)                # the factor's own entries: a direct factor holds its fill
         self.ctx.check(self.ctx.lib.ddm_ilu0_get_factors_host(self.ctx.h, self.h, _hp(out)))
         return out
 

@@ -34,21 +34,26 @@ static void enqueue_sn_panel(ddm_ctx *ctx, const ddm_ilu0 *F, int w, const doubl
 }
 // Host sparse direct factor: gather, the two level solves in the fill-reducing order, scatter.  block = false: the single vector
 // (nrhs = 1) on F->pd / F->px with the single-vector kernels, one workgroup per block where the factor has that order (Lb / Ub);
-// block = true: nrhs columns on the packed work blocks F->pD / F->pX, one launch per global level (Lc / Uc).
+// block = true: nrhs columns in panels of at most CSR_PANEL_COLS on the packed work blocks F->pD / F->pX (leading dimension: the
+// panel's width), one launch per global level (Lc / Uc) and panel.
+constexpr int CSR_PANEL_COLS = WG; // k_trsv_csr_level_multi gives every column of a row a thread of one workgroup
 static int enqueue_csr_direct(ddm_ctx *ctx, const ddm_ilu0 *F, bool block, int nrhs, const double *D, int64_t ldd, double *X, int64_t ldx)
 {
   const CsrDirect &C = *F->csr;
   double *wd = block ? F->pD : F->pd, *wx = block ? F->pX : F->px;
-  const dim3 grid(grid_for(F->n * nrhs));
-  hipLaunchKernelGGL(k_perm_gather, grid, dim3(WG), 0, ctx->stream, F->n, nrhs, C.perm, D, ldd, wd);
-  if (block) {
-    enqueue_multi_levels_csr(ctx, C.Lc, false, nrhs, wd, nrhs, wx, nrhs);
-    enqueue_multi_levels_csr(ctx, C.Uc, true, nrhs, wd, nrhs, wx, nrhs);
-  } else {
-    DDMCHECK(enqueue_tri_csr(ctx, C.Lb.nblocks ? C.Lb : C.Lc, false, wd, wx));
-    DDMCHECK(enqueue_tri_csr(ctx, C.Ub.nblocks ? C.Ub : C.Uc, true, wd, wx));
+  for (int c0 = 0; c0 < nrhs; c0 += CSR_PANEL_COLS) {
+    const int w = std::min(CSR_PANEL_COLS, nrhs - c0);
+    const dim3 grid(grid_for(F->n * w));
+    hipLaunchKernelGGL(k_perm_gather, grid, dim3(WG), 0, ctx->stream, F->n, w, C.perm, D + c0, ldd, wd);
+    if (block) {
+      enqueue_multi_levels_csr(ctx, C.Lc, false, w, wd, w, wx, w);
+      enqueue_multi_levels_csr(ctx, C.Uc, true, w, wd, w, wx, w);
+    } else {
+      DDMCHECK(enqueue_tri_csr(ctx, C.Lb.nblocks ? C.Lb : C.Lc, false, wd, wx));
+      DDMCHECK(enqueue_tri_csr(ctx, C.Ub.nblocks ? C.Ub : C.Uc, true, wd, wx));
+    }
+    hipLaunchKernelGGL(k_perm_scatter, grid, dim3(WG), 0, ctx->stream, F->n, w, C.perm, (const double *)wx, X + c0, ldx);
   }
-  hipLaunchKernelGGL(k_perm_scatter, grid, dim3(WG), 0, ctx->stream, F->n, nrhs, C.perm, (const double *)wx, X, ldx);
   return DDM_OK;
 }
 
@@ -233,7 +238,7 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
       F->graph.reset(); // (the single-vector graph holds the old residual buffer)
     }
   }
-  if (F->csr) HIPCHECK(ctx, reserve_cols<double>(F->pm_nrhs, nrhs, {{F->pX, F->n + F->csr->nvirt}, {F->pD, F->n}}));
+  if (F->csr) HIPCHECK(ctx, reserve_cols<double>(F->pm_nrhs, std::min(nrhs, CSR_PANEL_COLS), {{F->pX, F->n + F->csr->nvirt}, {F->pD, F->n}})); // one panel
   return capture_and_launch(ctx, F->mgraph, key, [&]() {
     if (F->sn) {
       for (int c0 = 0; c0 < nrhs; c0 += 48) enqueue_sn_panel(ctx, F, std::min(48, nrhs - c0), D + c0, ldd, X + c0, ldx, F->pD, nullptr, nullptr);

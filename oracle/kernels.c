@@ -186,3 +186,31 @@ void orc_dense_lu_solve(i64 n, const double *a, const i64 *piv, double *b)
     b[i] = s / a[i * n + i];
   }
 }
+
+/* Checker arithmetic of tests/direct_cases.py (no counterpart in the reference): r = d - L (U x) in long double for m vectors,
+ * one after the other in memory (xt, dt, rt: m x n, a vector contiguous), against a factor lu in the pattern rp / ci with sorted
+ * rows -- multipliers of the unit lower L left of the diagonal diag[i], U right of it, the INVERSE pivot on it (orc_ilu0_factor's
+ * layout).  rt holds r rounded to double.  The vectors are independent: one thread each. */
+void orc_lu_residual_ld(i64 n, const i64 *rp, const i64 *ci, const double *lu, const i64 *diag, i64 m, const double *xt, const double *dt, double *rt)
+{
+#pragma omp parallel
+  {
+    long double *ux = (long double *)malloc(sizeof(long double) * (size_t)(n > 0 ? n : 1));
+#pragma omp for schedule(dynamic, 1)
+    for (i64 j = 0; j < m; ++j) {
+      const double *x = xt + j * n, *d = dt + j * n;
+      double *r = rt + j * n;
+      for (i64 i = 0; i < n; ++i) {
+        long double s = (long double)x[i] / (long double)lu[diag[i]];
+        for (i64 k = diag[i] + 1; k < rp[i + 1]; ++k) s += (long double)lu[k] * (long double)x[ci[k]];
+        ux[i] = s;
+      }
+      for (i64 i = 0; i < n; ++i) {
+        long double s = ux[i];
+        for (i64 k = rp[i]; k < diag[i]; ++k) s += (long double)lu[k] * ux[ci[k]];
+        r[i] = (double)((long double)d[i] - s);
+      }
+    }
+    free(ux);
+  }
+}
