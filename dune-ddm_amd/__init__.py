@@ -82,6 +82,7 @@ SYMBOLS = {
     "ddm_csr_row_order_tiled_host": (_I32, [_I64, _P, _P, _P, _P]),
     "ddm_dia_build_and_apply_host": (_I32, [_I64, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ddm_dia_windows_host": (_I32, [_I64, _P, _P, _P, _I64, _P, _I64, _P, _P]),
+    "ddm_dia_codes_host": (_I32, [_I64, _P, _P, _P, _I32, _I64, _P, _P, _P, _P]),
     "ddm_ilu0_solve_multi": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_solve_multi_f32": (_I32, [_P, _P, _I32, _P, _P]),
     "ddm_ilu0_create": (_I32, [_P, _P, _I64, _P, _PP]),
@@ -1118,6 +1119,28 @@ def dia_windows_host(A):
         raise ValueError("ddm_dia_windows_host: bad arguments")
     out = [dict(staged=bool(s[0]), window=int(s[2]), runs=[tuple(r) for r in runs[s[3]:s[3] + s[1]].tolist()]) for s in segs[:counts[0]]]
     return out, int(counts[2])
+
+
+def dia_codes_host(A, threads=0, arrays=True):
+    """dict(coded, entries, slabs, dictionaries, codes, slots_built): the coded blocks of the same layout.  Per block: whether a
+    dictionary of at most 16 values and 4-bit codes stand for its values, the dictionary entries in use (0: not coded) and whether
+    its segment has value slabs; dictionaries: (coded blocks, 16) doubles in block order; codes: (rows, 4) uint32 words, nibble k
+    for diagonal k (both None with arrays=False); slots_built: doubles of the slabs that were built.  `threads`: host workers
+    of the build (0: the library's own number).  Host only."""
+    lib = load_library()
+    n = A.shape[0]
+    rp, ci, va = _np(A.indptr, np.int64), _np(A.indices, np.int32), _np(A.data, np.float64)
+    blocks = np.zeros((n + 1, 3), dtype=np.int32)
+    dicts = np.zeros((n + 1, 16), dtype=np.float64) if arrays else None
+    codes = np.zeros((n, 4), dtype=np.uint32) if arrays else None
+    counts = np.zeros(5, dtype=np.int64)
+    rc = lib.ddm_dia_codes_host(n, _hp(rp), _hp(ci), _hp(va), int(threads), n + 1, _hp(blocks), _hp(dicts), _hp(codes), _hp(counts))
+    if rc != DDM_OK:
+        raise ValueError("ddm_dia_codes_host: bad arguments")
+    assert counts[3] == 16 and counts[4] == 4
+    blocks = blocks[:counts[0]]
+    return dict(coded=blocks[:, 0] >= 0, entries=blocks[:, 1].copy(), slabs=blocks[:, 2].astype(bool),
+                dictionaries=dicts[:counts[1]] if arrays else None, codes=codes, slots_built=int(counts[2]))
 
 
 def blockvec_gram(ctx: Context, sub_ptr, U, V):

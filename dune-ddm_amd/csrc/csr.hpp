@@ -331,6 +331,13 @@ extern "C" int ddm_csr_mm(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double
 // the WG + (l - f) consecutive doubles x[r0 + f ...] (clamped to the vector): its window; the windows lie back to back, thread t
 // finds x[r + off[k]] at lds_pos[k] + t.  A segment whose windows fit DIA_WIN doubles is staged: its blocks load the windows into
 // LDS once instead of one x load per diagonal and row (stage_x = false, DDM_SPMV_STAGE_X=0: no segment is).
+// Coded blocks: the values of a structured operator repeat, so a block of a staged segment whose rows read at most DIA_DICT distinct
+// bit patterns (compared as uint64: +0.0 and -0.0 differ, NaN payloads are kept) stores them once, in a dictionary of DIA_DICT
+// doubles in order of first appearance (rows ascending, diagonals ascending inside a row; padded with +0.0), and every row a
+// 128-bit word of 4-bit codes, nibble k for diagonal k of the segment's table (absent entries and slots from nd on: code 0, the
+// mask decides).  The words are indexed by global row like the mask.  A segment whose blocks are all coded builds no slabs; one
+// with any uncoded block keeps them all.  Each block is coded on its own, so the result does not depend on host_threads()
+// (code = false, DDM_SPMV_CODE=0: no block is coded).
 constexpr int64_t DIA_SPLIT_ROWS = 256 * WG;
 struct DiaRun {
   int32_t first, len, start; // first offset, window doubles WG + (last - first), window position
@@ -346,13 +353,18 @@ struct DiaLayout {
   std::vector<int32_t> tab;    // per segment: a record of DIA_REC ints (kernels.hpp: DIA_TAB_*; tails of the rows repeat the last entry)
   std::vector<DiaSegWindows> win; // per segment: the runs of its offset table (all of them, staged or not)
   hvec<uint32_t> mask;         // per row: bit k set = the row has an entry on diagonal k of its block's table
-  hvec<double> val;            // absent entries 0.0 (loaded, never added)
+  hvec<double> val;            // absent entries 0.0 (loaded, never added); the segments whose blocks are all coded have no slabs
+  hvec<uint32_t> code;         // per row: DIA_CODE_WORDS words of 4-bit codes (rows of uncoded blocks: 0), or empty: no block is coded
+  hvec<double> dict;           // per coded block, in block order: DIA_DICT doubles
+  std::vector<int32_t> ndict;  // per block: dictionary entries in use (0: not coded)
+  std::vector<uint8_t> slabs;  // per block: its segment has value slabs (a diagonal block that is not coded reads them)
+  int64_t ncoded = 0, slots_slab = 0; // coded blocks; the value slots of the slab layout (what val would hold with no segment coded)
   int64_t ndia = 0, ncsr = 0, rows_dia = 0, nseg = 0, nseg_half = 0; // blocks of either kind, rows in diagonal blocks, segments, symmetric ones
 };
 template <class F>
-static void dia_parallel_for(int64_t njobs, F &&job)
+static void dia_parallel_for(unsigned threads, int64_t njobs, F &&job)
 {
-  const unsigned nth = (unsigned)std::max<int64_t>(1, std::min<int64_t>(host_threads(), njobs));
+  const unsigned nth = (unsigned)std::max<int64_t>(1, std::min<int64_t>(threads, njobs));
   std::atomic<int64_t> next{0};
   auto work = [&]() {
     for (int64_t j; (j = next.fetch_add(1)) < njobs;) job(j);
@@ -368,7 +380,14 @@ static bool dia_stage_x_from_env()
   const char *e = std::getenv("DDM_SPMV_STAGE_X");
   return !(e && !std::strcmp(e, "0"));
 }
-static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const double *va, DiaLayout &L, bool stage_x = true)
+// DDM_SPMV_CODE=0 (read at the same places): no block is coded by a dictionary, every segment keeps its slabs
+static bool dia_code_from_env()
+{
+  const char *e = std::getenv("DDM_SPMV_CODE");
+  return !(e && !std::strcmp(e, "0"));
+}
+static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const double *va, DiaLayout &L, bool stage_x = true, bool code = true,
+                      unsigned threads = host_threads())
 {
   L = DiaLayout();
   if (n <= 0 || n >= (int64_t)1 << 30) return; // (row + offset is computed in 32 bits)
@@ -388,7 +407,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
       if (rp[r + 1] > rp[r]) prefmax = std::max(prefmax, ci[rp[r + 1] - 1]);
     }
   }
-  dia_parallel_for(nparts, [&](int64_t p) {
+  dia_parallel_for(threads, nparts, [&](int64_t p) {
     Part &P = parts[(size_t)p];
     const int64_t c0 = p * DIA_SPLIT_ROWS, c1 = std::min(n, c0 + DIA_SPLIT_ROWS);
     int64_t csr_from = -1;
@@ -397,7 +416,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
         int64_t r1 = r;
         while (r1 < end && r1 - r < WG && rp[r1 + 1] - rp[r] <= SPMV_NNZ) ++r1;
         if (r1 == r) r1 = r + 1; // long row
-        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, 0, 0, 0, 0});
+        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, 0, 0, 0, 0, -1, 0});
         r = r1;
       }
       csr_from = -1;
@@ -419,7 +438,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
       }
       if (entries > 0 && 2 * entries >= (r1 - r) * nt) {
         flush_csr(r);
-        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, nt, (int32_t)P.off.size(), cut[(size_t)r] /* a segment starts here */, 0});
+        P.blk.push_back(DiaBlock{0, (int32_t)r, (int32_t)r1, nt, (int32_t)P.off.size(), cut[(size_t)r] /* a segment starts here */, 0, -1, 0});
         P.off.insert(P.off.end(), T, T + nt);
         r = r1;
       } else {
@@ -434,6 +453,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
     int64_t r0, r1, base = 0;
     int32_t off[DIA_MAX];
     int nd = 0, nlow = 0; // nlow > 0: symmetric, the nlow offsets < 0 are not stored
+    bool staged = false, slabs = true; // slabs = false: every block is coded
     std::atomic<bool> full{false};
     Seg(int64_t a) : r0(a), r1(a) {}
   };
@@ -454,13 +474,14 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
       seg_of.push_back(B.nd ? (int32_t)segs.size() - 1 : -1);
       L.blk.push_back(B);
     }
+  L.stored.assign(L.blk.size(), 0), L.ndict.assign(L.blk.size(), 0), L.slabs.assign(L.blk.size(), 0);
   if (!L.ndia) return; // all CSR: the caller keeps the CSR product
   for (Seg &S : segs) { // a table that is its own mirror image, else full storage
     bool mirror = true;
     for (int k = 0; k < S.nd; ++k) mirror = mirror && S.off[k] == -S.off[S.nd - 1 - k];
     S.full = !mirror;
   }
-  dia_parallel_for((int64_t)L.blk.size(), [&](int64_t b) { // every entry below the diagonal has its partner in the segment, bit for bit
+  dia_parallel_for(threads, (int64_t)L.blk.size(), [&](int64_t b) { // every entry below the diagonal has its partner in the segment, bit for bit
     if (seg_of[(size_t)b] < 0) return;
     Seg &S = segs[(size_t)seg_of[(size_t)b]];
     const DiaBlock &B = L.blk[(size_t)b];
@@ -474,14 +495,12 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
         }
       }
   });
-  int64_t slots = 0;
   L.nseg = (int64_t)segs.size();
   for (Seg &S : segs) {
     if (!S.full)
       while (S.off[S.nlow] < 0) ++S.nlow;
     L.nseg_half += S.nlow > 0;
-    S.base = slots;
-    slots += (S.nd - S.nlow) * (S.r1 - S.r0);
+    L.slots_slab += (S.nd - S.nlow) * (S.r1 - S.r0);
     DiaSegWindows Wd;
     int32_t pos[DIA_MAX];
     for (int k = 0; k < S.nd; ++k) {
@@ -499,7 +518,7 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
       rec[DIA_TAB_SHIFT + k] = q < S.nlow ? S.off[q] : 0;                      // ... at the partner's row
       rec[DIA_TAB_POS + k] = Wd.staged ? pos[q] : 0;
     }
-    rec[DIA_TAB_STAGED] = Wd.staged;
+    rec[DIA_TAB_STAGED] = S.staged = Wd.staged;
     for (int j = 0; j < DIA_RUNS; ++j) rec[DIA_TAB_RSTART + j] = DIA_WIN; // (a run that is not there starts behind every window)
     if (Wd.staged) { // (at most DIA_RUNS runs fit DIA_WIN doubles: each owns at least WG)
       rec[DIA_TAB_NRUNS] = (int32_t)Wd.runs.size(), rec[DIA_TAB_WINDOW] = Wd.window;
@@ -509,34 +528,95 @@ static void dia_build(int64_t n, const int64_t *rp, const int32_t *ci, const dou
     L.tab.insert(L.tab.end(), rec, rec + DIA_REC);
     L.win.push_back(std::move(Wd));
   }
-  L.stored.resize(L.blk.size(), 0);
+  // dictionaries and code words of the blocks of staged segments, block by block
+  bool any_staged = false;
+  for (const Seg &S : segs) any_staged = any_staged || S.staged;
+  if (code && any_staged) {
+    L.code.resize((size_t)n * DIA_CODE_WORDS);
+    hvec<double> found(L.blk.size() * (size_t)DIA_DICT); // (per block: the patterns in order of first appearance)
+    dia_parallel_for(threads, (int64_t)L.blk.size(), [&](int64_t b) {
+      const DiaBlock &B = L.blk[(size_t)b];
+      uint32_t *words = L.code.data() + (size_t)B.r0 * DIA_CODE_WORDS;
+      std::fill(words, words + (size_t)(B.r1 - B.r0) * DIA_CODE_WORDS, 0u);
+      if (seg_of[(size_t)b] < 0 || !segs[(size_t)seg_of[(size_t)b]].staged) return;
+      const Seg &S = segs[(size_t)seg_of[(size_t)b]];
+      uint64_t pat[DIA_DICT];
+      int np = 0;
+      for (int64_t r = B.r0; r < B.r1 && np <= DIA_DICT; ++r) {
+        int k = 0;
+        for (int64_t z = rp[r]; z < rp[r + 1]; ++z) {
+          while (S.off[k] < ci[z] - r) ++k; // both ascending; the offset is in the table
+          uint64_t bits;
+          std::memcpy(&bits, va + z, sizeof bits);
+          int c = 0;
+          while (c < np && pat[c] != bits) ++c;
+          if (c == np) {
+            if (np == DIA_DICT) { // the 17th pattern: not coded
+              np = DIA_DICT + 1;
+              break;
+            }
+            pat[np++] = bits;
+          }
+          words[(size_t)(r - B.r0) * DIA_CODE_WORDS + k / 8] |= (uint32_t)c << (4 * (k % 8));
+        }
+      }
+      if (np > DIA_DICT) {
+        std::fill(words, words + (size_t)(B.r1 - B.r0) * DIA_CODE_WORDS, 0u);
+        return;
+      }
+      L.ndict[(size_t)b] = np; // (a block of a diagonal segment has an entry: np >= 1)
+      std::fill(pat + np, pat + DIA_DICT, (uint64_t)0);
+      std::memcpy(found.data() + (size_t)b * DIA_DICT, pat, sizeof pat);
+    });
+    for (Seg &S : segs) S.slabs = false;
+    for (size_t b = 0; b < L.blk.size(); ++b) {
+      if (seg_of[b] >= 0 && !L.ndict[b]) segs[(size_t)seg_of[b]].slabs = true; // one uncoded block: the segment keeps its slabs
+      L.ncoded += L.ndict[b] > 0;
+    }
+    if (!L.ncoded) L.code = hvec<uint32_t>();
+    else {
+      L.dict.resize((size_t)L.ncoded * DIA_DICT);
+      int32_t at = 0;
+      for (size_t b = 0; b < L.blk.size(); ++b)
+        if (L.ndict[b]) {
+          std::memcpy(L.dict.data() + (size_t)at * DIA_DICT, found.data() + b * DIA_DICT, sizeof(double) * DIA_DICT);
+          L.blk[b].dict = at++;
+        }
+    }
+  }
+  int64_t slots = 0;
+  for (Seg &S : segs) {
+    S.base = slots;
+    if (S.slabs) slots += (S.nd - S.nlow) * (S.r1 - S.r0);
+  }
   for (size_t b = 0; b < L.blk.size(); ++b) {
     if (seg_of[b] < 0) continue;
     const Seg &S = segs[(size_t)seg_of[b]];
     DiaBlock &B = L.blk[b];
     B.nd = S.nd, B.tab = seg_of[b] * DIA_REC;
     B.t0 = (int32_t)(B.r0 - S.r0), B.stride = (int32_t)(S.r1 - S.r0);
-    B.base = S.base + B.t0;
-    L.stored[b] = S.nd - S.nlow;
+    B.base = S.slabs ? S.base + B.t0 : 0;
+    L.stored[b] = S.nd - S.nlow, L.slabs[b] = S.slabs;
   }
   L.mask.resize((size_t)n);
   L.val.resize((size_t)slots);
-  dia_parallel_for((int64_t)L.blk.size(), [&](int64_t b) {
+  dia_parallel_for(threads, (int64_t)L.blk.size(), [&](int64_t b) {
     const DiaBlock &B = L.blk[(size_t)b];
     if (!B.nd) {
       std::fill(L.mask.begin() + B.r0, L.mask.begin() + B.r1, 0u);
       return;
     }
+    const bool slabs = L.slabs[(size_t)b];
     const int nlow = B.nd - L.stored[(size_t)b];
     double *v = L.val.data() + B.base; // (slab 0, row r0)
-    for (int j = 0; j < B.nd - nlow; ++j) std::fill(v + (int64_t)j * B.stride, v + (int64_t)j * B.stride + (B.r1 - B.r0), 0.0);
+    for (int j = 0; slabs && j < B.nd - nlow; ++j) std::fill(v + (int64_t)j * B.stride, v + (int64_t)j * B.stride + (B.r1 - B.r0), 0.0);
     const int32_t *off = L.tab.data() + B.tab + DIA_TAB_OFF;
     for (int64_t r = B.r0; r < B.r1; ++r) {
       uint32_t m = 0;
       int k = 0;
       for (int64_t z = rp[r]; z < rp[r + 1]; ++z) {
         while (off[k] < ci[z] - r) ++k; // both ascending; the offset is in the table
-        if (k >= nlow) v[(int64_t)(k - nlow) * B.stride + (r - B.r0)] = va[z];
+        if (slabs && k >= nlow) v[(int64_t)(k - nlow) * B.stride + (r - B.r0)] = va[z];
         m |= 1u << k;
       }
       L.mask[(size_t)r] = m;
@@ -564,8 +644,14 @@ static void dia_apply_host(const DiaLayout &L, int64_t n, const int64_t *rp, con
         for (int64_t z = rp[r]; z < rp[r + 1]; ++z) s += va[z] * x[ci[z]];
       else
         for (int k = 0; k < B.nd; ++k) {
-          const int64_t at = (int64_t)slab[k] * B.stride + std::min(std::max(B.t0 + t + shift[k], 0), B.stride - 1);
-          const double v = L.val[(size_t)(B.base - B.t0 + at)];
+          double v;
+          if (B.dict >= 0) { // coded (and staged): nibble k of the row's word, through the block's dictionary
+            const uint32_t c = (L.code.at((size_t)r * DIA_CODE_WORDS + k / 8) >> (4 * (k % 8))) & (DIA_DICT - 1);
+            v = L.dict.at((size_t)B.dict * DIA_DICT + c);
+          } else {
+            const int64_t at = (int64_t)slab[k] * B.stride + std::min(std::max(B.t0 + t + shift[k], 0), B.stride - 1);
+            v = L.val.at((size_t)(B.base - B.t0 + at));
+          }
           const double xv = staged ? win.at((size_t)(pos[k] + t)) : x[std::min<int64_t>(std::max<int64_t>(r + off[k], 0), n - 1)];
           if ((L.mask[(size_t)r] >> k) & 1u) s += v * xv; // (-ffp-contract=off: product rounded, then added)
         }
@@ -583,11 +669,11 @@ extern "C" int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, co
   for (int64_t z = 0; z < rowptr[n]; ++z)
     if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
   DiaLayout L;
-  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env());
+  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env(), dia_code_from_env());
   dia_apply_host(L, n, rowptr, col, val, x, y);
   for (size_t b = 0; kinds_out && b < L.blk.size() && (int64_t)b < max_blocks; ++b)
-    kinds_out[4 * b] = L.blk[b].r0, kinds_out[4 * b + 1] = L.blk[b].r1, kinds_out[4 * b + 2] = L.blk[b].nd, kinds_out[4 * b + 3] = L.stored.empty() ? 0 : L.stored[b];
-  const int64_t counts[7] = {(int64_t)L.blk.size(), L.ndia, L.ncsr, L.rows_dia, (int64_t)L.val.size(), L.nseg, L.nseg_half};
+    kinds_out[4 * b] = L.blk[b].r0, kinds_out[4 * b + 1] = L.blk[b].r1, kinds_out[4 * b + 2] = L.blk[b].nd, kinds_out[4 * b + 3] = L.stored[b];
+  const int64_t counts[7] = {(int64_t)L.blk.size(), L.ndia, L.ncsr, L.rows_dia, L.slots_slab, L.nseg, L.nseg_half};
   std::copy(counts, counts + 7, counts_out);
   return DDM_OK;
 }
@@ -602,7 +688,7 @@ extern "C" int ddm_dia_windows_host(int64_t n, const int64_t *rowptr, const int3
   for (int64_t z = 0; z < rowptr[n]; ++z)
     if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
   DiaLayout L;
-  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env());
+  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env(), dia_code_from_env());
   int64_t nruns = 0;
   for (size_t s = 0; s < L.win.size(); ++s) {
     const DiaSegWindows &W = L.win[s];
@@ -615,5 +701,32 @@ extern "C" int ddm_dia_windows_host(int64_t n, const int64_t *rowptr, const int3
   }
   const int64_t counts[4] = {(int64_t)L.win.size(), nruns, DIA_WIN, WG};
   std::copy(counts, counts + 4, counts_out);
+  return DDM_OK;
+}
+// host-only entry for the CPU tests: the dictionaries and code words of the same layout (DDM_SPMV_STAGE_X and DDM_SPMV_CODE as above),
+// built on `threads` host workers (0: the library's own number).  blocks_out (may be null) receives, for the first max_blocks blocks,
+// (number of the block's dictionary or -1: not coded, dictionary entries in use, 1 when the block's segment has value slabs);
+// dict_out (may be null) the DIA_DICT doubles of every dictionary whose number is below max_blocks, one after the other; code_out
+// (may be null) DIA_CODE_WORDS words per row, all 0 when no block is coded; counts_out = {blocks, coded blocks, value slots in the
+// slabs that were built, entries of a dictionary, words of a row}.
+extern "C" int ddm_dia_codes_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int threads, int64_t max_blocks,
+                                  int32_t *blocks_out, double *dict_out, uint32_t *code_out, int64_t *counts_out)
+{
+  if (n < 0 || !rowptr || !counts_out || threads < 0 || (rowptr[n] > 0 && (!col || !val)) || (max_blocks > 0 && !blocks_out)) return DDM_EINVAL;
+  for (int64_t z = 0; z < rowptr[n]; ++z)
+    if (col[z] < 0 || col[z] >= n) return DDM_EINVAL;
+  DiaLayout L;
+  dia_build(n, rowptr, col, val, L, dia_stage_x_from_env(), dia_code_from_env(), threads ? (unsigned)threads : host_threads());
+  for (size_t b = 0; b < L.blk.size() && (int64_t)b < max_blocks; ++b) {
+    const DiaBlock &B = L.blk[b];
+    blocks_out[3 * b] = B.dict, blocks_out[3 * b + 1] = L.ndict[b], blocks_out[3 * b + 2] = L.slabs[b];
+    if (dict_out && B.dict >= 0 && B.dict < max_blocks) std::memcpy(dict_out + (size_t)B.dict * DIA_DICT, L.dict.data() + (size_t)B.dict * DIA_DICT, sizeof(double) * DIA_DICT);
+  }
+  if (code_out) {
+    if (L.code.empty()) std::fill(code_out, code_out + (size_t)n * DIA_CODE_WORDS, 0u);
+    else std::memcpy(code_out, L.code.data(), sizeof(uint32_t) * L.code.size());
+  }
+  const int64_t counts[5] = {(int64_t)L.blk.size(), L.ncoded, (int64_t)L.val.size(), DIA_DICT, DIA_CODE_WORDS};
+  std::copy(counts, counts + 5, counts_out);
   return DDM_OK;
 }

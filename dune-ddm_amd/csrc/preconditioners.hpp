@@ -73,7 +73,9 @@ struct ddm_op {
   dbuf<DiaBlock> dia_blk;
   dbuf<int32_t> dia_tab;
   dbuf<uint32_t> dia_mask;
-  dbuf<double> dia_val;
+  dbuf<double> dia_val;    // the slabs of the segments that have an uncoded block
+  dbuf<uint32_t> dia_code; // DIA_CODE_WORDS per row and the dictionaries of the coded blocks, or nothing
+  dbuf<double> dia_dict;
   int dia_nblk = 0;
 };
 // y = A x: bit-identical to ddm_csr_mv in either layout
@@ -83,7 +85,7 @@ static int op_mv(ddm_ctx *ctx, const ddm_op *op, const double *x, double *y)
   if (x == y) return fail(ctx, DDM_EINVAL, "operator product: x and y alias");
   const ddm_csr *A = op->A;
   hipLaunchKernelGGL(k_spmv_dia, dim3(op->dia_nblk), dim3(WG), 0, ctx->stream, (const DiaBlock *)op->dia_blk, op->dia_nblk, (const int32_t *)op->dia_tab,
-                     (const uint32_t *)op->dia_mask, (const double *)op->dia_val, A->rp, A->ci, A->va, (int)op->n, x, y);
+                     (const uint32_t *)op->dia_mask, (const double *)op->dia_val, reinterpret_cast<const uint4 *>(op->dia_code.get()), (const double *)op->dia_dict, A->rp, A->ci, A->va, (int)op->n, x, y);
   HIPCHECK(ctx, hipGetLastError());
   return DDM_OK;
 }
@@ -101,12 +103,14 @@ extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add
   const char *fmt = std::getenv("DDM_SPMV_FORMAT"); // "csr": keep the CSR-stream product (A/B runs, tests)
   if (!rc && !A->host_only && !(fmt && !std::strcmp(fmt, "csr"))) {
     DiaLayout L;
-    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L, dia_stage_x_from_env()); // DDM_SPMV_STAGE_X=0: no x windows in LDS
+    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L, dia_stage_x_from_env(), dia_code_from_env()); // DDM_SPMV_STAGE_X=0: no x windows in LDS, DDM_SPMV_CODE=0: no dictionaries
     if (L.ndia) {
       if (!rc) rc = upload(ctx, L.blk.data(), (int64_t)L.blk.size(), op->dia_blk);
       if (!rc) rc = upload(ctx, L.tab.data(), (int64_t)L.tab.size(), op->dia_tab);
       if (!rc) rc = upload(ctx, L.mask.data(), (int64_t)L.mask.size(), op->dia_mask);
       if (!rc) rc = upload(ctx, L.val.data(), (int64_t)L.val.size(), op->dia_val);
+      if (!rc && L.ncoded) rc = upload(ctx, L.code.data(), (int64_t)L.code.size(), op->dia_code);
+      if (!rc && L.ncoded) rc = upload(ctx, L.dict.data(), (int64_t)L.dict.size(), op->dia_dict);
       op->dia_nblk = (int)L.blk.size();
     }
   }

@@ -128,6 +128,18 @@ int ddm_dia_build_and_apply_host(int64_t n, const int64_t *rowptr, const int32_t
  * runs, segment after segment; counts_out[4] = {segments, runs, capacity in doubles, rows of a full block}. */
 int ddm_dia_windows_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t max_segments, int32_t *segs_out,
                          int64_t max_runs, int32_t *runs_out, int64_t *counts_out);
+/* Host only (for tests): the coded blocks of the same layout.  A block of a staged segment whose rows read at most 16 distinct
+ * values (compared bit for bit) keeps them in a dictionary of 16 doubles, in order of first appearance and padded with +0.0, and
+ * a 128-bit word of 4-bit codes per row, nibble k for diagonal k of the segment's table; a segment whose blocks are all coded
+ * builds no value slabs (no block is coded with DDM_SPMV_CODE=0 in the environment, which ddm_op_create reads as well).  The
+ * layout is built on `threads` host workers (0: the library's own number) and does not depend on them.  blocks_out (may be
+ * NULL): (number of the block's dictionary or -1, dictionary entries in use, 1 when the block's segment has slabs) of the first
+ * max_blocks blocks; dict_out (may be NULL): the 16 doubles of every dictionary whose number is below max_blocks, one after the
+ * other; code_out (may be NULL): 4 words per row, 0 for the rows of blocks that are not coded; counts_out[5] = {blocks, coded
+ * blocks, value slots of the slabs that were built, entries of a dictionary, words per row}.  The "value slots" that
+ * ddm_dia_build_and_apply_host reports stay those of the slab layout, coded or not. */
+int ddm_dia_codes_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int threads, int64_t max_blocks,
+                       int32_t *blocks_out, double *dict_out, uint32_t *code_out, int64_t *counts_out);
 
 /* ---- local subdomain solver: ILU(0), natural row order ------------------------------------
  * The InverseOperator behind schwarz.hh:57,92,133 for [subdomain_solver] type=loopsolver maxit=1,

@@ -1,4 +1,4 @@
-"""Condenses rocprofv3 counter passes of the operator kernel into one JSON document (profiles/dia_window_pmc_*.json).
+"""Condenses rocprofv3 counter passes of the operator kernel into one JSON document (profiles/dia_window_pmc_*.json, profiles/dia_code_pmc_*.json).
 
 usage: dia_pmc_json.py OUT.json LABEL COUNTER_CSV [COUNTER_CSV ...]
 
@@ -40,6 +40,10 @@ if "GRBM_GUI_ACTIVE" in m:
         derived["memory_unit_stalled"] = m["TCP_TCP_TA_DATA_STALL_CYCLES_sum"] / 256 / cycles   # mean over the 256 L1 caches
     if "TA_ADDR_STALLED_BY_TC_CYCLES_sum" in m:
         derived["address_unit_stalled_by_l1"] = m["TA_ADDR_STALLED_BY_TC_CYCLES_sum"] / 256 / cycles
+if "SQ_LDS_IDX_ACTIVE" in m and "SQ_LDS_BANK_CONFLICT" in m:                      # (summed over the 256 CUs)
+    derived["lds_bank_conflict_share_of_lds_cycles"] = m["SQ_LDS_BANK_CONFLICT"] / max(m["SQ_LDS_IDX_ACTIVE"], 1.0)
+    if "GRBM_GUI_ACTIVE" in m:
+        derived["lds_busy"] = m["SQ_LDS_IDX_ACTIVE"] / 256 / (m["GRBM_GUI_ACTIVE"] / 8)
 doc = {"kernel": "k_spmv_dia", "build": label, "cmd": "python bench.py --gpus 1 --steps 20 --warmup 5", "grid_threads": grid,
        "note": "one run per counter set, counters only (no tracing); values per launch",
        "counters": counters, "derived": derived}
