@@ -57,6 +57,7 @@ def test_pipe_solve_bit_exact(ddm, N, P, spread, monkeypatch):
         ctx.sync()
         assert F.status() == 0
         assert np.array_equal(xd.cpu().numpy(), _oracle_solve(M, bp, d))
+    assert F.engine() == "pipe"
     ctx.close()
 
 
@@ -79,6 +80,7 @@ def test_pipe_stress_many_solves_uneven(ddm, monkeypatch):
         a, b = b, a
     ctx.sync()
     assert F.status() == 0
+    assert F.engine() == "pipe"
     for it in range(40):
         ref = _oracle_solve(M, bp, ref)
     assert np.array_equal(a.cpu().numpy(), ref)
