@@ -48,7 +48,7 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
   HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
   int per_cu = 0;
-  HIPCHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_trsv_pipe<false>, 64 * (PIPE_NC + PIPE_NL), PIPE_LDS_BYTES));
+  HIPCHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_trsv_pipe<false>, 64 * PIPE_WAVES, PIPE_LDS_BYTES));
   per_cu = std::max(1, std::min(per_cu, 2));
   if (const char *e = std::getenv("DDM_PIPE_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));
   E->grid = per_cu * (ctx->num_cu / 8 * 8);
@@ -89,8 +89,8 @@ static hipError_t enqueue_pipe(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, doubl
   P.stamps = stamps;
   P.spread = E.spread;
   hipLaunchKernelGGL(k_pipe_prologue, dim3(1), dim3(64), 0, ctx->stream, F->xstate, E.queue, E.ngroups * 4);
-  if (stamps) hipLaunchKernelGGL((k_trsv_pipe<true>), dim3(E.grid), dim3(64 * (PIPE_NC + PIPE_NL)), PIPE_LDS_BYTES, ctx->stream, P);
-  else hipLaunchKernelGGL((k_trsv_pipe<false>), dim3(E.grid), dim3(64 * (PIPE_NC + PIPE_NL)), PIPE_LDS_BYTES, ctx->stream, P);
+  if (stamps) hipLaunchKernelGGL((k_trsv_pipe<true>), dim3(E.grid), dim3(64 * PIPE_WAVES), PIPE_LDS_BYTES, ctx->stream, P);
+  else hipLaunchKernelGGL((k_trsv_pipe<false>), dim3(E.grid), dim3(64 * PIPE_WAVES), PIPE_LDS_BYTES, ctx->stream, P);
   const hipError_t e = add_ready ? hipStreamWaitEvent(ctx->stream, add_ready, 0) : hipSuccess;
   if (e != hipSuccess) return e; // (x stays unwritten: the caller fails)
   hipLaunchKernelGGL(k_pipe_permute_out, dim3(perm_grid(ctx, E.nposU)), dim3(PERM_WG), 0, ctx->stream, E.nposU, E.rowU, (const double *)E.xpos, x, scale, add);

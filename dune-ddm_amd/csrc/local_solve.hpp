@@ -113,8 +113,8 @@ extern "C" int ddm_ilu0_debug_stamps(ddm_ctx *ctx, ddm_ilu0 *F, const double *d,
   return ddm_memcpy_d2h(ctx, out_host, st, 48);
 }
 
-// Diagnostic (not part of the product path): one solve with the stamped build of the pipe kernel.  Per task 8 words
-// (layout: trsv_pipe.hpp, STAMP) followed by nothing; returns the number of tasks in *ntasks.  out_host may be null
+// Diagnostic (not part of the product path): one solve with the stamped build of the pipe kernel.  Per task PIPE_STAMP_WORDS
+// words (layout: trsv_pipe.hpp, STAMP); returns the number of tasks in *ntasks.  out_host may be null
 // to query the size.  Also reports group / sweep of every task in meta_host[2 * ntasks] when given.
 extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned long long *out_host, int32_t *meta_host,
                                    int64_t capacity_tasks, int64_t *ntasks)

@@ -1,6 +1,6 @@
 // Device side of the "pipe" triangular-solve engine; schedule format and rationale: trsv_pipe_host.hpp.
 //
-// One workgroup = PIPE_NC compute waves + PIPE_NL loader waves; two workgroups per CU.  Workgroups pull tasks (64
+// One workgroup = one compute wave + PIPE_NL loader waves; two workgroups per CU.  Workgroups pull tasks (64
 // chains walked level by level) from a per-(subdomain, sweep) queue in topological order.  The loader waves stream the
 // task's tiles HBM -> LDS with LDS-DMA (global_load_lds_dwordx4, 1 KiB per instruction) into a byte ring, far ahead of
 // the compute wave.
@@ -11,9 +11,7 @@
 // are issued before the row sums of the current step.  A check that fails there is DEFERRED: the wave computes the current
 // step first (it has the operands), then waits for the producers and issues the gathers (fetch_late) -- a consumer that
 // runs right behind its producer does not idle with work at hand.
-// PIPE_NC = 2 (built, bit-exact, not faster -- docs/HISTORY.md section 3) lets two compute waves alternate the steps of a task:
-// wave w takes steps w, w + NC, ...; only the operands flagged in the tile's late mask are read after the previous
-// step has signalled (one LDS word).
+// (Several compute waves per task were measured and lost: docs/HISTORY.md section 3.)
 //
 // Visibility protocol (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility"):
 //   * XCD-local mode (every XCD that owns a subdomain hosts workgroups): all tasks of a subdomain run on ONE XCD; results
@@ -30,18 +28,12 @@
 
 namespace ddm {
 
-#ifndef DDM_PIPE_NC
-#define DDM_PIPE_NC 1
-#endif
-#ifndef DDM_PIPE_RING_KIB
-#define DDM_PIPE_RING_KIB 64
-#endif
-constexpr int PIPE_NC = DDM_PIPE_NC; // compute waves per workgroup (steps of a task alternate between them); experiments: -DDDM_PIPE_NC=2 -DDDM_PIPE_RING_KIB=112
 constexpr int PIPE_NL = 2;          // loader waves per workgroup
+constexpr int PIPE_WAVES = 1 + PIPE_NL; // wave 0 computes, waves 1 .. PIPE_NL load
 constexpr int PIPE_DEPTH = 3;       // tiles a loader keeps in flight
-constexpr int PIPE_RING_KIB = DDM_PIPE_RING_KIB; // LDS byte ring of tiles per workgroup (two workgroups per CU).  2 NC tiles (the current and the
-                                    // prefetched step of every compute wave) + one in flight must fit, or loaders and compute waves
-                                    // would wait for each other: 5 tiles of the widest row the builder accepts (pipe::MAX_W)
+constexpr int PIPE_RING_KIB = 64;   // LDS byte ring of tiles per workgroup (two workgroups per CU).  The current tile, the prefetched one
+                                    // and one in flight must fit, or loaders and compute wave would wait for each other
+static_assert(3 * (pipe::Geometry(pipe::MAX_W).tile_bytes / 1024) <= PIPE_RING_KIB, "tile ring too small for three of the widest tiles");
 constexpr int PIPE_STAMP_WORDS = 16 + 256; // stamped build: words per task (16 sums, then the time of every step's result store)
 constexpr int PIPE_WIDE = 12;       // further entries of a wide row handled with one gather latency
 constexpr int PIPE_READY = 32;      // ready words (tiles in flight < 32: the smallest tile is 3 KiB)
@@ -49,13 +41,12 @@ constexpr int PIPE_CHUNK = pipe::MIN_W; // entries of a row held in registers; e
 constexpr int PIPE_RINGAREA = (pipe::RING_BYTES + 4 * (PIPE_READY + 16) + 1023) / 1024 * 1024; // result ring + control words
 constexpr size_t PIPE_LDS_BYTES = (size_t)PIPE_RINGAREA + (size_t)PIPE_RING_KIB * 1024; // dynamic part
 
-struct PipeStep { // registers of one step, filled NC steps ahead of their use (the factor entries are read
+struct PipeStep { // registers of one step, filled one step ahead of their use (the factor entries are read
                   // from the tile when the step is computed: two sets of them would not fit the register budget)
   double xg[PIPE_CHUNK];
   uint32_t lofs[PIPE_CHUNK];   // LDS ring addresses of the operands (the zero row for operands that are gathered)
   double s0;
   int W;
-  unsigned late;       // entries whose ring operand may come from one of the NC - 1 steps before this one
   unsigned tpos, vend; // tile position in the LDS ring (KiB), virtual ring offset behind the tile
   int deferred;        // (uniform) the producers were not far enough when the step was prefetched: its gathers are issued by fetch_late()
 };
@@ -261,22 +252,19 @@ __device__ __forceinline__ void pipe_glds16(const unsigned char *gsrc, unsigned 
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc, (__attribute__((address_space(3))) void *)lds_dst, 16, 0, 0);
 }
 
-// STAMP (diagnostic build only): per task 8 words -- start / first step / end (s_memrealtime, 100 MHz), cycles of compute
-// wave 0 waiting for tiles / for producers / between the previous step's signal and its own (s_memtime), steps, XCC id
-template <bool STAMP>
-__global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipeParams P)
+// the two 16-bit progress requirements in a lane's header word: producers 2 lane and 2 lane + 1 (0 where the task has no such producer)
+__device__ __forceinline__ void pipe_split_need(int need, int lane, int nprod, int &need0, int &need1)
 {
-  static_assert(PIPE_NC >= 1 && PIPE_NC <= pipe::MAX_NC, "late masks exist for up to MAX_NC compute waves");
-  // every compute wave holds its current tile and prefetches its next one while a loader fills a further one: 2 NC + 1 tiles give full
-  // overlap.  With -DDDM_PIPE_TIGHT_RING the ring only has to hold NC + 1 of the WIDEST tiles (all current tiles and one more): a wave whose
-  // next tile does not fit yet waits for the oldest step to release its tile -- less overlap on the wide steps, no deadlock (steps complete
-  // in order, and a completed step frees the space the youngest prefetch is waiting for).
-#ifdef DDM_PIPE_TIGHT_RING
-  static_assert((PIPE_NC + 1) * (pipe::Geometry(pipe::MAX_W).tile_bytes / 1024) <= PIPE_RING_KIB, "tile ring too small for the widest tiles");
-  static_assert((2 * PIPE_NC + 1) * (pipe::Geometry(pipe::MIN_W).tile_bytes / 1024) <= PIPE_RING_KIB, "tile ring too small for full overlap on the narrow tiles");
-#else
-  static_assert((2 * PIPE_NC + 1) * (pipe::Geometry(pipe::MAX_W).tile_bytes / 1024) <= PIPE_RING_KIB, "tile ring too small for the widest tiles");
-#endif
+  need0 = 2 * lane < nprod ? (need & 0xffff) : 0;
+  need1 = 2 * lane + 1 < nprod ? (int)((unsigned)need >> 16) : 0;
+}
+// STAMP (diagnostic build only): per task PIPE_STAMP_WORDS words.  [0..2] start / first step / end (s_memrealtime, 100 MHz);
+// [3] [4] cycles (s_memtime) of the compute wave waiting for tiles / for producers; [5] unused (0); [6] steps; [7] XCC id; [8] [9] [11]
+// cycle sums of a step's segments: top -> gathers issued -> row sum of the register chunk done -> end; [10] unused (0); [12] [13] steps
+// behind the first that polled their producers, cycles spent there; [14] [15] unwritten; [16 + t] time of step t's result store
+template <bool STAMP>
+__global__ __launch_bounds__(64 * PIPE_WAVES) void k_trsv_pipe(PipeParams P)
+{
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   // All LDS is dynamic and the result ring sits at LDS address 0, so that ring operands are ds_read addresses as they
   // stand.  Control words between the waves: relaxed workgroup-scope atomics (plain ds_read / ds_write; ordering is by
@@ -287,8 +275,6 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
   unsigned &sh_vconsumed = ctl[PIPE_READY];    // virtual ring offset (KiB) behind the last tile that is no longer needed
   unsigned &sh_xcc = ctl[PIPE_READY + 1], &sh_gt = ctl[PIPE_READY + 2], &sh_fail = ctl[PIPE_READY + 3], &sh_q = ctl[PIPE_READY + 4];
   unsigned &sh_xt = ctl[PIPE_READY + 6];       // this workgroup's arrival number on its XCD
-  unsigned &sh_stepdone = ctl[PIPE_READY + 5]; // steps of the task whose results are in the LDS ring
-  unsigned *sh_stored = ctl + PIPE_READY + 8;  // [PIPE_NC] own steps of compute wave w whose global stores have completed
   unsigned char *tiles = smem + PIPE_RINGAREA; // byte ring of tiles
   auto lds_load = [](const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
   auto lds_store = [](unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
@@ -300,7 +286,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
     return;
   }
   // the ring is zeroed once: its last row stays zero for good, every other row is written before it is read
-  for (int k = wave; k <= pipe::RING; k += PIPE_NC + PIPE_NL) ringd[k * 64 + lane] = 0.0;
+  for (int k = wave; k <= pipe::RING; k += PIPE_WAVES) ringd[k * 64 + lane] = 0.0;
   if (threadIdx.x == 0) {
     const unsigned xcc = hw_xcc_id();
     sh_xcc = xcc;
@@ -347,8 +333,6 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
           sh_q = __hip_atomic_fetch_add(qbase + sweep * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           for (int k = 0; k < PIPE_READY; ++k) lds_store(&sh_ready[k], 0u);
           lds_store(&sh_vconsumed, 0u);
-          lds_store(&sh_stepdone, 0u);
-          for (int k = 0; k < PIPE_NC; ++k) lds_store(&sh_stored[k], 0u);
         }
         __syncthreads();
         const unsigned q = sh_q;
@@ -368,9 +352,9 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
           }
         };
 
-        if (wave >= PIPE_NC) {
-          // ---------------- loader: tiles wl, wl + NL, ... of the task by LDS-DMA, up to PIPE_DEPTH tiles in flight ----------------
-          const int wl = wave - PIPE_NC;
+        if (wave >= 1) {
+          // ---------------- loader wl: tiles wl, wl + NL, ... of the task by LDS-DMA, up to PIPE_DEPTH tiles in flight ----------------
+          const int wl = wave - 1;
           const int32_t *ko = P.koff + T->koff_base;
           const unsigned char *src_tiles = P.stream + T->tile_off;
           unsigned v = 0;       // virtual ring offset in KiB
@@ -400,7 +384,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               continue;
             }
             if ((int)(v + sz - lds_load(&sh_vconsumed)) > PIPE_RING_KIB) {
-              // about to wait for ring space: first hand over everything that is in flight (the compute waves may need it)
+              // about to wait for ring space: first hand over everything that is in flight (the compute wave may need it)
               while (nfl > 0) publish_oldest(0);
               for (unsigned spins = 0; (int)(v + sz - lds_load(&sh_vconsumed)) > PIPE_RING_KIB; ++spins) {
                 if (spins > (1u << 24)) {
@@ -427,8 +411,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
           }
           while (nfl > 0) publish_oldest(0);
         } else {
-          // ---------------- compute wave w: steps w, w + NC, ... ----------------
-          const int w = wave;
+          // ---------------- compute wave ----------------
           const int nprod = T->nprod;
           const int64_t pos_base = T->pos_base;
           // lane l watches producers 2l and 2l + 1 (16-bit requirements, two per header word)
@@ -439,9 +422,9 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
           double *dst = upper ? P.xpos : P.ypos;
           int have0 = 0, have1 = 0;
           unsigned long long st_start = 0, st_first = 0;
-          unsigned st_tile = 0, st_prog = 0, st_sum = 0; // cycles (32 bits are plenty for one task)
+          unsigned st_tile = 0, st_prog = 0; // cycles (32 bits are plenty for one task)
           unsigned st_nblock = 0, st_cblock = 0; // steps behind the first one that had to poll their producers, cycles spent there
-          unsigned st_a = 0, st_b = 0, st_c = 0, st_d = 0, st_t = 0; // step top -> gathers issued -> early part done -> previous step signalled; signal -> step end
+          unsigned st_a = 0, st_b = 0, st_d = 0, st_t = 0; // step top -> gathers issued -> row sum of the register chunk done -> step end
           if (STAMP) st_start = __builtin_amdgcn_s_memrealtime();
           if (upper) { // the forward sweep of this subdomain must be complete (its results are this sweep's right-hand side)
             for (unsigned spins = 0; __hip_atomic_load(qbase + 2 * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)ntaskL; ++spins) {
@@ -453,7 +436,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
           }
-          // ring positions of the tiles: every compute wave follows ALL tiles (sizes come with the headers it reads)
+          // ring positions of the tiles (sizes come with the headers the wave reads)
           auto place = [](unsigned &v, int sz, unsigned &pos) __attribute__((always_inline)) {
             pos = v % PIPE_RING_KIB;
             if (pos + sz > PIPE_RING_KIB) {
@@ -462,15 +445,10 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             }
             v += sz;
           };
-          unsigned v = 0;              // virtual offset in front of this wave's next tile
+          unsigned v = 0;              // virtual offset in front of the next tile
           int next_kib = T->first_kib; // its size
-          if (PIPE_NC == 2 && w == 1) {
-            unsigned dummy;
-            place(v, next_kib, dummy);
-            next_kib = T->second_kib;
-          }
           bool failed = false;
-          int nstored = 0; // own steps whose result store has completed
+          int nstored = 0; // steps whose result store has completed
           bool publish_pending = false; // the previous step's store (and the poll in front of it) has been issued but not yet drained and published
           unsigned long long pw0 = 0, pw1 = 0; // progress words of the two producers this lane watches (non-blocking poll)
           // waits (polling) until the producers have stored what the lanes need
@@ -495,7 +473,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               __builtin_amdgcn_s_sleep(1);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (STAMP && t > w) {
+            if (STAMP && t > 0) {
               st_nblock += 1;
               st_cblock += (unsigned)__builtin_amdgcn_s_memtime() - cb;
             }
@@ -526,15 +504,13 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             const int32_t *hdr = reinterpret_cast<const int32_t *>(tile);
             const int4 *idxp = reinterpret_cast<const int4 *>(tile + 1024 * (1 + PIPE_CHUNK / 2)) + lane;
             int need, own;
-            int4 wk; // hdr[2..5]: W, size of tile t+1, late mask (1 step), size of tile t+2
-            int late2;
+            int2 wk; // hdr[2..3]: W, size of tile t+1
             int32_t op[PIPE_CHUNK];
             bool drained = false; // the caller's hook has waited for every outstanding load: the poll issued with the last store is valid
             for (unsigned spins = 0;; ++spins) {
               asm volatile("" ::: "memory");
               const unsigned rdy_v = lds_load(&sh_ready[t % PIPE_READY]);
-              wk = make_int4(hdr[2], hdr[3], hdr[4], hdr[5]);
-              late2 = hdr[6];
+              wk = make_int2(hdr[2], hdr[3]);
               need = hdr[pipe::HDR_REQ0 + (lane < 56 ? lane : 0)];
               own = reinterpret_cast<const int32_t *>(tile + 256)[lane];
 #pragma unroll
@@ -561,15 +537,9 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               c0 = c;
             }
             S.W = __builtin_amdgcn_readfirstlane(wk.x);
-            S.late = PIPE_NC == 1 ? 0u : (unsigned)__builtin_amdgcn_readfirstlane(PIPE_NC == 2 ? wk.z : late2);
-            // this wave's next tile is NC tiles further
-            if (PIPE_NC == 1) next_kib = __builtin_amdgcn_readfirstlane(wk.y);
-            else {
-              unsigned dummy;
-              place(v, __builtin_amdgcn_readfirstlane(wk.y), dummy);
-              next_kib = __builtin_amdgcn_readfirstlane(wk.w);
-            }
-            const int need0 = 2 * lane < nprod ? (need & 0xffff) : 0, need1 = 2 * lane + 1 < nprod ? (int)((unsigned)need >> 16) : 0;
+            next_kib = __builtin_amdgcn_readfirstlane(wk.y);
+            int need0, need1;
+            pipe_split_need(need, lane, nprod, need0, need1);
             if (drained) { // (only a drain follows a poll)
               asm volatile("" : "+v"(pw0), "+v"(pw1));
               if ((unsigned)(pw0 >> 32) == epoch) have0 = max(have0, (int)(unsigned)pw0);
@@ -590,14 +560,6 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             if (STAMP) st_prog += (unsigned)__builtin_amdgcn_s_memtime() - c0;
             issue_gathers(S, op, own);
           };
-          // steps 0 .. prog-1 are stored: the first step of each compute wave that is not known to be stored bounds it
-          auto publish_progress = [&]() __attribute__((always_inline)) {
-            int prog = w + PIPE_NC * nstored;
-#pragma unroll
-            for (int k = 0; k < PIPE_NC; ++k)
-              if (k != w) prog = min(prog, k + PIPE_NC * (int)lds_load(&sh_stored[k]));
-            publish(prog);
-          };
           // second half of a deferred fetch(), behind the caller's own step: the operand words again (the tile is resident), the
           // wait for the producers, the gathers.  The first poll's drain also covers the caller's result store: published there.
           auto fetch_late = [&](int t, PipeStep &S, auto &&on_first_drain) __attribute__((always_inline)) {
@@ -614,13 +576,14 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               if (4 * q4 + 2 < PIPE_CHUNK) op[4 * q4 + 2] = o.z;
               if (4 * q4 + 3 < PIPE_CHUNK) op[4 * q4 + 3] = o.w;
             }
-            const int need0 = 2 * lane < nprod ? (need & 0xffff) : 0, need1 = 2 * lane + 1 < nprod ? (int)((unsigned)need >> 16) : 0;
+            int need0, need1;
+            pipe_split_need(need, lane, nprod, need0, need1);
             block_on_producers(t, need0, need1, on_first_drain);
             if (failed) return;
             issue_gathers(S, op, own);
             S.deferred = 0;
           };
-          // one step: "k4" = number of leading groups of 4 entries that no lane takes from the previous NC - 1 steps
+          // one step: prefetch of the next one, row sum, result store (drained and published at the top of the next step)
           auto step = [&](int t, PipeStep &cur, PipeStep &nxt) __attribute__((always_inline)) {
             asm volatile("" ::: "memory");
             if (STAMP) st_t = (unsigned)__builtin_amdgcn_s_memtime();
@@ -671,9 +634,8 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               if (publish_pending) {
                 drained = true; // the store of the previous step has had these instructions' time to complete
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                nstored = (t - w) / PIPE_NC;
-                if (lane == 0) lds_store(&sh_stored[w], (unsigned)nstored);
-                publish_progress();
+                nstored = t;
+                publish(nstored);
                 publish_pending = false;
               }
               if (W > PIPE_CHUNK) pipe_gather_asm_wide(src, ego0, eg0); // (behind the drain above, in front of the next step's gathers)
@@ -690,8 +652,8 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               }
               dinv = reinterpret_cast<const double *>(ctile + 512)[lane];
             };
-            const bool fetched_next = t + PIPE_NC < nsteps;
-            if (fetched_next) fetch(t + PIPE_NC, nxt, true, read_ring);
+            const bool fetched_next = t + 1 < nsteps;
+            if (fetched_next) fetch(t + 1, nxt, true, read_ring);
             else read_ring();
             if (failed) return;
             if (STAMP) {
@@ -700,7 +662,7 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               st_t = c;
             }
             read_entries(); // (behind the fetch: its temporaries and the factor entries need not be live together)
-            // behind this step's gathers: the result store of this wave's previous step and, if there is a next step, its
+            // behind this step's gathers: the result store of the previous step and, if there is a next step, its
             // PIPE_INFLIGHT loads => at most that many operations may still be outstanding
             // (the drain for the last step has no register operands: no copies of in-flight registers in front of it)
             const bool deferred_next = fetched_next && __builtin_amdgcn_readfirstlane(nxt.deferred) != 0; // (no gathers of the next step in flight)
@@ -708,26 +670,12 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             pipe_wait_gathers<PIPE_INFLIGHT>(cur.s0, cur.xg);
             if (W > PIPE_CHUNK) pipe_pin_wide(eg0); // (older than the gathers the wait left in flight: valid too)
             if (W > PIPE_CHUNK + PIPE_WHALF) pipe_pin_wide(eg1);
-            // Products of the groups of 4 entries that no lane takes from the previous NC - 1 steps; in the other groups p keeps
-            // the factor entry until the ring operands can be read (behind the previous step's signal).  The head of the row
-            // sum up to the first such group is final already.
-            const unsigned late = __builtin_amdgcn_readfirstlane(cur.late);
-            auto group = [&](int g0, bool final_operands) __attribute__((always_inline)) {
+            // the PIPE_CHUNK products and the row sum in ascending column order
 #pragma unroll
-              for (int u = g0; u < g0 + 4 && u < PIPE_CHUNK; ++u) {
-                if (final_operands) p[u] = p[u] * pipe_or(cur.xg[u], xl[u]);
-              }
-            };
-            group(0, (late & 0x000fu) == 0u);
-            group(4, (late & 0x00f0u) == 0u);
-            group(8, (late & 0x0f00u) == 0u);
-            group(12, (late & 0xf000u) == 0u);
-            const int k4 = late == 0u ? 4 : (__builtin_ctz(late) >> 2); // first group with late operands (4: none)
+            for (int u = 0; u < PIPE_CHUNK; ++u) p[u] = p[u] * pipe_or(cur.xg[u], xl[u]);
             double s = cur.s0;
-            if (k4 >= 1) s = (((s - p[0]) - p[1]) - p[2]) - p[3];
-            if (k4 >= 2) s = (((s - p[4]) - p[5]) - p[6]) - p[7];
-            if (k4 >= 3) s = (((s - p[8]) - p[9]) - p[10]) - p[11];
-            if (k4 >= 4) s = (s - p[12]) - p[13];
+#pragma unroll
+            for (int u = 0; u < PIPE_CHUNK; ++u) s -= p[u];
             // everything above is computed BEFORE the wait below (the compiler would sink it behind the wait otherwise)
             pipe_pin(s, p);
             if (STAMP) {
@@ -735,36 +683,6 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
               st_b += c - st_t;
               st_t = c;
             }
-            unsigned c0 = 0;
-            if (PIPE_NC > 1) { // the previous step's results must be in the ring now
-              for (unsigned spins = 0; (unsigned)__builtin_amdgcn_readfirstlane((int)lds_load(&sh_stepdone)) < (unsigned)t; ++spins) {
-                if (spins > (1u << 24)) {
-                  if (lane == 0) __hip_atomic_store(P.err, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                  failed = true;
-                  return;
-                }
-              }
-              asm volatile("" ::: "memory");
-              if (STAMP) {
-                c0 = (unsigned)__builtin_amdgcn_s_memtime();
-                st_c += c0 - st_t;
-              }
-              auto late_group = [&](int g0) __attribute__((always_inline)) {
-                double x2[4];
-#pragma unroll
-                for (int u = g0; u < g0 + 4 && u < PIPE_CHUNK; ++u) x2[u - g0] = pipe_lds_f64(cur.lofs[u]);
-#pragma unroll
-                for (int u = g0; u < g0 + 4 && u < PIPE_CHUNK; ++u) p[u] = p[u] * pipe_or(cur.xg[u], x2[u - g0]);
-              };
-              if (late & 0x000fu) late_group(0);
-              if (late & 0x00f0u) late_group(4);
-              if (late & 0x0f00u) late_group(8);
-              if (late & 0xf000u) late_group(12);
-            }
-            if (k4 < 1) s = (((s - p[0]) - p[1]) - p[2]) - p[3];
-            if (k4 < 2) s = (((s - p[4]) - p[5]) - p[6]) - p[7];
-            if (k4 < 3) s = (((s - p[8]) - p[9]) - p[10]) - p[11];
-            if (k4 < 4) s = (s - p[12]) - p[13];
             if (W > PIPE_CHUNK) {
               // a half: operand words and factor entries in one batch of LDS reads, then the ring operands, then the row sum
               auto wide_half = [&](int u0, const double (&eg)[PIPE_WHALF]) __attribute__((always_inline)) {
@@ -795,63 +713,55 @@ __global__ __launch_bounds__(64 * (PIPE_NC + PIPE_NL)) void k_trsv_pipe(PipePara
             const double out = s * dinv; // (forward sweep: scale 1)
             ringd[(t % pipe::RING) * 64 + lane] = out;
             asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(out) : "memory"); // the result is in the ring, every LDS read of this step has returned
-            if (lane == 0) {
-              lds_store(&sh_vconsumed, cur.vend);       // the tile's ring space goes back to the loaders ...
-              lds_store(&sh_stepdone, (unsigned)t + 1u); // ... and the next step may read the ring
-            }
-            if (STAMP && PIPE_NC > 1) {
-              st_t = (unsigned)__builtin_amdgcn_s_memtime();
-              st_sum += st_t - c0;
-            }
+            if (lane == 0) lds_store(&sh_vconsumed, cur.vend); // the tile's ring space goes back to the loaders
             const int64_t mypos = pos_base + (int64_t)t * 64 + lane;
             pipe_poll_asm(pword0, pword1, pw0, pw1); // (as late as possible: the drain of the next step is the first to need it)
             if (wt) st_sc1(dst + mypos, out);
             else dst[mypos] = out;
             publish_pending = true; // drained and published at the top of the next step, behind its first LDS reads
             if (deferred_next) { // the next step's producers were not far enough at the top of this step: now is the time to wait for them
-              fetch_late(t + PIPE_NC, nxt, [&]() {
-                nstored = (t - w) / PIPE_NC + 1; // (the drain behind the first poll has completed this step's store)
-                if (lane == 0) lds_store(&sh_stored[w], (unsigned)nstored);
-                publish_progress();
+              fetch_late(t + 1, nxt, [&]() {
+                nstored = t + 1; // (the drain behind the first poll has completed this step's store)
+                publish(nstored);
                 publish_pending = false;
               });
               if (failed) return;
             }
-            if (STAMP && w == 0 && lane == 0 && P.stamps && t < PIPE_STAMP_WORDS - 16) P.stamps[(size_t)tid * PIPE_STAMP_WORDS + 16 + t] = __builtin_amdgcn_s_memrealtime();
+            if (STAMP && lane == 0 && P.stamps && t < PIPE_STAMP_WORDS - 16) P.stamps[(size_t)tid * PIPE_STAMP_WORDS + 16 + t] = __builtin_amdgcn_s_memrealtime();
             if (STAMP) st_d += (unsigned)__builtin_amdgcn_s_memtime() - st_t;
           };
-          if (w < nsteps) {
+          if (wave < nsteps) { // (wave is 0 here: the task has steps; written with the literal, the kernel gets two more scalar instructions)
             PipeStep SA, SB;
-            fetch(w, SA, false, []() { return false; });
+            fetch(0, SA, false, []() { return false; });
             if (failed) return;
             if (STAMP) st_first = __builtin_amdgcn_s_memrealtime();
-            for (int t = w; t < nsteps; t += 2 * PIPE_NC) {
+            for (int t = 0; t < nsteps; t += 2) {
               step(t, SA, SB);
               if (failed) return;
-              if (t + PIPE_NC < nsteps) step(t + PIPE_NC, SB, SA);
+              if (t + 1 < nsteps) step(t + 1, SB, SA);
               if (failed) return;
             }
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every result store of this wave has completed
-          if (STAMP && w == 0 && lane == 0 && P.stamps) {
+          if (STAMP && lane == 0 && P.stamps) {
             unsigned long long *o = P.stamps + (size_t)tid * PIPE_STAMP_WORDS;
             o[0] = st_start;
             o[1] = st_first;
             o[2] = __builtin_amdgcn_s_memrealtime();
             o[3] = st_tile;
             o[4] = st_prog;
-            o[5] = st_sum;
+            o[5] = 0; // (unused)
             o[6] = (unsigned long long)nsteps;
             o[7] = xcc;
             o[8] = st_a;
             o[9] = st_b;
-            o[10] = st_c;
+            o[10] = 0; // (unused)
             o[11] = st_d;
             o[12] = st_nblock;
             o[13] = st_cblock;
           }
         }
-        __syncthreads(); // all steps are stored (every compute wave has drained)
+        __syncthreads(); // all steps are stored (the compute wave has drained)
         if (threadIdx.x == 0) {
           publish(nsteps);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

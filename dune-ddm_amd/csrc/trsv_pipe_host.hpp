@@ -50,7 +50,6 @@ constexpr int MIN_W = 14;                       // tiles hold at least this many
 inline int32_t ring_op(int step, int lane) { return (int32_t)(((step % RING) * LANES + lane) * 8); }
 constexpr int32_t PAD_OP = RING_Z;
 constexpr int MAXPROD = 112;   // producer tasks per task: two 16-bit step counts per header word HDR_REQ0 .. 63
-constexpr int MAX_NC = 3;      // the late-operand masks below are provided for up to MAX_NC compute waves per task
 constexpr int HDR_REQ0 = 8;
 constexpr int MAX_W = 26;      // widest triangular row taken (27-point stencil: all neighbours on one side); the kernel's LDS
                                // tile ring must hold 3 such tiles (21 KiB each) or loaders and compute wave could wait for each other
@@ -60,7 +59,7 @@ struct Task { // device-visible descriptor, 512 bytes
   int64_t pos_base;  // first position of the task in the position space of its sweep
   int64_t koff_base; // index of the task's nsteps + 1 cumulative tile offsets (KiB, relative to tile_off) in Schedule::koff
   int32_t nsteps, nprod, group, sweep;
-  int32_t W, first_kib, second_kib; // widest row of the task; sizes of its first two tiles in KiB
+  int32_t W, first_kib, pad0;       // widest row of the task; size of its first tile in KiB
   int32_t start_level, pad[2];      // dependency level of the task's first step (diagnostics)
   int32_t prod[MAXPROD]; // global task ids of the producers
 };
@@ -70,9 +69,7 @@ struct Group {
 };
 
 // Tile layout (bytes): [0,256) header int32[64]: [0] active rows, [1] flags, [2] W = widest row of the step,
-// [3] size of the task's NEXT tile in KiB (0 behind the last one), [5] of the tile after that, [4] / [6]: bit u set =
-// entry u of some lane is a ring operand produced 1 step / 1 or 2 steps earlier (what a compute wave that shares the task
-// with 1 / 2 other waves must read AFTER the previous step has signalled),
+// [3] size of the task's NEXT tile in KiB (0 behind the last one), [4..7] reserved (0),
 // word HDR_REQ0 + p/2, 16-bit half p%2: steps of producer p that must be stored; [256,512) int32[64]: BYTE offset of the row's right-hand side -- U: in the forward results (position order), L: in the caller's vector (natural row * 8); [512,1024) double[64]:
 // U: inverse pivot; then idx pieces (1 KiB each: lane l holds int32[4] = operands 4q..4q+3), then value pieces
 // (1 KiB each: lane l holds double[2] = entries 2q, 2q+1).  Operand encoding: see above; the U tile's "own" word is
@@ -579,7 +576,6 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
           }
           S.koff[(size_t)kb + B.tasks[q].nsteps] = k;
           T.first_kib = S.koff[(size_t)kb + 1];
-          T.second_kib = B.tasks[q].nsteps > 1 ? S.koff[(size_t)kb + 2] - S.koff[(size_t)kb + 1] : 0;
           kb += B.tasks[q].nsteps + 1;
           off += (int64_t)k * 1024;
           T.pos_base = pos;
@@ -610,7 +606,6 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
         const Task &T = S.tasks[(size_t)tb + q];
         std::vector<int32_t> req(MAXPROD, 0);
         for (int32_t t = 0; t < R.nsteps; ++t) {
-          uint32_t late1 = 0, late2 = 0;
           const Geometry G(R.stepW[t]);
           unsigned char *tile = S.stream.data() + T.tile_off + (int64_t)S.koff[(size_t)T.koff_base + t] * 1024;
           int32_t *hdr = reinterpret_cast<int32_t *>(tile);
@@ -647,8 +642,6 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
               if (tj == (int32_t)q && t - sj < RING) {
                 op = ring_op(sj, lj);
                 ++st.entries_local;
-                if (t - sj <= 1) late1 |= 1u << std::min(u, 31);
-                if (t - sj <= 2) late2 |= 1u << std::min(u, 31);
               } else {
                 op = (int32_t)(pos_of(B, tb, j) * 8);
                 if (tj == (int32_t)q) ++st.entries_self_global;
@@ -666,9 +659,6 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
           hdr[1] = t + 1 == R.nsteps ? 1 : 0;
           hdr[2] = G.W;
           hdr[3] = t + 1 < R.nsteps ? Geometry(R.stepW[t + 1]).tile_bytes / 1024 : 0;
-          hdr[5] = t + 2 < R.nsteps ? Geometry(R.stepW[t + 2]).tile_bytes / 1024 : 0;
-          hdr[4] = (int32_t)late1;
-          hdr[6] = (int32_t)late2;
           for (int p = 0; p < T.nprod; ++p) hdr[HDR_REQ0 + p / 2] |= (int32_t)((uint32_t)req[p] << (16 * (p & 1))); // cumulative: never decreases along the task
         }
       }
@@ -717,8 +707,7 @@ inline std::string emulate(const Schedule &S, int64_t n, const double *d, double
           const Geometry G(hdr[2]);
           if (hdr[3] != (t + 1 < T.nsteps ? S.koff[(size_t)T.koff_base + t + 2] - S.koff[(size_t)T.koff_base + t + 1] : 0)) return "next-tile size mismatch";
           if (t == 0 && T.first_kib != S.koff[(size_t)T.koff_base + 1]) return "first-tile size mismatch";
-          if (t == 0 && T.second_kib != (T.nsteps > 1 ? S.koff[(size_t)T.koff_base + 2] - S.koff[(size_t)T.koff_base + 1] : 0)) return "second-tile size mismatch";
-          if (hdr[5] != (t + 2 < T.nsteps ? S.koff[(size_t)T.koff_base + t + 3] - S.koff[(size_t)T.koff_base + t + 2] : 0)) return "second-next-tile size mismatch";
+          if (hdr[4] | hdr[5] | hdr[6] | hdr[7]) return "reserved header word is not zero";
           if (hdr[2] < MIN_W || G.W > std::max(T.W, MIN_W) || S.koff[(size_t)T.koff_base + t + 1] - S.koff[(size_t)T.koff_base + t] != G.tile_bytes / 1024) return "tile size mismatch";
           const int32_t *own = reinterpret_cast<const int32_t *>(tile + 256);
           const double *s0 = reinterpret_cast<const double *>(tile + 512);
@@ -746,8 +735,6 @@ inline std::string emulate(const Schedule &S, int64_t n, const double *d, double
                   int back = (t % RING) - row;
                   if (back <= 0) back += RING;
                   if (back > t) return "ring operand older than the task";
-                  if (back <= 1 && !((uint32_t)hdr[4] >> std::min(u, 31) & 1u)) return "late mask (1 step) misses an operand";
-                  if (back <= 2 && !((uint32_t)hdr[6] >> std::min(u, 31) & 1u)) return "late mask (2 steps) misses an operand";
                 }
                 xv = ring[(size_t)op / 8];
               } else {

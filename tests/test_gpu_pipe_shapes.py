@@ -12,7 +12,8 @@ classes breaks both checks below.  Per solve:
   (b) bit equality with the oracle's sequential solve: pipe sums every row in ascending column order.
 
 F.engine() must be exactly pipe_cases.EXPECT[name]: "pipe", or "xcd2" for the matrices the builder declines (a builder that starts
-declining a case would otherwise be tested on another engine without anyone noticing).  No case is skipped or filtered at run time."""
+declining a case would otherwise be tested on another engine without anyone noticing).  No case is skipped or filtered at run time.
+test_stamped_solve runs the kernel's stamped instantiation (the diagnostic build behind tools/pipe_trace.py) on three of the cases."""
 import numpy as np
 import pytest
 
@@ -98,4 +99,39 @@ def test_ten_solves_back_to_back(ddm, name, spread, monkeypatch):
     got = a.cpu().numpy()
     print(f"\n{name} spread {spread}: {int(np.sum(got != x))} of {c.n} entries differ from 10 oracle solves")
     assert np.array_equal(got, x), (name, spread)
+    ctx.close()
+
+
+STAMPED = ("mix9", "w26", "chains65")   # 9 uneven blocks (XCD-local mode); both wide halves; a dissolved schedule of 1 .. 3-step tasks
+
+
+@pytest.mark.parametrize("spread", ["0", "1"])
+@pytest.mark.parametrize("name", STAMPED)
+def test_stamped_solve(ddm, name, spread, monkeypatch):
+    """the stamped instantiation of the kernel (F.pipe_trace, tools/pipe_trace.py): status 0, x bit-equal to the oracle, and per task
+    the 16-word layout (csrc/trsv_pipe.hpp, STAMP): [6] = the task's steps in the host builder's schedule, [0] <= [1] <= [2],
+    [7] an XCC id, the unused words [5] and [10] zero, store times [16 ..] non-decreasing over the first min(steps, 256) steps"""
+    import torch
+    _pipe_mode(monkeypatch, spread)
+    ref = pc.ref(name)
+    c = ref.c
+    ctx = ddm.torch_context(0)
+    F, _ = _factor(ddm, ctx, c, ref.lu)
+    d = torch.tensor(ref.d[0]).cuda()
+    xd = torch.full_like(d, float("nan"))
+    st, meta = F.pipe_trace(d, xd)
+    ctx.sync()
+    assert F.status() == 0, (name, spread, F.status())
+    x = xd.cpu().numpy()
+    assert np.array_equal(x, ref.x[0]), (name, spread, int(np.sum(x != ref.x[0])))
+    tasks = pc.schedule(name).tasks
+    assert len(st) == len(tasks) and meta[:, 1].tolist() == [t[0] for t in tasks] and meta[:, 0].tolist() == [t[1] for t in tasks]
+    st = st.astype(np.int64)
+    for q, (_, _, _, widths) in enumerate(tasks):
+        nsteps = len(widths)
+        assert st[q, 6] == nsteps, (name, spread, q, int(st[q, 6]), nsteps)
+        assert st[q, 0] <= st[q, 1] <= st[q, 2], (name, spread, q, st[q, :3].tolist())
+        assert 0 <= st[q, 7] < 8, (name, spread, q, int(st[q, 7]))
+        assert st[q, 5] == 0 and st[q, 10] == 0, (name, spread, q, int(st[q, 5]), int(st[q, 10]))
+        assert (np.diff(st[q, 16:16 + min(nsteps, 256)]) >= 0).all(), (name, spread, q)
     ctx.close()
