@@ -36,14 +36,12 @@ struct ddm_ctx {
   // collectives of the iteration, counted as a run over several ranks issues them (one count = one RCCL launch: an all-reduce or a
   // grouped send/receive); ddm_ctx_comm_counts
   int64_t n_allreduce = 0, n_allreduce_doubles = 0, n_halo_groups = 0;
-  // a scalar waiting to ride on the next coarse-defect all-reduce (ddm_cg_steps: the squared defect norm of the previous iteration)
-  double *piggy = nullptr;
   bool rccl = false, rccl_self = false; // rccl_self: route the self segment through RCCL too (single-GPU self test)
   // side stream of the additive combination: the coarse level's restrict / solve / prolong run beside the latency-bound local solve
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   dbuf<double> partial; // RED_MAX_BLOCKS doubles
-  dbuf<double> scal;    // 16 device scalars
+  dbuf<double> scal;    // SCAL_SLOTS device scalars (the slots SCAL_*, kernels.hpp)
   int num_cu = 256;           // compute units of the device: persistent kernels launch at most this many workgroups
   bool timing = false;
   std::map<std::string, TimerEntry> timers;
@@ -128,13 +126,15 @@ static hipError_t dev_memset(void *p, int v, size_t bytes)
   return e != hipSuccess ? e : hipStreamSynchronize(t_transfer_stream);
 }
 
-// HIP-event timer on the context's stream.  Nothing synchronises while timing is on: the event
-// pairs are resolved (hipEventElapsedTime) when the totals are read, after the stream has drained.
+// HIP-event timer on the context's stream, or on the stream it is given (the side stream).  Nothing synchronises while timing is on:
+// the event pairs are resolved (hipEventElapsedTime) when the totals are read, after the stream has drained.
 struct ScopedTimer {
   ddm_ctx *ctx;
+  hipStream_t stream;
   TimerEntry *t = nullptr;
   std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-  ScopedTimer(ddm_ctx *c, const char *n) : ctx(c)
+  ScopedTimer(ddm_ctx *c, const char *n) : ScopedTimer(c, n, c->stream) {}
+  ScopedTimer(ddm_ctx *c, const char *n, hipStream_t s) : ctx(c), stream(s)
   {
     if (!ctx->timing) return;
     t = &ctx->timers[n];
@@ -145,12 +145,12 @@ struct ScopedTimer {
       (void)hipEventCreate(&ev.first);
       (void)hipEventCreate(&ev.second);
     }
-    (void)hipEventRecord(ev.first, ctx->stream);
+    (void)hipEventRecord(ev.first, stream);
   }
   ~ScopedTimer()
   {
     if (!t) return;
-    (void)hipEventRecord(ev.second, ctx->stream);
+    (void)hipEventRecord(ev.second, stream);
     t->pending.push_back(ev);
   }
 };
@@ -192,12 +192,12 @@ extern "C" int ddm_ctx_create(int device, void *hip_stream, ddm_ctx **out)
     }
     ctx->own_stream = true;
   }
-  if (ctx->partial.alloc(RED_MAX_BLOCKS) != hipSuccess || ctx->scal.alloc(16) != hipSuccess ||
+  if (ctx->partial.alloc(RED_MAX_BLOCKS) != hipSuccess || ctx->scal.alloc(SCAL_SLOTS) != hipSuccess ||
       hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
     delete ctx;
     return DDM_EHIP;
   }
-  (void)hipMemset(ctx->scal, 0, sizeof(double) * 16);
+  (void)hipMemset(ctx->scal, 0, sizeof(double) * SCAL_SLOTS);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->num_cu = prop.multiProcessorCount;
@@ -351,31 +351,31 @@ static int ctx_side_stream(ddm_ctx *ctx)
   ctx->side = s; // (set last: ddm_ctx_destroy releases the three together)
   return DDM_OK;
 }
-// in-place sum over all ranks of n doubles at a device pointer, enqueued on the context's stream
-static int ctx_allreduce(ddm_ctx *ctx, double *buf, int64_t n, const char *what)
+// in-place sum over all ranks of n doubles at a device pointer, enqueued on `stream`
+static int ctx_allreduce(ddm_ctx *ctx, double *buf, int64_t n, const char *what, hipStream_t stream)
 {
   ctx->n_allreduce += 1;
   ctx->n_allreduce_doubles += n;
   if (ctx->rccl) {
-    if (ctx->nranks > 1 || ctx->rccl_self) NCCLCHECK(ctx, ctx->nccl.AllReduce(buf, buf, (size_t)n, ncclDouble, ncclSum, ctx->rccl_comm, ctx->stream));
+    if (ctx->nranks > 1 || ctx->rccl_self) NCCLCHECK(ctx, ctx->nccl.AllReduce(buf, buf, (size_t)n, ncclDouble, ncclSum, ctx->rccl_comm, stream));
     return DDM_OK;
   }
   if (ctx->nranks > 1)
     if (ctx->allreduce(ctx->user, buf, n) != 0) return fail(ctx, DDM_ECOMM, "allreduce callback failed (%s)", what);
   return DDM_OK;
 }
+// ... on the context's stream
+static int ctx_allreduce(ddm_ctx *ctx, double *buf, int64_t n, const char *what) { return ctx_allreduce(ctx, buf, n, what, ctx->stream); }
 
-// the coarse defect (K doubles at d0, room for K + 1) summed over the ranks; a scalar waiting in ctx->piggy rides along as element K
-// (one RCCL launch instead of two) and is written back
+// the coarse defect (K doubles at d0, room for K + 1) summed over the ranks on `stream`; rider, where not null, is a device scalar
+// that rides along as element K (one RCCL launch instead of two) and is written back
 __global__ void k_copy_scalar(const double *__restrict__ src, double *__restrict__ dst) { *dst = *src; }
-static int coarse_allreduce(ddm_ctx *ctx, double *d0, int64_t K)
+static int coarse_allreduce(ddm_ctx *ctx, double *d0, int64_t K, double *rider, hipStream_t stream)
 {
-  double *rider = ctx->piggy;
-  ctx->piggy = nullptr;
-  if (!rider) return ctx_allreduce(ctx, d0, K, "coarse defect");
-  hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, ctx->stream, (const double *)rider, d0 + K);
-  DDMCHECK(ctx_allreduce(ctx, d0, K + 1, "coarse defect + deferred defect norm"));
-  hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, ctx->stream, (const double *)(d0 + K), rider);
+  if (!rider) return ctx_allreduce(ctx, d0, K, "coarse defect", stream);
+  hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, stream, (const double *)rider, d0 + K);
+  DDMCHECK(ctx_allreduce(ctx, d0, K + 1, "coarse defect + deferred defect norm", stream));
+  hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, stream, (const double *)(d0 + K), rider);
   return DDM_OK;
 }
 extern "C" int ddm_ctx_comm_counts(ddm_ctx *ctx, int64_t *counts)
@@ -456,6 +456,6 @@ static int ctx_multi_scratch(ddm_ctx *ctx)
   if (ctx->mscal) return DDM_OK;
   HIPCHECK(ctx, ctx->mpartial.alloc((int64_t)RED_MAX_BLOCKS * MULTI_MAX * 2)); // (two sums per column in one pass: k_fcg_dots_multi)
   HIPCHECK(ctx, ctx->mactive.alloc(MULTI_MAX));
-  HIPCHECK(ctx, ctx->mscal.alloc(std::max(8, BICG_SCALARS) * MULTI_MAX)); // (CG: 6 rows, the scratch of ddm_dot_multi: row 6; queued BiCGSTAB: 13)
+  HIPCHECK(ctx, ctx->mscal.alloc(SCAL_ROWS * MULTI_MAX)); // (the rows SCAL_* and BICG_*: kernels.hpp, multi_kernels.hpp)
   return DDM_OK;
 }

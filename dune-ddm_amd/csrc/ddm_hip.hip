@@ -51,7 +51,8 @@ using namespace ddm;
 #include "local_solver.hpp"     // creation: ilu0_create_impl, direct_create_impl, ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*.  Needs local_solve.hpp.
 #include "geneo.hpp"            // GeneoProblem, GeneoRun, ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, ddm_harmonic (pulls in dense_host.hpp and geneo_blocks.hpp: GeneoWork over geneo_kernels.hpp, ddm_blockvec_*).  Needs csr.hpp, local_solver.hpp.
 #include "halo.hpp"             // ddm_halo: single-vector and m-column exchange over one RCCL wire function.  Needs context.hpp.
-#include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp.
+#include "krylov_work.hpp"      // KrylovWork: the block Krylov drivers' work blocks, one pool per ddm_combined.  Needs device_buffer.hpp, multi_kernels.hpp.
+#include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp, krylov_work.hpp.
 #include "krylov.hpp"           // CG (begin / steps / defect / solve), GMRES, BiCGSTAB, flexible CG, block CG, block GMRES, block flexible CG.  Needs preconditioners.hpp.
 
 // ---- dense host helpers exposed for the CPU tests (host logic of the GenEO Rayleigh-Ritz step) -------------------------

@@ -1303,19 +1303,28 @@ __global__ __launch_bounds__(WG) void k_reduce_final(int nb, const double *__res
   if (threadIdx.x == 0) out[0] = s;
 }
 
+// The device scalars of the Krylov drivers, one numbering for slot s of ctx->scal (SCAL_SLOTS doubles) and row s of ctx->mscal (SCAL_ROWS
+// rows of MULTI_MAX doubles): rho of the last iteration, <p, q>, the step length (CG's lambda, flexible CG's alpha), rho, beta, <b, b>;
+// then the output row of ddm_dot_multi and ddm_fgmres_defect_multi and the output slot of ddm_dot.
+constexpr int SCAL_RHOLAST = 0, SCAL_PQ = 1, SCAL_STEP = 2, SCAL_RHO = 3, SCAL_BETA = 4, SCAL_DEF2 = 5, SCAL_DOT_MULTI = 6, SCAL_DOT = 8;
+constexpr int SCAL_SLOTS = 16, SCAL_ROWS = 13; // what ddm_ctx_create and ctx_multi_scratch allocate
+// CG, queued CG, flexible CG and ddm_fgmres_defect_multi use 0 .. SCAL_DOT_MULTI; queued BiCGSTAB names its own rows 0 .. BICG_SCALARS - 1
+// (multi_kernels.hpp) ON TOP of them: its rows 4 .. 12 cover SCAL_BETA .. SCAL_DOT_MULTI.  The overlap is meant: one driver runs at a
+// time on a context, and each writes a scalar before it reads it (a fresh CG slot's SCAL_RHOLAST = 1: k_column_load_multi).
+static_assert(SCAL_DEF2 < SCAL_DOT_MULTI && SCAL_DOT_MULTI < SCAL_ROWS && SCAL_DOT < SCAL_SLOTS, "CG family: rows 0 .. 6 of ctx->mscal, slots 0 .. 5 and 8 of ctx->scal");
+
 // CG scalar recurrences on the device (dune-istl CGSolver), one thread.
-// scal: [0]=rholast [1]=alpha=<p,q> [2]=lambda [3]=rho [4]=beta [5]=<b,b>
-__global__ void k_cg_lambda(double *scal) { scal[2] = scal[0] / scal[1]; }
+__global__ void k_cg_lambda(double *scal) { scal[SCAL_STEP] = scal[SCAL_RHOLAST] / scal[SCAL_PQ]; }
 __global__ void k_cg_beta(double *scal)
 {
-  scal[4] = scal[3] / scal[0];
-  scal[0] = scal[3];
+  scal[SCAL_BETA] = scal[SCAL_RHO] / scal[SCAL_RHOLAST];
+  scal[SCAL_RHOLAST] = scal[SCAL_RHO];
 }
 // x += lambda p ; b -= lambda q
 __global__ void k_cg_update(int64_t n, const double *__restrict__ scal, const double *__restrict__ p,
                             const double *__restrict__ q, double *__restrict__ x, double *__restrict__ b)
 {
-  const double lam = scal[2];
+  const double lam = scal[SCAL_STEP];
   for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
     x[i] += lam * p[i];
     b[i] -= lam * q[i];
@@ -1329,7 +1338,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm(int64_t n, const double *
                                                         double *__restrict__ b, double *__restrict__ partial)
 {
   __shared__ double red[4];
-  const double lam = scal[2];
+  const double lam = scal[SCAL_STEP];
   double s = 0.0;
   for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
     x[i] += lam * p[i];
@@ -1343,7 +1352,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm(int64_t n, const double *
 // p = beta p + q
 __global__ void k_cg_direction(int64_t n, const double *__restrict__ scal, const double *__restrict__ q, double *__restrict__ p)
 {
-  const double beta = scal[4];
+  const double beta = scal[SCAL_BETA];
   for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) p[i] = beta * p[i] + q[i];
 }
 
@@ -1424,13 +1433,13 @@ __global__ __launch_bounds__(WG) void k_fcg_dots(int64_t n, const uint8_t *__res
     partial[gridDim.x + blockIdx.x] = sb;
   }
 }
-// g_s = <d, Ad> into its slot and the step alpha = <d, b> / g_s into scal[2], where k_cg_update_norm reads it; dots: the two sums of
+// g_s = <d, Ad> into its slot and the step alpha = <d, b> / g_s into scal[SCAL_STEP], where k_cg_update_norm reads it; dots: the two sums of
 // k_fcg_dots.  g_s == 0 makes the step NaN whatever <d, b> is, so that the driver's NaN test on the defect reports the breakdown.
 __global__ void k_fcg_alpha(const double *__restrict__ dots, double *__restrict__ gslot, double *__restrict__ scal)
 {
   const double g = dots[0];
   gslot[0] = g;
-  scal[2] = g == 0.0 ? __builtin_nan("") : dots[1] / g;
+  scal[SCAL_STEP] = g == 0.0 ? __builtin_nan("") : dots[1] / g;
 }
 
 // ---------------------------------------------------------------------------------------------

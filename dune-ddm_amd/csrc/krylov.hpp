@@ -9,7 +9,8 @@
 // vector count (fcg_loop, fcg_loop_multi) behind ddm_fcg_solve and ddm_fcg_solve_multi; ddm_fcg_orth_multi runs its orthogonalisation on
 // its own for tests.  Block CG (ddm_bcg_solve_multi, with ddm_bcg_gram_multi / ddm_bcg_update_multi / ddm_bcg_direction_multi for tests) is
 // the one symmetric driver whose columns share a search space; block GMRES (ddm_bgmres_solve_multi, with ddm_bgmres_project_multi /
-// ddm_bgmres_combine_multi / ddm_bgmres_combine_gram_multi for tests) is its non-symmetric companion.  Needs preconditioners.hpp.
+// ddm_bgmres_combine_multi / ddm_bgmres_combine_gram_multi for tests) is its non-symmetric companion.  Device scalars are the slots SCAL_*
+// (kernels.hpp) and BICG_* (multi_kernels.hpp); the block drivers' work blocks come from prec->work (krylov_work.hpp).  Needs preconditioners.hpp.
 #pragma once
 
 // synchronises the context's stream when it goes out of scope: the Krylov drivers declare it AFTER their work arrays, so that an
@@ -119,7 +120,6 @@ struct ddm_cg {
 extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, ddm_cg **out)
 {
   if (!ctx || !op || !prec || !x || !b || !out) return fail(ctx, DDM_EINVAL, "ddm_cg_begin: bad arguments");
-  ctx->piggy = nullptr; // (nothing rides on an all-reduce outside ddm_cg_steps)
   auto S = std::make_unique<ddm_cg>();
   S->op = op;
   S->prec = prec;
@@ -129,39 +129,36 @@ extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double
   if (S->p.alloc(S->n) != hipSuccess || S->q.alloc(S->n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_cg_begin: allocation failed");
   DDMCHECK(ddm_op_applyscaleadd(ctx, op, -1.0, x, b)); // prec.pre(x,b); b -= A x
   double bb = 0.0;
-  DDMCHECK(dot_device(ctx, S->n, op->owner, b, b, ctx->scal + 5));
-  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double)));
+  DDMCHECK(dot_device(ctx, S->n, op->owner, b, b, ctx->scal + SCAL_DEF2));
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + SCAL_DEF2, sizeof(double)));
   S->def0 = std::sqrt(bb);
   *out = S.release();
   return DDM_OK;
 }
 extern "C" void ddm_cg_end(ddm_ctx *ctx, ddm_cg *S)
 {
-  if (ctx) ctx->piggy = nullptr;
   if (!S) return;
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
   delete S;
 }
 extern "C" double ddm_cg_def0(const ddm_cg *S) { return S->def0; }
 // Enqueues k iterations without synchronising; the squared defect of the last one is left in
-// device scalar 5 (read it with ddm_cg_defect).
+// device scalar SCAL_DEF2 (read it with ddm_cg_defect).
 extern "C" int ddm_cg_steps(ddm_ctx *ctx, ddm_cg *S, int k)
 {
-  // ctx->piggy is set below between one iteration and the next preconditioner apply: whichever way this function returns, it must
-  // not stay set, or the next unrelated coarse_allreduce reduces K + 1 doubles on this rank and K on the others (a hang)
-  struct PiggyGuard { ddm_ctx *ctx; ~PiggyGuard() { ctx->piggy = nullptr; } } piggy_guard{ctx};
   double *scal = ctx->scal;
+  double *rider = nullptr; // the previous iteration's squared defect norm, not yet summed over the ranks: handed to the next apply
   const int G = grid_for(S->n);
   for (int i = 0; i < k; ++i) {
     const bool first = S->it == 0;
-    DDMCHECK(ddm_combined_apply(ctx, S->prec, first ? S->p : S->q, S->b));                 // q = M^-1 b  (p on the first step)
-    DDMCHECK(dot_device(ctx, S->n, S->op->owner, first ? S->p : S->q, S->b, scal + (first ? 0 : 3))); // rho = <q, b>
+    DDMCHECK(combined_apply_impl(ctx, S->prec, first ? S->p : S->q, S->b, rider));         // q = M^-1 b  (p on the first step)
+    DDMCHECK(dot_device(ctx, S->n, S->op->owner, first ? S->p : S->q, S->b, scal + (first ? SCAL_RHOLAST : SCAL_RHO))); // rho = <q, b>
     if (!first) {
       hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(1), 0, ctx->stream, scal);                 // beta = rho / rholast; rholast = rho
       hipLaunchKernelGGL(k_cg_direction, dim3(G), dim3(WG), 0, ctx->stream, S->n, scal, S->q, S->p); // p = beta p + q
     }
     DDMCHECK(ddm_op_apply(ctx, S->op, S->p, S->q));                                          // q = A p
-    DDMCHECK(dot_device(ctx, S->n, S->op->owner, S->p, S->q, scal + 1));                     // alpha = <p, q>
+    DDMCHECK(dot_device(ctx, S->n, S->op->owner, S->p, S->q, scal + SCAL_PQ));               // alpha = <p, q>
     hipLaunchKernelGGL(k_cg_lambda, dim3(1), dim3(1), 0, ctx->stream, scal);                 // lambda = rholast / alpha
     { // x += lambda p; b -= lambda q; def^2 = <b, b> (partial sums in the same kernel)
       const int nb = grid_for(S->n, WG * 4, RED_MAX_BLOCKS);
@@ -169,23 +166,22 @@ extern "C" int ddm_cg_steps(ddm_ctx *ctx, ddm_cg *S, int k)
         hipLaunchKernelGGL(k_cg_update_norm<true>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial);
       else
         hipLaunchKernelGGL(k_cg_update_norm<false>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial);
-      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + 5);
+      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + SCAL_DEF2);
       // The rank-local sum is complete; its all-reduce rides on the coarse-defect all-reduce of the NEXT iteration's preconditioner
       // (one RCCL launch saved per iteration) unless this is the chunk's last iteration -- whoever reads the defect (ddm_cg_defect)
       // needs it now -- or there is no coarse level to ride on.
-      if (i + 1 < k && S->prec->galerkin) ctx->piggy = scal + 5;
-      else DDMCHECK(ctx_allreduce(ctx, scal + 5, 1, "scalar product"));
+      rider = i + 1 < k && S->prec->galerkin ? scal + SCAL_DEF2 : nullptr;
+      if (!rider) DDMCHECK(ctx_allreduce(ctx, scal + SCAL_DEF2, 1, "scalar product"));
     }
     S->it += 1;
   }
-  // (ctx->piggy is null here: the last iteration of a chunk reduces its own norm, every earlier one was consumed by the next apply)
   HIPCHECK(ctx, hipGetLastError());
   return DDM_OK;
 }
 extern "C" int ddm_cg_defect(ddm_ctx *ctx, ddm_cg *S, double *def_host) // synchronous
 {
   double bb = 0.0;
-  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + 5, sizeof(double)));
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, ctx->scal + SCAL_DEF2, sizeof(double)));
   *def_host = std::sqrt(bb);
   (void)S;
   return DDM_OK;
@@ -570,23 +566,23 @@ static int cg_multi_step(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int m, bo
   double *scal = ctx->mscal;
   const int64_t n = op->n;
   DDMCHECK(combined_apply_multi_impl(ctx, prec, m, first ? P : Q, B));                                       // q = M^-1 b (p on the first step)
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, first ? P : Q, B, scal + (first ? 0 : 3 * MULTI_MAX))); // rho = <q, b>
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, first ? P : Q, B, scal + (first ? SCAL_RHOLAST : SCAL_RHO) * MULTI_MAX)); // rho = <q, b>
   if (!first) {
     hipLaunchKernelGGL(k_cg_beta_multi, dim3(1), dim3(64), 0, ctx->stream, m, (const int32_t *)ctx->mactive, scal); // beta = rho / rholast
     hipLaunchKernelGGL(k_cg_direction_multi, dim3(grid_for(n * m)), dim3(WG), 0, ctx->stream, n, m, (const int32_t *)ctx->mactive, (const double *)scal,
                        (const double *)Q, P); // p = beta p + q
   }
   DDMCHECK(op_apply_multi(ctx, op, m, P, Q));                                           // q = A p
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, P, Q, scal + MULTI_MAX));           // alpha = <p, q>
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, P, Q, scal + SCAL_PQ * MULTI_MAX)); // alpha = <p, q>
   hipLaunchKernelGGL(k_cg_lambda_multi, dim3(1), dim3(64), 0, ctx->stream, m, (const int32_t *)ctx->mactive, scal); // lambda = rholast / alpha
   const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
   for_column_groups(m, [&](int c0, int cb) { // x += lambda p; b -= lambda q; <b, b> partials
     DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, (const int32_t *)ctx->mactive,
-                          (const double *)scal, 2, (const uint8_t *)op->owner, (const double *)P, (const double *)Q, X, B, ctx->mpartial);
+                          (const double *)scal, SCAL_STEP, (const uint8_t *)op->owner, (const double *)P, (const double *)Q, X, B, ctx->mpartial);
   });
-  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + 5 * MULTI_MAX);
+  hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + SCAL_DEF2 * MULTI_MAX);
   HIPCHECK(ctx, hipGetLastError());
-  return ctx_allreduce(ctx, scal + 5 * MULTI_MAX, m, "defect norms");
+  return ctx_allreduce(ctx, scal + SCAL_DEF2 * MULTI_MAX, m, "defect norms");
 }
 extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, int nrhs, double *X, double *B, double reduction, int maxit,
                                   double *hist_host, ddm_solve_result *res)
@@ -598,20 +594,20 @@ extern "C" int ddm_cg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   const int64_t n = op->n;
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
-  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // search directions p, q: block scratch of the preconditioner object
-  double *P = prec->mp, *Q = prec->mq;
+  HIPCHECK(ctx, prec->work.reserve(m, n, 2));
+  double *P = prec->work.block[0], *Q = prec->work.block[1]; // search directions p, q
   double bb[MULTI_MAX];
   MultiFrame f{ctx, "ddm_cg_solve_multi", m, reduction, hist_host, res};
   DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B)); // prec.pre(x, b); b -= A x
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, ctx->mscal + 5 * MULTI_MAX));
-  DDMCHECK(ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m));
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, ctx->mscal + SCAL_DEF2 * MULTI_MAX));
+  DDMCHECK(ddm_memcpy_d2h(ctx, bb, ctx->mscal + SCAL_DEF2 * MULTI_MAX, sizeof(double) * (size_t)m));
   DDMCHECK(multi_start(f, bb));
   (void)hipStreamSynchronize(ctx->stream);
   const auto t0 = std::chrono::steady_clock::now();
   int rc = DDM_OK;
   for (int i = 1; i <= maxit && f.nactive > 0 && !rc; ++i) {
     rc = cg_multi_step(ctx, op, prec, m, i == 1, X, B, P, Q);
-    if (!rc) rc = ddm_memcpy_d2h(ctx, bb, ctx->mscal + 5 * MULTI_MAX, sizeof(double) * (size_t)m); // the defects are tested every iteration
+    if (!rc) rc = ddm_memcpy_d2h(ctx, bb, ctx->mscal + SCAL_DEF2 * MULTI_MAX, sizeof(double) * (size_t)m); // the defects are tested every iteration
     for (int c = 0; c < m && !rc; ++c)
       if (f.active[c]) rc = multi_record(f, c, i, std::sqrt(bb[c]));
     if (!rc && f.nactive > 0) rc = multi_upload_mask(f);
@@ -685,9 +681,8 @@ extern "C" int ddm_bcg_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec,
   const int64_t n = op->n;
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
-  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // P and Q = A P: the blocks of ddm_cg_solve_multi
-  HIPCHECK(ctx, reserve_cols(prec->mbcg_cols, m, prec->mz, n));                          // Z = M^-1 R
-  double *P = prec->mp, *Q = prec->mq, *Z = prec->mz;
+  HIPCHECK(ctx, prec->work.reserve(m, n, 3));
+  double *P = prec->work.block[0], *Q = prec->work.block[1], *Z = prec->work.block[2]; // P, Q = A P, Z = M^-1 R
   dbuf<double> sdev, part; // sdev: [W | S] (2 m^2), [Q^T Z | norms] (m^2 + m), alpha (m^2), beta (m^2)
   HIPCHECK(ctx, sdev.alloc(5 * mm + m));
   HIPCHECK(ctx, part.alloc((int64_t)2 * mm * RED_MAX_BLOCKS));
@@ -872,9 +867,8 @@ extern "C" int ddm_bgmres_solve_multi(ddm_ctx *ctx, ddm_op *op, ddm_combined *pr
   DDMCHECK(gmres_memory_check(ctx, what, (int64_t)R + 4 + (npart + vstride - 1) / vstride, n, m));
   for (int c = 0; c < m; ++c) solve_result_reset(&res[c]);
   DDMCHECK(ctx_multi_scratch(ctx));
-  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, m, {{prec->mp, n}, {prec->mq, n}})); // U (cycle end) and W: the blocks of ddm_cg_solve_multi
-  HIPCHECK(ctx, reserve_cols(prec->mbcg_cols, m, prec->mz, n));                          // Z = M^-1 V_j, M^-1 U: block CG's
-  double *U = prec->mp, *W = prec->mq, *Z = prec->mz;
+  HIPCHECK(ctx, prec->work.reserve(m, n, 3));
+  double *U = prec->work.block[0], *W = prec->work.block[1], *Z = prec->work.block[2]; // U (cycle end), W = A Z, Z = M^-1 V_j or M^-1 U
   dbuf<double> Vb, hdev, cdev, part; // hdev: [H1 | H2 | G_W] of a step, norms; cdev: C0 / C / Y, then the unit matrix
   HIPCHECK(ctx, Vb.alloc(vstride * (R + 1)));
   HIPCHECK(ctx, hdev.alloc((int64_t)(2 * (R + 1) + 1) * mm + m));
@@ -1095,15 +1089,13 @@ extern "C" int ddm_cg_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, 
   const int64_t n = op->n;
   for (int64_t j = 0; j < ncols; ++j) solve_result_reset(&res[j]);
   DDMCHECK(ctx_multi_scratch(ctx));
-  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, w, {{prec->mp, n}, {prec->mq, n}}));   // directions p, q
-  HIPCHECK(ctx, reserve_cols<double>(prec->mqueue_cols, w, {{prec->mxw, n}, {prec->mbw, n}})); // the slots' x and defect
-  if (!prec->mqueue_tab) HIPCHECK(ctx, prec->mqueue_tab.alloc(2 * MULTI_MAX));
+  HIPCHECK(ctx, prec->work.reserve(w, n, 4));
   StreamDrain drain{ctx}; // every return waits for the kernels that read the caller's blocks
-  double *P = prec->mp, *Q = prec->mq, *XW = prec->mxw, *BW = prec->mbw;
-  int64_t *tabdev = prec->mqueue_tab; // (slot, column) pairs of one load or store launch
+  double *P = prec->work.block[0], *Q = prec->work.block[1], *XW = prec->work.block[2], *BW = prec->work.block[3]; // directions p, q; the slots' x and defect
+  int64_t *tabdev = prec->work.tab; // (slot, column) pairs of one load or store launch
   if (n > 0) // a slot that never holds a column stays zero
     for (double *blk : {P, XW, BW}) HIPCHECK(ctx, hipMemsetAsync(blk, 0, sizeof(double) * (size_t)(n * w), ctx->stream));
-  double *bbdev = ctx->mscal + 5 * MULTI_MAX;
+  double *bbdev = ctx->mscal + SCAL_DEF2 * MULTI_MAX;
   double bb[MULTI_MAX];
   ddm_solve_result sres[MULTI_MAX]; // the slots' results: MultiFrame works on these, a stored column's entry is copied to res
   int64_t column[MULTI_MAX], tab[2 * MULTI_MAX];
@@ -1239,13 +1231,11 @@ extern "C" int ddm_bicgstab_solve_queue(ddm_ctx *ctx, ddm_op *op, ddm_combined *
   for (int64_t j = 0; j < ncols; ++j) solve_result_reset(&res[j]);
   if (nhist) std::fill(nhist, nhist + ncols, 0);
   DDMCHECK(ctx_multi_scratch(ctx));
-  HIPCHECK(ctx, reserve_cols<double>(prec->mcg_cols, w, {{prec->mp, n}, {prec->mq, n}}));               // p, t
-  HIPCHECK(ctx, reserve_cols<double>(prec->mqueue_cols, w, {{prec->mxw, n}, {prec->mbw, n}}));           // the slots' x and defect r
-  HIPCHECK(ctx, reserve_cols<double>(prec->mbicg_cols, w, {{prec->mrt, n}, {prec->mv, n}, {prec->my, n}})); // shadow defect, v, y
-  if (!prec->mqueue_tab) HIPCHECK(ctx, prec->mqueue_tab.alloc(2 * MULTI_MAX));
+  HIPCHECK(ctx, prec->work.reserve(w, n, 7));
   StreamDrain drain{ctx}; // every return waits for the kernels that read the caller's blocks
-  double *P = prec->mp, *T = prec->mq, *XW = prec->mxw, *R = prec->mbw, *RT = prec->mrt, *V = prec->mv, *Y = prec->my;
-  int64_t *tabdev = prec->mqueue_tab; // (slot, column) pairs of one load or store launch
+  dbuf<double> *blk = prec->work.block;
+  double *P = blk[0], *T = blk[1], *XW = blk[2], *R = blk[3], *RT = blk[4], *V = blk[5], *Y = blk[6]; // p, t; the slots' x and defect r; shadow defect, v, y
+  int64_t *tabdev = prec->work.tab; // (slot, column) pairs of one load or store launch
   if (n > 0) // a slot that never holds a column stays zero
     for (double *blk : {P, XW, R, RT, V}) HIPCHECK(ctx, hipMemsetAsync(blk, 0, sizeof(double) * (size_t)(n * w), ctx->stream));
   double *scal = ctx->mscal;
@@ -1463,7 +1453,7 @@ extern "C" int ddm_fgmres_defect_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const
   const int m = nrhs;
   const int64_t n = op->n;
   DDMCHECK(ddm_memcpy_h2d(ctx, ctx->mactive, active_host, sizeof(int32_t) * (size_t)m));
-  double *out = ctx->mscal + 6 * MULTI_MAX;
+  double *out = ctx->mscal + SCAL_DOT_MULTI * MULTI_MAX;
   if (fused) {
     DDMCHECK(defect_norm_multi(ctx, op, m, T, B, out));
   } else {
@@ -1688,8 +1678,8 @@ static int fcg_loop(ddm_ctx *ctx, const char *what, bool complete, ddm_op *op, d
   HIPCHECK(ctx, hipMemsetAsync(sdev, 0, sizeof(double) * (size_t)(3 * M + 3), ctx->stream));
   double bb = 0.0;
   DDMCHECK(ddm_op_applyscaleadd(ctx, op, -1.0, x, b)); // b -= A x
-  DDMCHECK(dot_device(ctx, n, op->owner, b, b, scal + 5));
-  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, scal + 5, sizeof(double)));
+  DDMCHECK(dot_device(ctx, n, op->owner, b, b, scal + SCAL_DEF2));
+  DDMCHECK(ddm_memcpy_d2h(ctx, &bb, scal + SCAL_DEF2, sizeof(double)));
   const double def0 = std::sqrt(bb);
   res->def0 = def0;
   if (hist_host) hist_host[0] = def0;
@@ -1722,9 +1712,9 @@ static int fcg_loop(ddm_ctx *ctx, const char *what, bool complete, ddm_op *op, d
         hipLaunchKernelGGL(k_cg_update_norm<true>, dim3(nb), dim3(WG), 0, ctx->stream, n, (const double *)scal, (const uint8_t *)op->owner, (const double *)ds, (const double *)ads, x, b, ctx->partial);
       else
         hipLaunchKernelGGL(k_cg_update_norm<false>, dim3(nb), dim3(WG), 0, ctx->stream, n, (const double *)scal, (const uint8_t *)op->owner, (const double *)ds, (const double *)ads, x, b, ctx->partial);
-      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + 5);
-      rc = ctx_allreduce(ctx, scal + 5, 1, "scalar product");
-      if (!rc) rc = ddm_memcpy_d2h(ctx, &bb, scal + 5, sizeof(double)); // the one read-back of the iteration
+      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + SCAL_DEF2);
+      rc = ctx_allreduce(ctx, scal + SCAL_DEF2, 1, "scalar product");
+      if (!rc) rc = ddm_memcpy_d2h(ctx, &bb, scal + SCAL_DEF2, sizeof(double)); // the one read-back of the iteration
       if (rc) break;
       def = std::sqrt(bb);
       res->iterations = i;
@@ -1855,8 +1845,8 @@ static int fcg_loop_multi(ddm_ctx *ctx, const char *what, bool complete, ddm_op 
   double bb[MULTI_MAX];
   MultiFrame f{ctx, what, m, reduction, hist_host, res};
   DDMCHECK(op_applyscaleadd_multi(ctx, op, m, -1.0, X, B)); // b -= A x
-  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, scal + 5 * MULTI_MAX));
-  DDMCHECK(ddm_memcpy_d2h(ctx, bb, scal + 5 * MULTI_MAX, sizeof(double) * (size_t)m));
+  DDMCHECK(dot_multi_device(ctx, n, op->owner, m, B, B, scal + SCAL_DEF2 * MULTI_MAX));
+  DDMCHECK(ddm_memcpy_d2h(ctx, bb, scal + SCAL_DEF2 * MULTI_MAX, sizeof(double) * (size_t)m));
   DDMCHECK(multi_start(f, bb));
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<int> buf(M + 1), J;
@@ -1879,12 +1869,12 @@ static int fcg_loop_multi(ddm_ctx *ctx, const char *what, bool complete, ddm_op 
       if (rc) break;
       hipLaunchKernelGGL(k_fcg_alpha_multi, dim3(1), dim3(64), 0, ctx->stream, m, active, (const double *)dots, g + (int64_t)buf[s] * m, scal); // alpha = <d_s, b> / g_s
       for_column_groups(m, [&](int c0, int cb) { // x += alpha d_s; b -= alpha Ad_s; <b, b> partials
-        DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, active, (const double *)scal, 2,
+        DDM_MULTI_CB_DISPATCH(k_cg_update_norm_multi, op->owner != nullptr, cb, dim3(nb), dim3(WG), 0, ctx->stream, n, m, c0, active, (const double *)scal, SCAL_STEP,
                               (const uint8_t *)op->owner, (const double *)ds, (const double *)ads, X, B, ctx->mpartial);
       });
-      hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + 5 * MULTI_MAX);
-      rc = ctx_allreduce(ctx, scal + 5 * MULTI_MAX, m, "defect norms");
-      if (!rc) rc = ddm_memcpy_d2h(ctx, bb, scal + 5 * MULTI_MAX, sizeof(double) * (size_t)m); // the one read-back of the iteration
+      hipLaunchKernelGGL(k_reduce_final_multi, dim3(m), dim3(WG), 0, ctx->stream, nb, (const double *)ctx->mpartial, scal + SCAL_DEF2 * MULTI_MAX);
+      rc = ctx_allreduce(ctx, scal + SCAL_DEF2 * MULTI_MAX, m, "defect norms");
+      if (!rc) rc = ddm_memcpy_d2h(ctx, bb, scal + SCAL_DEF2 * MULTI_MAX, sizeof(double) * (size_t)m); // the one read-back of the iteration
       for (int c = 0; c < m && !rc; ++c)
         if (f.active[c]) rc = multi_record(f, c, i, std::sqrt(bb[c]));
       if (!rc && f.nactive > 0) rc = multi_upload_mask(f);

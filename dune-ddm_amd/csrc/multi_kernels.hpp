@@ -209,19 +209,19 @@ __global__ __launch_bounds__(WG) void k_reduce_final_multi(int nb, const double 
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 // per-column CG scalars of the ACTIVE columns (a converged column keeps its values; nothing is multiplied by a zero step).
-// scal: [0..M) rholast, [M..2M) alpha = <p, q>, [2M..3M) lambda, [3M..4M) rho, [4M..5M) beta, [5M..6M) <b, b>; M = MULTI_MAX
+// scal: the rows SCAL_* (kernels.hpp) of ctx->mscal
 __global__ void k_cg_beta_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
 {
   const int c = threadIdx.x;
   if (c < m && active[c]) {
-    scal[4 * MULTI_MAX + c] = scal[3 * MULTI_MAX + c] / scal[c];
-    scal[c] = scal[3 * MULTI_MAX + c];
+    scal[SCAL_BETA * MULTI_MAX + c] = scal[SCAL_RHO * MULTI_MAX + c] / scal[SCAL_RHOLAST * MULTI_MAX + c];
+    scal[SCAL_RHOLAST * MULTI_MAX + c] = scal[SCAL_RHO * MULTI_MAX + c];
   }
 }
 __global__ void k_cg_lambda_multi(int m, const int32_t *__restrict__ active, double *__restrict__ scal)
 {
   const int c = threadIdx.x;
-  if (c < m && active[c]) scal[2 * MULTI_MAX + c] = scal[c] / scal[MULTI_MAX + c];
+  if (c < m && active[c]) scal[SCAL_STEP * MULTI_MAX + c] = scal[SCAL_RHOLAST * MULTI_MAX + c] / scal[SCAL_PQ * MULTI_MAX + c];
 }
 // p = beta p + q in the active columns
 __global__ void k_cg_direction_multi(int64_t n, int m, const int32_t *__restrict__ active, const double *__restrict__ scal, const double *__restrict__ q,
@@ -230,12 +230,12 @@ __global__ void k_cg_direction_multi(int64_t n, int m, const int32_t *__restrict
   const int64_t total = n * m;
   for (int64_t t = blockIdx.x * (int64_t)WG + threadIdx.x; t < total; t += (int64_t)gridDim.x * WG) {
     const int c = (int)(t % m);
-    if (active[c]) p[t] = scal[4 * MULTI_MAX + c] * p[t] + q[t];
+    if (active[c]) p[t] = scal[SCAL_BETA * MULTI_MAX + c] * p[t] + q[t];
   }
 }
 // x += lambda p; b -= lambda q; partial sums of <b, b> for columns [c0, c0 + CB) -- k_cg_update_norm per column (same grid, rows per
 // thread and block_sum).  Columns that are not active are neither read nor written (their partials are 0).  lambda_c is
-// scal[slot * MULTI_MAX + c]: slot 2 in the CG drivers.
+// scal[slot * MULTI_MAX + c]: slot SCAL_STEP in the CG drivers.
 template <int CB, bool MASKED>
 __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, int c0, const int32_t *__restrict__ active, const double *__restrict__ scal,
                                                              int slot, const uint8_t *__restrict__ mask, const double *__restrict__ p, const double *__restrict__ q,
@@ -279,7 +279,7 @@ __global__ void k_column_load_multi(int64_t n, int m, int nload, const int64_t *
                                     double *__restrict__ scal)
 {
   const int64_t gid = blockIdx.x * (int64_t)WG + threadIdx.x;
-  if (gid < nload) scal[tab[2 * gid]] = 1.0;
+  if (gid < nload) scal[SCAL_RHOLAST * MULTI_MAX + tab[2 * gid]] = 1.0;
   const int64_t total = n * nload;
   for (int64_t t = gid; t < total; t += (int64_t)gridDim.x * WG) {
     const int64_t i = t / nload;
@@ -310,6 +310,7 @@ __global__ void k_column_store_multi(int64_t n, int m, int nstore, const int64_t
 //   refill            [10M..): <r, r> of the loaded slots;  [11M..): <t, t>, then <t, r> (2 m doubles)
 constexpr int BICG_RHO = 0, BICG_ALPHA = 1, BICG_OMEGA = 2, BICG_BETA = 3, BICG_HALF1 = 4, BICG_HALF2 = 8, BICG_LOAD = 10, BICG_TT = 11;
 constexpr int BICG_SCALARS = 13; // ... times MULTI_MAX doubles
+static_assert(BICG_SCALARS <= SCAL_ROWS, "queued BiCGSTAB: rows 0 .. BICG_SCALARS - 1 of ctx->mscal, over the CG family's rows (kernels.hpp)");
 
 // beta = (rho_new / rho) (alpha / omega) in the active columns; rho and omega as used go where the host reads them with the first
 // half step's defect (its breakdown checks run on exactly these operands)
@@ -607,7 +608,7 @@ __global__ void k_fcg_alpha_multi(int m, const int32_t *__restrict__ active, con
   if (c < m && active[c]) {
     const double g = dots[c];
     gslot[c] = g;
-    scal[2 * MULTI_MAX + c] = g == 0.0 ? __builtin_nan("") : dots[m + c] / g;
+    scal[SCAL_STEP * MULTI_MAX + c] = g == 0.0 ? __builtin_nan("") : dots[m + c] / g;
   }
 }
 

@@ -3,7 +3,8 @@
 // object's single-vector apply is followed by its apply to m columns (the ddm_*_multi entry points).  Block vectors are row-major
 // n x m (entry (i, c) at i * m + c), 1 <= m <= MULTI_MAX; every object keeps its own block scratch, allocated on first use for the
 // widest m seen so far.  The single-vector applies are NOT the block applies at m = 1: they use the fused epilogue of the pipe engine
-// and the all-reduce a scalar can ride on (coarse_allreduce); the headline number depends on them.  Needs halo.hpp and the local solver (local_factor.hpp .. local_solver.hpp).
+// and the all-reduce a scalar can ride on (the rider argument of combined_apply_impl, down to coarse_allreduce); the headline number depends
+// on them.  ddm_combined also holds the block drivers' work blocks (KrylovWork).  Needs halo.hpp, krylov_work.hpp and the local solver (local_factor.hpp .. local_solver.hpp).
 #pragma once
 
 // ---- reductions --------------------------------------------------------------------------------
@@ -137,8 +138,8 @@ extern "C" int ddm_op_applyscaleadd(ddm_ctx *ctx, ddm_op *op, double alpha, cons
 }
 extern "C" int ddm_dot(ddm_ctx *ctx, ddm_op *op, const double *x, const double *y, double *result_host)
 {
-  DDMCHECK(dot_device(ctx, op->n, op->owner, x, y, ctx->scal + 8));
-  return ddm_memcpy_d2h(ctx, result_host, ctx->scal + 8, sizeof(double));
+  DDMCHECK(dot_device(ctx, op->n, op->owner, x, y, ctx->scal + SCAL_DOT));
+  return ddm_memcpy_d2h(ctx, result_host, ctx->scal + SCAL_DOT, sizeof(double));
 }
 extern "C" int ddm_norm(ddm_ctx *ctx, ddm_op *op, const double *x, double *result_host)
 {
@@ -180,7 +181,7 @@ extern "C" int ddm_dot_multi(ddm_ctx *ctx, ddm_op *op, int nrhs, const double *X
   if (!ctx || !op || !X || !Y || !result_host) return fail(ctx, DDM_EINVAL, "ddm_dot_multi: bad arguments");
   DDMCHECK(multi_check(ctx, nrhs, "ddm_dot_multi"));
   DDMCHECK(ctx_multi_scratch(ctx));
-  double *out = ctx->mscal + 6 * MULTI_MAX;
+  double *out = ctx->mscal + SCAL_DOT_MULTI * MULTI_MAX;
   DDMCHECK(dot_multi_device(ctx, op->n, op->owner, nrhs, X, Y, out));
   return ddm_memcpy_d2h(ctx, result_host, out, sizeof(double) * (size_t)nrhs);
 }
@@ -422,30 +423,30 @@ extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, con
   return DDM_OK;
 }
 extern "C" void ddm_galerkin_destroy(ddm_galerkin *G) { delete G; }
-// restrict -> all-reduce (a scalar waiting in ctx->piggy rides along) -> A0^-1 d0 -> prolong into G->x_ovlp, on the context's current
-// stream.  spread_grid == 0: the full-grid passes over the basis, one workgroup per chunk; spread_grid > 0: the spread ones on that
+// restrict -> all-reduce (rider rides along: coarse_allreduce) -> A0^-1 d0 -> prolong into G->x_ovlp, all enqueued on `stream`.
+// spread_grid == 0: the full-grid passes over the basis, one workgroup per chunk; spread_grid > 0: the spread ones on that
 // many one-wave workgroups (the chain runs beside the local solve).  Same result bit for bit either way.
 // Not timed here: the callers' "GalerkinPrec/apply" scopes differ.
-static int coarse_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *dov, int spread_grid = 0)
+static int coarse_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *dov, hipStream_t stream, double *rider, int spread_grid = 0)
 {
   const unsigned sgrid = (unsigned)spread_grid;
   if (spread_grid > 0)
-    hipLaunchKernelGGL(k_coarse_restrict_spread, dim3(sgrid), dim3(SPREAD_WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk);
+    hipLaunchKernelGGL(k_coarse_restrict_spread, dim3(sgrid), dim3(SPREAD_WG), 0, stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk);
   else
-    hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk); // :165-167
-  hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, ctx->stream, (int)G->nsub, (int)G->kmax, G->sub_chunk_ptr, G->partial, G->coarse_index, G->K, G->d0);
+    hipLaunchKernelGGL(k_coarse_restrict_partial, dim3(G->nchunk), dim3(WG), 0, stream, (int)G->kmax, G->ld, G->basis, dov, G->chunks, G->partial, G->nchunk); // :165-167
+  hipLaunchKernelGGL(k_coarse_restrict_final, dim3(1), dim3(WG), 0, stream, (int)G->nsub, (int)G->kmax, G->sub_chunk_ptr, G->partial, G->coarse_index, G->K, G->d0);
   HIPCHECK(ctx, hipGetLastError());
-  DDMCHECK(coarse_allreduce(ctx, G->d0, G->K)); // replaces MPI_Gatherv (:170-171): every rank obtains the full coarse defect
-  hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((G->K + 3) / 4)), dim3(WG), 0, ctx->stream, G->K, G->a0inv, G->d0, G->x0); // :174-179 (replicated)
+  DDMCHECK(coarse_allreduce(ctx, G->d0, G->K, rider, stream)); // replaces MPI_Gatherv (:170-171): every rank obtains the full coarse defect
+  hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((G->K + 3) / 4)), dim3(WG), 0, stream, G->K, G->a0inv, G->d0, G->x0); // :174-179 (replicated)
   if (spread_grid > 0)
-    hipLaunchKernelGGL(k_coarse_prolong_spread, dim3(sgrid), dim3(SPREAD_WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk);
+    hipLaunchKernelGGL(k_coarse_prolong_spread, dim3(sgrid), dim3(SPREAD_WG), 0, stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk);
   else
-    hipLaunchKernelGGL(k_coarse_prolong, dim3(G->nchunk), dim3(WG), 0, ctx->stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk); // :186-188
+    hipLaunchKernelGGL(k_coarse_prolong, dim3(G->nchunk), dim3(WG), 0, stream, (int)G->kmax, G->ld, G->basis, G->x0, G->coarse_index, G->chunks, G->x_ovlp, G->nchunk); // :186-188
   return DDM_OK;
 }
 // d_ovlp_ready: the overlapping defect (extended + owner values copied to all holders) if the caller already has it -- in the
 // additive combination both levels start from the same defect (schwarz.hh:121-125 and galerkin_preconditioner.hh:159-162)
-static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d, bool acc, const double *d_ovlp_ready = nullptr)
+static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d, bool acc, double *rider, const double *d_ovlp_ready = nullptr)
 {
   ScopedTimer t(ctx, "GalerkinPrec/apply");
   const double *dov = d_ovlp_ready;
@@ -454,7 +455,7 @@ static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const d
     DDMCHECK(ddm_halo_exchange(ctx, G->copy, G->d_ovlp));                                                         // :162
     dov = G->d_ovlp;
   }
-  DDMCHECK(coarse_chain(ctx, G, dov));
+  DDMCHECK(coarse_chain(ctx, G, dov, ctx->stream, rider));
   DDMCHECK(ddm_halo_exchange(ctx, G->add, G->x_ovlp)); // :190
   if (acc)
     hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(G->n)), dim3(WG), 0, ctx->stream, G->n, G->ext_map, G->x_ovlp, (const double *)nullptr, x);
@@ -465,7 +466,7 @@ static int galerkin_apply_impl(ddm_ctx *ctx, ddm_galerkin *G, double *x, const d
 }
 extern "C" int ddm_galerkin_apply(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d)
 {
-  return galerkin_apply_impl(ctx, G, x, d, false);
+  return galerkin_apply_impl(ctx, G, x, d, false, nullptr);
 }
 // Diagnostic (not part of the product path): the coarse chain alone on an overlapping defect the caller supplies (n doubles on the
 // device), with the full-grid basis passes (spread_grid == 0) or the spread ones on spread_grid one-wave workgroups; copies the chunk
@@ -478,7 +479,7 @@ extern "C" int ddm_galerkin_debug_chain(ddm_ctx *ctx, ddm_galerkin *G, const dou
   *npartial = (int64_t)G->nchunk * G->kmax;
   if (!partial_out && !d0_out && !x_ovlp_out) return DDM_OK;
   if (!d_ovlp || !partial_out || !d0_out || !x_ovlp_out) return fail(ctx, DDM_EINVAL, "ddm_galerkin_debug_chain: bad arguments");
-  DDMCHECK(coarse_chain(ctx, G, d_ovlp, spread_grid));
+  DDMCHECK(coarse_chain(ctx, G, d_ovlp, ctx->stream, nullptr, spread_grid));
   HIPCHECK(ctx, hipMemcpyAsync(partial_out, G->partial, sizeof(double) * (size_t)*npartial, hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(d0_out, G->d0, sizeof(double) * (size_t)G->K, hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(x_ovlp_out, G->x_ovlp, sizeof(double) * (size_t)G->n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -599,12 +600,9 @@ struct ddm_combined {
   bool fused = false;   // additive mode: the levels' overlapping results are summed before ONE halo add (combined_apply_fused)
   int overlap = 0;      // ... and the coarse chain runs on a side stream beside the local solve: 0 never, 1 always, 2 where the local engine is pipe
   int side_grid = 0;    // one-wave workgroups of the chain's two basis passes on the side stream
-  dbuf<double> mdnext, mp, mq; // multi-RHS blocks: multiplicative defect (mcols), CG directions (mcg_cols)
-  dbuf<double> mxw, mbw;       // ddm_cg_solve_queue: the slots' x and defect blocks (mqueue_cols)
-  dbuf<int64_t> mqueue_tab;    // ... and its table of (slot, column) pairs, 2 * MULTI_MAX entries
-  dbuf<double> mrt, mv, my;    // ddm_bicgstab_solve_queue: shadow defect, v and y (mbicg_cols); its x, r, p, t are mxw, mbw, mp, mq
-  dbuf<double> mz;             // ddm_bcg_solve_multi: the preconditioned defect block Z (mbcg_cols); its P and Q are mp, mq.  ddm_bgmres_solve_multi: its Z, U, W
-  int mcols = 0, mcg_cols = 0, mqueue_cols = 0, mbicg_cols = 0, mbcg_cols = 0;
+  dbuf<double> mdnext; // multi-RHS block: multiplicative defect (mcols columns)
+  int mcols = 0;
+  KrylovWork work;     // the block drivers' work blocks, kept between calls (krylov_work.hpp): not preconditioner state
 };
 extern "C" int ddm_combined_create(ddm_ctx *ctx, int mode, ddm_op *op, ddm_schwarz *schwarz, ddm_galerkin *galerkin, ddm_combined **out)
 {
@@ -647,7 +645,7 @@ extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
 // which applies "x *= pou; x += x_coarse" as on one stream: the same kernels' sums in the same order, the result is bit-identical.
 // The other engines join behind the solve with k_scale + k_axpy (the same operations as separate passes).
 // Measurements, the losing configurations included: DESIGN.md section 4.
-static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d)
+static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider)
 {
   ddm_schwarz *S = C->schwarz;
   ddm_galerkin *G = C->galerkin;
@@ -660,25 +658,20 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
     hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp);
     DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));
   }
-  auto timed_chain = [&](int spread_grid) -> int { // (the timer records on whichever stream the chain is enqueued on)
-    ScopedTimer t(ctx, "GalerkinPrec/apply");
-    return coarse_chain(ctx, G, S->d_ovlp, spread_grid);
-  };
+  // The coarse chain (kernels, RCCL all-reduce, timer) goes to the side stream, or runs first on the one stream, so that the local
+  // solve's last kernel can also apply "x *= pou; x += x_coarse".
+  // inter-rank operations stay totally ordered: copy-halo (main) -> all-reduce (side) -> [join] -> halo add (main)
+  const hipStream_t chain = two_streams ? ctx->side : ctx->stream;
   if (two_streams) {
-    // inter-rank operations stay totally ordered: copy-halo (main) -> all-reduce (side) -> [join] -> halo add (main)
     HIPCHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    hipStream_t main = ctx->stream;
     HIPCHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    ctx->stream = ctx->side; // the coarse chain is enqueued on the side stream (kernels, RCCL all-reduce, timer)
-    const int rc = timed_chain(C->side_grid);
-    const hipError_t e = hipEventRecord(ctx->ev_join, ctx->side);
-    ctx->stream = main;
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, DDM_EHIP, "hipEventRecord failed: %s", hipGetErrorString(e));
   }
+  {
+    ScopedTimer t(ctx, "GalerkinPrec/apply", chain);
+    DDMCHECK(coarse_chain(ctx, G, S->d_ovlp, chain, rider, two_streams ? C->side_grid : 0));
+  }
+  if (two_streams) HIPCHECK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
   const double *pou = S->type == 1 ? S->pou : nullptr;
-  // one stream: the coarse chain runs first, so that the local solve's last kernel can also apply "x *= pou; x += x_coarse"
-  if (!two_streams) DDMCHECK(timed_chain(0));
   const bool fold = !two_streams || pipe_engine; // the solve's output pass applies the POU scale and adds the coarse correction
   {
     ScopedTimer t(ctx, "Schwarz/local solve");
@@ -699,11 +692,14 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
   return DDM_OK;
 }
 
-extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d)
+// rider: a device scalar to be summed over the ranks, or null.  Wherever C has a Galerkin level, exactly ONE coarse_allreduce of the
+// apply receives it -- fused, additive unfused and multiplicative alike -- so a caller that passes one need not reduce it itself
+// (ddm_cg_steps: the squared defect norm of the previous iteration); without a Galerkin level it is ignored.
+static int combined_apply_impl(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider)
 {
   ScopedTimer t(ctx, "CombinedPreconditioner/apply");
   DDMCHECK(local_status_check(ctx, C->schwarz));
-  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d);
+  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d, rider);
   // x = 0; precs[0]->apply(x, d)  (:133-134)  -- the restrict kernel overwrites every entry of x
   DDMCHECK(schwarz_apply_impl(ctx, C->schwarz, x, d, false));
   if (!C->galerkin) return DDM_OK;
@@ -711,13 +707,14 @@ extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, cons
     // both levels extend the same defect over the same interface: the Schwarz level's copy is reused (the local solves read it only)
     static const bool no_share = std::getenv("DDM_NO_SHARED_DEFECT") != nullptr; // diagnostic switch
     const bool share = !no_share && C->galerkin->copy == C->schwarz->copy && C->galerkin->n == C->schwarz->n && C->galerkin->n_novlp == C->schwarz->n_novlp;
-    return galerkin_apply_impl(ctx, C->galerkin, x, d, true, share ? C->schwarz->d_ovlp : nullptr);
+    return galerkin_apply_impl(ctx, C->galerkin, x, d, true, rider, share ? C->schwarz->d_ovlp : nullptr);
   }
   // multiplicative: dnext = d - A x; x += P1 dnext (:149-158)
   HIPCHECK(ctx, hipMemcpyAsync(C->dnext, d, sizeof(double) * (size_t)C->n, hipMemcpyDeviceToDevice, ctx->stream));
   DDMCHECK(ddm_op_applyscaleadd(ctx, C->op, -1.0, x, C->dnext));
-  return galerkin_apply_impl(ctx, C->galerkin, x, C->dnext, true);
+  return galerkin_apply_impl(ctx, C->galerkin, x, C->dnext, true, rider);
 }
+extern "C" int ddm_combined_apply(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d) { return combined_apply_impl(ctx, C, x, d, nullptr); }
 // ... and for m columns (combined_preconditioner.hh:127-163)
 static int combined_apply_multi_impl(ddm_ctx *ctx, ddm_combined *C, int m, double *X, const double *D)
 {

@@ -221,3 +221,45 @@ def test_multi_argument_checks_and_local_status(ddm):
     r1, h1, _ = tl.solve(maxit=200)
     assert r[0].converged and r[0].iterations == r1.iterations
     tl.ctx.close()
+
+
+def test_block_drivers_share_one_work_pool(ddm):
+    """All block drivers take their n x width work blocks from one grow-only pool of the preconditioner object (KrylovWork).  Run back
+    to back on ONE preconditioner -- the pool grown (3 -> 5 columns: dropped and allocated afresh), kept (5 -> 2, 4, 2, 3) and reused
+    with whatever another driver left in it -- every call returns bit for bit what the same call returns on a preconditioner made
+    fresh for it: x, histories, ranks / widths and results.  The first and the last call are the same call and agree as well.  No
+    tolerance: that each driver's numbers are right is what its own tests assert."""
+    import torch
+    from dune_ddm_amd.solver import TwoLevelSchwarz
+    from tests.test_apply_shapes_reference import consistent_columns
+    from tests.test_fgmres_cpu import golden_poisson
+    dec = golden_poisson(ddm)
+    tl = TwoLevelSchwarz(dec, coarse="pou", schwarz_type="standard", mode="additive")
+    B5 = consistent_columns(dec, 5, seed=23)
+    kw = dict(reduction=1e-8, maxit=200)
+    calls = [                                            # (driver, its width argument or None, columns)
+        (ddm.bicgstab_solve_queue, 3, 5),
+        (ddm.bcg_solve_multi, None, 5),
+        (ddm.cg_solve_queue, 2, 5),
+        (ddm.cg_solve_multi, None, 4),
+        (lambda *a, **k: ddm.bgmres_solve_multi(*a, restart=5, **k), None, 2),
+        (ddm.bicgstab_solve_queue, 3, 5),
+    ]
+
+    def run(fn, width, m):
+        X, B = torch.zeros((tl.rl.n_o, m), dtype=torch.float64, device=tl.dev), tl.to_device(B5[:, :m])
+        out = fn(tl.ctx, tl.op, tl.prec, X, B, *(() if width is None else (width,)), **kw)
+        tl.prec.check_status()
+        res = [(r.iterations, r.converged, r.def0, r.reduction) for r in out[0]]
+        return X.cpu().numpy(), res, [np.asarray(a).copy() for a in out[1:]]
+
+    def same(a, b):
+        return np.array_equal(a[0], b[0]) and a[1] == b[1] and len(a[2]) == len(b[2]) and all(np.array_equal(u, v, equal_nan=True) for u, v in zip(a[2], b[2]))
+
+    shared = [run(*c) for c in calls]                    # one preconditioner, one pool
+    for k, c in enumerate(calls):
+        tl.rebuild_combined("additive")                  # a fresh preconditioner: an empty pool
+        assert same(shared[k], run(*c)), k
+    assert same(shared[0], shared[-1])
+    assert all(all(r[1] == 1 for r in s[1]) for s in shared)   # (every column converged: the runs are whole solves)
+    tl.ctx.close()

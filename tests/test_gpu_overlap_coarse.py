@@ -89,8 +89,8 @@ def test_overlapped_apply_and_cg_are_bit_identical(ddm, monkeypatch, grid, coars
 def test_failed_cg_call_leaves_no_rider_behind(ddm, monkeypatch):
     """ddm_cg_steps that returns an error (the local solver's status word is set: the first preconditioner apply of the call fails)
     and ddm_cg_end leave no scalar waiting for the next coarse all-reduce: the Galerkin apply that follows reduces exactly K doubles,
-    with the chain on the side stream as on one.  (The status word cannot be set between two iterations of one call, so the rider
-    that is pending mid-call is not reached from here.)"""
+    with the chain on the side stream as on one.  (The pending scalar is a local of ddm_cg_steps that reaches the all-reduce as an
+    argument of the preconditioner apply, so it cannot outlive the call whichever way the call returns: this test pins that.)"""
     tl, p_on, p_off = build_pair(ddm, monkeypatch, 24, "ragged", None, None)
     lib, n = tl.ctx.lib, tl.rl.n_o
     F = ctypes.c_void_p(tl.schwarz.local_solver())
