@@ -73,6 +73,11 @@ SYMBOLS = {
     "ddm_memcpy_d2h": (_I32, [_P, _P, _P, _I64]),
     "ddm_csr_create": (_I32, [_P, _I64, _I64, _P, _P, _P, _PP]),
     "ddm_csr_create_host": (_I32, [_P, _I64, _I64, _P, _P, _P, _PP]),
+    "ddm_csr_set_values": (_I32, [_P, _P, _P]),
+    "ddm_ilu0_refresh": (_I32, [_P, _P]),
+    "ddm_schwarz_refresh": (_I32, [_P, _P]),
+    "ddm_op_refresh": (_I32, [_P, _P]),
+    "ddm_galerkin_set_inverse": (_I32, [_P, _P, _P]),
     "ddm_csr_destroy": (None, [_P]),
     "ddm_csr_rows": (_I64, [_P]),
     "ddm_csr_nnz": (_I64, [_P]),
@@ -353,6 +358,14 @@ class CsrMatrix:
         self.h = h
         self.nnz = int(M.nnz)
 
+    def set_values(self, values):
+        """new values in the matrix's pattern (nnz doubles in CSR order with sorted column indices): ddm_csr_set_values.  Objects built
+        on the matrix keep the old values until their refresh() is called."""
+        va = _np(values, np.float64)
+        if va.shape != (self.nnz,):
+            raise ValueError(f"set_values: {va.size} values for a pattern of {self.nnz} entries")
+        self.ctx.check(self.ctx.lib.ddm_csr_set_values(self.ctx.h, self.h, _hp(va)))
+
     def mv(self, x, y):
         self.ctx.check(self.ctx.lib.ddm_csr_mv(self.ctx.h, self.h, _ptr(x), _ptr(y)))
 
@@ -452,6 +465,11 @@ class Ilu0:
         om = np.zeros(5)
         steps = int(self.ctx.lib.ddm_ilu0_refinement(self.h, _hp(om)))
         return steps, om
+
+    def refresh(self):
+        """refactorises from the current values of the matrix (CsrMatrix.set_values): ddm_ilu0_refresh.  DdmError with code
+        DDM_ENOTIMPL for a direct factor and the box engine, DDM_ENUMERIC for a vanishing pivot (the factor stays the previous one)."""
+        self.ctx.check(self.ctx.lib.ddm_ilu0_refresh(self.ctx.h, self.h))
 
     def solve(self, d, x):
         self.ctx.check(self.ctx.lib.ddm_ilu0_solve(self.ctx.h, self.h, _ptr(d), _ptr(x)))
@@ -554,6 +572,10 @@ class NonOverlappingOperator:
         ctx.check(ctx.lib.ddm_op_create(ctx.h, A.h, novlp_add.h if novlp_add else None, _hp(m), ctypes.byref(h)))
         self.h = h
 
+    def refresh(self):
+        """rebuilds the product's storage from the matrix's current values (CsrMatrix.set_values): ddm_op_refresh"""
+        self.ctx.check(self.ctx.lib.ddm_op_refresh(self.ctx.h, self.h))
+
     def apply(self, x, y):
         self.ctx.check(self.ctx.lib.ddm_op_apply(self.ctx.h, self.h, _ptr(x), _ptr(y)))
 
@@ -603,6 +625,11 @@ class SchwarzPreconditioner:
                                                 ovlp_add.h if ovlp_add else None, ctypes.byref(h)))
         self.h = h
         self._keep = (A_dir, ovlp_copy, ovlp_add)
+
+    def refresh(self):
+        """the local solver again from A_dir's current values (CsrMatrix.set_values): ddm_schwarz_refresh.  DdmError with code
+        DDM_ENOTIMPL for direct local solvers and the box engine: build a new SchwarzPreconditioner instead."""
+        self.ctx.check(self.ctx.lib.ddm_schwarz_refresh(self.ctx.h, self.h))
 
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_schwarz_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))
@@ -665,7 +692,15 @@ class GalerkinPreconditioner:
                                               K, _hp(inv), ovlp_copy.h if ovlp_copy else None, ovlp_add.h if ovlp_add else None,
                                               ctypes.byref(h)))
         self.h = h
+        self.K = int(K)
         self._keep = (ovlp_copy, ovlp_add)
+
+    def set_inverse(self, a0inv):
+        """a new inverse of the coarse matrix (K x K) for the same basis: ddm_galerkin_set_inverse"""
+        inv = _np(a0inv, np.float64)
+        if inv.shape != (self.K, self.K):
+            raise ValueError(f"set_inverse: shape {inv.shape}, the coarse space has {self.K} vectors")
+        self.ctx.check(self.ctx.lib.ddm_galerkin_set_inverse(self.ctx.h, self.h, _hp(inv)))
 
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_galerkin_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))

@@ -131,6 +131,20 @@ static int csr_wait_upload(ddm_ctx *ctx, const ddm_csr *A)
   if (M->upload_rc) return fail(ctx, M->upload_rc, "%s", M->upload_err.c_str());
   return DDM_OK;
 }
+// New values in the pattern the matrix has (Newton step, time step): h_va, and the device `va` on the context's stream.  Objects
+// built on the matrix keep what they made of the old values until their own refresh is called (ddm_op_refresh, ddm_ilu0_refresh,
+// ddm_schwarz_refresh).  Synchronous: the host array is free again when the call returns.
+extern "C" int ddm_csr_set_values(ddm_ctx *ctx, ddm_csr *A, const double *val_host)
+{
+  if (!ctx || !A || (!val_host && A->nnz > 0)) return fail(ctx, DDM_EINVAL, "ddm_csr_set_values: bad arguments");
+  DDMCHECK(csr_wait_upload(ctx, A)); // (a helper thread may still be reading h_va)
+  if (A->nnz == 0) return DDM_OK;
+  if (val_host != A->h_va.data()) hvec_copy(A->h_va, val_host, (size_t)A->nnz);
+  if (A->host_only) return DDM_OK;
+  HIPCHECK(ctx, hipMemcpyAsync(A->va, A->h_va.data(), sizeof(double) * (size_t)A->nnz, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return DDM_OK;
+}
 // Cache-blocked processing order of the rows of a block-diagonal matrix whose blocks come from a STRUCTURED grid in lexicographic
 // numbering (possibly followed by irregularly numbered rows, e.g. an overlap shell): the strides s2 (one grid line) and s3 (one grid
 // plane) are read off the column offsets that most rows share; rows are then visited brick by brick (16 x 4 x 4 points, bricks in

@@ -46,6 +46,7 @@ using namespace ddm;
 #include "tri_csr.hpp"          // CSR level schedules of the host direct factor: supernodes, build_csr_schedule, enqueue_tri_csr, enqueue_multi_levels_csr.  Needs local_factor.hpp.
 #include "engine_xcd2.hpp"      // xcd2 engine: build_xcd_schedule, enqueue_xcd2.  Needs local_factor.hpp.
 #include "engine_pipe.hpp"      // pipe engine: build_pipe_schedule, enqueue_pipe.  Needs local_factor.hpp, trsv_pipe.hpp.
+#include "ilu0_refactor.hpp"    // value refresh of an ILU(0) factor: device factorisation, scatter into the engines, ddm_ilu0_refresh.  Needs tri_levels.hpp, engine_xcd2.hpp, engine_pipe.hpp.
 #include "engine_box.hpp"       // box engine: build_box_engine, enqueue_box, ddm_ilu0_box_check.  Needs local_factor.hpp, trsv_box.hpp.
 #include "local_solve.hpp"      // the solves: ilu0_enqueue, graph capture, ilu0_solve_epilogue, ilu0_solve_multi_ld, ddm_ilu0_solve*.  Needs tri_*.hpp, engine_*.hpp.
 #include "local_solver.hpp"     // creation: ilu0_create_impl, direct_create_impl, ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*.  Needs local_solve.hpp.

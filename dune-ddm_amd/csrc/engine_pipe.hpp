@@ -6,6 +6,7 @@
 static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
 {
   const ddm_csr *A = F->A;
+  DDMCHECK(ilu0_sync_host_factor(ctx, F)); // (nothing to do at creation; the trace entry point may build after a value refresh)
   pipe::Options opt;
   if (const char *e = std::getenv("DDM_PIPE_DELTA")) opt.delta = std::atoi(e);
   if (const char *e = std::getenv("DDM_PIPE_SPAN")) opt.max_span = std::atoi(e);
@@ -30,6 +31,11 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   DDMCHECK(upload(ctx, S.stream.data(), (int64_t)S.stream.size(), E->stream));
   DDMCHECK(upload(ctx, S.koff.data(), (int64_t)S.koff.size(), E->koff));
   DDMCHECK(upload(ctx, S.posU.data(), (int64_t)S.posU.size(), E->posU));
+  {
+    std::vector<int64_t> slot(S.slot[0]);
+    slot.insert(slot.end(), S.slot[1].begin(), S.slot[1].end());
+    DDMCHECK(upload(ctx, slot.data(), (int64_t)slot.size(), E->slot));
+  }
   {
     std::vector<int32_t> rowU((size_t)std::max<int64_t>(S.nposU, 1), -1);
     for (size_t i = 0; i < S.posU.size(); ++i) rowU[(size_t)S.posU[i]] = (int32_t)i;

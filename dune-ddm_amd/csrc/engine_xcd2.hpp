@@ -6,6 +6,7 @@
 static int build_xcd_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
 {
   const ddm_csr *A = F->A;
+  DDMCHECK(ilu0_sync_host_factor(ctx, F)); // (a value refresh drops this part: it is rebuilt here from the refreshed factor)
   const int64_t *rp = A->h_rp.data();
   const int32_t *ci = A->h_ci.data();
   const hvec<double> &lu = F->h_lu;

@@ -80,6 +80,7 @@ struct PipeEngine { // pipe: chains x tasks, see trsv_pipe_host.hpp
   dbuf<double> ypos, xpos;
   dbuf<unsigned long long> progress;
   dbuf<unsigned> queue;
+  dbuf<int64_t> slot;             // [2 n] pipe::row_slot of every row's L entries, then of its U entries (the value refresh)
   int64_t nposU = 0;
   int spread = 0; // placement-independent mode (set when a subdomain has more work per level than one XCD's workgroups take)
   int grid = 0;
@@ -138,6 +139,15 @@ struct SnDirect { // supernodal factor computed ON THE DEVICE (sn_chol.hpp); sol
   int pr_cols = 0;
 };
 
+struct Refactor { // what ddm_ilu0_refresh keeps on the device (ilu0_refactor.hpp), allocated by the first refresh
+  dbuf<double> lu;      // the factor in the pattern of A as the last successful refresh left it
+  dbuf<double> scratch; // the factor being computed: exchanged with `lu` once the status word says that every pivot was fine
+  dbuf<int64_t> diag;   // h_diag
+  dbuf<unsigned> status;
+  std::vector<TriSchedule::Launch> plan; // launches of the factorisation over the levels of F->lev->L
+  bool host_stale = false; // h_lu is older than `lu`: ilu0_sync_host_factor brings it up to date for whoever reads it next
+};
+
 struct SolveKey { // the arguments a captured solve is bound to; the single-vector cache leaves nrhs, ldd, ldx, f32 as they stand here
   const double *d = nullptr, *scale = nullptr, *add = nullptr;
   double *x = nullptr;
@@ -180,6 +190,7 @@ struct ddm_ilu0 {
   std::unique_ptr<BoxEngine> box;
   std::unique_ptr<CsrDirect> csr;
   std::unique_ptr<SnDirect> sn;
+  std::unique_ptr<Refactor> refac;
   // HIP graph caches: the single-vector solve for one (d, x, scale, add), the multi-RHS solve for one (D, X, nrhs, ld, f32)
   GraphCache graph, mgraph;
   ~ddm_ilu0() // the body runs before any member goes: the builder thread writes the parts, the graph execs point into the arrays
@@ -236,6 +247,16 @@ static void ilu0_join_builder(ddm_ilu0 *F)
 {
   if (F->builder.joinable()) F->builder.join();
   settle_engine(F);
+}
+// h_lu after a value refresh (ddm_ilu0_refresh leaves the new factor on the device): copied back when somebody reads it --
+// ddm_ilu0_get_factors_host and the builders that run after creation (xcd2 on first use, the pipe trace).  Synchronous.
+static int ilu0_sync_host_factor(ddm_ctx *ctx, ddm_ilu0 *F)
+{
+  if (!F->refac || !F->refac->host_stale) return DDM_OK;
+  HIPCHECK(ctx, hipMemcpyAsync(F->h_lu.data(), F->refac->lu, sizeof(double) * (size_t)F->nnz, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  F->refac->host_stale = false;
+  return DDM_OK;
 }
 // waits for the background part of the setup; its failure is reported by every call that needs the result
 static int ilu0_join(ddm_ctx *ctx, ddm_ilu0 *F)

@@ -667,6 +667,7 @@ extern "C" int ddm_ilu0_get_factors_host(ddm_ctx *ctx, const ddm_ilu0 *F, double
 {
   if (!F || !lu_host) return fail(ctx, DDM_EINVAL, "bad arguments");
   if (F->sn) return fail(ctx, DDM_ENOTIMPL, "ddm_ilu0_get_factors_host: the device supernodal factor has no CSR form");
+  DDMCHECK(ilu0_sync_host_factor(ctx, const_cast<ddm_ilu0 *>(F))); // (after ddm_ilu0_refresh the factor is on the device)
   std::memcpy(lu_host, F->h_lu.data(), sizeof(double) * (size_t)F->nnz);
   return DDM_OK;
 }

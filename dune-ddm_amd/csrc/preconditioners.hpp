@@ -90,6 +90,27 @@ static int op_mv(ddm_ctx *ctx, const ddm_op *op, const double *x, double *y)
   HIPCHECK(ctx, hipGetLastError());
   return DDM_OK;
 }
+// the diagonal-block storage of op->A's current values (replaces what the operator held); the CSR-stream product where none applies
+static int op_build_dia(ddm_ctx *ctx, ddm_op *op)
+{
+  const ddm_csr *A = op->A;
+  int rc = DDM_OK;
+  op->dia_nblk = 0;
+  (void)op->dia_blk.reset(), (void)op->dia_tab.reset(), (void)op->dia_mask.reset(), (void)op->dia_val.reset(), (void)op->dia_code.reset(), (void)op->dia_dict.reset();
+  const char *fmt = std::getenv("DDM_SPMV_FORMAT"); // "csr": keep the CSR-stream product (A/B runs, tests)
+  if (A->host_only || (fmt && !std::strcmp(fmt, "csr"))) return DDM_OK;
+  DiaLayout L;
+  dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L, dia_stage_x_from_env(), dia_code_from_env()); // DDM_SPMV_STAGE_X=0: no x windows in LDS, DDM_SPMV_CODE=0: no dictionaries
+  if (!L.ndia) return DDM_OK;
+  rc = upload(ctx, L.blk.data(), (int64_t)L.blk.size(), op->dia_blk);
+  if (!rc) rc = upload(ctx, L.tab.data(), (int64_t)L.tab.size(), op->dia_tab);
+  if (!rc) rc = upload(ctx, L.mask.data(), (int64_t)L.mask.size(), op->dia_mask);
+  if (!rc) rc = upload(ctx, L.val.data(), (int64_t)L.val.size(), op->dia_val);
+  if (!rc && L.ncoded) rc = upload(ctx, L.code.data(), (int64_t)L.code.size(), op->dia_code);
+  if (!rc && L.ncoded) rc = upload(ctx, L.dict.data(), (int64_t)L.dict.size(), op->dia_dict);
+  if (!rc) op->dia_nblk = (int)L.blk.size();
+  return rc;
+}
 extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out)
 {
   if (!ctx || !A || !out || !owner_mask_host) return fail(ctx, DDM_EINVAL, "ddm_op_create: bad arguments");
@@ -101,22 +122,20 @@ extern "C" int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add
   op->n = A->nrows;
   int rc = upload(ctx, owner_mask_host, op->n, op->owner);
   if (!rc && op->tmp.alloc(op->n) != hipSuccess) rc = DDM_EHIP;
-  const char *fmt = std::getenv("DDM_SPMV_FORMAT"); // "csr": keep the CSR-stream product (A/B runs, tests)
-  if (!rc && !A->host_only && !(fmt && !std::strcmp(fmt, "csr"))) {
-    DiaLayout L;
-    dia_build(A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), L, dia_stage_x_from_env(), dia_code_from_env()); // DDM_SPMV_STAGE_X=0: no x windows in LDS, DDM_SPMV_CODE=0: no dictionaries
-    if (L.ndia) {
-      if (!rc) rc = upload(ctx, L.blk.data(), (int64_t)L.blk.size(), op->dia_blk);
-      if (!rc) rc = upload(ctx, L.tab.data(), (int64_t)L.tab.size(), op->dia_tab);
-      if (!rc) rc = upload(ctx, L.mask.data(), (int64_t)L.mask.size(), op->dia_mask);
-      if (!rc) rc = upload(ctx, L.val.data(), (int64_t)L.val.size(), op->dia_val);
-      if (!rc && L.ncoded) rc = upload(ctx, L.code.data(), (int64_t)L.code.size(), op->dia_code);
-      if (!rc && L.ncoded) rc = upload(ctx, L.dict.data(), (int64_t)L.dict.size(), op->dia_dict);
-      op->dia_nblk = (int)L.blk.size();
-    }
-  }
+  if (!rc) rc = op_build_dia(ctx, op.get());
   if (rc) return fail(ctx, rc, "ddm_op_create: allocation failed");
   *out = op.release();
+  return DDM_OK;
+}
+// The diagonal-block storage again, from the values A has now (ddm_csr_set_values).  Whether a block can be coded by a dictionary
+// depends on its values, so the layout is built anew and the six arrays are replaced: what ddm_op_create builds on these values.
+// The products are not captured in graphs, so nothing holds the old addresses.
+extern "C" int ddm_op_refresh(ddm_ctx *ctx, ddm_op *op)
+{
+  if (!ctx || !op) return fail(ctx, DDM_EINVAL, "ddm_op_refresh: bad arguments");
+  DDMCHECK(csr_wait_upload(ctx, op->A));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream)); // (products in flight read the arrays that go)
+  if (const int rc = op_build_dia(ctx, op)) return fail(ctx, rc, "ddm_op_refresh: allocation failed");
   return DDM_OK;
 }
 extern "C" void ddm_op_destroy(ddm_op *op) { delete op; }
@@ -250,6 +269,12 @@ extern "C" int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
   if (S->d_ovlp.alloc(n) != hipSuccess || S->x_ovlp.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "alloc");
   *out = S.release();
   return DDM_OK;
+}
+// the local solver again from A_dir's current values (ddm_ilu0_refresh: DDM_ENOTIMPL for direct local solvers and the box engine)
+extern "C" int ddm_schwarz_refresh(ddm_ctx *ctx, ddm_schwarz *S)
+{
+  if (!ctx || !S) return fail(ctx, DDM_EINVAL, "ddm_schwarz_refresh: bad arguments");
+  return ddm_ilu0_refresh(ctx, S->solver);
 }
 extern "C" void ddm_schwarz_destroy(ddm_schwarz *S) { delete S; }
 extern "C" int64_t ddm_schwarz_num_levels(const ddm_schwarz *S, int upper) { return ddm_ilu0_num_levels(S->solver, upper); }
@@ -421,6 +446,12 @@ extern "C" int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, con
     return fail(ctx, DDM_EHIP, "galerkin: basis upload failed");
   *out = G.release();
   return DDM_OK;
+}
+// a new inverse of the coarse matrix (K x K, row-major) into the buffer the applies read, on the context's stream; synchronous
+extern "C" int ddm_galerkin_set_inverse(ddm_ctx *ctx, ddm_galerkin *G, const double *a0inv_host)
+{
+  if (!ctx || !G || !a0inv_host) return fail(ctx, DDM_EINVAL, "ddm_galerkin_set_inverse: bad arguments");
+  return ddm_memcpy_h2d(ctx, G->a0inv, a0inv_host, (int64_t)sizeof(double) * G->K * G->K);
 }
 extern "C" void ddm_galerkin_destroy(ddm_galerkin *G) { delete G; }
 // restrict -> all-reduce (rider rides along: coarse_allreduce) -> A0^-1 d0 -> prolong into G->x_ovlp, all enqueued on `stream`.

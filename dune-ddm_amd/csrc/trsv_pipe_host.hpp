@@ -87,6 +87,9 @@ struct Geometry {
   PIPE_HD int idx_off(int u, int lane) const { return 1024 * idx_piece(u >> 2) + lane * 16 + (u & 3) * 4; }
 };
 
+// (tile offset in the stream in KiB) << 16 | (the tile's W) << 8 | lane
+PIPE_HD inline int64_t row_slot(int64_t tile_kib, int W, int lane) { return tile_kib << 16 | (int64_t)W << 8 | lane; }
+
 struct Options {
   int delta = 24;   // chains are queued by (start level / delta, head row): tasks are blocks of neighbouring chains of one band
   int vote = 1;     // 1: lanes are re-used by later chains; 0: one chain per lane
@@ -110,6 +113,9 @@ struct Schedule {
   std::vector<int32_t> koff;  // per task nsteps + 1 cumulative tile offsets in KiB
   std::vector<int32_t> rowL; // per L position: natural row or -1
   std::vector<int32_t> posU; // per natural row: U position
+  // per natural row, [0] its L and [1] its U entries: where the row's factor values sit in the stream, packed by row_slot() --
+  // all a value refresh needs to recompute every destination (refresh_values below, k_pipe_scatter on the device)
+  std::vector<int64_t> slot[2];
   int64_t nposL = 0, nposU = 0;
   Stats stats;
   std::string error;
@@ -555,6 +561,7 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
   S.koff.assign((size_t)nkoff, 0);
   S.rowL.assign((size_t)npos[0], -1);
   S.posU.assign((size_t)n, 0);
+  for (auto &sl : S.slot) sl.assign((size_t)n, 0);
   S.stats.rows = n;
   {
     int64_t off = 0, kb = 0;
@@ -623,6 +630,7 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
             ++active;
             const int64_t g = r0 + i;
             const int64_t pos = T.pos_base + (int64_t)t * LANES + l;
+            S.slot[sweep][(size_t)g] = row_slot(T.tile_off / 1024 + S.koff[(size_t)T.koff_base + t], G.W, l);
             if (!upper) {
               S.rowL[(size_t)pos] = (int32_t)g;
               own[l] = (int32_t)(g * 8); // the row's right-hand side entry, read from the caller's vector in natural order
@@ -671,6 +679,23 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
     S.stats.entries_remote += b.entries_remote;
   }
   return true;
+}
+
+// New factor values in the same pattern into an existing stream: every row's entries (and, U, its inverse pivot in the s0 slot at
+// byte 512 of the tile) go where build() put them, found from the row's slot word alone.  The host twin of k_pipe_scatter
+// (ilu0_refactor.hpp): the stream afterwards is byte for byte what build() makes of the new values.
+inline void refresh_values(unsigned char *stream, const int64_t *slotL, const int64_t *slotU, int64_t n, const int64_t *rp, const int64_t *diag, const double *lu)
+{
+  for (int sweep = 0; sweep < 2; ++sweep)
+    for (int64_t g = 0; g < n; ++g) {
+      const int64_t word = (sweep ? slotU : slotL)[g];
+      unsigned char *tile = stream + (word >> 16) * 1024;
+      const Geometry G((int)(word >> 8 & 0xff));
+      const int lane = (int)(word & 0xff);
+      const int64_t k0 = sweep ? diag[g] + 1 : rp[g], k1 = sweep ? rp[g + 1] : diag[g];
+      for (int64_t k = k0; k < k1; ++k) *reinterpret_cast<double *>(tile + G.val_off((int)(k - k0), lane)) = lu[k];
+      if (sweep) *reinterpret_cast<double *>(tile + 512 + lane * 8) = lu[diag[g]];
+    }
 }
 
 // CPU emulation of the device kernel's data flow on the tile stream (test infrastructure for the builder):

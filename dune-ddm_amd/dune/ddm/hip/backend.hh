@@ -129,6 +129,17 @@ public:
   }
   DeviceCsr(const DeviceCsr&) = delete;
   ~DeviceCsr() { ddm_csr_destroy(h_); }
+  // the values A holds now, in the pattern this object was built on (ddm_csr_set_values)
+  template <class Mat>
+  void set_values(const Mat& A)
+  {
+    if (A.N() != n_ || (int64_t)A.nonzeroes() != ddm_csr_nnz(h_)) DUNE_THROW(Dune::InvalidStateException, "DeviceCsr::set_values: the matrix has another pattern than the one on the device");
+    std::vector<double> va;
+    va.reserve(A.nonzeroes());
+    for (auto ri = A.begin(); ri != A.end(); ++ri)
+      for (auto cit = ri->begin(); cit != ri->end(); ++cit) va.push_back((*cit)[0][0]);
+    check(ctx_->handle(), ddm_csr_set_values(ctx_->handle(), h_, va.data()), "ddm_csr_set_values");
+  }
   ddm_csr* handle() const { return h_; }
   std::size_t N() const { return n_; }
 

@@ -169,6 +169,21 @@ public:
     ddm_hip::check(ctx->handle(), ddm_galerkin_apply(ctx->handle(), G, dx->data(), dd->data()), "ddm_galerkin_apply");
     dx->download(x);
   }
+  // A holds new values in the pattern this level was built on: R A R^T again with the SAME basis, its inverse into the device
+  // object (ddm_galerkin_set_inverse).  Basis, layout and halos stay.
+  template <class Mat>
+  void refresh(const Mat& A)
+  {
+    if (A.N() != n) DUNE_THROW(Dune::Exception, "Template vectors must match size of matrix");
+    dA->set_values(A);
+    typename Communication::OwnerCopySet oc;
+    typename Communication::AllSet all;
+    Dune::Interface add_if;
+    add_if.build(comm->remoteIndices(), oc, all);
+    const auto& cc = comm->communicator();
+    build_solver(A, add_if, cc.rank(), cc.size(), (int)(basis.size() / n));
+    if (G) ddm_hip::check(ctx->handle(), ddm_galerkin_set_inverse(ctx->handle(), G, A0inv.data()), "ddm_galerkin_set_inverse");
+  }
   ddm_galerkin* galerkin_handle(std::size_t n_novlp) override { return handle(n_novlp); }
   ddm_galerkin* handle(std::size_t n_novlp)
   {

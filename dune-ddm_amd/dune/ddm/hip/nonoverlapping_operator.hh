@@ -46,6 +46,13 @@ public:
 
   Dune::SolverCategory::Category category() const override { return Dune::SolverCategory::nonoverlapping; }
 
+  // the matrix holds new values in its old pattern: re-read them and rebuild the product's storage (ddm_op_refresh)
+  void refresh()
+  {
+    dA->set_values(*A);
+    ddm_hip::check(ctx->handle(), ddm_op_refresh(ctx->handle(), op), "ddm_op_refresh");
+  }
+
   void apply(const X& x, Y& y) const override   // :34-39
   {
     dx->upload(x);

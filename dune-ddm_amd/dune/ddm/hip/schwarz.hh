@@ -115,6 +115,20 @@ public:
     ddm_hip::check(ctx->handle(), ddm_schwarz_apply(ctx->handle(), S, dx->data(), dd->data()), "ddm_schwarz_apply");
     dx->download(x);
   }
+  // The overlapping matrix holds new values in its old pattern (a Newton step): re-read them and refactorise on the device, keeping
+  // the schedules (ddm_schwarz_refresh).  A local solver the library does not refresh in place (the direct solvers, the box engine:
+  // DDM_ENOTIMPL) is dropped and built again on first use, as after construction; the adaptor object stays the same.
+  void refresh()
+  {
+    dA->set_values(*Aovlp);
+    if (!S) return;
+    const int rc = ddm_schwarz_refresh(ctx->handle(), S);
+    if (rc == DDM_ENOTIMPL) {
+      ddm_schwarz_destroy(S);
+      S = nullptr;
+    } else
+      ddm_hip::check(ctx->handle(), rc, "ddm_schwarz_refresh");
+  }
   ddm_schwarz* schwarz_handle(std::size_t n_novlp) override { return handle(n_novlp); }
   ddm_schwarz* handle(std::size_t n_novlp)
   {

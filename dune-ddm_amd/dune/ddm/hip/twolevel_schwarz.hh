@@ -3,7 +3,8 @@
 //
 // Layout of this file
 //   ddm_hip::krylov_settings        the "solver" sub-tree of one solve, with the backend's defaults (reference :119-131)
-//   ddm_hip::TwoLevelSchwarzCore    what happens on EVERY apply(): the two levels are rebuilt around the current matrix, the Krylov
+//   ddm_hip::TwoLevelSchwarzCore    what happens on EVERY apply(): the two levels are built (first call) or refreshed in place from the
+//                                   refilled overlapping matrix (later calls: schedules and coarse basis kept), the Krylov
 //                                   loop runs on the device, one upload and one download per solve.  Native dune-istl types only, so it
 //                                   compiles and is GPU-tested without PDELab (tests/cpp/twolevel_adaptor.cc).
 //   ddm_hip::OverlapObjects         (HAVE_DUNE_PDELAB) the overlapping matrix / communication / partition of unity of a rank, produced
@@ -68,6 +69,8 @@ public:
     for (const auto& t : templates_on_overlap)
       if (t.N() != matrix->N()) DUNE_THROW(Dune::Exception, "Template vectors must match size of matrix");
     ovlp = Overlapping{std::move(matrix), std::move(communication), std::move(partition), std::move(templates_on_overlap)};
+    fine.reset();   // (the levels belong to the objects they were built on)
+    coarse.reset();
   }
   bool has_overlapping() const { return (bool)ovlp.comm; }
   const std::shared_ptr<NativeMat>& overlapping_matrix() const { return ovlp.matrix; }
@@ -112,12 +115,23 @@ private:
   // "fine" = Schwarz level on the overlapping matrix (it also needs the non-overlapping communication for its restriction),
   // "coarse" = Galerkin level on the partition-of-unity-weighted template vectors; how the two are combined is the "mode" key of the
   // backend's own sub-tree, which is why the combination is configured with an empty sub-tree name.
+  // The first solve after set_overlapping builds the two levels.  A further solve finds the overlapping matrix refilled in place
+  // (same rows, same number of non-zeros: a Newton or time step) and REFRESHES them: the fine level refactorises on the device with
+  // its schedules kept, the coarse level recomputes R A R^T with its basis kept; `fine` and `coarse` stay the same objects.  Only the
+  // combination, a few pointers, is made per solve (it holds the operator, which belongs to the matrix of this solve).
   std::shared_ptr<Levels> build_levels(const std::shared_ptr<Operator>& op)
   {
-    fine = std::make_shared<FineLevel>(ovlp.matrix, ovlp.comm, ovlp.pou, cfg, "fine");
-    fine->novlp_comm = novlp;
-    const POUCoarseSpace<NativeVec> space(ovlp.templates, *ovlp.pou);
-    coarse = std::make_shared<CoarseLevel>(*ovlp.matrix, space.get_basis(), ovlp.comm, cfg, "coarse");
+    if (fine && coarse && built_rows == ovlp.matrix->N() && built_nonzeroes == ovlp.matrix->nonzeroes()) {
+      fine->refresh();
+      coarse->refresh(*ovlp.matrix);
+    } else {
+      fine = std::make_shared<FineLevel>(ovlp.matrix, ovlp.comm, ovlp.pou, cfg, "fine");
+      fine->novlp_comm = novlp;
+      const POUCoarseSpace<NativeVec> space(ovlp.templates, *ovlp.pou);
+      coarse = std::make_shared<CoarseLevel>(*ovlp.matrix, space.get_basis(), ovlp.comm, cfg, "coarse");
+      built_rows = ovlp.matrix->N();
+      built_nonzeroes = ovlp.matrix->nonzeroes();
+    }
     auto both = std::make_shared<Levels>(cfg, "");
     both->set_op(op);
     both->add(fine);
@@ -128,6 +142,7 @@ private:
   std::shared_ptr<Communication> novlp;
   Dune::ParameterTree cfg;
   Overlapping ovlp;
+  std::size_t built_rows = 0, built_nonzeroes = 0;   // the overlapping matrix `fine` and `coarse` were built on
 };
 
 }  // namespace ddm_hip

@@ -157,6 +157,8 @@ class TwoLevelSchwarz:
         self.schwarz = SchwarzPreconditioner(ctx, self.A_dir, rl.block_ptr, rl.n_o, rl.ext_map,
                                              rl.pou if use_pou_in_schwarz else None, schwarz_type, self.h_copy, self.h_add,
                                              subdomain_solver=subdomain_solver)   # [schwarz.subdomain_solver] type (schwarz.hh:85-92)
+        self._schwarz_args = (rl.pou if use_pou_in_schwarz else None, schwarz_type, subdomain_solver)   # (update_values may build the level anew)
+        self._mode = mode
         lap("halo plans, operator, local solver (factorisation, schedules)")
         self.galerkin = None
         self.a0 = None
@@ -169,6 +171,7 @@ class TwoLevelSchwarz:
         return self.schwarz.num_levels()
 
     def rebuild_combined(self, mode="additive"):
+        self._mode = mode
         self.prec = CombinedPreconditioner(self.ctx, mode, self.op, self.schwarz, self.galerkin)
 
     def host_basis(self):
@@ -188,6 +191,7 @@ class TwoLevelSchwarz:
         rl, dec, torch = self.rl, self.dec, self.torch
         P = dec.nsub
         self.basis_by_sub = {s: np.asarray(basis_by_sub[s], dtype=np.float64) for s in rl.local}
+        basis_by_sub = self.basis_by_sub                       # (arrays, also where the caller passed lists of vectors: host_basis())
         k_local = {s: int(basis_by_sub[s].shape[0]) for s in rl.local}
         k_all = self._allgather_small(k_local, P)              # MPI_Allgather of num_t (galerkin_preconditioner.hh:248)
         kmax = max(k_all)
@@ -209,6 +213,57 @@ class TwoLevelSchwarz:
                                                a0inv, self.h_copy, self.h_add)
         self.setup_times["coarse matrix R A R^T"] = t1 - t0
         self.setup_times["coarse inverse, basis upload"] = time.perf_counter() - t1
+
+    def update_values(self, A_values, A_dir_values):
+        """New matrix values in the patterns the object was built on (a Newton step, a time step with a changing coefficient):
+        A_values / A_dir_values are the ``data`` arrays of the rank-local A and A_dir in CSR order with sorted column indices.  The
+        decomposition, the halo plans, the schedules of the local solver and the coarse basis are kept; refreshed are the two matrices,
+        the operator's storage, the ILU(0) factor (on the device: SchwarzPreconditioner.refresh), R A R^T with the existing basis and
+        its inverse.  A local solver that cannot be refreshed in place (direct solvers, the box engine: DDM_ENOTIMPL) is built anew,
+        that level only.  The result is bit for bit what a new TwoLevelSchwarz on the new matrices with ``coarse=host_basis()`` gives.
+        A caller who wants a new GenEO basis calls set_coarse_basis afterwards.  The phases add to setup_times under "refresh: ..."."""
+        va, vd = np.ascontiguousarray(A_values, dtype=np.float64), np.ascontiguousarray(A_dir_values, dtype=np.float64)
+        if va.shape != (self.A.nnz,) or vd.shape != (self.A_dir.nnz,):       # (before anything is touched)
+            raise ValueError(f"update_values: {va.size} and {vd.size} values for patterns of {self.A.nnz} (A) and {self.A_dir.nnz} (A_dir) entries")
+        import time
+        from . import DDM_ENOTIMPL, DdmError
+        t = [time.perf_counter()]
+
+        def lap(name):
+            self.ctx.sync()
+            now = time.perf_counter()
+            self.setup_times["refresh: " + name] = now - t[0]
+            t[0] = now
+        recreated = False
+        self.A.set_values(va)
+        self.A_dir.set_values(vd)
+        for M, v in ((self.rl.A, va), (self.rl.A_dir, vd)):                 # (the host copies, where they are in the same order)
+            if getattr(M, "has_sorted_indices", False) and M.data.shape == v.shape:
+                M.data[:] = v
+        lap("matrix values (A, A_dir)")
+        self.op.refresh()
+        lap("operator storage")
+        try:
+            self.schwarz.refresh()
+            lap("local solver (device factorisation, scatter)")
+        except DdmError as e:
+            if e.code != DDM_ENOTIMPL:
+                raise
+            self.schwarz = SchwarzPreconditioner(self.ctx, self.A_dir, self.rl.block_ptr, self.rl.n_o, self.rl.ext_map, self._schwarz_args[0],
+                                                 self._schwarz_args[1], self.h_copy, self.h_add, subdomain_solver=self._schwarz_args[2])
+            lap("local solver (created anew)")
+            recreated = True
+        if self.galerkin is not None:
+            kmax = max(self.k_all)
+            basis = np.zeros((kmax, self.rl.n))
+            for s in self.rl.local:
+                basis[:self.k_all[s], self.rl.off[s]:self.rl.off[s] + self.dec.subs[s].n] = self.basis_by_sub[s]
+            self.a0 = self._build_coarse_matrix(basis, self.k_all, self.coarse_offset, self.K)
+            lap("coarse matrix R A R^T")
+            self.galerkin.set_inverse(np.linalg.inv(self.a0))
+            lap("coarse inverse")
+        if recreated:                                                        # (the combination holds the level it was built with)
+            self.prec = CombinedPreconditioner(self.ctx, self._mode, self.op, self.schwarz, self.galerkin)
 
     def _allgather_small(self, local: dict, P):
         if self.comm is None:

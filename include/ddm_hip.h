@@ -95,6 +95,10 @@ int ddm_csr_create(ddm_ctx *ctx, int64_t nrows, int64_t ncols, const int64_t *ro
  * pencil A_neu + sigma D B D is assembled from the host arrays; at 216^3 the two device copies were 7 GB and 0.6 s for nothing).
  * Entry points that need the device arrays (products, factorisations) return DDM_EINVAL for it. */
 int ddm_csr_create_host(ddm_ctx *ctx, int64_t nrows, int64_t ncols, const int64_t *rowptr, const int32_t *col, const double *val, ddm_csr **out); /* host arrays are copied */
+/* New values in the pattern of A (nnz doubles, copied): the host copy and, unless A came from ddm_csr_create_host, the device
+ * values on the context's stream.  Objects built on A keep what they made of the old values until they are refreshed
+ * (ddm_op_refresh, ddm_ilu0_refresh, ddm_schwarz_refresh).  Synchronous. */
+int ddm_csr_set_values(ddm_ctx *ctx, ddm_csr *A, const double *val_host);
 void ddm_csr_destroy(ddm_csr *A);
 int64_t ddm_csr_rows(const ddm_csr *A);
 int64_t ddm_csr_nnz(const ddm_csr *A);
@@ -147,6 +151,15 @@ int ddm_dia_codes_host(int64_t n, const int64_t *rowptr, const int32_t *col, con
  * blocks (subdomains) of A; pass nblocks=1, block_ptr={0,n} for one subdomain. */
 int ddm_ilu0_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, ddm_ilu0 **out);
 void ddm_ilu0_destroy(ddm_ilu0 *F);
+/* Refactorises from the CURRENT values of the matrix the factor was created on (ddm_csr_set_values; A outlives the factor): the
+ * numeric ILU(0) runs on the device along the factor's own L level schedule, then the new factor is scattered into the engines'
+ * layouts.  Same pattern, same blocks, same schedules.  Afterwards every solve and ddm_ilu0_get_factors_host give bit for bit what
+ * a factor created on the new values gives.  The level and pipe engines are rewritten in place (their buffers keep their addresses,
+ * so solves captured before the refresh stay valid); a built xcd2 part is dropped and rebuilt by the next solve.
+ * DDM_ENOTIMPL (nothing touched) for a sparse direct factor and for the box engine: create a new factor.
+ * DDM_ENUMERIC for a zero or non-finite pivot (the message names the block, as at creation): the factor still is the previous one.
+ * Synchronous. */
+int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F);
 /* x = (LU)^-1 d ; d and x must not alias */
 int ddm_ilu0_solve(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x);
 /* X = (LU)^-1 D for row-major n x nrhs block vectors (cf. the reference's multi-RHS triangular
@@ -280,6 +293,8 @@ double *ddm_halo_recvbuf(ddm_halo *H);
 
 /* ---- NonOverlappingOperator + NonOverlappingScalarProduct (nonoverlapping_operator.hh) ---- */
 int ddm_op_create(ddm_ctx *ctx, const ddm_csr *A, ddm_halo *novlp_add, const uint8_t *owner_mask_host, ddm_op **out);
+/* the operator's diagonal-block storage again from A's current values (ddm_csr_set_values): what ddm_op_create builds on them */
+int ddm_op_refresh(ddm_ctx *ctx, ddm_op *op);
 void ddm_op_destroy(ddm_op *op);
 int ddm_op_apply(ddm_ctx *ctx, ddm_op *op, const double *x, double *y);                       /* :34-39 */
 int ddm_op_applyscaleadd(ddm_ctx *ctx, ddm_op *op, double alpha, const double *x, double *y); /* :41-50 */
@@ -289,7 +304,7 @@ int ddm_norm(ddm_ctx *ctx, ddm_op *op, const double *x, double *result_host);   
 /* ---- SchwarzPreconditioner (schwarz.hh:54-220) --------------------------------------------
  * type: 0 = standard, 1 = restricted (schwarz.hh:80-83).  pou may be NULL (schwarz.hh:140).
  * ext_map[n]  : index into the non-overlapping vector or -1  ("extend": schwarz.hh:121-122)
- * A_dir is only read during creation (factorisation). */
+ * A_dir is only read during creation (factorisation) and by ddm_schwarz_refresh. */
 int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
                        const int32_t *ext_map_host, const double *pou_host, int type, ddm_halo *ovlp_copy,
                        ddm_halo *ovlp_add, ddm_schwarz **out);
@@ -299,6 +314,9 @@ int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, cons
 int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
                           const int32_t *ext_map_host, const double *pou_host, int type, const char *subdomain_solver,
                           ddm_halo *ovlp_copy, ddm_halo *ovlp_add, ddm_schwarz **out);
+/* the local solver again from A_dir's current values: ddm_ilu0_refresh on it, with its return codes (DDM_ENOTIMPL for a direct
+ * local solver and for the box engine: create a new level) */
+int ddm_schwarz_refresh(ddm_ctx *ctx, ddm_schwarz *S);
 void ddm_schwarz_destroy(ddm_schwarz *S);
 int ddm_schwarz_apply(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d); /* :115-149 */
 int64_t ddm_schwarz_num_levels(const ddm_schwarz *S, int upper); /* dependency levels of the local L / U solve */
@@ -322,6 +340,8 @@ int ddm_galerkin_create(ddm_ctx *ctx, int64_t n, int64_t n_novlp, const int32_t 
                         const int64_t *sub_ptr, int64_t kmax, const double *basis_host, const int64_t *coarse_index,
                         int64_t K, const double *a0inv_host, ddm_halo *ovlp_copy, ddm_halo *ovlp_add,
                         ddm_galerkin **out);
+/* a new inverse of the coarse matrix (K x K doubles, row-major) into the buffer the applies read; basis and layout stay */
+int ddm_galerkin_set_inverse(ddm_ctx *ctx, ddm_galerkin *G, const double *a0inv_host);
 void ddm_galerkin_destroy(ddm_galerkin *G);
 int ddm_galerkin_apply(ddm_ctx *ctx, ddm_galerkin *G, double *x, const double *d); /* :151-194 */
 /* Local slab of the Galerkin product (build_solver, :219-349; layout helpers.hh:252):
