@@ -56,6 +56,7 @@ def lib():
         L.orc_dense_lu.restype = ctypes.c_int
         L.orc_dense_lu_solve.argtypes = [I, P, P, P]
         L.orc_lu_residual_ld.argtypes = [I, P, P, P, P, I, P, P, P]
+        L.orc_csr_residual_ld.argtypes = [I, P, P, P, I, P, P, P]
         _LIB = L
     return _LIB
 

@@ -187,6 +187,22 @@ void orc_dense_lu_solve(i64 n, const double *a, const i64 *piv, double *b)
   }
 }
 
+/* Checker arithmetic of tests/sn_cases.py (no counterpart in the reference): r = d - A x in long double for m vectors, one after
+ * the other in memory (xt, dt, rt: m x n, a vector contiguous), A in CSR.  rt holds r rounded to double; one thread per vector. */
+void orc_csr_residual_ld(i64 n, const i64 *rp, const i32 *ci, const double *v, i64 m, const double *xt, const double *dt, double *rt)
+{
+#pragma omp parallel for schedule(dynamic, 1)
+  for (i64 j = 0; j < m; ++j) {
+    const double *x = xt + j * n, *d = dt + j * n;
+    double *r = rt + j * n;
+    for (i64 i = 0; i < n; ++i) {
+      long double s = (long double)d[i];
+      for (i64 k = rp[i]; k < rp[i + 1]; ++k) s -= (long double)v[k] * (long double)x[ci[k]];
+      r[i] = (double)s;
+    }
+  }
+}
+
 /* Checker arithmetic of tests/direct_cases.py (no counterpart in the reference): r = d - L (U x) in long double for m vectors,
  * one after the other in memory (xt, dt, rt: m x n, a vector contiguous), against a factor lu in the pattern rp / ci with sorted
  * rows -- multipliers of the unit lower L left of the diagonal diag[i], U right of it, the INVERSE pivot on it (orc_ilu0_factor's

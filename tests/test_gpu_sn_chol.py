@@ -88,7 +88,9 @@ def test_device_cholesky_matches_superlu(ddm, torch_cuda, device_engine, shape, 
     assert F2.status() == 0
     assert torch.equal(x3, x) and torch.equal(X2, X)
     steps, om = F.refinement()
+    print(f"\n[sn chol {shape} in {parts}] refinement steps {steps}, probe backward errors {om[:steps + 1]}")
     assert steps <= 1 and om[steps] < 1e-12, (steps, om)      # SPD: the probe is at rounding level at once (or after one step)
+    assert steps == 0 or om[0] < 1e-9, (steps, om)            # a factor that NEEDS its one step has lost digits, not the matrix (unrefined: tests/test_gpu_sn_routes.py)
     ctx.close()
 
 
