@@ -191,6 +191,11 @@ SYMBOLS = {
     "ddm_bgmres_combine_gram_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "ddm_dense_bgmres_factor_host": (_I32, [_I32, _P, _P, _D, _P, _P, _P]),
     "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
+    "ddm_local_maps_host": (_I32, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "ddm_schwarz_debug_local": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_int), _PP, _PP]),
+    "ddm_ctx_scalars": (_P, [_P]),
+    "ddm_schwarz_debug_sum_restrict": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "ddm_debug_reduction": (_I32, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "ddm_cg_begin": (_I32, [_P, _P, _P, _P, _P, _PP]),
     "ddm_cg_steps": (_I32, [_P, _P, _I32]),
     "ddm_cg_defect": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_double)]),
@@ -1137,6 +1142,32 @@ def dia_build_and_apply_host(A, x):
     if rc != DDM_OK:
         raise ValueError("ddm_dia_build_and_apply_host: bad arguments")
     return y, kinds[:counts[0]], dict(zip(("blocks", "dia", "csr", "rows_dia", "slots", "segments", "symmetric_segments"), counts.tolist()))
+
+
+def local_maps_host(n, n_novlp, ext_map, plan_copy, plan_add):
+    """dict(src_of, own_of, cp_ptr, cp_idx) or None: the index tables of the rank-local Schwarz passes (ddm_local_maps_host) for an
+    extension map and the copy / add plans as Halo takes them (None: no exchange).  None where the tables do not exist.  Host only."""
+    lib = load_library()
+    em = _np(ext_map, np.int32)
+    assert len(em) == n
+    args, keep, max_cp = [], [], 0
+    for plan in (plan_copy, plan_add):
+        if plan is None:
+            args += [0, None, 0, None, None, None]
+            continue
+        a = {k: _np(plan[k], np.int64) for k in ("send_idx", "dst_idx", "dst_ptr", "src_pos")}
+        keep.append(a)
+        max_cp = len(a["src_pos"])
+        args += [len(a["send_idx"]), _hp(a["send_idx"]), len(a["dst_idx"]), _hp(a["dst_idx"]), _hp(a["dst_ptr"]), _hp(a["src_pos"])]
+    src_of, own_of = np.empty(max(n, 1), dtype=np.int32), np.empty(max(n_novlp, 1), dtype=np.int32)
+    cp_ptr, cp_idx = np.empty(n_novlp + 1, dtype=np.int32), np.empty(max(max_cp, 1), dtype=np.int32)
+    counts = np.zeros(2, dtype=np.int64)
+    rc = lib.ddm_local_maps_host(int(n), int(n_novlp), _hp(em), *args, _hp(src_of), _hp(own_of), _hp(cp_ptr), max_cp, _hp(cp_idx), _hp(counts))
+    if rc != DDM_OK:
+        raise ValueError("ddm_local_maps_host: bad arguments")
+    if not counts[0]:
+        return None
+    return dict(src_of=src_of[:n], own_of=own_of[:n_novlp], cp_ptr=cp_ptr, cp_idx=cp_idx[:counts[1]])
 
 
 def dia_windows_host(A):

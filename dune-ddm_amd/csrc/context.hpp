@@ -42,6 +42,7 @@ struct ddm_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   dbuf<double> partial; // RED_MAX_BLOCKS doubles
   dbuf<double> scal;    // SCAL_SLOTS device scalars (the slots SCAL_*, kernels.hpp)
+  dbuf<unsigned> ticket; // arrival counter of the one self-finishing reduction in flight on the stream (reduce_finish): 0 between launches
   int num_cu = 256;           // compute units of the device: persistent kernels launch at most this many workgroups
   bool timing = false;
   std::map<std::string, TimerEntry> timers;
@@ -192,12 +193,13 @@ extern "C" int ddm_ctx_create(int device, void *hip_stream, ddm_ctx **out)
     }
     ctx->own_stream = true;
   }
-  if (ctx->partial.alloc(RED_MAX_BLOCKS) != hipSuccess || ctx->scal.alloc(SCAL_SLOTS) != hipSuccess ||
+  if (ctx->partial.alloc(RED_MAX_BLOCKS) != hipSuccess || ctx->scal.alloc(SCAL_SLOTS) != hipSuccess || ctx->ticket.alloc(1) != hipSuccess ||
       hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
     delete ctx;
     return DDM_EHIP;
   }
   (void)hipMemset(ctx->scal, 0, sizeof(double) * SCAL_SLOTS);
+  (void)hipMemset(ctx->ticket, 0, sizeof(unsigned));
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->num_cu = prop.multiProcessorCount;

@@ -1272,11 +1272,10 @@ __global__ void k_unpack(int64_t ndst, const int64_t *__restrict__ dst_idx, cons
 // ---------------------------------------------------------------------------------------------
 // K20 / a3: owner-masked dot products (nonoverlapping_operator.hh:76-83), two-stage and
 // deterministic: partial[b] per workgroup, then one workgroup sums the partials in index order.
+// a thread's share of sum_i [mask_i] x_i y_i: rows blockIdx.x * WG + threadIdx.x + t * gridDim.x * WG for ascending t
 template <bool MASKED>
-__global__ __launch_bounds__(WG) void k_dot_partial(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ x,
-                                                     const double *__restrict__ y, double *__restrict__ partial)
+__device__ __forceinline__ double dot_thread_sum(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ x, const double *__restrict__ y)
 {
-  __shared__ double red[4];
   double s = 0.0;
   const int64_t step = (int64_t)gridDim.x * WG;
   int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x;
@@ -1291,7 +1290,14 @@ __global__ __launch_bounds__(WG) void k_dot_partial(int64_t n, const uint8_t *__
   }
   for (; i < n; i += step)
     if (!MASKED || mask[i]) s += x[i] * y[i];
-  s = block_sum(s, red);
+  return s;
+}
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_dot_partial(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ x,
+                                                     const double *__restrict__ y, double *__restrict__ partial)
+{
+  __shared__ double red[4];
+  const double s = block_sum(dot_thread_sum<MASKED>(n, mask, x, y), red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(WG) void k_reduce_final(int nb, const double *__restrict__ partial, double *__restrict__ out)
@@ -1301,6 +1307,114 @@ __global__ __launch_bounds__(WG) void k_reduce_final(int nb, const double *__res
   for (int i = threadIdx.x; i < nb; i += WG) s += partial[i];
   s = block_sum(s, red);
   if (threadIdx.x == 0) out[0] = s;
+}
+// A reduction that finishes itself (the *_fin kernels): the workgroup's sum s (valid in thread 0) goes to partial[blockIdx.x], and
+// the workgroup that arrives last -- told by the value its add to *ticket returned -- sums the gridDim.x partials as k_reduce_final
+// does (same strides, same block_sum: the same bits), writes out[0] and puts the ticket back to 0 for the next launch on the stream.
+// Nobody waits.  The hand-off (MI355X: the L2s of the XCDs are not coherent with each other, a CU's L1 with nobody): thread 0 stores
+// its partial write-through and drains the store before its agent-scope add; the last arriver's thread 0 invalidates its CU's L1
+// after the add has returned, the other waves load behind the barrier it then joins; the partials are read past L1.
+__device__ __forceinline__ void reduce_finish(double s, double *partial, unsigned *ticket, double *out, double *red)
+{
+  __shared__ unsigned last;
+  if (threadIdx.x == 0) {
+    st_sc1(partial + blockIdx.x, s);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == gridDim.x - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    last = t == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  double v = 0.0;
+  for (int i = threadIdx.x; i < (int)gridDim.x; i += WG) v += ld_sc1(partial + i);
+  v = block_sum(v, red);
+  if (threadIdx.x == 0) {
+    out[0] = v;
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// k_dot_partial + k_reduce_final in one launch: out[0] = sum_i [mask_i] x_i y_i
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_dot_fin(int64_t n, const uint8_t *__restrict__ mask, const double *__restrict__ x, const double *__restrict__ y,
+                                                 double *partial, unsigned *ticket, double *out)
+{
+  __shared__ double red[4];
+  const double s = block_sum(dot_thread_sum<MASKED>(n, mask, x, y), red);
+  reduce_finish(s, partial, ticket, out, red);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rank-local forms of the two halo passes of a Schwarz apply, for a plan whose copies all live on this rank (LocalMaps, halo.hpp).
+// Defect: every row of the overlapping defect is a copy of one entry of the non-overlapping one (k_extend, then owner copied to all).
+__global__ void k_defect_gather(int64_t n, const int32_t *__restrict__ src_of, const double *__restrict__ d, double *__restrict__ dov)
+{
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    const int32_t m = src_of[i];
+    dov[i] = m >= 0 ? d[m] : 0.0;
+  }
+}
+// Solution: z[m] = xov[own_of[m]] + the other copies of that row in the order k_unpack<true> adds them (cp_idx[cp_ptr[m] ..
+// cp_ptr[m + 1])), which is what k_pack + k_unpack<true> + k_restrict<false, false> leave in z; the non-owner rows of xov are not
+// updated.  DOT: also out[0] = sum_m [mask_m] z_m r_m on the grid and with the rows per thread of k_dot_partial, a thread's products
+// added in ascending trip order as there, finished by reduce_finish: the bits of dot_device(z, r).
+// A thread takes HALO_TRIPS of its rows at a time: their table entries, then their owner values, then copy j of every row that has
+// one for ascending j (most rows have none, rows on a face one, on a corner seven) -- four dependent round trips per group where a
+// row-by-row loop makes as many per row with copies.  Rows past the end are clamped to the group's first row, loaded and dropped.
+constexpr int HALO_TRIPS = 8;
+template <bool MASKED, bool DOT>
+__global__ __launch_bounds__(WG) void k_halo_sum_restrict(int64_t n, const int32_t *__restrict__ own_of, const int32_t *__restrict__ cp_ptr,
+                                                           const int32_t *__restrict__ cp_idx, const double *__restrict__ xov, double *__restrict__ z,
+                                                           const uint8_t *__restrict__ mask, const double *__restrict__ r, double *partial, unsigned *ticket,
+                                                           double *out)
+{
+  __shared__ double red[4];
+  double s = 0.0;
+  const int64_t step = (int64_t)gridDim.x * WG;
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += HALO_TRIPS * step) {
+    int64_t row[HALO_TRIPS];
+    int32_t o[HALO_TRIPS], k0[HALO_TRIPS], k1[HALO_TRIPS];
+    double v[HALO_TRIPS], b[HALO_TRIPS];
+    bool ok[HALO_TRIPS], own[HALO_TRIPS];
+#pragma unroll
+    for (int u = 0; u < HALO_TRIPS; ++u) ok[u] = i + u * step < n, row[u] = ok[u] ? i + u * step : i;
+#pragma unroll
+    for (int u = 0; u < HALO_TRIPS; ++u) o[u] = own_of[row[u]], k0[u] = cp_ptr[row[u]], k1[u] = cp_ptr[row[u] + 1];
+#pragma unroll
+    for (int u = 0; u < HALO_TRIPS; ++u) {
+      v[u] = xov[o[u]];
+      if (DOT) b[u] = r[row[u]], own[u] = ok[u] && (!MASKED || mask[row[u]]);
+    }
+    int cmax = 0;
+#pragma unroll
+    for (int u = 0; u < HALO_TRIPS; ++u) {
+      if (!ok[u]) k1[u] = k0[u];
+      cmax = max(cmax, k1[u] - k0[u]);
+    }
+    for (int j = 0; j < cmax; ++j) {
+      int32_t c[HALO_TRIPS];
+      double w[HALO_TRIPS];
+#pragma unroll
+      for (int u = 0; u < HALO_TRIPS; ++u) c[u] = k0[u] + j < k1[u] ? cp_idx[k0[u] + j] : -1;
+#pragma unroll
+      for (int u = 0; u < HALO_TRIPS; ++u) w[u] = c[u] >= 0 ? xov[c[u]] : 0.0;
+#pragma unroll
+      for (int u = 0; u < HALO_TRIPS; ++u)
+        if (c[u] >= 0) v[u] = v[u] + w[u];
+    }
+#pragma unroll
+    for (int u = 0; u < HALO_TRIPS; ++u)
+      if (ok[u]) {
+        z[row[u]] = v[u];
+        if (DOT && own[u]) s += v[u] * b[u];
+      }
+  }
+  if (!DOT) return;
+  s = block_sum(s, red);
+  reduce_finish(s, partial, ticket, out, red);
 }
 
 // The device scalars of the Krylov drivers, one numbering for slot s of ctx->scal (SCAL_SLOTS doubles) and row s of ctx->mscal (SCAL_ROWS
@@ -1354,6 +1468,41 @@ __global__ void k_cg_direction(int64_t n, const double *__restrict__ scal, const
 {
   const double beta = scal[SCAL_BETA];
   for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) p[i] = beta * p[i] + q[i];
+}
+// The loop of ddm_cg_steps without k_cg_beta, k_cg_lambda and k_reduce_final: the consumer of a quotient forms it itself, every
+// thread by the division k_cg_beta / k_cg_lambda make on the same two operands, and one thread stores it for later readers.
+// k_cg_beta's second statement, rholast = rho, moves to the update kernel: no thread of THAT launch reads SCAL_RHOLAST (the threads
+// of k_cg_direction_beta do), and behind it lambda = rholast / <p, q> is rho / <p, q>.
+// p = (rho / rholast) p + q
+__global__ void k_cg_direction_beta(int64_t n, double *scal, const double *__restrict__ q, double *__restrict__ p)
+{
+  const double beta = scal[SCAL_RHO] / scal[SCAL_RHOLAST];
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) p[i] = beta * p[i] + q[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) scal[SCAL_BETA] = beta;
+}
+// k_cg_update_norm with lambda = scal[num] / scal[SCAL_PQ] (num: SCAL_RHOLAST in the first iteration, where nothing has written
+// SCAL_RHO, SCAL_RHO afterwards), rholast = scal[num], and the sum finished by reduce_finish into out[0]
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_cg_update_norm_fin(int64_t n, double *scal, int num, const uint8_t *__restrict__ mask, const double *__restrict__ p,
+                                                            const double *__restrict__ q, double *__restrict__ x, double *__restrict__ b, double *partial,
+                                                            unsigned *ticket, double *out)
+{
+  __shared__ double red[4];
+  const double rho = scal[num];
+  const double lam = rho / scal[SCAL_PQ];
+  double s = 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * WG) {
+    x[i] += lam * p[i];
+    const double bi = b[i] - lam * q[i];
+    b[i] = bi;
+    if (!MASKED || mask[i]) s += bi * bi;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scal[SCAL_STEP] = lam;
+    if (num != SCAL_RHOLAST) scal[SCAL_RHOLAST] = rho;
+  }
+  s = block_sum(s, red);
+  reduce_finish(s, partial, ticket, out, red);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -116,6 +116,9 @@ struct ddm_cg {
   int64_t n = 0;
   int it = 0;
   double def0 = 0.0;
+  // The loop without its one-workgroup launches (self-finishing reductions, quotients formed by their consumers: kernels.hpp) and
+  // with <q, b> taken by the apply's last pass: where the Schwarz level applies through its rank-local tables (ddm_schwarz::local).
+  bool fuse = false;
 };
 extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double *x, double *b, ddm_cg **out)
 {
@@ -127,6 +130,7 @@ extern "C" int ddm_cg_begin(ddm_ctx *ctx, ddm_op *op, ddm_combined *prec, double
   S->b = b;
   S->n = op->n;
   if (S->p.alloc(S->n) != hipSuccess || S->q.alloc(S->n) != hipSuccess) return fail(ctx, DDM_EHIP, "ddm_cg_begin: allocation failed");
+  S->fuse = prec->schwarz && schwarz_is_local(ctx, prec->schwarz); // (the Schwarz level read the switch when it was created)
   DDMCHECK(ddm_op_applyscaleadd(ctx, op, -1.0, x, b)); // prec.pre(x,b); b -= A x
   double bb = 0.0;
   DDMCHECK(dot_device(ctx, S->n, op->owner, b, b, ctx->scal + SCAL_DEF2));
@@ -149,7 +153,26 @@ extern "C" int ddm_cg_steps(ddm_ctx *ctx, ddm_cg *S, int k)
   double *scal = ctx->scal;
   double *rider = nullptr; // the previous iteration's squared defect norm, not yet summed over the ranks: handed to the next apply
   const int G = grid_for(S->n);
-  for (int i = 0; i < k; ++i) {
+  for (int i = 0; i < k && S->fuse; ++i) { // the same iteration in fewer launches: every scalar and vector bit for bit what the loop below leaves
+    const bool first = S->it == 0;
+    double *z = first ? S->p : S->q, *rho = scal + (first ? SCAL_RHOLAST : SCAL_RHO);
+    ApplyDot dot{S->op->owner, S->b, rho, false};
+    DDMCHECK(combined_apply_impl(ctx, S->prec, z, S->b, rider, &dot));                      // q = M^-1 b and rho = <q, b> where the apply can take it
+    if (!dot.done) DDMCHECK(dot_device_fin(ctx, S->n, S->op->owner, z, S->b, rho));
+    if (!first) hipLaunchKernelGGL(k_cg_direction_beta, dim3(G), dim3(WG), 0, ctx->stream, S->n, scal, S->q, S->p); // beta = rho / rholast; p = beta p + q
+    DDMCHECK(ddm_op_apply(ctx, S->op, S->p, S->q));                                          // q = A p
+    DDMCHECK(dot_device_fin(ctx, S->n, S->op->owner, S->p, S->q, scal + SCAL_PQ));           // alpha = <p, q>
+    const int nb = grid_for(S->n, WG * 4, RED_MAX_BLOCKS);
+    const int num = first ? SCAL_RHOLAST : SCAL_RHO; // lambda = rholast / alpha; rholast = rho; x += lambda p; b -= lambda q; def^2 = <b, b>
+    if (S->op->owner)
+      hipLaunchKernelGGL(k_cg_update_norm_fin<true>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, num, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial, ctx->ticket, scal + SCAL_DEF2);
+    else
+      hipLaunchKernelGGL(k_cg_update_norm_fin<false>, dim3(nb), dim3(WG), 0, ctx->stream, S->n, scal, num, S->op->owner, S->p, S->q, S->x, S->b, ctx->partial, ctx->ticket, scal + SCAL_DEF2);
+    rider = i + 1 < k && S->prec->galerkin ? scal + SCAL_DEF2 : nullptr; // (as below)
+    if (!rider) DDMCHECK(ctx_allreduce(ctx, scal + SCAL_DEF2, 1, "scalar product"));
+    S->it += 1;
+  }
+  for (int i = 0; i < k && !S->fuse; ++i) {
     const bool first = S->it == 0;
     DDMCHECK(combined_apply_impl(ctx, S->prec, first ? S->p : S->q, S->b, rider));         // q = M^-1 b  (p on the first step)
     DDMCHECK(dot_device(ctx, S->n, S->op->owner, first ? S->p : S->q, S->b, scal + (first ? SCAL_RHOLAST : SCAL_RHO))); // rho = <q, b>

@@ -22,6 +22,19 @@ static int dot_device(ddm_ctx *ctx, int64_t n, const uint8_t *mask, const double
   return DDM_OK;
 }
 
+// the same sum from ONE launch: the reduction finishes itself (k_dot_fin), bit-identical to dot_device
+static int dot_device_fin(ddm_ctx *ctx, int64_t n, const uint8_t *mask, const double *x, const double *y, double *result_dev)
+{
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  if (mask)
+    hipLaunchKernelGGL(k_dot_fin<true>, dim3(nb), dim3(WG), 0, ctx->stream, n, mask, x, y, ctx->partial, ctx->ticket, result_dev);
+  else
+    hipLaunchKernelGGL(k_dot_fin<false>, dim3(nb), dim3(WG), 0, ctx->stream, n, mask, x, y, ctx->partial, ctx->ticket, result_dev);
+  HIPCHECK(ctx, hipGetLastError());
+  DDMCHECK(ctx_allreduce(ctx, result_dev, 1, "scalar product"));
+  return DDM_OK;
+}
+
 // ... and for m columns: m owner-masked dots, one kernel per group of up to 8 columns, one all-reduce of m doubles
 template <class Launch>
 static void for_column_groups(int m, Launch &&launch)
@@ -217,6 +230,10 @@ struct ddm_schwarz {
   dbuf<double> md_ovlp, mx_ovlp; // multi-RHS blocks (mcols columns)
   int mcols = 0;
   bool multi_f32 = false; // ddm_schwarz_set_multi_precision: single-precision sweeps in the block local solve
+  // The single-vector apply's two exchanges as index tables (local_maps_build, halo.hpp), where both plans are rank-local and
+  // DDM_FUSE_LOCAL is not "0"; otherwise (local == false) the apply runs k_extend, the exchanges and k_restrict.
+  dbuf<int32_t> src_of, own_of, cp_ptr, cp_idx;
+  bool local = false;
   ~ddm_schwarz() { ddm_ilu0_destroy(solver); }
 };
 extern "C" int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
@@ -267,6 +284,17 @@ extern "C" int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t
   DDMCHECK(upload(ctx, ext_map_host, n, S->ext_map));
   if (pou_host) DDMCHECK(upload(ctx, pou_host, n, S->pou));
   if (S->d_ovlp.alloc(n) != hipSuccess || S->x_ovlp.alloc(n) != hipSuccess) return fail(ctx, DDM_EHIP, "alloc");
+  const char *fl = std::getenv("DDM_FUSE_LOCAL"); // "0": the general path also where the plans are rank-local (A/B runs, tests)
+  if (!(fl && fl[0] == '0') && halo_is_local(ctx, ovlp_copy) && halo_is_local(ctx, ovlp_add)) {
+    LocalMapsHost M;
+    if (local_maps_build(n, n_novlp, ext_map_host, halo_plan_host(ovlp_copy), halo_plan_host(ovlp_add), M)) {
+      DDMCHECK(upload(ctx, M.src_of.data(), (int64_t)M.src_of.size(), S->src_of));
+      DDMCHECK(upload(ctx, M.own_of.data(), (int64_t)M.own_of.size(), S->own_of));
+      DDMCHECK(upload(ctx, M.cp_ptr.data(), (int64_t)M.cp_ptr.size(), S->cp_ptr));
+      DDMCHECK(upload(ctx, M.cp_idx.data(), (int64_t)M.cp_idx.size(), S->cp_idx));
+      S->local = true;
+    }
+  }
   *out = S.release();
   return DDM_OK;
 }
@@ -299,14 +327,65 @@ static int local_status_check(ddm_ctx *ctx, const ddm_schwarz *S)
     return fail(ctx, DDM_ENUMERIC, "an earlier local triangular solve timed out waiting for a dependency (code %u): results since then are invalid", e);
   return DDM_OK;
 }
-// x (= or +=) R~^T [D] A_dir^-1 R~ d
-static int schwarz_apply_impl(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d, bool acc)
+// A caller's wish for sum_m [mask_m] z_m r_m of the vector z an apply is about to produce (CG's rho = <z, r>).  An apply whose last
+// pass over z can form it on the way does so -- into out, summed over the ranks, the bits of dot_device(z, r) -- and sets done;
+// otherwise it leaves the request alone and the caller takes the dot product itself.
+struct ApplyDot {
+  const uint8_t *mask;
+  const double *r;
+  double *out;
+  bool done;
+};
+static bool schwarz_is_local(const ddm_ctx *ctx, const ddm_schwarz *S) { return S->local && halo_is_local(ctx, S->copy) && halo_is_local(ctx, S->add); }
+// k_extend + the copy exchange (schwarz.hh:121-125), in one gather where the plans are rank-local
+static int schwarz_get_defect(ddm_ctx *ctx, ddm_schwarz *S, const double *d)
+{
+  if (schwarz_is_local(ctx, S)) {
+    hipLaunchKernelGGL(k_defect_gather, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, (const int32_t *)S->src_of, d, S->d_ovlp);
+    halo_count_local(ctx, S->copy);
+    HIPCHECK(ctx, hipGetLastError());
+    return DDM_OK;
+  }
+  hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp); // :121-122
+  return ddm_halo_exchange(ctx, S->copy, S->d_ovlp);                                                            // :125
+}
+// the add exchange + k_restrict<false, false> (schwarz.hh:138/:142, :146): x = the restriction of the summed S->x_ovlp.  Where the
+// plans are rank-local one pass does both (the non-owner rows of S->x_ovlp are then NOT updated: nothing reads them before the next
+// local solve overwrites them) and takes the dot product of a request on the way.
+static int schwarz_sum_restrict(ddm_ctx *ctx, ddm_schwarz *S, double *x, ApplyDot *dot)
+{
+  if (!schwarz_is_local(ctx, S)) {
+    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));
+    hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
+    HIPCHECK(ctx, hipGetLastError());
+    return DDM_OK;
+  }
+  const int64_t n = S->n_novlp;
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS); // (the grid of dot_device: the dot's partial sums are those of k_dot_partial)
+  const int32_t *own = S->own_of, *cp = S->cp_ptr, *ci = S->cp_idx;
+  const double *xov = S->x_ovlp;
+  halo_count_local(ctx, S->add);
+  if (!dot)
+    hipLaunchKernelGGL((k_halo_sum_restrict<false, false>), dim3(nb), dim3(WG), 0, ctx->stream, n, own, cp, ci, xov, x, (const uint8_t *)nullptr, (const double *)nullptr,
+                       (double *)nullptr, (unsigned *)nullptr, (double *)nullptr);
+  else if (dot->mask)
+    hipLaunchKernelGGL((k_halo_sum_restrict<true, true>), dim3(nb), dim3(WG), 0, ctx->stream, n, own, cp, ci, xov, x, dot->mask, dot->r, ctx->partial, ctx->ticket, dot->out);
+  else
+    hipLaunchKernelGGL((k_halo_sum_restrict<false, true>), dim3(nb), dim3(WG), 0, ctx->stream, n, own, cp, ci, xov, x, dot->mask, dot->r, ctx->partial, ctx->ticket, dot->out);
+  HIPCHECK(ctx, hipGetLastError());
+  if (dot) {
+    DDMCHECK(ctx_allreduce(ctx, dot->out, 1, "scalar product"));
+    dot->done = true;
+  }
+  return DDM_OK;
+}
+// x (= or +=) R~^T [D] A_dir^-1 R~ d; dot: a request the apply may serve (acc == false only), or null
+static int schwarz_apply_impl(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d, bool acc, ApplyDot *dot = nullptr)
 {
   DDMCHECK(local_status_check(ctx, S));
   {
     ScopedTimer t(ctx, "Schwarz/get defect");
-    hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp); // :121-122
-    DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));                                                          // :125
+    DDMCHECK(schwarz_get_defect(ctx, S, d));
   }
   {
     ScopedTimer t(ctx, "Schwarz/local solve");
@@ -316,11 +395,9 @@ static int schwarz_apply_impl(ddm_ctx *ctx, ddm_schwarz *S, double *x, const dou
     ScopedTimer t(ctx, "Schwarz/add solution");
     if (S->type == 1 && S->pou)
       hipLaunchKernelGGL(k_scale, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->pou, S->x_ovlp); // :139-141
-    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));                                                     // :138/:142
-    if (acc)
-      hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
-    else
-      hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x); // :146
+    if (!acc) return schwarz_sum_restrict(ctx, S, x, dot);                                                   // :138/:142, :146
+    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));
+    hipLaunchKernelGGL((k_restrict<true, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
     HIPCHECK(ctx, hipGetLastError());
   }
   return DDM_OK;
@@ -676,7 +753,7 @@ extern "C" void ddm_combined_destroy(ddm_combined *C) { delete C; }
 // which applies "x *= pou; x += x_coarse" as on one stream: the same kernels' sums in the same order, the result is bit-identical.
 // The other engines join behind the solve with k_scale + k_axpy (the same operations as separate passes).
 // Measurements, the losing configurations included: DESIGN.md section 4.
-static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider)
+static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider, ApplyDot *dot)
 {
   ddm_schwarz *S = C->schwarz;
   ddm_galerkin *G = C->galerkin;
@@ -686,8 +763,7 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
   if (two_streams) DDMCHECK(ctx_side_stream(ctx));
   {
     ScopedTimer t(ctx, "Schwarz/get defect");
-    hipLaunchKernelGGL(k_extend, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, d, S->d_ovlp);
-    DDMCHECK(ddm_halo_exchange(ctx, S->copy, S->d_ovlp));
+    DDMCHECK(schwarz_get_defect(ctx, S, d));
   }
   // The coarse chain (kernels, RCCL all-reduce, timer) goes to the side stream, or runs first on the one stream, so that the local
   // solve's last kernel can also apply "x *= pou; x += x_coarse".
@@ -716,9 +792,7 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
       HIPCHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
       hipLaunchKernelGGL(k_axpy, dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, 1.0, (const double *)G->x_ovlp, S->x_ovlp);
     }
-    DDMCHECK(ddm_halo_exchange(ctx, S->add, S->x_ovlp));
-    hipLaunchKernelGGL((k_restrict<false, false>), dim3(grid_for(S->n)), dim3(WG), 0, ctx->stream, S->n, S->ext_map, S->x_ovlp, (const double *)nullptr, x);
-    HIPCHECK(ctx, hipGetLastError());
+    DDMCHECK(schwarz_sum_restrict(ctx, S, x, dot));
   }
   return DDM_OK;
 }
@@ -726,13 +800,15 @@ static int combined_apply_fused(ddm_ctx *ctx, ddm_combined *C, double *x, const 
 // rider: a device scalar to be summed over the ranks, or null.  Wherever C has a Galerkin level, exactly ONE coarse_allreduce of the
 // apply receives it -- fused, additive unfused and multiplicative alike -- so a caller that passes one need not reduce it itself
 // (ddm_cg_steps: the squared defect norm of the previous iteration); without a Galerkin level it is ignored.
-static int combined_apply_impl(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider)
+// dot: a request for <x, r> (ApplyDot) or null; served where the Schwarz level's restriction is the apply's last pass over x (the
+// fused additive combination, no Galerkin level) and its plans are rank-local.
+static int combined_apply_impl(ddm_ctx *ctx, ddm_combined *C, double *x, const double *d, double *rider, ApplyDot *dot = nullptr)
 {
   ScopedTimer t(ctx, "CombinedPreconditioner/apply");
   DDMCHECK(local_status_check(ctx, C->schwarz));
-  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d, rider);
+  if (C->mode == 0 && C->galerkin && C->fused) return combined_apply_fused(ctx, C, x, d, rider, dot);
   // x = 0; precs[0]->apply(x, d)  (:133-134)  -- the restrict kernel overwrites every entry of x
-  DDMCHECK(schwarz_apply_impl(ctx, C->schwarz, x, d, false));
+  DDMCHECK(schwarz_apply_impl(ctx, C->schwarz, x, d, false, C->galerkin ? nullptr : dot));
   if (!C->galerkin) return DDM_OK;
   if (C->mode == 0) { // additive: xnext = P1 d; x += xnext (:136-142) -- fused into the restrict of the coarse level
     // both levels extend the same defect over the same interface: the Schwarz level's copy is reused (the local solves read it only)
@@ -795,4 +871,80 @@ extern "C" int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs,
   if (!ctx || !C || !X || !D || X == D) return fail(ctx, DDM_EINVAL, "ddm_combined_apply_multi: bad arguments");
   DDMCHECK(multi_check(ctx, nrhs, "ddm_combined_apply_multi"));
   return combined_apply_multi_impl(ctx, C, nrhs, X, D);
+}
+
+// ---- diagnostics of the rank-local passes and the self-finishing reductions (not part of the product path) ------------------------
+// Whether S applies through the rank-local tables, and its two overlapping work vectors (n doubles each; either may be null).
+extern "C" int ddm_schwarz_debug_local(ddm_ctx *ctx, ddm_schwarz *S, int *local, double **d_ovlp, double **x_ovlp)
+{
+  if (!ctx || !S || !local) return fail(ctx, DDM_EINVAL, "ddm_schwarz_debug_local: bad arguments");
+  *local = schwarz_is_local(ctx, S) ? 1 : 0;
+  if (d_ovlp) *d_ovlp = S->d_ovlp;
+  if (x_ovlp) *x_ovlp = S->x_ovlp;
+  return DDM_OK;
+}
+extern "C" double *ddm_ctx_scalars(ddm_ctx *ctx) { return ctx ? ctx->scal.get() : nullptr; } // the SCAL_SLOTS device scalars
+// The second half of a Schwarz apply on an overlapping vector the caller supplies (n device doubles, copied into S's work vector):
+// z = restriction of its sum over the copies, out[0] = <z, r> with the owner mask (null: none).  general != 0: the add exchange,
+// k_restrict and dot_device, whatever S would take; general == 0: what S takes (the one pass where its plans are rank-local).
+extern "C" int ddm_schwarz_debug_sum_restrict(ddm_ctx *ctx, ddm_schwarz *S, const double *x_ovlp, int general, const uint8_t *mask, const double *r, double *z, double *out)
+{
+  if (!ctx || !S || !x_ovlp || !r || !z || !out) return fail(ctx, DDM_EINVAL, "ddm_schwarz_debug_sum_restrict: bad arguments");
+  HIPCHECK(ctx, hipMemcpyAsync(S->x_ovlp, x_ovlp, sizeof(double) * (size_t)S->n, hipMemcpyDeviceToDevice, ctx->stream));
+  ApplyDot dot{mask, r, out, false};
+  if (general) {
+    const bool keep = S->local;
+    S->local = false;
+    const int rc = schwarz_sum_restrict(ctx, S, z, &dot);
+    S->local = keep;
+    DDMCHECK(rc);
+  } else
+    DDMCHECK(schwarz_sum_restrict(ctx, S, z, &dot));
+  if (!dot.done) DDMCHECK(dot_device(ctx, S->n_novlp, mask, z, r, out));
+  return DDM_OK;
+}
+// One reduction of the CG loop on n rows, enqueued without synchronising; fin != 0: the self-finishing kernel, fin == 0: the kernels
+// it stands in for.  mask: n bytes or null.  out: device doubles.
+//   kind 0  out[0] = <a, b>                                    k_dot_fin                | k_dot_partial + k_reduce_final
+//   kind 1  a += lambda c, b -= lambda d, lambda = rho / pq;    k_cg_update_norm_fin     | [k_cg_beta +] k_cg_lambda + k_cg_update_norm + k_reduce_final
+//           out[0 .. 2] = <b, b>, lambda, rholast.  The caller has put pq into SCAL_PQ and rho into SCAL_RHOLAST (first != 0: the
+//           first iteration) or into SCAL_RHO with the last rho in SCAL_RHOLAST (first == 0) of ddm_ctx_scalars.
+//   kind 2  a = rows of c summed by the tables (own_of, cp_ptr, cp_idx over n rows), out[0] = <a, b>
+//                                                               k_halo_sum_restrict<., true> | the same kernel without the dot + the kind 0 pair
+extern "C" int ddm_debug_reduction(ddm_ctx *ctx, int kind, int fin, int64_t n, const uint8_t *mask, double *a, double *b, const double *c, const double *d,
+                                   int first, const int32_t *own_of, const int32_t *cp_ptr, const int32_t *cp_idx, double *out)
+{
+  if (!ctx || n < 1 || !a || !b || !out || kind < 0 || kind > 2) return fail(ctx, DDM_EINVAL, "ddm_debug_reduction: bad arguments");
+  const int nb = grid_for(n, WG * 4, RED_MAX_BLOCKS);
+  double *scal = ctx->scal;
+  if (kind == 0) return fin ? dot_device_fin(ctx, n, mask, a, b, out) : dot_device(ctx, n, mask, a, b, out);
+  if (kind == 1) {
+    if (!c || !d) return fail(ctx, DDM_EINVAL, "ddm_debug_reduction: bad arguments");
+    if (fin) {
+      const int num = first ? SCAL_RHOLAST : SCAL_RHO;
+      if (mask) hipLaunchKernelGGL(k_cg_update_norm_fin<true>, dim3(nb), dim3(WG), 0, ctx->stream, n, scal, num, mask, c, d, a, b, ctx->partial, ctx->ticket, scal + SCAL_DEF2);
+      else hipLaunchKernelGGL(k_cg_update_norm_fin<false>, dim3(nb), dim3(WG), 0, ctx->stream, n, scal, num, mask, c, d, a, b, ctx->partial, ctx->ticket, scal + SCAL_DEF2);
+    } else {
+      if (!first) hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(1), 0, ctx->stream, scal);
+      hipLaunchKernelGGL(k_cg_lambda, dim3(1), dim3(1), 0, ctx->stream, scal);
+      if (mask) hipLaunchKernelGGL(k_cg_update_norm<true>, dim3(nb), dim3(WG), 0, ctx->stream, n, (const double *)scal, mask, c, d, a, b, ctx->partial);
+      else hipLaunchKernelGGL(k_cg_update_norm<false>, dim3(nb), dim3(WG), 0, ctx->stream, n, (const double *)scal, mask, c, d, a, b, ctx->partial);
+      hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(WG), 0, ctx->stream, nb, ctx->partial, scal + SCAL_DEF2);
+    }
+    hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, ctx->stream, (const double *)(scal + SCAL_DEF2), out);
+    hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, ctx->stream, (const double *)(scal + SCAL_STEP), out + 1);
+    hipLaunchKernelGGL(k_copy_scalar, dim3(1), dim3(1), 0, ctx->stream, (const double *)(scal + SCAL_RHOLAST), out + 2);
+    HIPCHECK(ctx, hipGetLastError());
+    return DDM_OK;
+  }
+  if (!c || !own_of || !cp_ptr || !cp_idx) return fail(ctx, DDM_EINVAL, "ddm_debug_reduction: bad arguments");
+  if (fin) {
+    if (mask) hipLaunchKernelGGL((k_halo_sum_restrict<true, true>), dim3(nb), dim3(WG), 0, ctx->stream, n, own_of, cp_ptr, cp_idx, c, a, mask, (const double *)b, ctx->partial, ctx->ticket, out);
+    else hipLaunchKernelGGL((k_halo_sum_restrict<false, true>), dim3(nb), dim3(WG), 0, ctx->stream, n, own_of, cp_ptr, cp_idx, c, a, mask, (const double *)b, ctx->partial, ctx->ticket, out);
+    HIPCHECK(ctx, hipGetLastError());
+    return DDM_OK;
+  }
+  hipLaunchKernelGGL((k_halo_sum_restrict<false, false>), dim3(nb), dim3(WG), 0, ctx->stream, n, own_of, cp_ptr, cp_idx, c, a, (const uint8_t *)nullptr, (const double *)nullptr,
+                     (double *)nullptr, (unsigned *)nullptr, (double *)nullptr);
+  return dot_device(ctx, n, mask, a, b, out);
 }

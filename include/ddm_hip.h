@@ -356,6 +356,28 @@ int ddm_galerkin_products(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nleft, con
 int ddm_galerkin_debug_chain(ddm_ctx *ctx, ddm_galerkin *G, const double *d_ovlp, int spread_grid, double *partial_out, double *d0_out,
                              double *x_ovlp_out, int64_t *npartial);
 
+/* ---- rank-local Schwarz passes and self-finishing reductions: tables and diagnostics -----------------------------------------------
+ * Where both plans of a Schwarz level are rank-local (single rank, or an in-library exchange with no off-rank pair) and
+ * DDM_FUSE_LOCAL is not "0" when the objects are created, the single-vector apply gathers the overlapping defect in one pass and sums,
+ * restricts (and, for ddm_cg_steps, takes <z, r> of) the overlapping result in one pass, and ddm_cg_steps runs without its
+ * one-workgroup launches; every result is bit-identical to the general path.
+ * ddm_local_maps_host: the index tables of those passes from an extension map (n overlapping rows -> n_novlp non-overlapping rows or
+ * -1) and the two plans as ddm_halo_create takes them (a plan with nsend = ndst = 0 and null arrays: no exchange).  src_of[n],
+ * own_of[n_novlp], cp_ptr[n_novlp + 1], cp_idx[at most max_cp]; counts[2] = {1 if the tables exist else 0, entries of cp_idx}.
+ * Host only, no device needed. */
+int ddm_local_maps_host(int64_t n, int64_t n_novlp, const int32_t *ext_map, int64_t copy_nsend, const int64_t *copy_send_idx, int64_t copy_ndst,
+                        const int64_t *copy_dst_idx, const int64_t *copy_dst_ptr, const int64_t *copy_src_pos, int64_t add_nsend,
+                        const int64_t *add_send_idx, int64_t add_ndst, const int64_t *add_dst_idx, const int64_t *add_dst_ptr,
+                        const int64_t *add_src_pos, int32_t *src_of, int32_t *own_of, int32_t *cp_ptr, int64_t max_cp, int32_t *cp_idx, int64_t *counts);
+/* Diagnostics (device pointers; nothing synchronises unless said): whether S applies through the tables and its overlapping work
+ * vectors; the context's device scalars; the second half of a Schwarz apply on a supplied overlapping vector (general != 0: add
+ * exchange + restriction + dot product as separate kernels); one reduction of the CG loop alone (kinds: csrc/preconditioners.hpp). */
+int ddm_schwarz_debug_local(ddm_ctx *ctx, ddm_schwarz *S, int *local, double **d_ovlp, double **x_ovlp);
+double *ddm_ctx_scalars(ddm_ctx *ctx);
+int ddm_schwarz_debug_sum_restrict(ddm_ctx *ctx, ddm_schwarz *S, const double *x_ovlp, int general, const uint8_t *mask, const double *r, double *z, double *out);
+int ddm_debug_reduction(ddm_ctx *ctx, int kind, int fin, int64_t n, const uint8_t *mask, double *a, double *b, const double *c, const double *d,
+                        int first, const int32_t *own_of, const int32_t *cp_ptr, const int32_t *cp_idx, double *out);
+
 /* ---- GenEO coarse-basis builder ---------------------------------------------------------------
  * GenEOCoarseSpace(A, B, pou, ptree, taskflow, prefix) -> get_basis() (dune/ddm/coarsespaces/coarse_spaces.hh:219-256, 286-331):
  * C = D B_neu D, the lowest nev eigenpairs of A_neu x = lambda C x per subdomain, v <- D v / ||D v||_2, entries of Dirichlet
