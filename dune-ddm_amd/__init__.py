@@ -75,6 +75,7 @@ SYMBOLS = {
     "ddm_csr_create_host": (_I32, [_P, _I64, _I64, _P, _P, _P, _PP]),
     "ddm_csr_set_values": (_I32, [_P, _P, _P]),
     "ddm_ilu0_refresh": (_I32, [_P, _P]),
+    "ddm_ilu0_refresh_count": (_I32, [_P]),
     "ddm_schwarz_refresh": (_I32, [_P, _P]),
     "ddm_op_refresh": (_I32, [_P, _P]),
     "ddm_galerkin_set_inverse": (_I32, [_P, _P, _P]),
@@ -472,9 +473,17 @@ class Ilu0:
         return steps, om
 
     def refresh(self):
-        """refactorises from the current values of the matrix (CsrMatrix.set_values): ddm_ilu0_refresh.  DdmError with code
-        DDM_ENOTIMPL for a direct factor and the box engine, DDM_ENUMERIC for a vanishing pivot (the factor stays the previous one)."""
+        """refactorises from the current values of the matrix (CsrMatrix.set_values): ddm_ilu0_refresh.  ILU(0): DdmError with code
+        DDM_ENUMERIC for a vanishing pivot (the factor stays the previous one).  Device supernodal direct factor (engine()
+        'supernodal'): factorised again on the kept structure, refinement decided again; its panels are overwritten, so after a
+        DdmError (DDM_ENUMERIC: not positive definite; DDM_ENOTIMPL: values an unforced creation hands to the host engine) the factor
+        is invalid and every solve raises DDM_ENUMERIC until a refresh succeeds.  DDM_ENOTIMPL, nothing touched, for the host-engine
+        direct factor and the box engine: create a new factor."""
         self.ctx.check(self.ctx.lib.ddm_ilu0_refresh(self.ctx.h, self.h))
+
+    def refresh_count(self):
+        """successful in-place refreshes since creation (ddm_ilu0_refresh_count)"""
+        return int(self.ctx.lib.ddm_ilu0_refresh_count(self.h))
 
     def solve(self, d, x):
         self.ctx.check(self.ctx.lib.ddm_ilu0_solve(self.ctx.h, self.h, _ptr(d), _ptr(x)))
@@ -632,9 +641,16 @@ class SchwarzPreconditioner:
         self._keep = (A_dir, ovlp_copy, ovlp_add)
 
     def refresh(self):
-        """the local solver again from A_dir's current values (CsrMatrix.set_values): ddm_schwarz_refresh.  DdmError with code
-        DDM_ENOTIMPL for direct local solvers and the box engine: build a new SchwarzPreconditioner instead."""
+        """the local solver again from A_dir's current values (CsrMatrix.set_values): ddm_schwarz_refresh.  ILU(0) and the device
+        supernodal direct factor are refreshed in place (Ilu0.refresh says what that means for each).  DdmError with code
+        DDM_ENOTIMPL for the host-engine direct factor, the box engine and a device factor whose new values belong to the host
+        engine: build a new SchwarzPreconditioner instead."""
         self.ctx.check(self.ctx.lib.ddm_schwarz_refresh(self.ctx.h, self.h))
+
+    def refresh_count(self):
+        """successful in-place refreshes of the local solver since this object was created (ddm_ilu0_refresh_count)"""
+        F = self.ctx.lib.ddm_schwarz_local_solver(self.h)
+        return int(self.ctx.lib.ddm_ilu0_refresh_count(ctypes.c_void_p(F))) if F else 0
 
     def apply(self, x, d):
         self.ctx.check(self.ctx.lib.ddm_schwarz_apply(self.ctx.h, self.h, _ptr(x), _ptr(d)))

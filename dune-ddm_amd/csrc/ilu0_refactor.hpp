@@ -9,7 +9,8 @@
 //   * PipeEngine: the value slots and the s0 slots of the tile stream are rewritten in place; F->graph stays valid.
 //   * XcdEngine: a built part is DROPPED (and F->graph with it when xcd2 is the settled engine); the next solve rebuilds it from
 //     the refreshed h_lu, as the first solve after creation builds it.
-//   * direct factors and the box engine are refused (DDM_ENOTIMPL, nothing touched): the caller creates a new factor.
+//   * the host-engine direct factor (F->csr) and the box engine are refused (DDM_ENOTIMPL, nothing touched): the caller creates a
+//     new factor.  The device supernodal factor (F->sn) is refreshed by sn_refresh.hpp.
 //   * h_lu is brought up to date when it is next read (ilu0_sync_host_factor).
 // The factorisation writes a scratch array; the engines are touched only after the status word has come back clean, so a vanishing
 // pivot (DDM_ENUMERIC) leaves the previous factor in place everywhere.
@@ -233,10 +234,11 @@ static int ilu0_scatter_enqueue(ddm_ctx *ctx, ddm_ilu0 *F, const double *lu)
   return DDM_OK;
 }
 
-extern "C" int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F)
+static int sn_refresh(ddm_ctx *ctx, ddm_ilu0 *F); // sn_refresh.hpp
+static int ilu0_refresh_impl(ddm_ctx *ctx, ddm_ilu0 *F)
 {
-  if (!ctx || !F) return fail(ctx, DDM_EINVAL, "ddm_ilu0_refresh: bad arguments");
-  if (F->csr || F->sn) return fail(ctx, DDM_ENOTIMPL, "ddm_ilu0_refresh: a sparse direct factor is not refreshed in place: create a new factor on the new values");
+  if (F->csr) return fail(ctx, DDM_ENOTIMPL, "ddm_ilu0_refresh: a sparse direct factor is not refreshed in place: create a new factor on the new values");
+  if (F->sn) return sn_refresh(ctx, F);
   DDMCHECK(ilu0_join(ctx, F)); // (the background builder writes the parts the scatter fills; the engine is settled afterwards)
   if (F->engine == Engine::Box) return fail(ctx, DDM_ENOTIMPL, "ddm_ilu0_refresh: the box engine is not refreshed in place: create a new factor on the new values");
   if (F->n == 0) return DDM_OK;
@@ -287,3 +289,12 @@ extern "C" int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F)
   R.host_stale = true;
   return DDM_OK;
 }
+extern "C" int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F)
+{
+  if (!ctx || !F) return fail(ctx, DDM_EINVAL, "ddm_ilu0_refresh: bad arguments");
+  DDMCHECK(ilu0_refresh_impl(ctx, F));
+  ++F->refresh_count;
+  return DDM_OK;
+}
+// successful in-place refreshes since creation (0 after creation; a failed or refused refresh does not count)
+extern "C" int ddm_ilu0_refresh_count(const ddm_ilu0 *F) { return F ? F->refresh_count : 0; }

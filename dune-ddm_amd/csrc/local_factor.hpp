@@ -137,6 +137,9 @@ struct SnDirect { // supernodal factor computed ON THE DEVICE (sn_chol.hpp); sol
   dbuf<int32_t> ref_ci;
   dbuf<double> ref_va, pr; // pr: residual block (n x pr_cols)
   int pr_cols = 0;
+  // a value refresh (sn_refresh.hpp) overwrites the panels in place: when it fails they hold no factor, and every solve entry
+  // returns DDM_ENUMERIC until a later refresh succeeds
+  bool invalid = false;
 };
 
 struct Refactor { // what ddm_ilu0_refresh keeps on the device (ilu0_refactor.hpp), allocated by the first refresh
@@ -179,6 +182,7 @@ struct ddm_ilu0 {
   dbuf<double> pD, pX;
   int pm_nrhs = 0;
   double direct_flops = 0.0;
+  int refresh_count = 0; // successful in-place value refreshes since creation (ddm_ilu0_refresh_count)
   // the pipe / box part is built in the background (its own host threads + uploads; 2.6 s at 216^3, nothing of it is needed before
   // the first single-vector solve): every reader of those parts or of `engine` joins first (ilu0_join)
   std::thread builder;

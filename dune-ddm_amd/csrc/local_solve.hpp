@@ -153,6 +153,14 @@ static int ilu0_is_pipe(ddm_ctx *ctx, ddm_ilu0 *F, bool *yes)
   return DDM_OK;
 }
 
+// Both solve entry points start with this: the panels of a device supernodal factor whose last value refresh failed hold no factor
+// (sn_refresh.hpp), and the captured graphs are gone with it.
+static int sn_check_valid(ddm_ctx *ctx, const ddm_ilu0 *F)
+{
+  if (F->sn && F->sn->invalid) return fail(ctx, DDM_ENUMERIC, "sparse direct solver (device): the factor is invalid after a failed refresh");
+  return DDM_OK;
+}
+
 // x = (LU)^-1 d, then optionally x *= scale and x += add (the tail of the Schwarz level: partition of unity of the restricted
 // variant and the coarse correction); the pipe and box engines fold both into their output pass, the others append the two kernels.
 // add_ready (pipe engine only, ilu0_is_pipe): `add` is being written on another stream and is complete when this event fires.  The
@@ -161,6 +169,7 @@ static int ilu0_solve_epilogue(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, doubl
 {
   if (F && F->n == 0) return DDM_OK;
   if (!F || !d || !x || d == x) return fail(ctx, DDM_EINVAL, "ddm_ilu0_solve: bad arguments (d and x must not alias)");
+  DDMCHECK(sn_check_valid(ctx, F));
   if (add_ready) {
     bool pipe_engine = false;
     DDMCHECK(ilu0_is_pipe(ctx, F, &pipe_engine));
@@ -199,6 +208,7 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
 {
   if (!F || !D || !X || D == X || nrhs < 1 || ldd < nrhs || ldx < nrhs) return fail(ctx, DDM_EINVAL, "ddm_ilu0_solve_multi: bad arguments");
   if (F->n == 0) return DDM_OK;
+  DDMCHECK(sn_check_valid(ctx, F));
   // single precision only for plain ILU(0) factors on aligned blocks of a multiple of 4 columns without wide levels
   f32 = f32 && F->lev && nrhs % 4 == 0 && ldd % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)D & 31) == 0 && ((uintptr_t)X & 31) == 0;
   if (f32)

@@ -484,6 +484,7 @@ static int sn_direct_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, con
   F->nnz = S->entries + S->uentries;
   F->direct_flops = (lu ? 2.0 : 1.0) * S->flops;
   F->engine = Engine::Supernodal;
+  F->A = A; // (not owned, as for ILU(0) factors: read again by a value refresh only, sn_refresh.hpp)
   F->sn = std::make_unique<SnDirect>();
   F->sn->f.reset(S);
   int rc = ilu0_alloc_status(ctx, F);

@@ -75,6 +75,7 @@ struct Factor {
   dbuf<int64_t> d_chain_offs;
   dbuf<double> d_chain_w, d_chain_e, d_chain_v, d_chain_u; // inverse triangles / blocks of the external rows (L; L U: also U^T)
   bool chains_ready = false;
+  double chain_setup_s = 0.0;    // host seconds of the last chain_setup (temporaries, kernels, synchronisation): diagnostics
   dbuf<int64_t> d_tptr, d_tmid;  // transposed row lists (Meta::tptr / tmid / tidx)
   dbuf<int32_t> d_tidx, d_tpos;
   dbuf<double> d_contrib; // slots of the forward sweep: one per entry of `rows` and right-hand side
@@ -721,7 +722,9 @@ static inline hipError_t factorize(Factor &F, hipStream_t st, const int64_t *d_r
   e = hipMemcpy(words, F.d_err, 16, hipMemcpyDeviceToHost);
   *bad = words[0];
   if (perturbed) *perturbed = words[2];
+  const auto t0 = std::chrono::steady_clock::now();
   if (e == hipSuccess && words[0] == 0) e = chain_setup(F, st); // the dense inverses of the top chains (single-vector solves)
+  F.chain_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return e;
 }
 

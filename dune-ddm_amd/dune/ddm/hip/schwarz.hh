@@ -116,8 +116,11 @@ public:
     dx->download(x);
   }
   // The overlapping matrix holds new values in its old pattern (a Newton step): re-read them and refactorise on the device, keeping
-  // the schedules (ddm_schwarz_refresh).  A local solver the library does not refresh in place (the direct solvers, the box engine:
-  // DDM_ENOTIMPL) is dropped and built again on first use, as after construction; the adaptor object stays the same.
+  // the schedules (ddm_schwarz_refresh): ILU(0), and the device supernodal factor of the direct solvers (cholmod / umfpack on the
+  // device engine), whose ordering, analysis and solve plans are kept -- S stays, ddm_ilu0_refresh_count on its local solver counts.
+  // A local solver the library does not refresh in place (the host-engine direct factor, the box engine, a device direct factor
+  // whose new values belong to the host engine: DDM_ENOTIMPL) is dropped and built again on first use, as after construction; the
+  // adaptor object stays the same.  Any other failure throws; a device direct factor is then invalid until a refresh succeeds.
   void refresh()
   {
     dA->set_values(*Aovlp);

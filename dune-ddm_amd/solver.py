@@ -218,9 +218,10 @@ class TwoLevelSchwarz:
         """New matrix values in the patterns the object was built on (a Newton step, a time step with a changing coefficient):
         A_values / A_dir_values are the ``data`` arrays of the rank-local A and A_dir in CSR order with sorted column indices.  The
         decomposition, the halo plans, the schedules of the local solver and the coarse basis are kept; refreshed are the two matrices,
-        the operator's storage, the ILU(0) factor (on the device: SchwarzPreconditioner.refresh), R A R^T with the existing basis and
-        its inverse.  A local solver that cannot be refreshed in place (direct solvers, the box engine: DDM_ENOTIMPL) is built anew,
-        that level only.  The result is bit for bit what a new TwoLevelSchwarz on the new matrices with ``coarse=host_basis()`` gives.
+        the operator's storage, the local factor -- ILU(0) or the device supernodal direct factor -- on the device
+        (SchwarzPreconditioner.refresh: ``schwarz`` stays the same object, schwarz.refresh_count() counts), R A R^T with the existing
+        basis and its inverse.  A local solver that cannot be refreshed in place (the host-engine direct factor, the box engine, a
+        device direct factor whose new values belong to the host engine: DDM_ENOTIMPL) is built anew, that level only.  The result is bit for bit what a new TwoLevelSchwarz on the new matrices with ``coarse=host_basis()`` gives.
         A caller who wants a new GenEO basis calls set_coarse_basis afterwards.  The phases add to setup_times under "refresh: ..."."""
         va, vd = np.ascontiguousarray(A_values, dtype=np.float64), np.ascontiguousarray(A_dir_values, dtype=np.float64)
         if va.shape != (self.A.nnz,) or vd.shape != (self.A_dir.nnz,):       # (before anything is touched)

@@ -156,10 +156,20 @@ void ddm_ilu0_destroy(ddm_ilu0 *F);
  * layouts.  Same pattern, same blocks, same schedules.  Afterwards every solve and ddm_ilu0_get_factors_host give bit for bit what
  * a factor created on the new values gives.  The level and pipe engines are rewritten in place (their buffers keep their addresses,
  * so solves captured before the refresh stay valid); a built xcd2 part is dropped and rebuilt by the next solve.
- * DDM_ENOTIMPL (nothing touched) for a sparse direct factor and for the box engine: create a new factor.
+ * DDM_ENOTIMPL (nothing touched) for the HOST-engine sparse direct factor and for the box engine: create a new factor.
  * DDM_ENUMERIC for a zero or non-finite pivot (the message names the block, as at creation): the factor still is the previous one.
- * Synchronous. */
+ * A DEVICE supernodal direct factor (ddm_ilu0_engine == 16) is refreshed too: the numeric factorisation runs again on the kept
+ * supernodes, colours and solve plans, the refinement steps are decided again by the probe of the creation; its captured solves are
+ * dropped and captured again by the next solve.  Its panels are overwritten in place, so a failure leaves NO factor: the object is
+ * invalid and every solve through it (ddm_ilu0_solve*, the Schwarz applies) returns DDM_ENUMERIC ("the factor is invalid after a
+ * failed refresh") until a later refresh succeeds.  Return codes as a creation on the same values: DDM_ENUMERIC where it fails (not
+ * positive definite; with DDM_DIRECT_ENGINE=device also a vanishing pivot column or a probe above 1e-9), DDM_ENOTIMPL ("create a new
+ * factor") where an unforced creation hands the matrix to the host engine.  See the sparse direct block below.
+ * Synchronous; not to be called while the context's stream is being captured. */
 int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F);
+/* successful in-place refreshes of F since its creation, for every kind of factor: 0 after creation, unchanged by a failed or
+ * refused ddm_ilu0_refresh -- tells "refreshed" from "built anew".  NULL: 0. */
+int ddm_ilu0_refresh_count(const ddm_ilu0 *F);
 /* x = (LU)^-1 d ; d and x must not alias */
 int ddm_ilu0_solve(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x);
 /* X = (LU)^-1 D for row-major n x nrhs block vectors (cf. the reference's multi-RHS triangular
@@ -240,6 +250,10 @@ int ddm_direct_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int
  *           panels do not fit into the free device memory.
  *   host    up-looking factorisation on host threads (L U without pivoting for general = 1), CSR level solves on the device
  *           (bitwise reproducible).
+ * New values in the old pattern (ddm_csr_set_values + ddm_ilu0_refresh / ddm_schwarz_refresh): the DEVICE engine's factor is
+ * refreshed in place -- ordering, analysis, colours, plans and uploads are kept, sn::factorize and the refinement probe run again,
+ * bit for bit a factor created on the new values; the matrix must outlive the factor (it is read again).  No second panel array
+ * is held: a failed refresh leaves the factor INVALID (see ddm_ilu0_refresh).  The HOST engine's factor is refused (DDM_ENOTIMPL).
  * The host half of the device engine alone (no device needed; CPU tests): */
 typedef struct ddm_sn_host ddm_sn_host;
 int ddm_sn_host_create(int64_t n, const int64_t *rowptr, const int32_t *col, int64_t nblocks, const int64_t *block_ptr, ddm_sn_host **out);
@@ -314,8 +328,10 @@ int ddm_schwarz_create(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, cons
 int ddm_schwarz_create_ex(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nblocks, const int64_t *block_ptr, int64_t n_novlp,
                           const int32_t *ext_map_host, const double *pou_host, int type, const char *subdomain_solver,
                           ddm_halo *ovlp_copy, ddm_halo *ovlp_add, ddm_schwarz **out);
-/* the local solver again from A_dir's current values: ddm_ilu0_refresh on it, with its return codes (DDM_ENOTIMPL for a direct
- * local solver and for the box engine: create a new level) */
+/* the local solver again from A_dir's current values: ddm_ilu0_refresh on it, with its return codes.  ILU(0) and the device
+ * supernodal direct factor are refreshed in place; DDM_ENOTIMPL for the host-engine direct factor, for the box engine and for a
+ * device factor whose new values an unforced creation would hand to the host engine: create a new level.  After a failed refresh
+ * of a device direct factor the applies return DDM_ENUMERIC until a refresh succeeds (or the level is created anew). */
 int ddm_schwarz_refresh(ddm_ctx *ctx, ddm_schwarz *S);
 void ddm_schwarz_destroy(ddm_schwarz *S);
 int ddm_schwarz_apply(ddm_ctx *ctx, ddm_schwarz *S, double *x, const double *d); /* :115-149 */
