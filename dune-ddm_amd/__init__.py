@@ -157,6 +157,13 @@ SYMBOLS = {
     "ddm_blockvec_gram": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, _I32, _P]),
     "ddm_blockvec_gram2_sym": (_I32, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "ddm_blockvec_rotate": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64]),
+    "ddm_csr_mm_ld": (_I32, [_P, _P, _I32, _P, _I64, _P, _I64]),
+    "ddm_csr_pair_create": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _PP, _PP]),
+    "ddm_csr_has_row_order": (_I32, [_P]),
+    "ddm_csr_mm2_ld": (_I32, [_P, _P, _P, _I32, _P, _I64, _P, _P, _I64]),
+    "ddm_ilu0_solve_multi_ld": (_I32, [_P, _P, _I32, _P, _I64, _P, _I64, _I32]),
+    "ddm_blockvec_rotate_multi": (_I32, [_P, _I64, _P, _I32, _P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _I32, _I32]),
+    "ddm_geneo_debug_helper": (_I32, [_P, _I32, _I64, _P, _I32, _I32, ctypes.c_uint64, _P, _I64, _P, _I64, _P, _P, _I64]),
     "ddm_dense_sym_eig_host": (_I32, [_I32, _P, _P]),
     "ddm_dense_rayleigh_ritz_host": (_I32, [_I32, _P, _P, _I32, _D, _P, _P]),
     "ddm_combined_create": (_I32, [_P, _I32, _P, _P, _P, _PP]),
@@ -383,10 +390,71 @@ class CsrMatrix:
         assert X.shape == Y.shape and X.is_contiguous() and Y.is_contiguous() and X.shape[0] == self.shape[1]
         self.ctx.check(self.ctx.lib.ddm_csr_mm(self.ctx.h, self.h, int(X.shape[1]), _ptr(X), _ptr(Y)))
 
+    def mm_ld(self, X, Y):
+        """Y = A X for (n, nrhs) device tensors or column slices of wider row-major ones (ddm_csr_mm_ld, for tests)"""
+        _csr_mm_ld(self.ctx, self.h, X, Y)
+
     def __del__(self):
         try:
             if self.h and self.ctx.h:
                 self.ctx.lib.ddm_csr_destroy(self.h)
+        except Exception:
+            pass
+
+
+def _block_ld(*blocks):
+    """(columns, leading dimensions) of 2-d device tensors of one shape whose rows are contiguous (column slices of row-major blocks)"""
+    shape = tuple(blocks[0].shape)
+    for t in blocks:
+        if t.dim() != 2 or tuple(t.shape) != shape or t.stride(1) != 1:
+            raise ValueError("blocks must be (n, m) tensors of one shape with contiguous rows")
+    return int(shape[1]), [int(t.stride(0)) for t in blocks]
+
+
+def _csr_mm_ld(ctx, h, X, Y):
+    m, (ldx, ldy) = _block_ld(X, Y)
+    ctx.check(ctx.lib.ddm_csr_mm_ld(ctx.h, h, m, _ptr(X), ldx, _ptr(Y), ldy))
+
+
+class CsrPair:
+    """Two matrices on one pattern as the GenEO eigensolver makes its pencil (ddm_csr_pair_create, for tests): M gives the pattern
+    and the first values, values2 (nnz, in M's sorted CSR order) the second; block_ptr: the diagonal blocks in which the cache-blocked
+    row order of the block products is looked for (None: natural order)."""
+
+    def __init__(self, ctx: Context, M, values2, block_ptr=None):
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        assert M.has_sorted_indices and M.shape[0] == M.shape[1]
+        self.ctx, self.shape, self.nnz = ctx, M.shape, int(M.nnz)
+        rp, ci, va, vc = _np(M.indptr, np.int64), _np(M.indices, np.int32), _np(M.data, np.float64), _np(values2, np.float64)
+        assert vc.shape == va.shape
+        bp = _np(block_ptr, np.int64) if block_ptr is not None else None
+        self.h, self.h2 = ctypes.c_void_p(), ctypes.c_void_p()
+        ctx.check(ctx.lib.ddm_csr_pair_create(ctx.h, M.shape[0], _hp(rp), _hp(ci), _hp(va), _hp(vc), len(bp) - 1 if bp is not None else 0, _hp(bp),
+                                              ctypes.byref(self.h), ctypes.byref(self.h2)))
+
+    def has_row_order(self):
+        return bool(self.ctx.lib.ddm_csr_has_row_order(self.h))
+
+    def mm_ld(self, X, Y, second=False):
+        """Y = A1 X (second: A2 X) through the single-matrix product"""
+        _csr_mm_ld(self.ctx, self.h2 if second else self.h, X, Y)
+
+    def mm2_ld(self, X, Y1, Y2):
+        """Y1 = A1 X, Y2 = A2 X in one pass (ddm_csr_mm2_ld); Y1 and Y2 share their leading dimension"""
+        m, (ldx, ld1, ld2) = _block_ld(X, Y1, Y2)
+        assert ld1 == ld2
+        self.ctx.check(self.ctx.lib.ddm_csr_mm2_ld(self.ctx.h, self.h, self.h2, m, _ptr(X), ldx, _ptr(Y1), _ptr(Y2), ld1))
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ddm_csr_destroy(self.h2)
+            self.ctx.lib.ddm_csr_destroy(self.h)
+        self.h = self.h2 = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -493,6 +561,12 @@ class Ilu0:
         assert D.shape == X.shape and D.is_contiguous() and X.is_contiguous()
         fn = self.ctx.lib.ddm_ilu0_solve_multi_f32 if single_precision else self.ctx.lib.ddm_ilu0_solve_multi
         self.ctx.check(fn(self.ctx.h, self.h, int(D.shape[1]), _ptr(D), _ptr(X)))
+
+    def solve_multi_ld(self, D, X, single_precision=False):
+        """the same for column slices of wider row-major blocks: leading dimensions D.stride(0), X.stride(0) (ddm_ilu0_solve_multi_ld,
+        for tests)"""
+        m, (ldd, ldx) = _block_ld(D, X)
+        self.ctx.check(self.ctx.lib.ddm_ilu0_solve_multi_ld(self.ctx.h, self.h, m, _ptr(D), ldd, _ptr(X), ldx, int(bool(single_precision))))
 
     def num_levels(self, upper=False):
         return int(self.ctx.lib.ddm_ilu0_num_levels(self.h, int(upper)))
@@ -1226,9 +1300,10 @@ def dia_codes_host(A, threads=0, arrays=True):
 
 
 def blockvec_gram(ctx: Context, sub_ptr, U, V):
-    """per-subdomain U^T V of row-major device tensors (n, pu), (n, pv) -> ndarray (nsub, pu, pv)"""
+    """per-subdomain U^T V of device tensors (n, pu), (n, pv) with contiguous rows (column slices of row-major blocks: the leading
+    dimensions are their row strides; U and V may be the same tensor) -> ndarray (nsub, pu, pv)"""
     bp = _np(sub_ptr, np.int64)
-    assert U.is_contiguous() and V.is_contiguous() and U.shape[0] == V.shape[0] == bp[-1]
+    assert U.dim() == V.dim() == 2 and U.stride(1) == V.stride(1) == 1 and U.shape[0] == V.shape[0] == bp[-1]
     out = np.empty((len(bp) - 1, U.shape[1], V.shape[1]), dtype=np.float64)
     ctx.check(ctx.lib.ddm_blockvec_gram(ctx.h, len(bp) - 1, _hp(bp), _ptr(U), U.stride(0), U.shape[1], _ptr(V), V.stride(0), V.shape[1], _hp(out)))
     return out
@@ -1251,3 +1326,67 @@ def blockvec_rotate(ctx: Context, sub_ptr, U, Y, out, base=None):
     Yh = _np(Y, np.float64)
     ctx.check(ctx.lib.ddm_blockvec_rotate(ctx.h, len(bp) - 1, _hp(bp), _ptr(U), U.stride(0), U.shape[1], _hp(Yh), Yh.shape[2],
                                           _ptr(base) if base is not None else None, base.stride(0) if base is not None else 0, _ptr(out), out.stride(0)))
+
+
+def blockvec_rotate_multi(ctx: Context, sub_ptr, U, Y, out, base=None, gap_from=1 << 30, gap=0):
+    """out[k][rows of s, c(j)] = (base[k][rows of s, j] -) U[k][rows of s] @ Y[s][:, j] for up to three arrays that share Y (lists of
+    device tensors with contiguous rows and one row stride per list); c(j) = j for j < gap_from, j + gap from there on: the rotation
+    as the eigensolver's Rayleigh-Ritz step and its orthogonalisation run it (ddm_blockvec_rotate_multi, for tests)"""
+    bp = _np(sub_ptr, np.int64)
+    Yh = _np(Y, np.float64)
+    narr, p, q = len(U), int(Yh.shape[1]), int(Yh.shape[2])
+    assert 1 <= narr <= 3 and len(out) == narr and (base is None or len(base) == narr) and Yh.shape[0] == len(bp) - 1
+    lds = []
+    for group in (U, out, base):
+        if group is None:
+            lds.append(0)
+            continue
+        assert all(t.dim() == 2 and t.stride(1) == 1 and t.stride(0) == group[0].stride(0) and t.shape[0] == bp[-1] for t in group)
+        lds.append(int(group[0].stride(0)))
+    assert all(t.shape[1] >= p for t in U)
+    arr = ctypes.c_void_p * narr
+    pu, po = arr(*[t.data_ptr() for t in U]), arr(*[t.data_ptr() for t in out])
+    pb = arr(*[t.data_ptr() for t in base]) if base is not None else None
+    ctx.check(ctx.lib.ddm_blockvec_rotate_multi(ctx.h, len(bp) - 1, _hp(bp), narr, pu, lds[0], p, _hp(Yh), q, pb, lds[2], po, lds[1], int(gap_from), int(gap)))
+
+
+def _geneo_helper(ctx, op, sub_ptr, m, out, ldo, a=None, lda=0, b=None, ldb=0, s=None, nev=0, seed=0):
+    bp = _np(sub_ptr, np.int64)
+    ctx.check(ctx.lib.ddm_geneo_debug_helper(ctx.h, op, len(bp) - 1, _hp(bp), int(m), int(nev), int(seed), _ptr(a) if a is not None else None, int(lda),
+                                             _ptr(b) if b is not None else None, int(ldb), _ptr(s) if s is not None else None, _ptr(out), int(ldo)))
+
+
+def geneo_random(ctx: Context, sub_ptr, seed, mask, X):
+    """k_geneo_random as the eigensolver launches it: X[i, j] = uniform[-0.5, 0.5)(seed, i m + j) * mask[i] into the (n, m) view X"""
+    m, (ld,) = _block_ld(X)
+    _geneo_helper(ctx, 0, sub_ptr, m, X, ld, a=mask, seed=seed)
+
+
+def geneo_residual(ctx: Context, sub_ptr, mu, AX, CX, R):
+    """k_geneo_residual: R = CX - mu[sub] .* AX; mu a device tensor (nsub, m), the blocks (n, m) views"""
+    m, (lda, ldc, ldr) = _block_ld(AX, CX, R)
+    assert mu.is_contiguous() and mu.shape[1] == m
+    _geneo_helper(ctx, 1, sub_ptr, m, R, ldr, a=AX, lda=lda, b=CX, ldb=ldc, s=mu)
+
+
+def geneo_copy_cols(ctx: Context, sub_ptr, src, dst):
+    m, (lds_, ldd) = _block_ld(src, dst)
+    _geneo_helper(ctx, 2, sub_ptr, m, dst, ldd, a=src, lda=lds_)
+
+
+def geneo_rowscale(ctx: Context, sub_ptr, w, X):
+    m, (ld,) = _block_ld(X)
+    _geneo_helper(ctx, 3, sub_ptr, m, X, ld, s=w)
+
+
+def geneo_invsqrt_diag(ctx: Context, sub_ptr, G, s):
+    """k_geneo_invsqrt_diag: s[sub, j] = 1 / sqrt(G[sub, j, j]), 0 for diagonals <= 1e-300; G (nsub, m, m), s (nsub, m) contiguous"""
+    assert G.is_contiguous() and s.is_contiguous() and G.shape[1] == G.shape[2] == s.shape[1]
+    _geneo_helper(ctx, 4, sub_ptr, G.shape[1], s, 0, a=G)
+
+
+def geneo_finalize(ctx: Context, sub_ptr, scale, V, basis):
+    """k_geneo_finalize: basis[j, i] = scale[sub(i), j] V[i, j] for j < nev = basis.shape[0]; scale (nsub, m), V an (n, m) view"""
+    m, (ldv,) = _block_ld(V)
+    assert scale.is_contiguous() and scale.shape[1] == m and basis.is_contiguous() and basis.shape[1] == V.shape[0]
+    _geneo_helper(ctx, 5, sub_ptr, m, basis, 0, a=V, lda=ldv, s=scale, nev=basis.shape[0])

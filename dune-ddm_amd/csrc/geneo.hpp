@@ -97,6 +97,35 @@ __global__ void k_geneo_random(int64_t n, int m, int64_t ld, unsigned long long 
   X[i * ld + j] = ((double)(z >> 11) * (1.0 / 9007199254740992.0) - 0.5) * mask[i];
 }
 
+// The launches of the column-wise helper kernels (geneo_kernels.hpp and k_geneo_random above), one function per kernel: GeneoRun and the
+// test exports at the end of this file (ddm_geneo_debug_helper) go through these, so that both run the same grids.
+static unsigned geneo_grid(int64_t threads) { return (unsigned)((threads + 255) / 256); }
+static void launch_geneo_random(ddm_ctx *ctx, int64_t n, int m, int64_t ld, unsigned long long seed, const double *mask, double *X)
+{
+  hipLaunchKernelGGL(k_geneo_random, dim3(geneo_grid(n * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, ld, seed, mask, X);
+}
+static void launch_geneo_residual(ddm_ctx *ctx, int64_t n, int m, const int32_t *sub_of_row, const double *mu, const double *AX, int64_t lda, const double *CX, int64_t ldc,
+                                  double *R, int64_t ldr)
+{
+  hipLaunchKernelGGL(k_geneo_residual, dim3(geneo_grid(n * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, sub_of_row, mu, AX, lda, CX, ldc, R, ldr);
+}
+static void launch_geneo_copy_cols(ddm_ctx *ctx, int64_t n, int m, const double *src, int64_t lds, double *dst, int64_t ldd)
+{
+  hipLaunchKernelGGL(k_geneo_copy_cols, dim3(geneo_grid(n * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, src, lds, dst, ldd);
+}
+static void launch_geneo_rowscale(ddm_ctx *ctx, int64_t n, int m, const double *w, double *X, int64_t ldx)
+{
+  hipLaunchKernelGGL(k_geneo_rowscale, dim3(geneo_grid(n * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, w, X, ldx);
+}
+static void launch_geneo_invsqrt_diag(ddm_ctx *ctx, int64_t nsub, int m, const double *G, double *s)
+{
+  hipLaunchKernelGGL(k_geneo_invsqrt_diag, dim3(geneo_grid(nsub * m)), dim3(256), 0, ctx->stream, (int)nsub, m, G, s);
+}
+static void launch_geneo_finalize(ddm_ctx *ctx, int64_t n, int nev, const int32_t *sub_of_row, const double *scale, int mscale, const double *V, int64_t ldv, double *basis)
+{
+  hipLaunchKernelGGL(k_geneo_finalize, dim3(geneo_grid(n)), dim3(256), 0, ctx->stream, n, nev, sub_of_row, scale, mscale, V, ldv, basis);
+}
+
 // widest block the eigensolver iterates (nev + extra): the dense kernels work in column panels beyond 48 (round 3; the threshold mode
 // of the reference doubles nev up to nev_max, spectra.hh:157-163), the limit is the memory of the six n x 3m blocks
 constexpr int GENEO_MAX_BLOCK = 132;
@@ -366,7 +395,6 @@ struct GeneoRun {
   const int64_t n, nsub;
   const int nev, m, p, q2; // block width m = nev + extra, p = 3 m columns of S = [X | W | P], q2 = 2 m: the fused rotation [X_new | P_new]
   const int64_t ld;
-  const unsigned gnm;
   const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
   double t_pencil = 0.0, t_upload = 0.0, t_direct = 0.0, t_prec = 0.0, t_setup = 0.0; // ends of the setup intervals, seconds after t_begin
   // ORDER OF THE MEMBERS BELOW = reverse order of destruction, on every return path.  The two helper threads are declared last, so
@@ -391,8 +419,7 @@ struct GeneoRun {
   Helper probe_thread, ilu_thread;
 
   GeneoRun(ddm_ctx *c, const GeneoProblem &q, const ddm_geneo_params &par, int nev_)
-      : ctx(c), Q(q), P(par), n(q.A->nrows), nsub(q.nsub), nev(nev_), m(nev_ + std::max(par.extra, 1)), p(3 * m), q2(2 * m), ld(p),
-        gnm((unsigned)((n * (int64_t)m + 255) / 256)), rank_min(p)
+      : ctx(c), Q(q), P(par), n(q.A->nrows), nsub(q.nsub), nev(nev_), m(nev_ + std::max(par.extra, 1)), p(3 * m), q2(2 * m), ld(p), rank_min(p)
   {
   }
   // A~ X and C~ X of the same m-column block in one pass (the two matrices share their pattern: build_pencil_host)
@@ -512,7 +539,7 @@ struct GeneoRun {
   // ---- initial block: random on the free DoFs (the first pass of the loop is then a Rayleigh-Ritz step on span X alone) ----
   int start_block()
   {
-    hipLaunchKernelGGL(k_geneo_random, dim3(gnm), dim3(256), 0, ctx->stream, n, m, ld, 0x5DEECE66Dull + (unsigned long long)P.seed, maskd, S[0]);
+    launch_geneo_random(ctx, n, m, ld, 0x5DEECE66Dull + (unsigned long long)P.seed, maskd, S[0]);
     if (Q.con) DDMCHECK(harmonic_apply(ctx, Q.con, m, S[0], ld, true));
     return apply_AC(S[0], AS[0], CS[0]);
   }
@@ -520,7 +547,7 @@ struct GeneoRun {
   // ---- search directions: R = C X - mu A~ X ; column norms ; W = T R, orthogonalised against X, and its products ----
   int search_directions()
   {
-    hipLaunchKernelGGL(k_geneo_residual, dim3(gnm), dim3(256), 0, ctx->stream, n, m, W.sub_of_row, mud, AS[cur], ld, CS[cur], ld, R, (int64_t)m);
+    launch_geneo_residual(ctx, n, m, W.sub_of_row, mud, AS[cur], ld, CS[cur], ld, R, m);
     if (Q.con) DDMCHECK(harmonic_apply_transposed(ctx, Q.con, m, R, m)); // residual of the constrained problem: P^T r
     DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
     HIPCHECK(ctx, hipMemcpyAsync(h_rr.data(), gmm[0], sizeof(double) * h_rr.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -669,12 +696,12 @@ struct GeneoRun {
   {
     for (int64_t s = 0; s < nsub; ++s)
       for (int j = 0; j < nev; ++j) eig_host[(size_t)s * nev + j] = 1.0 / hmu[(size_t)s * m + j] - P.shift;
-    hipLaunchKernelGGL(k_geneo_copy_cols, dim3(gnm), dim3(256), 0, ctx->stream, n, m, (const double *)S[cur], ld, R, (int64_t)m);
-    if (!P.raw) hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, poud, R, (int64_t)m); // v <- D v
+    launch_geneo_copy_cols(ctx, n, m, S[cur], ld, R, m);
+    if (!P.raw) launch_geneo_rowscale(ctx, n, m, poud, R, m); // v <- D v
     DDMCHECK(W.gram(R, m, m, R, m, m, gmm[0]));
-    hipLaunchKernelGGL(k_geneo_invsqrt_diag, dim3((unsigned)((nsub * m + 255) / 256)), dim3(256), 0, ctx->stream, (int)nsub, m, gmm[0], svec[0]); // 1 / ||D v||_2  (raw: 1 / ||v||_2)
-    hipLaunchKernelGGL(k_geneo_rowscale, dim3(gnm), dim3(256), 0, ctx->stream, n, m, maskd, R, (int64_t)m);      // zero_at_dirichlet
-    hipLaunchKernelGGL(k_geneo_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, nev, W.sub_of_row, svec[0], m, R, (int64_t)m, basis_dev);
+    launch_geneo_invsqrt_diag(ctx, nsub, m, gmm[0], svec[0]); // 1 / ||D v||_2  (raw: 1 / ||v||_2)
+    launch_geneo_rowscale(ctx, n, m, maskd, R, m);            // zero_at_dirichlet
+    launch_geneo_finalize(ctx, n, nev, W.sub_of_row, svec[0], m, R, m, basis_dev);
     HIPCHECK(ctx, hipGetLastError());
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     return DDM_OK;
@@ -871,4 +898,98 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   DDMCHECK(geneo_basis_impl(ctx, Q, &P, n_vectors, basis_host, nconv.data(), eig.data(), info));
   for (size_t k = 0; k < eig.size(); ++k) singular_values_host[k] = 1.0 / std::sqrt(std::max(eig[k], 1e-300)); // mu = sigma^2 = 1 / lambda
   return DDM_OK;
+}
+
+// ---- the device steps of GeneoRun on their own (for tests: tests/test_gpu_geneo_steps.py) -------------------------------------------
+// Each export forwards to the function GeneoRun calls -- csr_mm_ld, csr_adopt + csr_mm2_ld, ilu0_solve_multi_ld, GeneoWork::rotate,
+// the launch_geneo_* functions -- with the caller's pointers and leading dimensions; none repeats a dispatch or a grid computation.
+// Block pointers are DEVICE pointers; nothing synchronises unless said.
+extern "C" int ddm_csr_mm_ld(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double *X, int64_t ldx, double *Y, int64_t ldy)
+{
+  if (!ctx) return DDM_EINVAL;
+  return csr_mm_ld(ctx, A, nrhs, X, ldx, Y, ldy);
+}
+extern "C" int ddm_csr_pair_create(ddm_ctx *ctx, int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, const double *val2, int64_t nblocks,
+                                   const int64_t *block_ptr, ddm_csr **out, ddm_csr **companion)
+{
+  if (!ctx || !rowptr || !out || !companion || n < 1 || n >= (int64_t)1 << 31 || rowptr[0] != 0 || (nblocks > 0 && (!block_ptr || block_ptr[0] != 0 || block_ptr[nblocks] != n)))
+    return fail(ctx, DDM_EINVAL, "ddm_csr_pair_create: bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    if (rowptr[i + 1] < rowptr[i]) return fail(ctx, DDM_EINVAL, "ddm_csr_pair_create: row pointers not monotone at row %lld", (long long)i);
+  const int64_t nnz = rowptr[n];
+  if (nnz > 0 && (!col || !val || !val2)) return fail(ctx, DDM_EINVAL, "ddm_csr_pair_create: bad arguments");
+  for (int64_t k = 0; k < nnz; ++k)
+    if (col[k] < 0 || col[k] >= n) return fail(ctx, DDM_EINVAL, "ddm_csr_pair_create: column index out of range at entry %lld", (long long)k);
+  hvec<int64_t> rp;
+  hvec<int32_t> ci;
+  hvec<double> va, vc;
+  hvec_copy(rp, rowptr, (size_t)n + 1);
+  hvec_copy(ci, col, (size_t)nnz);
+  hvec_copy(va, val, (size_t)nnz);
+  hvec_copy(vc, val2, (size_t)nnz);
+  csr_ptr C, A;
+  A.reset(csr_adopt(ctx, n, std::move(rp), std::move(ci), std::move(va), std::move(vc), out_ptr(C), nblocks, nblocks > 0 ? block_ptr : nullptr));
+  DDMCHECK(csr_wait_upload(ctx, A.get()));
+  *out = A.release();
+  *companion = C.release();
+  return DDM_OK;
+}
+extern "C" int ddm_csr_has_row_order(const ddm_csr *A) { return (A && A->row_order) ? 1 : 0; }
+extern "C" int ddm_csr_mm2_ld(ddm_ctx *ctx, const ddm_csr *A1, const ddm_csr *A2, int nrhs, const double *X, int64_t ldx, double *Y1, double *Y2, int64_t ldy)
+{
+  if (!ctx || !A1 || !A2 || !X || !Y1 || !Y2 || Y1 == Y2) return fail(ctx, DDM_EINVAL, "ddm_csr_mm2_ld: bad arguments");
+  return csr_mm2_ld(ctx, A1, A2, nrhs, X, ldx, Y1, Y2, ldy);
+}
+extern "C" int ddm_ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double *D, int64_t ldd, double *X, int64_t ldx, int f32)
+{
+  if (!ctx) return DDM_EINVAL;
+  return ilu0_solve_multi_ld(ctx, F, nrhs, D, ldd, X, ldx, f32 != 0);
+}
+// Out_k = (Base_k -) U_k Y[sub] for k < narr <= 3 arrays that share Y (nsub matrices p x q, host), output columns >= gap_from written
+// gap columns further right: GeneoWork::rotate with all its arguments.  Base: null, or narr pointers.  Synchronous.
+extern "C" int ddm_blockvec_rotate_multi(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, int narr, const double *const *U, int64_t ldu, int p, const double *Y_host,
+                                         int q, const double *const *Base, int64_t ldb, double *const *Out, int64_t ldo, int gap_from, int gap)
+{
+  if (!ctx || !sub_ptr || !U || !Y_host || !Out || nsub < 1 || narr < 1 || narr > 3 || p < 1 || q < 1 || ldu < p || gap_from < 0 || gap < 0 ||
+      ldo < q + (gap_from < q ? gap : 0) || (Base && ldb < q))
+    return fail(ctx, DDM_EINVAL, "ddm_blockvec_rotate_multi: bad arguments");
+  for (int k = 0; k < narr; ++k)
+    if (!U[k] || !Out[k] || (Base && !Base[k])) return fail(ctx, DDM_EINVAL, "ddm_blockvec_rotate_multi: bad arguments");
+  GeneoWork W;
+  DDMCHECK(W.setup(ctx, nsub, sub_ptr, 1));
+  dbuf<double> Y;
+  DDMCHECK(W.alloc(Y, (size_t)nsub * p * q));
+  DDMCHECK(ddm_memcpy_h2d(ctx, Y, Y_host, (int64_t)sizeof(double) * nsub * p * q));
+  DDMCHECK(W.rotate(narr, U, Out, Base, ldu, p, Y, q, ldo, ldb, gap_from, gap));
+  return ddm_ctx_sync(ctx);
+}
+// One helper kernel of the eigensolver through its launch function.  sub_of_row comes from GeneoWork::setup(.., rows_to_sub = true) on
+// sub_ptr.  n = sub_ptr[nsub]; a, b, s, out are device pointers.  Synchronous.
+//   op 0  k_geneo_random      out[i, j] (ld ldo) = uniform(seed, i m + j) * a[i]                         a: mask (n)
+//   op 1  k_geneo_residual    out[i, j] = b[i, j] - s[sub(i), j] a[i, j]                                  a: A~X (lda), b: C~X (ldb), s: mu (nsub x m)
+//   op 2  k_geneo_copy_cols   out[i, j] = a[i, j]
+//   op 3  k_geneo_rowscale    out[i, j] *= s[i]                                                           s: weights (n)
+//   op 4  k_geneo_invsqrt_diag  out[sub, j] = 1 / sqrt(a[sub, j, j]) or 0                                 a: nsub Gram matrices m x m
+//   op 5  k_geneo_finalize    out[j, i] = s[sub(i), j] a[i, j], j < nev  (out: nev x n)                   s: scales (nsub x m)
+extern "C" int ddm_geneo_debug_helper(ddm_ctx *ctx, int op, int64_t nsub, const int64_t *sub_ptr, int m, int nev, uint64_t seed, const double *a, int64_t lda,
+                                      const double *b, int64_t ldb, const double *s, double *out, int64_t ldo)
+{
+  if (!ctx || !sub_ptr || !out || nsub < 1 || m < 1 || op < 0 || op > 5 || sub_ptr[0] != 0) return fail(ctx, DDM_EINVAL, "ddm_geneo_debug_helper: bad arguments");
+  const bool need_a = op != 3, need_b = op == 1, need_s = op == 1 || op == 3 || op == 5;
+  if ((need_a && !a) || (need_b && !b) || (need_s && !s) || (op <= 3 && ldo < m) || ((op == 1 || op == 2 || op == 5) && lda < m) || (need_b && ldb < m) ||
+      (op == 5 && (nev < 1 || nev > m)))
+    return fail(ctx, DDM_EINVAL, "ddm_geneo_debug_helper: bad arguments");
+  GeneoWork W;
+  DDMCHECK(W.setup(ctx, nsub, sub_ptr, 1, /*rows_to_sub=*/true));
+  const int64_t n = W.n;
+  switch (op) {
+  case 0: launch_geneo_random(ctx, n, m, ldo, (unsigned long long)seed, a, out); break;
+  case 1: launch_geneo_residual(ctx, n, m, W.sub_of_row, s, a, lda, b, ldb, out, ldo); break;
+  case 2: launch_geneo_copy_cols(ctx, n, m, a, lda, out, ldo); break;
+  case 3: launch_geneo_rowscale(ctx, n, m, s, out, ldo); break;
+  case 4: launch_geneo_invsqrt_diag(ctx, nsub, m, a, out); break;
+  default: launch_geneo_finalize(ctx, n, nev, W.sub_of_row, s, m, a, lda, out); break;
+  }
+  HIPCHECK(ctx, hipGetLastError());
+  return ddm_ctx_sync(ctx);
 }

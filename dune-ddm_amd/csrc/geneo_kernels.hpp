@@ -416,15 +416,6 @@ __global__ void k_geneo_residual(int64_t n, int m, const int32_t *__restrict__ s
   const int j = (int)(t - i * m);
   R[i * ldr + j] = CX[i * ldc + j] - mu[(int64_t)sub_of_row[i] * m + j] * AX[i * lda + j];
 }
-// X[:, j] *= s[sub][j]
-__global__ void k_geneo_colscale(int64_t n, int m, const int32_t *__restrict__ sub_of_row, const double *__restrict__ s, double *__restrict__ X, int64_t ldx)
-{
-  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t >= n * m) return;
-  const int64_t i = t / m;
-  const int j = (int)(t - i * m);
-  X[i * ldx + j] *= s[(int64_t)sub_of_row[i] * m + j];
-}
 // s[sub][j] = 1 / sqrt(max(G[sub][j][j], tiny))  from m x m Gram matrices; zero for non-positive diagonals (dropped directions)
 __global__ void k_geneo_invsqrt_diag(int nsub, int m, const double *__restrict__ G, double *__restrict__ s)
 {

@@ -475,6 +475,34 @@ int ddm_blockvec_gram2_sym(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, c
                            double *G1_host, double *G2_host);
 int ddm_blockvec_rotate(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, const double *U, int64_t ldu, int p, const double *Y_host, int q,
                         const double *Base, int64_t ldb, double *Out, int64_t ldo);
+/* The device steps of the block eigensolver on their own (for tests): each forwards to the function the eigensolver calls, with the
+ * caller's DEVICE pointers and leading dimensions, so that blocks can be passed as the eigensolver passes them -- slots of an
+ * n x 3m array S = [X | W | P] with ld = 3m.  Nothing synchronises unless said.
+ *   ddm_csr_mm_ld            Y = A X with leading dimensions (ddm_csr_mm is the case ldx == ldy == nrhs)
+ *   ddm_csr_pair_create      two matrices on ONE pattern the way the eigensolver makes its pencil: host arrays adopted, uploaded by a
+ *                            helper thread (joined before the call returns); nblocks > 0: the cache-blocked row order of the block
+ *                            products is looked for (not when DDM_SPMM_NATURAL_ORDER is set).  *companion holds values only and views
+ *                            the pattern of *out; both are destroyed with ddm_csr_destroy, *companion first.
+ *   ddm_csr_has_row_order    1 when the matrix carries such a row order (its two-matrix products of at most 32 columns then run
+ *                            the cache-blocked kernel)
+ *   ddm_csr_mm2_ld           Y1 = A1 X, Y2 = A2 X in one pass for such a pair
+ *   ddm_ilu0_solve_multi_ld  ddm_ilu0_solve_multi(_f32) with leading dimensions
+ *   ddm_blockvec_rotate_multi  Out_k[rows of s, c(j)] = (Base_k[rows of s, j] -) U_k[rows of s, 0:p) Y_host[s][:, j] for k < narr <= 3 arrays
+ *                            that share Y, j < q, c(j) = j for j < gap_from and j + gap from there on; Base: NULL or narr pointers.
+ *                            Synchronous.
+ *   ddm_geneo_debug_helper   one of the column-wise helper kernels (op 0 .. 5: random start block, residual, column copy, row scaling,
+ *                            inverse square roots of Gram diagonals, finalisation with transpose; the arguments per op are listed at
+ *                            its definition in csrc/geneo.hpp).  Synchronous. */
+int ddm_csr_mm_ld(ddm_ctx *ctx, const ddm_csr *A, int nrhs, const double *X, int64_t ldx, double *Y, int64_t ldy);
+int ddm_csr_pair_create(ddm_ctx *ctx, int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, const double *val2, int64_t nblocks,
+                        const int64_t *block_ptr, ddm_csr **out, ddm_csr **companion);
+int ddm_csr_has_row_order(const ddm_csr *A);
+int ddm_csr_mm2_ld(ddm_ctx *ctx, const ddm_csr *A1, const ddm_csr *A2, int nrhs, const double *X, int64_t ldx, double *Y1, double *Y2, int64_t ldy);
+int ddm_ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double *D, int64_t ldd, double *X, int64_t ldx, int f32);
+int ddm_blockvec_rotate_multi(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr, int narr, const double *const *U, int64_t ldu, int p, const double *Y_host,
+                              int q, const double *const *Base, int64_t ldb, double *const *Out, int64_t ldo, int gap_from, int gap);
+int ddm_geneo_debug_helper(ddm_ctx *ctx, int op, int64_t nsub, const int64_t *sub_ptr, int m, int nev, uint64_t seed, const double *a, int64_t lda,
+                           const double *b, int64_t ldb, const double *s, double *out, int64_t ldo);
 /* host logic of the Rayleigh-Ritz step, exposed for the CPU tests: symmetric eigen-decomposition (V: matrix in, eigenvectors as
  * columns out; w ascending) and the rank-revealing Rayleigh-Ritz of gC y = mu gA y (returns the rank used, < 0 on failure) */
 int ddm_dense_sym_eig_host(int n, double *V, double *w);

@@ -1,7 +1,8 @@
 """-m gpu: the FP64-MFMA contractions of the GenEO block eigensolver (csrc/geneo_kernels.hpp) against an FP64 host reference:
 per-subdomain Gram products U^T V and basis rotations U Y of tall-skinny row-major blocks, for ragged subdomain sizes (not
 multiples of the 4-row MFMA step, the 16-row slab or the 2048-row chunk), widths that are not multiples of the 16-column tile,
-strided views, and asymmetric data (a transposed result must not pass).  Tolerance: 1e-13 relative to sum |a||b| -- the MFMA
+operands that are column slices of wider row-major blocks (the Gram products read U and V with leading dimensions pu + 5 and
+pv + 3, the rotation writes into a block q + 4 wide), and asymmetric data (a transposed result must not pass).  Tolerance: 1e-13 relative to sum |a||b| -- the MFMA
 sums the same FP64 products in a different order."""
 import numpy as np
 import pytest
@@ -20,7 +21,7 @@ def test_gram_matches_fp64_reference(ddm, pu, pv):
     big_u = rng.standard_normal((n, pu + 5))
     big_v = rng.standard_normal((n, pv + 3)) + np.arange(pv + 3)[None, :]      # asymmetric columns
     Ud, Vd = torch.as_tensor(big_u).cuda(), torch.as_tensor(big_v).cuda()
-    for U, V, Uh, Vh in ((Ud[:, :pu].contiguous(), Vd[:, :pv].contiguous(), big_u[:, :pu], big_v[:, :pv]),):
+    for U, V, Uh, Vh in ((Ud[:, :pu], Vd[:, :pv], big_u[:, :pu], big_v[:, :pv]),):                  # strided views: ld = pu + 5, pv + 3
         G = ddm.blockvec_gram(ctx, bp, U, V)
         for s in range(len(sizes)):
             ref = Uh[bp[s]:bp[s + 1]].T @ Vh[bp[s]:bp[s + 1]]
