@@ -149,6 +149,15 @@ SYMBOLS = {
     "ddm_galerkin_debug_chain": (_I32, [_P, _P, _P, _I32, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     "ddm_geneo_params_default": (_I32, [ctypes.POINTER(GeneoParams)]),
     "ddm_geneo_basis": (_I32, [_P, _P, _P, _I64, _P, _P, _P, ctypes.POINTER(GeneoParams), _I64, _P, _P, _P, ctypes.POINTER(GeneoInfo)]),
+    "ddm_geneo_create": (_I32, [_P, _P, _P, _I64, _P, _P, _P, ctypes.POINTER(GeneoParams), _PP]),
+    "ddm_geneo_compute": (_I32, [_P, _P, _I32, _I64, _P, _P, _P, ctypes.POINTER(GeneoInfo)]),
+    "ddm_geneo_refresh": (_I32, [_P, _P]),
+    "ddm_geneo_state": (_I32, [_P, _P]),
+    "ddm_geneo_destroy": (None, [_P]),
+    "ddm_geneo_pencil_host": (_I32, [_I64, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P]),
+    "ddm_geneo_pencil_refresh_host": (_I32, [_I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P]),
+    "ddm_geneo_debug_start_block": (_I32, [_P, _I64, _I32, _I32, ctypes.c_uint64, _P, _P, _P]),
+    "ddm_geneo_debug_pencil": (_I32, [_P, _P, _P, _P, _P, _P, _P]),
     "ddm_msgfem_basis": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, ctypes.POINTER(GeneoParams), _I64, _P, _P, _P, ctypes.POINTER(GeneoInfo)]),
     "ddm_svd_basis": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _D, _I32, _P, _P, ctypes.POINTER(GeneoInfo)]),
     "ddm_harmonic_create": (_I32, [_P, _P, _I64, _P, _I64, _P, _I64, _P, _PP]),
@@ -1390,3 +1399,58 @@ def geneo_finalize(ctx: Context, sub_ptr, scale, V, basis):
     m, (ldv,) = _block_ld(V)
     assert scale.is_contiguous() and scale.shape[1] == m and basis.is_contiguous() and basis.shape[1] == V.shape[0]
     _geneo_helper(ctx, 5, sub_ptr, m, basis, 0, a=V, lda=ldv, s=scale, nev=basis.shape[0])
+
+
+def geneo_start_block(ctx: Context, seed, mask, kept, S):
+    """k_geneo_start_block as a warm eigensolver run launches it: S (n, 3m) contiguous from the first min(m_kept, m) columns of kept
+    (n, m_kept) contiguous, the generator of geneo_random for the other columns of the X slot, zero W / P slots, zero rows where mask is 0"""
+    assert S.is_contiguous() and kept.is_contiguous() and mask.is_contiguous() and S.shape[1] % 3 == 0
+    assert S.shape[0] == kept.shape[0] == mask.shape[0]
+    ctx.check(ctx.lib.ddm_geneo_debug_start_block(ctx.h, int(S.shape[0]), int(S.shape[1]) // 3, int(kept.shape[1]), int(seed), _ptr(mask), _ptr(kept), _ptr(S)))
+
+
+def _csr_arrays(M):
+    import scipy.sparse as sp
+    M = sp.csr_matrix(M)
+    if not M.has_sorted_indices:
+        M = M.sorted_indices()
+    return _np(M.indptr, np.int64), _np(M.indices, np.int32), _np(M.data, np.float64)
+
+
+def geneo_pencil_host(A, B, pou, dirichlet=None, sigma=1e-3):
+    """(rowptr, col, val_At, val_C, origin): the GenEO pencil A~ = A + sigma C~, C~ = D B D without Dirichlet rows / columns on the union
+    pattern of two scipy CSR matrices, and its origin map (uint32 per entry: low half 1 + offset in A's row, high half 1 + offset in
+    B's row, 0 = absent) -- the eigensolver's host assembly, no device needed"""
+    lib = load_library()
+    arp, aci, ava = _csr_arrays(A)
+    brp, bci, bva = _csr_arrays(B)
+    n = len(arp) - 1
+    cap = max(len(aci) + len(bci), 1)
+    rp, ci = np.empty(n + 1, dtype=np.int64), np.empty(cap, dtype=np.int32)
+    vt, vc, org = np.empty(cap), np.empty(cap), np.empty(cap, dtype=np.uint32)
+    nnz = ctypes.c_int64()
+    pou = _np(pou, np.float64)
+    dm = _np(dirichlet, np.uint8) if dirichlet is not None else None
+    rc = lib.ddm_geneo_pencil_host(n, _hp(arp), _hp(aci), _hp(ava), _hp(brp), _hp(bci), _hp(bva), _hp(pou), _hp(dm) if dm is not None else None, float(sigma),
+                                   _hp(rp), _hp(ci), _hp(vt), _hp(vc), _hp(org), ctypes.byref(nnz))
+    if rc:
+        raise ValueError(f"ddm_geneo_pencil_host: error {rc}")
+    k = nnz.value
+    return rp, ci[:k].copy(), vt[:k].copy(), vc[:k].copy(), org[:k].copy()
+
+
+def geneo_pencil_refresh_host(rowptr, col, origin, A, B, pou, dirichlet=None, sigma=1e-3):
+    """(val_At, val_C) of the pencil from the current values of A and B (same patterns as at assembly) through the origin map"""
+    lib = load_library()
+    arp, _, ava = _csr_arrays(A)
+    brp, _, bva = _csr_arrays(B)
+    rp, ci, org = _np(rowptr, np.int64), _np(col, np.int32), _np(origin, np.uint32)
+    n = len(rp) - 1
+    vt, vc = np.empty(max(len(ci), 1)), np.empty(max(len(ci), 1))
+    pou = _np(pou, np.float64)
+    dm = _np(dirichlet, np.uint8) if dirichlet is not None else None
+    rc = lib.ddm_geneo_pencil_refresh_host(n, _hp(rp), _hp(ci), _hp(org), _hp(arp), _hp(ava), _hp(brp), _hp(bva), _hp(pou), _hp(dm) if dm is not None else None,
+                                           float(sigma), _hp(vt), _hp(vc))
+    if rc:
+        raise ValueError(f"ddm_geneo_pencil_refresh_host: error {rc}")
+    return vt[:len(ci)], vc[:len(ci)]

@@ -51,7 +51,7 @@ using namespace ddm;
 #include "local_solve.hpp"      // the solves: ilu0_enqueue, graph capture, ilu0_solve_epilogue, ilu0_solve_multi_ld, ddm_ilu0_solve*.  Needs tri_*.hpp, engine_*.hpp.
 #include "local_solver.hpp"     // creation: ilu0_create_impl, direct_create_impl, ddm_ilu0_* / ddm_chol_* / ddm_direct_* / ddm_sn_host_*.  Needs local_solve.hpp.
 #include "sn_refresh.hpp"       // value refresh of a device supernodal factor: sn_refresh (behind ddm_ilu0_refresh).  Needs local_solver.hpp.
-#include "geneo.hpp"            // GeneoProblem, GeneoRun, ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, ddm_harmonic (pulls in dense_host.hpp and geneo_blocks.hpp: GeneoWork over geneo_kernels.hpp, ddm_blockvec_*).  Needs csr.hpp, local_solver.hpp.
+#include "geneo.hpp"            // GeneoProblem, GeneoSetup, GeneoRun, ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, ddm_harmonic (pulls in dense_host.hpp, geneo_blocks.hpp: GeneoWork over geneo_kernels.hpp, ddm_blockvec_*, and geneo_solver.hpp: the kept eigensolver ddm_geneo_*).  Needs csr.hpp, local_solver.hpp.
 #include "halo.hpp"             // ddm_halo: single-vector and m-column exchange over one RCCL wire function.  Needs context.hpp.
 #include "krylov_work.hpp"      // KrylovWork: the block Krylov drivers' work blocks, one pool per ddm_combined.  Needs device_buffer.hpp, multi_kernels.hpp.
 #include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp, krylov_work.hpp.

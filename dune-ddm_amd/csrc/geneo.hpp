@@ -24,9 +24,10 @@
 // A~-norm, sqrt(r^T A~^-1 r) / mu  (r = C~ x - mu A~ x, x^T A~ x = 1) -- the quantity Spectra bounds by tol for its B-norm
 // Lanczos residual (HermEigsBase.h:158-175); with ILU(0) the Euclidean relative residual ||r|| / (mu ||A~ x||).
 //
-// In this file: GeneoProblem (what an entry point asks for), GeneoRun (the state of one run at a fixed block width, one method per
-// phase), geneo_run (the loop above, phase by phase), geneo_basis_impl (threshold mode: a fresh run per doubling), the entry points
-// ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis, and before them the harmonic extension the last two iterate with.
+// In this file: GeneoProblem (what an entry point asks for), GeneoSetup (pencil and preconditioner: what outlives a run), GeneoRun (the
+// state of one run at a fixed block width, one method per phase), the entry points ddm_geneo_basis / ddm_msgfem_basis / ddm_svd_basis,
+// and before them the harmonic extension the last two iterate with.  geneo_solver.hpp, included below GeneoRun, has geneo_run (the loop
+// above, phase by phase), the kept object ddm_geneo with its value refresh and warm start, and the threshold mode around the runs.
 #pragma once
 #include <functional>
 
@@ -130,24 +131,41 @@ static void launch_geneo_finalize(ddm_ctx *ctx, int64_t n, int nev, const int32_
 // of the reference doubles nev up to nev_max, spectra.hh:157-163), the limit is the memory of the six n x 3m blocks
 constexpr int GENEO_MAX_BLOCK = 132;
 
-// A~ = A + sigma C~ and C~ = D B D without Dirichlet rows / columns, on the union pattern, as host CSR
-static void build_pencil_host(const ddm_csr *A, const ddm_csr *B, const double *pou, const uint8_t *dir, double sigma, hvec<int64_t> &rpT,
-                              hvec<int32_t> &ciT, hvec<double> &vaT, hvec<double> &vaC)
+// A~ = A + sigma C~ and C~ = D B D without Dirichlet rows / columns, on the union pattern, as host CSR.  origin (optional): per pencil
+// entry where it comes from, as geneo_pencil_refresh_host and k_geneo_pencil_refresh read it -- low 16 bits: 1 + the entry's offset
+// inside A's row, high 16 bits: 1 + the offset inside B's row, 0 = absent there.  Returns false when a row of A or B has more
+// entries than 16 bits address (origin is then not filled).
+struct PencilInput {
+  int64_t n;
+  const int64_t *a_rp;
+  const int32_t *a_ci;
+  const double *a_va;
+  const int64_t *b_rp;
+  const int32_t *b_ci;
+  const double *b_va;
+};
+constexpr int64_t GENEO_ORIGIN_MAX_ROW = 65535;
+// (WITH_ORIGIN = false compiles the loops of the one-call entry points without the map's bookkeeping)
+template <bool WITH_ORIGIN>
+static bool build_pencil_host_impl(const PencilInput &M, const double *pou, const uint8_t *dir, double sigma, hvec<int64_t> &rpT, hvec<int32_t> &ciT, hvec<double> &vaT,
+                                   hvec<double> &vaC, hvec<uint32_t> *origin)
 {
-  const int64_t n = A->nrows;
+  const int64_t n = M.n;
   rpT.resize((size_t)n + 1);
   rpT[0] = 0;
   const unsigned hw = host_threads();
   const int nth = (int)std::min<int64_t>(hw, std::max<int64_t>(1, n / 65536));
   std::vector<std::thread> th;
+  std::atomic<bool> origin_fits{true};
   // pass 1: sizes of the merged rows (threads), then the prefix sum
   for (int t = 0; t < nth; ++t)
     th.emplace_back([&, t]() {
       for (int64_t i = n * t / nth; i < n * (t + 1) / nth; ++i) {
-        int64_t a = A->h_rp[i], b = B->h_rp[i], cnt = 0;
-        const int64_t a1 = A->h_rp[i + 1], b1 = B->h_rp[i + 1];
+        int64_t a = M.a_rp[i], b = M.b_rp[i], cnt = 0;
+        const int64_t a1 = M.a_rp[i + 1], b1 = M.b_rp[i + 1];
+        if (WITH_ORIGIN && (a1 - a > GENEO_ORIGIN_MAX_ROW || b1 - b > GENEO_ORIGIN_MAX_ROW)) origin_fits = false;
         while (a < a1 || b < b1) {
-          const int32_t ca = a < a1 ? A->h_ci[a] : INT32_MAX, cb = b < b1 ? B->h_ci[b] : INT32_MAX;
+          const int32_t ca = a < a1 ? M.a_ci[a] : INT32_MAX, cb = b < b1 ? M.b_ci[b] : INT32_MAX;
           a += ca <= cb;
           b += cb <= ca;
           ++cnt;
@@ -161,29 +179,117 @@ static void build_pencil_host(const ddm_csr *A, const ddm_csr *B, const double *
   ciT.resize((size_t)rpT[n]);
   vaT.resize((size_t)rpT[n]);
   vaC.resize((size_t)rpT[n]);
+  uint32_t *const org = WITH_ORIGIN && origin_fits ? (origin->resize((size_t)rpT[n]), origin->data()) : nullptr;
   for (int t = 0; t < nth; ++t)
     th.emplace_back([&, t]() {
       for (int64_t i = n * t / nth; i < n * (t + 1) / nth; ++i) {
-        int64_t a = A->h_rp[i], b = B->h_rp[i], q = rpT[i];
-        const int64_t a1 = A->h_rp[i + 1], b1 = B->h_rp[i + 1];
+        const int64_t a0 = M.a_rp[i], b0 = M.b_rp[i];
+        int64_t a = a0, b = b0, q = rpT[i];
+        const int64_t a1 = M.a_rp[i + 1], b1 = M.b_rp[i + 1];
         const bool di = dir && dir[i];
         while (a < a1 || b < b1) {
-          const int32_t ca = a < a1 ? A->h_ci[a] : INT32_MAX, cb = b < b1 ? B->h_ci[b] : INT32_MAX;
+          const int32_t ca = a < a1 ? M.a_ci[a] : INT32_MAX, cb = b < b1 ? M.b_ci[b] : INT32_MAX;
           const int32_t c = std::min(ca, cb);
           double va = 0.0, vc = 0.0;
-          if (ca == c) va = A->h_va[a++];
+          uint32_t o = 0;
+          if (ca == c) {
+            if (WITH_ORIGIN) o |= (uint32_t)(a - a0 + 1);
+            va = M.a_va[a++];
+          }
           if (cb == c) {
-            vc = (di || (dir && dir[c])) ? 0.0 : B->h_va[b] * pou[i] * pou[c]; // scale_matrix_with_pou (coarse_spaces.hh:74-96)
+            if (WITH_ORIGIN) o |= (uint32_t)(b - b0 + 1) << 16;
+            vc = (di || (dir && dir[c])) ? 0.0 : M.b_va[b] * pou[i] * pou[c]; // scale_matrix_with_pou (coarse_spaces.hh:74-96)
             ++b;
           }
           ciT[(size_t)q] = c;
           vaC[(size_t)q] = vc;
           vaT[(size_t)q] = va + sigma * vc;
+          if (WITH_ORIGIN && org) org[(size_t)q] = o;
           ++q;
         }
       }
     });
   for (auto &t : th) t.join();
+  return origin_fits;
+}
+static bool build_pencil_host(const PencilInput &M, const double *pou, const uint8_t *dir, double sigma, hvec<int64_t> &rpT, hvec<int32_t> &ciT, hvec<double> &vaT,
+                              hvec<double> &vaC, hvec<uint32_t> *origin = nullptr)
+{
+  return origin ? build_pencil_host_impl<true>(M, pou, dir, sigma, rpT, ciT, vaT, vaC, origin) : build_pencil_host_impl<false>(M, pou, dir, sigma, rpT, ciT, vaT, vaC, nullptr);
+}
+static PencilInput pencil_input(const ddm_csr *A, const ddm_csr *B)
+{
+  return PencilInput{A->nrows, A->h_rp.data(), A->h_ci.data(), A->h_va.data(), B->h_rp.data(), B->h_ci.data(), B->h_va.data()};
+}
+// New values of A and / or B through the origin map, in place: the formula and the operation order of build_pencil_host entry by
+// entry.  The device twin is k_geneo_pencil_refresh.
+static void geneo_pencil_refresh_host(int64_t n, const int64_t *rpT, const int32_t *ciT, const uint32_t *origin, const int64_t *a_rp, const double *a_va, const int64_t *b_rp,
+                                      const double *b_va, const double *pou, const uint8_t *dir, double sigma, double *vaT, double *vaC)
+{
+  for (int64_t i = 0; i < n; ++i) {
+    const bool di = dir && dir[i];
+    for (int64_t q = rpT[i]; q < rpT[i + 1]; ++q) {
+      const uint32_t oa = origin[q] & 0xffffu, ob = origin[q] >> 16;
+      const int32_t c = ciT[q];
+      double va = 0.0, vc = 0.0;
+      if (oa) va = a_va[a_rp[i] + oa - 1];
+      if (ob) vc = (di || (dir && dir[c])) ? 0.0 : b_va[b_rp[i] + ob - 1] * pou[i] * pou[c];
+      vaC[q] = vc;
+      vaT[q] = va + sigma * vc;
+    }
+  }
+}
+// One wave per row, the lanes over the row's pencil entries (in rounds of 64).  mask: 0.0 on Dirichlet rows, 1.0 elsewhere.  The two
+// patterns need not be equal and neither needs the diagonal: absent entries (origin half 0) contribute 0.
+constexpr int PENCIL_WAVES = 4;
+__global__ __launch_bounds__(64 * PENCIL_WAVES) void k_geneo_pencil_refresh(int64_t n, const int64_t *__restrict__ rpT, const int32_t *__restrict__ ciT,
+                                                                             const uint32_t *__restrict__ origin, const int64_t *__restrict__ a_rp,
+                                                                             const double *__restrict__ a_va, const int64_t *__restrict__ b_rp,
+                                                                             const double *__restrict__ b_va, const double *__restrict__ pou,
+                                                                             const double *__restrict__ mask, double sigma, double *__restrict__ vaT,
+                                                                             double *__restrict__ vaC)
+{
+  const int64_t i = blockIdx.x * (int64_t)PENCIL_WAVES + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t q1 = rpT[i + 1], a0 = a_rp[i], b0 = b_rp[i];
+  const double pi = pou[i];
+  const bool di = mask[i] == 0.0;
+  for (int64_t q = rpT[i] + lane; q < q1; q += 64) {
+    const uint32_t o = origin[q], oa = o & 0xffffu, ob = o >> 16;
+    const int32_t c = ciT[q];
+    double va = 0.0, vc = 0.0;
+    if (oa) va = a_va[a0 + oa - 1];
+    if (ob) vc = (di || mask[c] == 0.0) ? 0.0 : b_va[b0 + ob - 1] * pi * pou[c];
+    vaC[q] = vc;
+    vaT[q] = va + sigma * vc;
+  }
+}
+// The start block of a warm run at the eigensolver's strides: S is n x 3m (ld = 3m).  Columns [0, mk) of the X slot come from the kept
+// block (n x ldk, its first mk columns), columns [mk, m) from the generator of k_geneo_random at the same entry index i m + j, the W and
+// P slots [m, 3m) are zero; Dirichlet rows (mask 0) are zero.
+__global__ void k_geneo_start_block(int64_t n, int m, int mk, int64_t ldk, unsigned long long seed, const double *__restrict__ mask, const double *__restrict__ kept,
+                                    double *__restrict__ S)
+{
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int p = 3 * m;
+  if (t >= n * p) return;
+  const int64_t i = t / p;
+  const int j = (int)(t - i * p);
+  double v = 0.0;
+  if (j < mk) v = mask[i] == 0.0 ? 0.0 : kept[i * ldk + j];
+  else if (j < m) {
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(i * m + j + 1); // splitmix64 of the entry index, as k_geneo_random
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    v = ((double)(z >> 11) * (1.0 / 9007199254740992.0) - 0.5) * mask[i];
+  }
+  S[t] = v;
+}
+static void launch_geneo_start_block(ddm_ctx *ctx, int64_t n, int m, int mk, int64_t ldk, unsigned long long seed, const double *mask, const double *kept, double *S)
+{
+  hipLaunchKernelGGL(k_geneo_start_block, dim3(geneo_grid(n * 3 * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, mk, ldk, seed, mask, kept, S);
 }
 
 // X = keep .* X - Y  (rows: keep = 0 / 1): tail of the harmonic projection / extension
@@ -378,29 +484,38 @@ struct GeneoProblem {
 
 static double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
-// One run of the block eigensolver at a fixed block width: everything its phases share.  geneo_run calls the phases in order.
-struct GeneoRun {
-  struct Helper { // a helper thread that an early error return cannot leave running
-    std::thread t;
-    void join()
-    {
-      if (t.joinable()) t.join();
-    }
-    ~Helper() { join(); }
-  };
-  static constexpr double tau = 1e-11; // rank tolerance of the Rayleigh-Ritz step
+// Helper thread that an early error return cannot leave running
+struct GeneoHelper {
+  std::thread t;
+  void join()
+  {
+    if (t.joinable()) t.join();
+  }
+  ~GeneoHelper() { join(); }
+};
+
+// What outlives a run of the block eigensolver: the pencil, the chosen preconditioner, the Dirichlet mask and the POU on the device.
+// Built once per problem (geneo_setup_create); every block width of the threshold mode and every later compute of a kept ddm_geneo
+// iterate on it.  refresh_pencil_and_preconditioner (geneo_solver.hpp) gives it new values in place.
+struct GeneoSetup {
   ddm_ctx *const ctx;
-  const GeneoProblem &Q;
-  const ddm_geneo_params &P;
+  const GeneoProblem Q;          // (a copy: the pointers in it are borrowed)
+  const ddm_geneo_params *const P; // borrowed: read again by every compute
   const int64_t n, nsub;
-  const int nev, m, p, q2; // block width m = nev + extra, p = 3 m columns of S = [X | W | P], q2 = 2 m: the fused rotation [X_new | P_new]
-  const int64_t ld;
-  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  const double sigma;            // the shift the pencil was assembled with
+  std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
   double t_pencil = 0.0, t_upload = 0.0, t_direct = 0.0, t_prec = 0.0, t_setup = 0.0; // ends of the setup intervals, seconds after t_begin
+  // a value refresh that builds the preconditioner anew: its intervals count from here, the pencil was not assembled again
+  void restart_clock()
+  {
+    t_begin = std::chrono::steady_clock::now();
+    t_pencil = t_upload = 0.0;
+  }
   // ORDER OF THE MEMBERS BELOW = reverse order of destruction, on every return path.  The two helper threads are declared last, so
   // they are joined first: the probe reads Q.A and writes probe_flops, the ILU(0) build reads At's host arrays and writes T_ilu,
-  // rc_ilu and err_ilu.  Then the buffers go, then the preconditioner(s), then At, whose deleter (ddm_csr_destroy) joins the upload
-  // thread that fills the device arrays of At AND of C -- which is why C is declared before At and outlives it.
+  // rc_ilu and err_ilu.  Then the preconditioner(s) go, then At, whose deleter (ddm_csr_destroy) joins the upload thread that fills
+  // the device arrays of At AND of C -- which is why C is declared before At and outlives it.
+  dbuf<double> maskd, poud; // Dirichlet mask (0 on Dirichlet rows, else 1), POU of the finalisation
   csr_ptr C, At;      // the pencil: C~ (values only, on At's pattern) and A~ = A + sigma C~
   ilu0_ptr T, T_ilu;  // the chosen preconditioner; the speculative ILU(0) until the choice is made
   double probe_flops = 0.0;
@@ -409,38 +524,22 @@ struct GeneoRun {
   int direct = 0; // T is the sparse direct factor of A~
   bool prec_f32 = false;
   int refresh_period = 0, orth_passes = 0;
-  GeneoWork W;
-  dbuf<double> S[2], AS[2], CS[2], R, maskd, poud; // double-buffered [X | W | P] and its products, residual block, Dirichlet mask, POU
-  dbuf<double> gA, gC, gmm[5], svec[2], Yd, mud;
-  std::vector<double> hA, hC, hY, hmu, h_rr, h_rw, h_aa;
-  std::vector<double> dscale; // column scaling of S = [X | W | P] folded into the projected problem
-  int cur = 0, rank_min = 0;
-  double worst = 0.0;
-  Helper probe_thread, ilu_thread;
+  GeneoHelper probe_thread, ilu_thread;
 
-  GeneoRun(ddm_ctx *c, const GeneoProblem &q, const ddm_geneo_params &par, int nev_)
-      : ctx(c), Q(q), P(par), n(q.A->nrows), nsub(q.nsub), nev(nev_), m(nev_ + std::max(par.extra, 1)), p(3 * m), q2(2 * m), ld(p), rank_min(p)
-  {
-  }
-  // A~ X and C~ X of the same m-column block in one pass (the two matrices share their pattern: build_pencil_host)
-  int apply_AC(const double *X, double *YA, double *YC)
-  {
-    if (!Q.op_C) return csr_mm2_ld(ctx, At.get(), C.get(), m, X, ld, YA, YC, ld);
-    DDMCHECK(csr_mm_ld(ctx, At.get(), m, X, ld, YA, ld));
-    return (*Q.op_C)(m, X, ld, YC, ld);
-  }
+  GeneoSetup(ddm_ctx *c, const GeneoProblem &q, const ddm_geneo_params *par) : ctx(c), Q(q), P(par), n(q.A->nrows), nsub(q.nsub), sigma(par->shift) {}
 
   // ---- pencil ----
-  void assemble_pencil()
+  void assemble_pencil(hvec<uint32_t> *origin, bool *origin_fits)
   {
     // "auto": whether the sparse direct factor of A~ is affordable at all is estimated on a helper thread from the first separator of the
     // largest block of A's pattern (the pencil's pattern, or a superset of B's), while the pencil is being assembled
-    if (P.preconditioner == 0 && P.max_direct_flops > 0.0 && nsub > 1 && !std::getenv("DDM_DIRECT_ENGINE"))
+    if (P->preconditioner == 0 && P->max_direct_flops > 0.0 && nsub > 1 && !std::getenv("DDM_DIRECT_ENGINE"))
       probe_thread.t = std::thread([this]() { probe_flops = sn_probe_largest_block(Q.A->h_rp.data(), Q.A->h_ci.data(), nsub, Q.sub_ptr, false); });
     hvec<int64_t> rpT;
     hvec<int32_t> ciT;
     hvec<double> vaT, vaC;
-    build_pencil_host(Q.A, Q.B, Q.pou_pencil ? Q.pou_pencil : Q.pou, Q.dirichlet, P.shift, rpT, ciT, vaT, vaC);
+    const bool fits = build_pencil_host(pencil_input(Q.A, Q.B), Q.pou_pencil ? Q.pou_pencil : Q.pou, Q.dirichlet, sigma, rpT, ciT, vaT, vaC, origin);
+    if (origin_fits) *origin_fits = fits;
     t_pencil = seconds_since(t_begin);
     // the host arrays move into At; its device copy and the values of C~ (same pattern, device only) are uploaded by a helper thread
     // while this one factorises / analyses on the host
@@ -451,10 +550,13 @@ struct GeneoRun {
   // ---- preconditioner ----
   // "auto": the ILU(0) factorisation starts on a helper thread while this one orders and analyses for the sparse direct factor
   // (at the headline size the analysis ends in "too expensive" after 0.9 s and the ILU(0) setup takes 2.3 s); whichever is not
-  // needed is dropped
+  // needed is dropped.  Called again by a value refresh whose factor cannot be refreshed in place: T and T_ilu are empty then.
   int choose_preconditioner()
   {
-    if (P.preconditioner != 2)
+    direct = 0;
+    rc_ilu = DDM_OK;
+    err_ilu.clear();
+    if (P->preconditioner != 2)
       ilu_thread.t = std::thread([this]() {
         (void)hipSetDevice(ctx->device);
         rc_ilu = ilu0_create_impl(ctx, At.get(), nsub, Q.sub_ptr, /*multi_rhs_only=*/true, out_ptr(T_ilu));
@@ -463,14 +565,14 @@ struct GeneoRun {
     int rc_direct = DDM_OK;
     std::string why_not;
     probe_thread.join();
-    if (P.preconditioner == 0 && probe_flops > 4.0 * P.max_direct_flops) { // declined by the early probe: no second analysis
+    if (P->preconditioner == 0 && probe_flops > 4.0 * P->max_direct_flops) { // declined by the early probe: no second analysis
       char buf[256];
       std::snprintf(buf, sizeof buf, "sparse direct solver: the factorisation needs about %.1g flops (estimate from the first separator of the largest block; limit %.3g)",
-                    probe_flops, P.max_direct_flops);
+                    probe_flops, P->max_direct_flops);
       why_not = buf;
       rc_direct = DDM_ENOTIMPL;
-    } else if (P.preconditioner != 1) {
-      rc_direct = direct_create_impl(ctx, At.get(), nsub, Q.sub_ptr, 0, P.preconditioner == 2 ? 0.0 : P.max_direct_flops, /*setup_use=*/true, out_ptr(T));
+    } else if (P->preconditioner != 1) {
+      rc_direct = direct_create_impl(ctx, At.get(), nsub, Q.sub_ptr, 0, P->preconditioner == 2 ? 0.0 : P->max_direct_flops, /*setup_use=*/true, out_ptr(T));
       if (rc_direct == DDM_OK) direct = 1;
       else why_not = last_error_of_this_thread();
     }
@@ -479,8 +581,8 @@ struct GeneoRun {
     if (direct) {
       T_ilu.reset(); // (speculative work, not needed)
     } else {
-      if (P.preconditioner != 1 && (P.preconditioner == 2 || (rc_direct != DDM_ENOTIMPL && rc_direct != DDM_ENUMERIC))) return fail(ctx, rc_direct, "%s", why_not.c_str());
-      if (P.preconditioner != 1 && P.verbose) std::fprintf(stderr, "[ddm geneo] sparse Cholesky not used (%s): ILU(0) preconditioner\n", why_not.c_str());
+      if (P->preconditioner != 1 && (P->preconditioner == 2 || (rc_direct != DDM_ENOTIMPL && rc_direct != DDM_ENUMERIC))) return fail(ctx, rc_direct, "%s", why_not.c_str());
+      if (P->preconditioner != 1 && P->verbose) std::fprintf(stderr, "[ddm geneo] sparse Cholesky not used (%s): ILU(0) preconditioner\n", why_not.c_str());
       if (rc_ilu) return fail(ctx, rc_ilu, "%s", err_ilu.c_str());
       T = std::move(T_ilu);
     }
@@ -495,10 +597,57 @@ struct GeneoRun {
     t_prec = seconds_since(t_begin);
     DDMCHECK(csr_wait_upload(ctx, At.get()));
     t_setup = seconds_since(t_begin);
-    if (P.verbose)
+    if (P->verbose)
       std::fprintf(stderr, "[ddm geneo] setup: pencil %.2f s, sparse direct attempt %.2f s (%s), rest of the ILU(0) setup (helper thread) %.2f s, rest of the matrix upload (helper thread) %.2f s\n",
                    t_pencil, t_direct - t_upload, direct ? "used" : "declined", t_prec - t_direct, t_setup - t_prec);
     return DDM_OK;
+  }
+
+  // ---- Dirichlet mask and POU on the device ----
+  int upload_masks()
+  {
+    std::vector<double> mk((size_t)n);
+    for (int64_t i = 0; i < n; ++i) mk[(size_t)i] = (Q.dirichlet && Q.dirichlet[i]) ? 0.0 : 1.0;
+    DDMCHECK(upload(ctx, mk.data(), n, maskd));
+    return upload(ctx, Q.pou, n, poud);
+  }
+};
+
+// One run of the block eigensolver at a fixed block width on a GeneoSetup: the work space and the loop.  geneo_run calls the phases in order.
+struct GeneoRun {
+  static constexpr double tau = 1e-11; // rank tolerance of the Rayleigh-Ritz step
+  ddm_ctx *const ctx;
+  GeneoSetup &K;
+  const GeneoProblem &Q;
+  const ddm_geneo_params &P;
+  const int64_t n, nsub;
+  const int nev, m, p, q2; // block width m = nev + extra, p = 3 m columns of S = [X | W | P], q2 = 2 m: the fused rotation [X_new | P_new]
+  const int64_t ld;
+  const csr_ptr &C, &At; // the setup's pencil and preconditioner, under the names the phases use
+  const ilu0_ptr &T;
+  const int direct;
+  const bool prec_f32;
+  const int refresh_period, orth_passes;
+  const double *const maskd, *const poud;
+  GeneoWork W;
+  dbuf<double> S[2], AS[2], CS[2], R; // double-buffered [X | W | P] and its products, residual block
+  dbuf<double> gA, gC, gmm[5], svec[2], Yd, mud;
+  std::vector<double> hA, hC, hY, hmu, h_rr, h_rw, h_aa;
+  std::vector<double> dscale; // column scaling of S = [X | W | P] folded into the projected problem
+  int cur = 0, rank_min = 0;
+  double worst = 0.0;
+
+  GeneoRun(GeneoSetup &k, int nev_)
+      : ctx(k.ctx), K(k), Q(k.Q), P(*k.P), n(k.n), nsub(k.nsub), nev(nev_), m(nev_ + std::max(k.P->extra, 1)), p(3 * m), q2(2 * m), ld(p), C(k.C), At(k.At), T(k.T),
+        direct(k.direct), prec_f32(k.prec_f32), refresh_period(k.refresh_period), orth_passes(k.orth_passes), maskd(k.maskd), poud(k.poud), rank_min(p)
+  {
+  }
+  // A~ X and C~ X of the same m-column block in one pass (the two matrices share their pattern: build_pencil_host)
+  int apply_AC(const double *X, double *YA, double *YC)
+  {
+    if (!Q.op_C) return csr_mm2_ld(ctx, At.get(), C.get(), m, X, ld, YA, YC, ld);
+    DDMCHECK(csr_mm_ld(ctx, At.get(), m, X, ld, YA, ld));
+    return (*Q.op_C)(m, X, ld, YC, ld);
   }
 
   // ---- work space ----
@@ -514,14 +663,6 @@ struct GeneoRun {
       HIPCHECK(ctx, hipMemsetAsync(CS[b], 0, sizeof(double) * (size_t)n * p, ctx->stream));
     }
     DDMCHECK(W.alloc(R, (size_t)n * m));
-    DDMCHECK(W.alloc(maskd, (size_t)n));
-    DDMCHECK(W.alloc(poud, (size_t)n));
-    {
-      std::vector<double> mk((size_t)n);
-      for (int64_t i = 0; i < n; ++i) mk[(size_t)i] = (Q.dirichlet && Q.dirichlet[i]) ? 0.0 : 1.0;
-      HIPCHECK(ctx, hipMemcpy(maskd, mk.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-      HIPCHECK(ctx, hipMemcpy(poud, Q.pou, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    }
     DDMCHECK(W.alloc(gA, (size_t)nsub * p * p));
     DDMCHECK(W.alloc(gC, (size_t)nsub * p * p));
     for (int k = 0; k < 5; ++k) DDMCHECK(W.alloc(gmm[k], (size_t)nsub * m * m));
@@ -537,9 +678,13 @@ struct GeneoRun {
   }
 
   // ---- initial block: random on the free DoFs (the first pass of the loop is then a Rayleigh-Ritz step on span X alone) ----
-  int start_block()
+  // kept (optional): an n x ldk block whose first mk columns start the run instead (a warm run: the previous eigenvectors of a slightly
+  // changed pencil); the remaining columns are drawn as in the cold start, the products are computed fresh.
+  int start_block(const double *kept = nullptr, int mk = 0, int64_t ldk = 0)
   {
-    launch_geneo_random(ctx, n, m, ld, 0x5DEECE66Dull + (unsigned long long)P.seed, maskd, S[0]);
+    const unsigned long long seed = 0x5DEECE66Dull + (unsigned long long)P.seed;
+    if (kept && mk > 0) launch_geneo_start_block(ctx, n, m, std::min(mk, m), ldk, seed, maskd, kept, S[0]);
+    else launch_geneo_random(ctx, n, m, ld, seed, maskd, S[0]);
     if (Q.con) DDMCHECK(harmonic_apply(ctx, Q.con, m, S[0], ld, true));
     return apply_AC(S[0], AS[0], CS[0]);
   }
@@ -708,94 +853,16 @@ struct GeneoRun {
   }
 };
 
-// The LOBPCG loop of the head of this file at block width nev + extra: basis_dev is nev x n, eig_host nsub x nev.
-static int geneo_run(ddm_ctx *ctx, const GeneoProblem &Q, const ddm_geneo_params &P, int nev, double *basis_dev, double *eig_host, ddm_geneo_info *info)
-{
-  const int m = nev + std::max(P.extra, 1);
-  if (m > GENEO_MAX_BLOCK) return fail(ctx, DDM_ENOTIMPL, "GenEO: nev + extra = %d exceeds %d vectors per subdomain", m, GENEO_MAX_BLOCK);
-  for (int64_t s = 0; s < Q.nsub; ++s)
-    if (Q.sub_ptr[s + 1] - Q.sub_ptr[s] < 3 * (int64_t)m) return fail(ctx, DDM_EINVAL, "GenEO: subdomain %lld has fewer than 3 (nev + extra) = %d rows", (long long)s, 3 * m);
-  GeneoRun G(ctx, Q, P, nev);
-  G.assemble_pencil();
-  DDMCHECK(G.choose_preconditioner());
-  DDMCHECK(G.allocate());
-  DDMCHECK(G.start_block());
-  int it = 0, converged = 0;
-  const auto t_iter = std::chrono::steady_clock::now();
-  for (it = 0; it <= P.maxit; ++it) {
-    if (it > 0) DDMCHECK(G.search_directions());
-    DDMCHECK(G.projected_problem());
-    if (it > 0) {
-      if (G.residual_test(it)) {
-        converged = 1;
-        break;
-      }
-      if (it == P.maxit) break;
-    }
-    DDMCHECK(G.rayleigh_ritz(/*with_wp=*/it > 0));
-    DDMCHECK(G.rotate_blocks());
-    if (it > 0 && it % G.refresh_period == 0) DDMCHECK(G.refresh());
-  }
-  const double t_loop = seconds_since(t_iter);
-  DDMCHECK(G.output(basis_dev, eig_host));
-  if (info) {
-    info->iterations = it;
-    info->converged = converged;
-    info->used_direct = G.direct;
-    info->worst_residual = G.worst;
-    info->setup_s = G.t_setup;
-    info->iterate_s = t_loop;
-    info->nev = nev;
-    info->direct_flops = G.direct ? ilu0_direct_flops(G.T.get()) : 0.0;
-  }
-  return DDM_OK;
-}
+#include "geneo_solver.hpp"
 
+// One path for every entry point: an object without origin map, one cold compute, gone.
 static int geneo_basis_impl(ddm_ctx *ctx, const GeneoProblem &Q, const ddm_geneo_params *params, int64_t kmax, double *basis_host, int32_t *nconv, double *eigenvalues_host,
                             ddm_geneo_info *info)
 {
-  const int64_t nsub = Q.nsub;
-  if (!ctx || !Q.A || !Q.B || !Q.sub_ptr || !Q.pou || !params || !basis_host || !nconv || !eigenvalues_host || nsub < 1) return fail(ctx, DDM_EINVAL, "%s: bad arguments", Q.who);
-  if (Q.A->nrows != Q.A->ncols || Q.B->nrows != Q.A->nrows || Q.B->ncols != Q.A->ncols)
-    return fail(ctx, DDM_EINVAL, "The matrix and the partition of unity must have the same size"); // coarse_spaces.hh:323
-  if (Q.sub_ptr[0] != 0 || Q.sub_ptr[nsub] != Q.A->nrows) return fail(ctx, DDM_EINVAL, "sub_ptr does not cover the matrix");
-  const ddm_geneo_params &P = *params;
-  if (P.nev < 1 || P.extra < 1 || !(P.tolerance > 0.0)) return fail(ctx, DDM_EINVAL, "%s: bad eigensolver parameters", Q.who);
-  const int64_t n = Q.A->nrows;
-  int nev = P.nev;
-  // threshold mode of spectra_gevp_op (eigensolvers/spectra.hh:157-163, 186-189): keep the eigenvalues below the threshold (at least
-  // one), double nev until the largest computed one exceeds it or nev >= nev_max
-  for (;;) {
-    if (nev > kmax) return fail(ctx, DDM_EINVAL, "%s: kmax = %lld is smaller than nev = %d", Q.who, (long long)kmax, nev);
-    dbuf<double> basis_dev;
-    HIPCHECK(ctx, basis_dev.alloc(nev * std::max<int64_t>(n, 1)));
-    std::vector<double> eig((size_t)nsub * nev);
-    int rc = geneo_run(ctx, Q, P, nev, basis_dev, eig.data(), info);
-    if (!rc && hipMemcpy(basis_host, basis_dev, sizeof(double) * (size_t)nev * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, DDM_EHIP, "%s: basis download failed", Q.who);
-    if (rc) return rc;
-    bool done = true;
-    if (P.threshold > 0.0) {
-      for (int64_t s = 0; s < nsub; ++s) done = done && eig[(size_t)s * nev + nev - 1] >= P.threshold;
-      // the block eigensolver takes nev + extra <= GENEO_MAX_BLOCK vectors per subdomain: the doubling stops there and the last
-      // converged block is returned (info->nev tells the caller how far it got) instead of failing the whole basis build
-      done = done || nev >= P.nev_max || 2 * nev > kmax || 2 * nev + P.extra > GENEO_MAX_BLOCK;
-    }
-    if (done) {
-      for (int64_t s = 0; s < nsub; ++s) {
-        int cnt = nev;
-        if (P.threshold > 0.0) {
-          cnt = 0;
-          while (cnt < nev - 1 && eig[(size_t)s * nev + cnt] < P.threshold) ++cnt;
-          cnt = std::max(cnt, 1);
-        }
-        nconv[s] = cnt;
-        for (int j = 0; j < nev; ++j) eigenvalues_host[(size_t)s * kmax + j] = eig[(size_t)s * nev + j];
-      }
-      if (info) info->nev = nev;
-      return DDM_OK;
-    }
-    nev *= 2;
-  }
+  if (!basis_host || !nconv || !eigenvalues_host) return fail(ctx, DDM_EINVAL, "%s: bad arguments", Q.who);
+  geneo_ptr G;
+  DDMCHECK(geneo_create_impl(ctx, Q, params, /*want_origin=*/false, out_ptr(G)));
+  return geneo_compute_impl(ctx, G.get(), /*start=*/0, /*keep=*/false, kmax, basis_host, nconv, eigenvalues_host, info);
 }
 
 extern "C" int ddm_geneo_basis(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, int64_t nsub, const int64_t *sub_ptr, const double *pou_host,

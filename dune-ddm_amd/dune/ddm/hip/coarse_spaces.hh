@@ -179,12 +179,15 @@ public:
   void setup_geneo_impl(std::shared_ptr<const Mat> A, std::shared_ptr<const Mat> B, std::shared_ptr<const PartitionOfUnity> pou, const Dune::ParameterTree& eig_ptree)
   {
     if (pou->size() != A->N()) DUNE_THROW(Dune::Exception, "The matrix and the partition of unity must have the same size");   // :323
-    auto ctx = ddm_hip::Context::get();
-    ddm_geneo_params par = ddm_hip::eigensolver_params(eig_ptree);
-    const std::size_t n = A->N();
-    ddm_hip::DeviceCsr dA(ctx, *A);
-    std::unique_ptr<ddm_hip::DeviceCsr> dBown;
-    if (A.get() != B.get()) dBown = std::make_unique<ddm_hip::DeviceCsr>(ctx, *B);
+    geneo_.reset();   // (before the matrices it borrows)
+    ctx_ = ddm_hip::Context::get();
+    par_ = ddm_hip::eigensolver_params(eig_ptree);
+    kept_nev_ = 0;
+    n_ = A->N();
+    const std::size_t n = n_;
+    dA_ = std::make_unique<ddm_hip::DeviceCsr>(ctx_, *A);
+    dB_.reset();
+    if (A.get() != B.get()) dB_ = std::make_unique<ddm_hip::DeviceCsr>(ctx_, *B);
     std::vector<double> w(n);
     for (std::size_t i = 0; i < n; ++i) w[i] = (*pou)[i];
     // rows turned into unit rows by the symmetric Dirichlet elimination: only the diagonal is non-zero, in A and in B
@@ -201,24 +204,74 @@ public:
     };
     for (std::size_t i = 0; i < n; ++i) dir[i] = (unit_row(*A, i, false) && unit_row(*B, i, true)) ? 1 : 0;
     const int64_t sub_ptr[2] = {0, (int64_t)n};
-    const int kmax = par.threshold > 0 ? std::max(par.nev, par.nev_max) : par.nev;
+    // the eigensolver is kept (ddm_geneo): refresh() gives it new values and restarts it from the vectors it has
+    ddm_geneo* g = nullptr;
+    ddm_hip::check(ctx_->handle(),
+                   ddm_geneo_create(ctx_->handle(), dA_->handle(), dB_ ? dB_->handle() : dA_->handle(), 1, sub_ptr, w.data(), dir.data(), &par_, &g), "ddm_geneo_create");
+    geneo_.reset(g);
+    compute(/*start=*/0);
+  }
+
+  // A_neu and B_neu hold new values in the patterns this coarse space was set up on (a Newton step, a time step with a changing
+  // coefficient): the values go to the device (ddm_csr_set_values), pencil and preconditioner of the kept eigensolver follow there
+  // (ddm_geneo_refresh), and the basis is recomputed starting from the eigenvectors of the previous one.  get_basis() and
+  // eigenvalues() then return the new vectors; their number may change in threshold mode.  The Dirichlet rows are those found at
+  // setup.  Throws before anything is changed when a matrix has another size or number of non-zeros.  Pass the same object twice
+  // where B was A at setup.
+  void refresh(const Mat& A_neu, const Mat& B_neu)
+  {
+    if (!geneo_) DUNE_THROW(Dune::InvalidStateException, "GenEOCoarseSpace::refresh: the coarse space has not been set up");
+    const bool same = &A_neu == &B_neu;
+    if (!dB_ && !same) DUNE_THROW(Dune::InvalidStateException, "GenEOCoarseSpace::refresh: B_neu is A_neu in this coarse space; pass the same matrix twice");
+    if (A_neu.N() != n_ || A_neu.M() != n_ || B_neu.N() != n_ || B_neu.M() != n_)
+      DUNE_THROW(Dune::InvalidStateException, "GenEOCoarseSpace::refresh: the matrices have another size than the ones of the setup");
+    if ((int64_t)A_neu.nonzeroes() != ddm_csr_nnz(dA_->handle()) || (int64_t)B_neu.nonzeroes() != ddm_csr_nnz(dB_ ? dB_->handle() : dA_->handle()) || (same && dB_))
+      DUNE_THROW(Dune::InvalidStateException, "GenEOCoarseSpace::refresh: the matrices have another pattern than the ones of the setup");
+    dA_->set_values(A_neu);
+    if (dB_) dB_->set_values(B_neu);
+    ddm_hip::check(ctx_->handle(), ddm_geneo_refresh(ctx_->handle(), geneo_.get()), "ddm_geneo_refresh");
+    compute(/*start=*/1);
+  }
+
+  // {width of the kept block, pencil refreshes, preconditioner refreshed in place, preconditioner built anew} (ddm_geneo_state)
+  std::array<int32_t, 4> state() const
+  {
+    std::array<int32_t, 4> s{};
+    if (geneo_) ddm_geneo_state(geneo_.get(), s.data());
+    return s;
+  }
+
+private:
+  void compute(int start)
+  {
+    const std::size_t n = n_;
+    const ddm_geneo_params& par = par_;
+    // (a warm run begins at the nev of the kept block, whatever nev and extra say now)
+    const int kmax = std::max(par.threshold > 0 ? std::max(par.nev, par.nev_max) : par.nev, start ? kept_nev_ : 0);
     std::vector<double> basis((std::size_t)kmax * n), eig((std::size_t)kmax);
     int32_t nconv = 0;
-    ddm_hip::check(ctx->handle(),
-                   ddm_geneo_basis(ctx->handle(), dA.handle(), dBown ? dBown->handle() : dA.handle(), 1, sub_ptr, w.data(), dir.data(), &par, kmax, basis.data(), &nconv,
-                                   eig.data(), &info_),
-                   "ddm_geneo_basis");
+    ddm_hip::check(ctx_->handle(), ddm_geneo_compute(ctx_->handle(), geneo_.get(), start, kmax, basis.data(), &nconv, eig.data(), &info_), "ddm_geneo_compute");
     if (!info_.converged)   // the reference aborts when Spectra fails (spectra.hh:149-210)
       DUNE_THROW(Dune::Exception, "GenEO eigensolver did not converge in " << info_.iterations << " block iterations (worst residual " << info_.worst_residual << ")");
+    kept_nev_ = info_.nev;
     this->basis_.assign(nconv, Vec(n));
     eigenvalues_.assign(eig.begin(), eig.begin() + nconv);
     for (int j = 0; j < nconv; ++j)
       for (std::size_t i = 0; i < n; ++i) this->basis_[j][i] = basis[(std::size_t)j * n + i];
   }
 
-private:
+  struct GeneoDelete {
+    void operator()(ddm_geneo* g) const { ddm_geneo_destroy(g); }
+  };
   std::vector<double> eigenvalues_;
   ddm_geneo_info info_{};
+  // (declared in this order: the eigensolver goes first, then the matrices it borrows, then the context)
+  std::shared_ptr<ddm_hip::Context> ctx_;
+  ddm_geneo_params par_{};                  // borrowed by the eigensolver, read again by every compute (the object cannot be copied or moved: CoarseSpaceBuilder)
+  int kept_nev_ = 0;                        // nev of the block the eigensolver keeps (info_.nev of the last compute)
+  std::size_t n_ = 0;
+  std::unique_ptr<ddm_hip::DeviceCsr> dA_, dB_;
+  std::unique_ptr<ddm_geneo, GeneoDelete> geneo_;
 };
 
 template <class Vec = Dune::BlockVector<Dune::FieldVector<double, 1>>>

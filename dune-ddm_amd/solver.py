@@ -214,7 +214,7 @@ class TwoLevelSchwarz:
         self.setup_times["coarse matrix R A R^T"] = t1 - t0
         self.setup_times["coarse inverse, basis upload"] = time.perf_counter() - t1
 
-    def update_values(self, A_values, A_dir_values):
+    def update_values(self, A_values, A_dir_values, *, A_neu_values=None, B_neu_values=None, coarse="keep"):
         """New matrix values in the patterns the object was built on (a Newton step, a time step with a changing coefficient):
         A_values / A_dir_values are the ``data`` arrays of the rank-local A and A_dir in CSR order with sorted column indices.  The
         decomposition, the halo plans, the schedules of the local solver and the coarse basis are kept; refreshed are the two matrices,
@@ -222,10 +222,27 @@ class TwoLevelSchwarz:
         (SchwarzPreconditioner.refresh: ``schwarz`` stays the same object, schwarz.refresh_count() counts), R A R^T with the existing
         basis and its inverse.  A local solver that cannot be refreshed in place (the host-engine direct factor, the box engine, a
         device direct factor whose new values belong to the host engine: DDM_ENOTIMPL) is built anew, that level only.  The result is bit for bit what a new TwoLevelSchwarz on the new matrices with ``coarse=host_basis()`` gives.
-        A caller who wants a new GenEO basis calls set_coarse_basis afterwards.  The phases add to setup_times under "refresh: ..."."""
+        coarse="keep" (default) keeps the basis.  coarse="refresh" makes the coarse space follow as well: it needs the kept eigensolver
+        ``self.geneo`` (geneo_basis(..., keep=True)) and A_neu_values (B_neu_values where B_neu is its own matrix), per subdomain as
+        GeneoSolver.update takes them; the eigensolver's pencil and preconditioner are refreshed on the device, the basis is recomputed
+        from the kept eigenvectors and handed to set_coarse_basis (the number of vectors may change in threshold mode).
+        The phases add to setup_times under "refresh: ..."."""
         va, vd = np.ascontiguousarray(A_values, dtype=np.float64), np.ascontiguousarray(A_dir_values, dtype=np.float64)
         if va.shape != (self.A.nnz,) or vd.shape != (self.A_dir.nnz,):       # (before anything is touched)
             raise ValueError(f"update_values: {va.size} and {vd.size} values for patterns of {self.A.nnz} (A) and {self.A_dir.nnz} (A_dir) entries")
+        if coarse not in ("keep", "refresh"):
+            raise ValueError(f"update_values: coarse = {coarse!r} (keep or refresh)")
+        if coarse == "refresh":
+            geneo = getattr(self, "geneo", None)
+            if geneo is None or geneo.h is None:
+                raise ValueError("update_values(coarse='refresh') needs the kept eigensolver: geneo_basis(tl, ..., keep=True)")
+            if A_neu_values is None:
+                raise ValueError("update_values(coarse='refresh') needs A_neu_values")
+            if B_neu_values is not None and geneo.dB is geneo.dA:
+                raise ValueError("update_values: B_neu is A_neu in the kept eigensolver; pass its values as A_neu_values only")
+            geneo._values(A_neu_values, geneo._nnz_A, "A_neu")                # (lengths, before anything is touched)
+            if B_neu_values is not None:
+                geneo._values(B_neu_values, geneo._nnz_B, "B_neu")
         import time
         from . import DDM_ENOTIMPL, DdmError
         t = [time.perf_counter()]
@@ -254,7 +271,15 @@ class TwoLevelSchwarz:
                                                  self._schwarz_args[1], self.h_copy, self.h_add, subdomain_solver=self._schwarz_args[2])
             lap("local solver (created anew)")
             recreated = True
-        if self.galerkin is not None:
+        if coarse == "refresh":
+            self.geneo.update(A_neu_values, B_neu_values)
+            lap("GenEO pencil and preconditioner")
+            basis = self.geneo.compute("kept")
+            lap("GenEO basis from the kept block")
+            self.set_coarse_basis(basis)
+            lap("GenEO coarse matrix, inverse, basis upload")
+            recreated = True                                                  # (a new Galerkin level: the combination is rebuilt)
+        elif self.galerkin is not None:
             kmax = max(self.k_all)
             basis = np.zeros((kmax, self.rl.n))
             for s in self.rl.local:

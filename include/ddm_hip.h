@@ -431,6 +431,48 @@ int ddm_geneo_params_default(ddm_geneo_params *p);
 int ddm_geneo_basis(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, int64_t nsub, const int64_t *sub_ptr, const double *pou_host,
                     const uint8_t *dirichlet_host, const ddm_geneo_params *params, int64_t kmax, double *basis_host, int32_t *nconv,
                     double *eigenvalues_host, ddm_geneo_info *info);
+/* The same eigensolver as an object that outlives one call, for matrices whose values change in an unchanged pattern (a Newton step,
+ * a time step with a changing coefficient).  ddm_geneo_basis is create + compute(0) + destroy.
+ *   create  : assembles the pencil A~ = A_neu + shift C~, C~ = D B_neu D and chooses and builds the preconditioner; nothing else.  The
+ *             object owns the pencil, the preconditioner, the Dirichlet mask and the POU on the device, and a map from every pencil entry
+ *             to its place in A_neu and B_neu (4 bytes per entry).  A_neu, B_neu (which must outlive it, as a factor's matrix must) and
+ *             *params are BORROWED: params is read again by every compute, so nev, nev_max, extra, threshold, tolerance, maxit and seed
+ *             may change between two of them; shift, preconditioner and max_direct_flops are those of the creation.  sub_ptr, pou_host
+ *             and dirichlet_host are copied.
+ *   compute : allocates the work space (six n x 3 (nev + extra) blocks), iterates, writes basis_host / nconv / eigenvalues_host / info
+ *             as ddm_geneo_basis does, frees the work space.  Kept on the device afterwards: the raw block X of the last run
+ *             (n x (nev + extra) doubles, before v <- D v).  start = 0: random start block -- bit for bit ddm_geneo_basis.  start = 1:
+ *             the run begins at nev = max(params->nev, nev of the kept block) from the kept block, further columns drawn as in the cold
+ *             start; a doubling of the threshold mode starts from the block just converged.  Without a kept block start = 1 is start = 0.
+ *             kmax must not be smaller than the nev the run begins at: info->nev of the last compute is the nev of the kept block.
+ *             info->setup_s: the seconds of setup since the last compute -- the creation, or the last successful refresh; 0 for a
+ *             compute that follows another without a refresh.
+ *   refresh : after ddm_csr_set_values on A_neu and / or B_neu: both value arrays of the pencil are recomputed on the device, in place,
+ *             bit for bit what an assembly on the new values gives; the preconditioner is refreshed in place (ILU(0): ddm_ilu0_refresh's
+ *             machinery; device supernodal factor: same plans) or, where that is not possible (host-engine direct factor), chosen and
+ *             built anew by the rules of the creation.  X is kept.  Synchronous, not to be called under stream capture.  A failure
+ *             (DDM_ENUMERIC from the factor, ...) is returned, and compute then answers the same code until a refresh succeeds; that
+ *             refresh builds the preconditioner anew where the failed one left none.  A refusal that touched nothing leaves the
+ *             object as it was: DDM_ENOTIMPL for a row of A_neu or B_neu of more than 65535 entries, DDM_EINVAL for other matrices.
+ *   state   : out = {width of the kept block (0: none), pencil refreshes, preconditioner refreshed in place (count), built anew (count)} */
+typedef struct ddm_geneo ddm_geneo;
+int ddm_geneo_create(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_csr *B_neu, int64_t nsub, const int64_t *sub_ptr, const double *pou_host,
+                     const uint8_t *dirichlet_host, const ddm_geneo_params *params, ddm_geneo **out);
+int ddm_geneo_compute(ddm_ctx *ctx, ddm_geneo *G, int start, int64_t kmax, double *basis_host, int32_t *nconv, double *eigenvalues_host,
+                      ddm_geneo_info *info);
+int ddm_geneo_refresh(ddm_ctx *ctx, ddm_geneo *G);
+int ddm_geneo_state(const ddm_geneo *G, int32_t out[4]);
+void ddm_geneo_destroy(ddm_geneo *G);
+/* Host twins of the pencil assembly and of its value refresh (no device, no context; for tests).  pencil_host: the pencil of (A, B) on
+ * the union pattern and its origin map -- per entry, low 16 bits: 1 + offset inside A's row, high 16 bits: 1 + offset inside B's row,
+ * 0 = absent.  rowptr_out: n + 1; col_out, val_At_out, val_C_out, origin_out: room for nnz(A) + nnz(B) entries, *nnz_out are used.
+ * pencil_refresh_host: val_At / val_C from new a_val / b_val through the map.  dirichlet may be NULL. */
+int ddm_geneo_pencil_host(int64_t n, const int64_t *a_rowptr, const int32_t *a_col, const double *a_val, const int64_t *b_rowptr, const int32_t *b_col,
+                          const double *b_val, const double *pou, const uint8_t *dirichlet, double sigma, int64_t *rowptr_out, int32_t *col_out,
+                          double *val_At_out, double *val_C_out, uint32_t *origin_out, int64_t *nnz_out);
+int ddm_geneo_pencil_refresh_host(int64_t n, const int64_t *rowptr, const int32_t *col, const uint32_t *origin, const int64_t *a_rowptr, const double *a_val,
+                                  const int64_t *b_rowptr, const double *b_val, const double *pou, const uint8_t *dirichlet, double sigma, double *val_At,
+                                  double *val_C);
 /* MsGFEMCoarseSpace(A_neu, A_dir, pou, dirichlet_mask, subdomain_boundary_mask, ptree, taskflow, prefix = "msgfem")
  * (coarse_spaces.hh:663-831; the default coarse space of examples/poisson.ini:36): GenEO's eigenproblem with right-hand side
  * D A_neu D on the interior DoFs, restricted to the a-harmonic functions (A_dir u = 0 in interior rows); Dirichlet DoFs are left
@@ -503,6 +545,12 @@ int ddm_blockvec_rotate_multi(ddm_ctx *ctx, int64_t nsub, const int64_t *sub_ptr
                               int q, const double *const *Base, int64_t ldb, double *const *Out, int64_t ldo, int gap_from, int gap);
 int ddm_geneo_debug_helper(ddm_ctx *ctx, int op, int64_t nsub, const int64_t *sub_ptr, int m, int nev, uint64_t seed, const double *a, int64_t lda,
                            const double *b, int64_t ldb, const double *s, double *out, int64_t ldo);
+/*   ddm_geneo_debug_start_block  the start block of a warm run: S (n x 3m, DEVICE) from the first min(m_kept, m) columns of kept (n x m_kept,
+ *                            DEVICE), the generator of op 0 for the other columns of the X slot, zero W and P slots, zero rows where
+ *                            mask (n, DEVICE) is 0.  Synchronous.
+ *   ddm_geneo_debug_pencil   the pencil a ddm_geneo holds on the device: *nnz always, the arrays (host) where not NULL.  Synchronous. */
+int ddm_geneo_debug_start_block(ddm_ctx *ctx, int64_t n, int m, int m_kept, uint64_t seed, const double *mask, const double *kept, double *S);
+int ddm_geneo_debug_pencil(ddm_ctx *ctx, const ddm_geneo *G, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val_At, double *val_C);
 /* host logic of the Rayleigh-Ritz step, exposed for the CPU tests: symmetric eigen-decomposition (V: matrix in, eigenvectors as
  * columns out; w ascending) and the rank-revealing Rayleigh-Ritz of gC y = mu gA y (returns the rank used, < 0 on failure) */
 int ddm_dense_sym_eig_host(int n, double *V, double *w);
