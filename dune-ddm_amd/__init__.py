@@ -108,6 +108,7 @@ SYMBOLS = {
     "ddm_chol_create": (_I32, [_P, _P, _I64, _P, _D, _PP]),
     "ddm_ilu0_is_direct": (_I32, [_P]),
     "ddm_ilu0_refinement": (_I32, [_P, _P]),
+    "ddm_ilu0_sn_pivots": (_I32, [_P, _P, _P]),
     "ddm_sn_host_create": (_I32, [_I64, _P, _P, _I64, _P, _PP]),
     "ddm_sn_host_destroy": (None, [_P]),
     "ddm_sn_host_sizes": (_I32, [_P, _I64, _P, ctypes.POINTER(ctypes.c_double)]),
@@ -548,6 +549,13 @@ class Ilu0:
         om = np.zeros(5)
         steps = int(self.ctx.lib.ddm_ilu0_refinement(self.h, _hp(om)))
         return steps, om
+
+    def sn_pivots(self):
+        """the row order the pivoting of a device L U factor chose (ddm_ilu0_sn_pivots, for tests): int32[n] in the permuted
+        numbering, entry first[s] + k = the block-local row of supernode s that ended in position k."""
+        out = np.empty(int(self.A.shape[0]), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.ddm_ilu0_sn_pivots(self.ctx.h, self.h, _hp(out)))
+        return out
 
     def refresh(self):
         """refactorises from the current values of the matrix (CsrMatrix.set_values): ddm_ilu0_refresh.  ILU(0): DdmError with code

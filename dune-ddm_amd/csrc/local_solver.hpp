@@ -640,6 +640,14 @@ extern "C" int ddm_ilu0_refinement(const ddm_ilu0 *F, double *omega)
     for (int k = 0; k < 5; ++k) omega[k] = F->sn ? F->sn->refine_omega[k] : 0.0;
   return F->sn ? F->sn->refine_steps : 0;
 }
+// the row order k_sn_lu_diag chose, read-only (tests): out_n[first[s] + k] = block-local row of supernode s that ended in position k
+extern "C" int ddm_ilu0_sn_pivots(ddm_ctx *ctx, const ddm_ilu0 *F, int32_t *out_n)
+{
+  if (!ctx || !F || !out_n || !F->sn || !F->sn->f || !F->sn->f->lu) return fail(ctx, DDM_EINVAL, "ddm_ilu0_sn_pivots: not a device L U factor");
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (F->n > 0) HIPCHECK(ctx, hipMemcpy(out_n, F->sn->f->d_piv, sizeof(int32_t) * (size_t)F->n, hipMemcpyDeviceToHost));
+  return DDM_OK;
+}
 extern "C" int64_t ddm_ilu0_nnz(const ddm_ilu0 *F) { return F ? F->nnz : 0; }
 extern "C" void ddm_ilu0_destroy(ddm_ilu0 *F) { delete F; }
 // 0 = ok, 1 = a wave of the persistent kernel gave up waiting (results invalid); synchronous

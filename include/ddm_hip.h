@@ -227,8 +227,10 @@ int ddm_ilu0_get_factors_host(ddm_ctx *ctx, const ddm_ilu0 *F, double *lu_host);
  * max_flops > 0: analyse first and return DDM_ENOTIMPL without factorising if the factorisation needs more floating-point
  * operations (sum of squared column counts) -- the caller then stays with ILU(0).  DDM_ENUMERIC: not positive definite. */
 int ddm_chol_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, double max_flops, ddm_ilu0 **out);
-/* general != 0: L U without pivoting on the pattern of A + A^T, for non-symmetric matrices whose symmetric part is positive
- * definite (the DG convection-diffusion operator; `type = umfpack`); DDM_ENUMERIC on a vanishing pivot.  general == 0 = ddm_chol_create. */
+/* general != 0: L U on the pattern of A + A^T, for non-symmetric matrices (the DG convection-diffusion operator; `type = umfpack`):
+ * the host engine eliminates WITHOUT pivoting (matrices whose symmetric part is positive definite; DDM_ENUMERIC on a vanishing
+ * pivot), the device engine with threshold partial pivoting inside the diagonal block of a supernode (below).  general == 0 =
+ * ddm_chol_create. */
 int ddm_direct_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, int general, double max_flops, ddm_ilu0 **out);
 /* Engines of ddm_chol_create / ddm_direct_create, environment DDM_DIRECT_ENGINE = device | host.  Default: the device engine when the
  * factorisation needs at least DDM_DIRECT_DEVICE_MIN_FLOPS multiply-adds -- 2e10 for ddm_direct_create / the Schwarz local solver
@@ -267,6 +269,11 @@ int64_t ddm_ilu0_nnz(const ddm_ilu0 *F);   /* stored factor entries (L + D + U) 
 /* iterative refinement of a device factor: returns the steps every solve performs; omega[5] (may be NULL) = backward error of the probe
  * right-hand side after 0, 1, .. steps (0 where not run) */
 int ddm_ilu0_refinement(const ddm_ilu0 *F, double *omega);
+/* read-only, for tests: the row order the threshold pivoting of a DEVICE L U factor chose, copied to the host after a
+ * synchronisation of the context's stream.  out_n[n] in the permuted numbering: entry first[s] + k is the row of the diagonal block
+ * of supernode s (block-local, before pivoting) that ended in position k; the identity where no row was exchanged.  DDM_EINVAL for
+ * any other factor (ILU(0), the host engine, the device Cholesky). */
+int ddm_ilu0_sn_pivots(ddm_ctx *ctx, const ddm_ilu0 *F, int32_t *out_n);
 /* The host part alone (no device needed; used by the CPU tests): va == NULL stops after the symbolic analysis.
  * get: perm[n] (perm[new] = old), and the factor in the storage convention of ddm_ilu0_get_factors_host -- CSR over the
  * PERMUTED indices with pattern L + D + L^T: unit lower factor, inverse pivots on the diagonal, D L^T above. */

@@ -10,8 +10,8 @@ the top levels and their links.  (decide_top_levels also asks the device for a c
 threads; an MI355X gives 512.  The colours of a level are not restated: the host reports none.)  `single_vector_plan` /
 `block_plan` list the kernels a route launches, level by level.
 
-The reference (`Reference`): the factor of P A P^T, P the library's permutation, WITHOUT pivoting on the library's supernodal
-pattern, right-looking in float64 with numpy / scipy.linalg only (dense Cholesky or unpivoted L U of a diagonal block, triangular
+The reference (`Reference`): the factor of P A P^T, P the library's permutation, WITHOUT pivoting (L U: of Q P A P^T, Q the row
+exchanges the device's threshold rule makes inside the diagonal blocks -- none for lu13 / lu17) on the library's supernodal pattern, right-looking in float64 with numpy / scipy.linalg only (dense Cholesky or unpivoted L U of a diagonal block, triangular
 SUBSTITUTION for the rows below -- no inverse is formed); the two sweeps by substitution; the same solve repeated on residuals formed
 in long double (`refined`) until the correction is at rounding level.
 
@@ -22,6 +22,16 @@ sum_{i != j} |a_ij - a_ik a_kj / a_kk| <= sum_{i != j, k} |a_ij| + |a_kj| / |a_k
 column in every trailing matrix, in particular inside every diagonal block of a supernode, so the device's threshold test
 (|a_kk| >= 0.1 max_i |a_ik|, k_sn_lu_diag) never exchanges a row and its factor is the unpivoted L U: the reference's.
 `column_dominance` is asserted on the CPU.
+Row-exchanging L U cases (lx13, lx17, lx21; `_row_exchanging`).  A is built from a permutation Q of rows INSIDE diagonal blocks
+(pairs and 3-cycles) such that Q A is strictly column dominant while the entries Q moves off the diagonal are 100 times smaller
+than their column's largest.  The argument above holds for Q A: the largest entry of every column of every trailing matrix of
+Q A is the diagonal one, so the threshold test restricted to the block picks exactly Q and the device's factor is the unpivoted
+L U of Q A, multipliers below 1, no growth.  `Reference` replays the rule (`threshold_pivots`) and eliminates D[piv] without
+pivoting; the rows of the U panel and the gather of the right-hand side follow the order.  The bound below is then that of the
+system (Q A) x = Q d, unchanged in form and derived as it stands, Q A being column dominant and eliminated without pivoting: row i
+of it is row Q^-1(i) of A x = d, so g and h -- formed from the pivoted Ld, Ud of the units -- are mapped back through the orders
+before they are compared with d - A x.  C keeps its value: w_L and w_U are maxima over the rows of the supernodal pattern, and an
+exchange stays inside one supernode, whose columns share one row list and one dense U panel.
 
 The bound (u = 2^-53; no number in it comes from the code under test).  Let w_L (w_U) be the largest number of entries of a row of
 L (of U) in the supernodal pattern, diagonal included.  Every entry of the factors is a_ij minus at most w_L - 1 products and one
@@ -270,21 +280,69 @@ SOLVE_KERNELS = ("k_sn_fwd1<64>", "k_sn_fwd1<128>", "k_sn_bwd1_diag<64>", "k_sn_
 
 
 # ---- the reference factor ----------------------------------------------------------------------------------------------------------
-def _lu_nopivot(D):
-    """dense L U without pivoting, in place: unit lower L below the diagonal, U on and above it"""
-    for k in range(D.shape[0] - 1):
-        D[k + 1:, k] /= D[k, k]
-        D[k + 1:, k + 1:] -= np.outer(D[k + 1:, k], D[k, k + 1:])
+def _lu_nopivot(D, tiny=0.0):
+    """dense L U without pivoting, in place: unit lower L below the diagonal, U on and above it.  tiny > 0: a pivot that is exactly
+    0.0 when it is reached is replaced by tiny (k_sn_lu_diag's static perturbation of a pivot column that vanishes)"""
+    for k in range(D.shape[0]):
+        if tiny > 0.0 and D[k, k] == 0.0:
+            D[k, k] = tiny
+        if k + 1 < D.shape[0]:
+            D[k + 1:, k] /= D[k, k]
+            D[k + 1:, k + 1:] -= np.outer(D[k + 1:, k], D[k, k + 1:])
     return D
 
 
-class Reference:
-    """P A P^T = L U (general) or L L^T on the supernodal pattern in float64, right-looking, no pivoting.  Per supernode: Ld (nc x nc
-    lower, unit diagonal when general), Ud (nc x nc upper), R = L[rows, s] (nr x nc), V = U[s, rows]^T (nr x nc; R itself for L L^T).
-    skip_update = (s, r): the mutant that leaves row rows(s)[r] out of the update supernode s sends to its ancestors."""
+PIVOT_THRESHOLD = 0.1            # LU_PIVOT_THRESHOLD of sn_chol.hpp (UMFPACK's default)
 
-    def __init__(self, M, S, general, skip_update=None):
+
+def threshold_pivots(D, tiny=0.0):
+    """k_sn_lu_diag's choice of rows, replayed in float64 on the diagonal block D as it stands when its supernode is reached: the
+    diagonal entry is kept when |a_kk| > 0 and |a_kk| >= 0.1 amax, amax the largest modulus in rows k .. nc - 1 of column k;
+    otherwise the FIRST largest entry becomes the pivot and its row is exchanged with row k (whole rows: the multipliers already
+    computed go with them).  A column that vanishes keeps its row (and gets the pivot tiny).
+    Returns (piv, decisions): position k holds the row piv[k] of D; decisions[k] = (|a_kk| / amax, second largest candidate / amax,
+    row exchanged?), NaN ratios for a vanishing column."""
+    a = np.array(D, dtype=np.float64)
+    nc = a.shape[0]
+    piv = np.arange(nc)
+    decisions = []
+    for k in range(nc):
+        col = np.abs(a[k:, k])
+        imax = int(np.argmax(col))                                       # (the first of equal maxima, as the device's `v > amax`)
+        amax, dg = float(col[imax]), float(col[0])
+        p = k if dg > 0.0 and dg >= PIVOT_THRESHOLD * amax else k + imax
+        if not amax > 0.0:
+            a[k, k], p = tiny, k
+            decisions.append((np.nan, np.nan, False))
+        else:
+            second = float(np.partition(col, -2)[-2]) if len(col) > 1 else 0.0
+            decisions.append((dg / amax, second / amax, p != k))
+        if p != k:
+            a[[k, p]] = a[[p, k]]
+            piv[[k, p]] = piv[[p, k]]
+        if k + 1 < nc:
+            a[k + 1:, k] /= a[k, k]
+            a[k + 1:, k + 1:] -= np.outer(a[k + 1:, k], a[k, k + 1:])
+    return piv, decisions
+
+
+class Reference:
+    """P A P^T = L U (general) or L L^T on the supernodal pattern in float64, right-looking.  Per supernode: Ld (nc x nc lower, unit
+    diagonal when general), Ud (nc x nc upper), R = L[rows, s] (nr x nc), V = U[s, rows]^T (nr x nc; R itself for L L^T).
+    general: the rows of every diagonal block are first put into the order `threshold_pivots` chooses on the block as it stands when
+    its supernode is reached (piv[s]: position k holds the block's row piv[s][k]; the identity for the column dominant cases), then
+    the block D[piv] is factorised WITHOUT pivoting, the columns of V_s are taken in that order, and `solve` gathers its right-hand
+    side in that order when the forward sweep reaches s -- nothing is applied to the columns on the left, the device's convention
+    (sn_chol.hpp, "L U variant").  With Q the product of these exchanges the factors are the unpivoted L U of Q P A P^T; the rows of
+    R_s are still named by the rows of P A P^T (`abs_factors` and `unit_blocks` put them where Q sends them).
+    pivoting = False leaves the replay out (every piv[s] the identity: the reference as it was before the exchanges were added).
+    tiny: the pivot a vanishing column of a diagonal block gets.
+    Mutants: skip_update = (s, r) leaves row rows(s)[r] out of the update supernode s sends to its ancestors; unpivoted_panel = s takes
+    the columns of V_s in the order of the matrix."""
+
+    def __init__(self, M, S, general, skip_update=None, pivoting=True, unpivoted_panel=None, tiny=0.0):
         self.S, self.general = S, general
+        self.piv, self.decisions = [], []
         n, first, nc = S.n, S.first, S.nc
         Ap = sp.csc_matrix(sp.csr_matrix(M)[S.perm][:, S.perm])
         At = sp.csc_matrix(Ap.T) if general else None
@@ -296,11 +354,15 @@ class Reference:
             k, rows = int(nc[s]), S.rows_of(s)
             D, A_rs = P[s][:k], P[s][k:]
             if general:
-                D = _lu_nopivot(D.copy())
+                piv, dec = threshold_pivots(D, tiny) if pivoting else (np.arange(k), [])
+                self.piv.append(piv), self.decisions.append(dec)
+                D = _lu_nopivot(D[piv] if pivoting else D.copy(), tiny)
                 Ld, Ud = np.tril(D, -1) + np.eye(k), np.triu(D)
                 R = sla.solve_triangular(Ud, A_rs.T, trans="T", lower=False).T if len(rows) else A_rs
-                Vs = sla.solve_triangular(Ld, V[s].T, lower=True, unit_diagonal=True).T if len(rows) else V[s]
+                Vp = V[s][:, piv] if pivoting and unpivoted_panel != s else V[s]
+                Vs = sla.solve_triangular(Ld, Vp.T, lower=True, unit_diagonal=True).T if len(rows) else V[s]
             else:
+                self.piv.append(np.arange(k)), self.decisions.append([])
                 Ld = np.linalg.cholesky(np.tril(D) + np.tril(D, -1).T)
                 Ud = Ld.T
                 R = sla.solve_triangular(Ld, A_rs.T, lower=True).T if len(rows) else A_rs
@@ -325,33 +387,42 @@ class Reference:
                 if general:
                     V[t][np.ix_(below - nc[t], cols)] -= W[a:b, b:].T
         self._abs = None
+        # Q: position i of the eliminated matrix holds the row src[i] of P A P^T, which stands at pos[src[i]] = i
+        self.src = np.concatenate([first[s] + self.piv[s] for s in range(S.nsn)]).astype(np.int64)
+        self.pos = np.argsort(self.src)
+        self.exchanging = np.array([not np.array_equal(p, np.arange(len(p))) for p in self.piv])
 
-    # sparse |L| and |U| in the permuted numbering
+    # sparse |L| and |U| of Q P A P^T = L U: rows of L in the order of Q, columns of both in the permuted numbering
     def abs_factors(self):
         if self._abs is None:
             S = self.S
-            ri, cj, lv, uv = [], [], [], []
+            ri, rl, cj, lv, uv = [], [], [], [], []
             for s in range(S.nsn):
                 k = int(S.nc[s])
                 col = np.arange(S.first[s], S.first[s + 1])
                 idx = np.concatenate([col, S.rows_of(s)])
                 ri.append(np.tile(idx, k)), cj.append(np.repeat(col, len(idx)))
+                rl.append(np.tile(np.concatenate([col, self.pos[S.rows_of(s)]]), k))
                 lv.append(np.abs(np.vstack([self.Ld[s], self.R[s]])).T.ravel())
                 uv.append(np.abs(np.vstack([self.Ud[s].T, self.V[s]])).T.ravel())
-            ri, cj = np.concatenate(ri), np.concatenate(cj)
-            aL = sp.csr_matrix((np.concatenate(lv), (ri, cj)), shape=(S.n, S.n))
+            ri, rl, cj = np.concatenate(ri), np.concatenate(rl), np.concatenate(cj)
+            aL = sp.csr_matrix((np.concatenate(lv), (rl, cj)), shape=(S.n, S.n))
             aU = sp.csr_matrix((np.concatenate(uv), (cj, ri)), shape=(S.n, S.n))
             self._abs = (aL, aU)
         return self._abs
 
-    def solve(self, d, drop=None, no_pivot=None):
-        """x = A^-1 d (one vector or the columns of a block) by the two substitutions in float64.  Mutants: drop = (s, r, k): the
-        entry R_s[r, k] of L is left out of the forward sweep; no_pivot = (s, k): the division by the pivot of column k of
-        supernode s is left out of the backward sweep."""
+    def solve(self, d, drop=None, no_pivot=None, no_exchange=None, inverse_exchange=None):
+        """x = A^-1 d (one vector or the columns of a block) by the two substitutions in float64; the right-hand side of supernode s
+        is gathered in the order piv[s] when the forward sweep reaches s.  Mutants: drop = (s, r, k): the entry R_s[r, k] of L is
+        left out of the forward sweep; no_pivot = (s, k): the division by the pivot of column k of supernode s is left out of the
+        backward sweep; no_exchange = s: the right-hand side of s is not gathered; inverse_exchange = s: it is gathered in the
+        inverse of the order."""
         S = self.S
         y = np.array(np.asarray(d, dtype=np.float64)[S.perm])
         for s in range(S.nsn):
             a, b = S.first[s], S.first[s + 1]
+            if self.exchanging[s] and no_exchange != s:
+                y[a:b] = y[a:b][np.argsort(self.piv[s]) if inverse_exchange == s else self.piv[s]]
             y[a:b] = sla.solve_triangular(self.Ld[s], y[a:b], lower=True, unit_diagonal=self.general)
             if S.nr[s]:
                 R = self.R[s]
@@ -387,7 +458,7 @@ class Reference:
                 TL[a:b, a:b], TU[a:b, a:b] = self.Ld[s], self.Ud[s]
                 rows = S.rows_of(s)
                 ins = rows < c1                                          # the in-chain part of the rows below
-                TL[rows[ins] - c0, a:b] = self.R[s][ins]
+                TL[self.pos[rows[ins]] - c0, a:b] = self.R[s][ins]     # (a row of a later link stands where that link's order puts it)
                 TU[a:b, rows[ins] - c0] = self.V[s][ins].T
             eye = np.eye(m)
             Li = sla.solve_triangular(TL, eye, lower=True, unit_diagonal=self.general)
@@ -483,6 +554,99 @@ def column_dominance(M):
     return float(np.min((2.0 * dg - np.asarray(abs(M).sum(axis=0)).ravel()) / dg))
 
 
+class Design:
+    """the exchanges a row-exchanging case is built to make: groups = [(supernode, rows of its diagonal block)], a pair (k, p) or a
+    3-cycle (k, p, q) in ascending order; src[i] = the row of P A P^T that the elimination puts into position i"""
+
+    def __init__(self, groups, src):
+        self.groups, self.src = groups, src
+
+    def of(self, s):
+        return [g for t, g in self.groups if t == s]
+
+
+EXCHANGE_KINDS = ("pair", "several", "cycle", "straddle")
+
+
+def _row_exchanging(MB, seed):
+    """Non-symmetric values on the pattern of _column_dominant(MB), built so that the threshold pivoting of k_sn_lu_diag exchanges
+    exactly the rows of `Design` and the factor has no growth.  Two of every three supernodes get groups of rows of their diagonal
+    block, drawn (seeded) among the entries the pattern stores: a pair (k, p), k < p, with a_pk and a_kp stored, or a 3-cycle
+    (k, p, q), k < p < q, with a_pk, a_qp, a_kq stored; by the kind drawn one pair, several disjoint groups (about one per eight
+    columns), a 3-cycle, or a pair on either side of a multiple of 32 (of column 64 in every other supernode of more than 64
+    columns); the pair of the first and the last column wherever the pattern stores it (a few supernodes of 8 columns).  Q sends the rows where the elimination will: pair k <-> p; cycle p -> k, q -> p,
+    k -> q.  Off the diagonal the values are standard normal; the entries Q moves ONTO the diagonal (a_pk, a_kp; a_pk, a_qp, a_kq)
+    are 2 (1 + the sum of the moduli of the other entries of their column), the entries it moves OFF it (a_kk, a_pp; and a_qq) are
+    0.01 x standard normal, every other a_jj is 2 (1 + column sum).  A cycle is made in two exchanges, k <-> p and then p <-> q, and
+    between them row k stands in position p: the second threshold test has a_kp on the diagonal, so a_kp is 0.01 x standard normal
+    too (a standard normal a_kp reaches 0.1 of the 2 (1 + column sum) ~ 44 of a 27-point column, and the diagonal would be kept:
+    seen at 0.102 in lx17 before this was added).  Q A is strictly column dominant, so (module docstring) the
+    largest entry of every column of every trailing matrix of Q A is the diagonal one: the threshold test picks Q and nothing else,
+    and the factor is the unpivoted L U of Q A with multipliers below 1.  Returns (A, block_ptr, Design)."""
+    A0, bp = _column_dominant(MB, seed)
+    S = Symbolic(A0, bp)
+    n = S.n
+    iperm = np.empty(n, dtype=np.int64)
+    iperm[S.perm] = np.arange(n)
+    C = sp.coo_matrix(A0)
+    pi, pj = iperm[C.row], iperm[C.col]
+    rng = np.random.default_rng(seed + 1000)
+    lower = (S.sn_of_col[pi] == S.sn_of_col[pj]) & (pi > pj)
+    by_sn = {}
+    for i, j in zip(pi[lower], pj[lower]):
+        by_sn.setdefault(int(S.sn_of_col[j]), []).append((int(j - S.first[S.sn_of_col[j]]), int(i - S.first[S.sn_of_col[j]])))
+    groups = []
+    for s in range(S.nsn):
+        pairs = sorted(by_sn.get(s, []))
+        if s % 3 == 0 or not pairs:
+            continue
+        nc = int(S.nc[s])
+        adj = {}
+        for k, p in pairs:
+            adj.setdefault(k, set()).add(p), adj.setdefault(p, set()).add(k)
+        order = [pairs[i] for i in rng.permutation(len(pairs))]
+        kind = EXCHANGE_KINDS[int(rng.integers(len(EXCHANGE_KINDS)))]
+        chosen = []
+        if (0, nc - 1) in pairs:                                         # (rare -- a few supernodes of 8 columns: taken wherever it is stored)
+            chosen = [(0, nc - 1)]
+        elif kind == "straddle":
+            at64 = [g for g in order if g[0] < 64 <= g[1]]
+            at32 = [g for g in order if g[0] // 32 != g[1] // 32 and not g[0] < 64 <= g[1]]
+            chosen = (at64 if s % 2 else at32)[:1] or (at32 + at64)[:1]
+        elif kind == "cycle":
+            for k, p in order:
+                q = sorted(t for t in adj[k] & adj[p] if t > p)
+                if q:
+                    chosen = [(k, p, q[int(rng.integers(len(q)))])]
+                    break
+        elif kind == "several":
+            used = set()
+            for g in order:
+                if len(chosen) < max(2, nc // 8) and not used & set(g):
+                    chosen.append(g)
+                    used |= set(g)
+        groups += [(s, g) for g in (chosen or order[:1])]
+    src = np.arange(n)
+    for s, g in groups:
+        f = int(S.first[s])
+        src[[f + r for r in g]] = [f + r for r in g[1:] + g[:1]]       # pair: src[k] = p, src[p] = k; cycle: src[k] = p, src[p] = q, src[q] = k
+    vals = np.array(C.data)
+    moved = src != np.arange(n)
+    off_diag = (pi == pj) & moved[pj]
+    # (a cycle's first exchange puts row k into position p, so the second decision has a_kp on the diagonal: small like a_pp)
+    a_kp = [(int(S.first[s]) + g[0]) * n + int(S.first[s]) + g[1] for s, g in groups if len(g) == 3]
+    off_diag |= np.isin(pi * n + pj, a_kp)
+    vals[off_diag] = 0.01 * rng.standard_normal(int(off_diag.sum()))
+    onto = pi == src[pj]                                                 # the diagonal of Q A
+    assert int(onto.sum()) == n, "the entries Q moves onto the diagonal are stored"
+    vals[onto] = 0.0
+    vals[onto] = 2.0 * (1.0 + np.bincount(pj, weights=np.abs(vals), minlength=n)[pj[onto]])
+    A = sp.csr_matrix((vals, (C.row, C.col)), shape=A0.shape)
+    A.sort_indices()
+    assert A.nnz == A0.nnz and np.array_equal(A.indptr, A0.indptr) and np.array_equal(A.indices, A0.indices)
+    return A, bp, Design(groups, src)
+
+
 # No top levels in the DEFAULT configuration (fewer than four levels of at most 128 supernodes) and bottom levels of all three kinds.
 # Searched among grids of 13 .. 26 points and 2 .. 6 parts per direction: 26 x 26 x 21 in 5 x 5 x 4 (76 176 rows) and
 # 21 x 21 x 13 in 5 x 5 x 3 (38 663) have the property too; 21 x 21 x 9 in 5 x 5 x 2 (23 534) has no top levels but no <64> level either.
@@ -498,7 +662,14 @@ _CASES = {
     "chain1d": (_chain1d, False, WIDTHS_FULL),
     "lu13": (lambda: _column_dominant(_poisson((13, 12, 11), (1, 1, 1)), 29), True, WIDTHS_FULL),
     "lu17": (lambda: _column_dominant(_poisson((17, 16, 15), (2, 2, 2)), 31), True, WIDTHS_SHORT),
+    # rows ARE exchanged, without growth (_row_exchanging): the grids and blocks of lu13, lu17 and -- for supernodes with more than
+    # BWD_SMALL row tiles, which those two do not have -- of one21
+    "lx13": (lambda: _row_exchanging(_poisson((13, 12, 11), (1, 1, 1)), 37), True, WIDTHS_FULL),
+    "lx17": (lambda: _row_exchanging(_poisson((17, 16, 15), (2, 2, 2)), 41), True, WIDTHS_SHORT),
+    "lx21": (lambda: _row_exchanging(_poisson((21, 20, 19), (1, 1, 1)), 43), True, WIDTHS_SHORT),
 }
+EXCHANGING = ("lx13", "lx17", "lx21")
+SAME_PATTERN = {"lx13": "lu13", "lx17": "lu17"}                          # the column dominant case on the same pattern
 NAMES = tuple(_CASES)
 # the matrices of tests/test_gpu_sn_chol.py: (levels, levels in the persistent top kernel, bottom levels small / <64> / <128>, big at the bottom)
 EXISTING = {
@@ -525,11 +696,71 @@ def pivoting_matrix():
     return M, bp
 
 
+# ---- a pivot column that vanishes inside its diagonal block ---------------------------------------------------------------------------
+# (supernode of lu13, column of its diagonal block): a leaf of the tree with rows below.  The multipliers of 1e6 under the replaced pivot
+# take the column dominance from the ancestors' blocks, and most choices make the threshold test exchange rows there, some at ratios
+# near 0.1; with this one the reference keeps every diagonal entry, the closest decision at 0.38 (tests/test_sn_cases_reference.py)
+VANISHING = (6, 0)
+SQRT_EPS = 2.0 ** -26            # sn_direct_create: tiny = sqrt(eps) max |a_ij|
+
+
+def vanishing_column_matrix():
+    """lu13's values with every entry of ONE column set to an explicit 0.0 inside the diagonal block of one supernode (the entries of
+    the column below the block stay, so the matrix stays regular).  The supernode is a leaf, so nothing is added to its block before
+    it is eliminated, and inside the block a column of zeros stays one (a_ij -= a_ik a_kj with a_kj = 0): when the elimination
+    reaches it, k_sn_lu_diag finds amax = 0, writes tiny onto the diagonal and counts it.  Returns (M, block_ptr, tiny)."""
+    c = case("lu13")
+    S = c.S
+    s, j = VANISHING
+    assert S.level[s] == 0 and S.nr[s] > 0 and S.nc[s] >= 2 and j < S.nc[s]
+    iperm = np.empty(c.n, dtype=np.int64)
+    iperm[S.perm] = np.arange(c.n)
+    M = sp.csr_matrix(c.M).copy()
+    pi, pj = iperm[np.repeat(np.arange(c.n), np.diff(M.indptr))], iperm[M.indices]
+    hit = (pj == S.first[s] + j) & (pi >= S.first[s]) & (pi < S.first[s + 1])
+    assert hit.sum() >= 2 and np.all(M.data[hit] != 0.0)
+    M.data[hit] = 0.0
+    return M, c.block_ptr, SQRT_EPS * float(np.abs(M.data).max())
+
+
+def probe_rhs(n):
+    """the right-hand side of the refinement probe (sn_probe_refinement): a 64-bit linear congruential sequence mapped to [-1, 1)"""
+    b, lcg = np.empty(n), 0x9E3779B97F4A7C15
+    for i in range(n):
+        lcg = (lcg * 6364136223846793005 + 1442695040888963407) % 2 ** 64
+        b[i] = float(lcg >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0
+    return b
+
+
+def probe_omega(M, b, x):
+    """the probe's backward error as include/ddm_hip.h states it: max(||b - A x|| / (||A||_inf ||x|| + ||b||), 0.01 max_i |b - A x|_i /
+    (|A| |x| + |b|)_i)"""
+    M = sp.csr_matrix(M)
+    r = b - M @ x
+    den = abs(M) @ np.abs(x) + np.abs(b)
+    comp = float(np.max(np.abs(r)[den > 0] / den[den > 0]))
+    return max(float(np.linalg.norm(r) / (abs(M).sum(axis=1).max() * np.linalg.norm(x) + np.linalg.norm(b))), 1e-2 * comp)
+
+
+def predict_refinement(M, solve, max_steps=3):
+    """(steps, [omega after 0, 1, .. steps]) of the rule of include/ddm_hip.h with `solve` in place of the device's sweeps: stop below
+    1e-14 or when a step does not halve omega, at most 3 steps"""
+    b = probe_rhs(M.shape[0])
+    x = solve(b)
+    om = [probe_omega(M, b, x)]
+    while len(om) - 1 < max_steps:
+        if om[-1] < 1e-14 or (len(om) > 1 and om[-1] > om[-2] / 2.0):
+            break
+        x = x + solve(b - M @ x)
+        om.append(probe_omega(M, b, x))
+    return len(om) - 1, om
+
+
 class Case:
     def __init__(self, name):
         self.name = name
         make, self.general, self.widths = _CASES[name]
-        self.M, self.block_ptr = make()
+        self.M, self.block_ptr, self.design = (tuple(make()) + (None,))[:3]
         self.n, self.nblocks = self.M.shape[0], len(self.block_ptr) - 1
         self.S = Symbolic(self.M, self.block_ptr)
         self.routes = routes_of(self.nblocks)
@@ -559,8 +790,8 @@ class Case:
         with np.errstate(invalid="ignore", over="ignore"):
             ax = np.abs(np.asarray(x, dtype=np.float64))[S.perm]
             aUx = aU @ ax
-            bound = np.empty_like(ax)
-            bound[S.perm] = U64 * (self.C * (aL @ aUx) + 2.0 * (EL @ aUx + aL @ (EU @ ax)))
+            bound = np.empty_like(ax)                                    # row i of Q P A P^T x = Q P d is row perm[src[i]] of A x = d
+            bound[S.perm[self.ref.src]] = U64 * (self.C * (aL @ aUx) + 2.0 * (EL @ aUx + aL @ (EU @ ax)))
         return Evaluated(residual_ld(self.M, d, x), bound)
 
     def refined(self, d, steps=3):
@@ -617,4 +848,16 @@ def mutants(c, seed=5):
         if abs(ref.Ud[s][k, k] - 1.0) > 0.1 and abs(xp[S.first[s] + k]) > 1e-3 * np.abs(xp).max():
             break
     out.append(("pivot not applied", f"column {S.first[s] + k} (pivot {ref.Ud[s][k, k]:.3g}, supernode {s})", ref.solve(c.d, no_pivot=(s, k))))
+    if c.design is None:
+        return out
+    # the consumers of the pivot order: one exchanging supernode; then a supernode with a 3-cycle (where the order and its inverse
+    # differ) and rows below (a U panel)
+    s = int(rng.choice(np.flatnonzero(ref.exchanging)))
+    out.append(("exchange not applied", f"supernode {s} ({S.nc[s]} columns, groups {c.design.of(s)})", ref.solve(c.d, no_exchange=s)))
+    s = int(rng.choice([t for t, g in c.design.groups if len(g) == 3 and S.nr[t] > 0]))
+    out.append(("inverse exchange applied", f"supernode {s} ({S.nc[s]} columns, groups {c.design.of(s)})", ref.solve(c.d, inverse_exchange=s)))
+    out.append(("U panel in unpivoted order", f"supernode {s} ({S.nr[s]} rows below)", Reference(c.M, S, c.general, unpivoted_panel=s).solve(c.d)))
     return out
+
+
+PIVOT_MUTANTS = ("exchange not applied", "inverse exchange applied", "U panel in unpivoted order")

@@ -9,7 +9,9 @@ pair, so the values stay exactly symmetric; then the diagonal raised to 1.05 sum
 handed to a Cholesky factor.
 
 L U cases (`lu_values`): sn_cases._column_dominant with another seed on the case's own matrix -- its pattern is already the
-symmetrised one, so the pattern stays; strictly column dominant, hence no row exchange (sn_cases' module docstring).
+symmetrised one, so the pattern stays; strictly column dominant, hence no row exchange (sn_cases' module docstring).  The
+row-exchanging cases (sn_cases.EXCHANGING) get such values too: their refresh goes from a pivot order that exchanges rows to the
+identity and back.
 
 `pivoting_benign`: standard-normal values off the diagonal of the pattern of sn_cases.pivoting_matrix(), the diagonal 1 + the
 column's sum of moduli: the benign partner of the matrix that needs refinement by design.  `pivoting_like(scale)`: that matrix's
@@ -26,7 +28,7 @@ from tests import sn_cases as sc
 
 CHOLESKY = tuple(n for n in sc.NAMES if not sc._CASES[n][1])
 LU = tuple(n for n in sc.NAMES if sc._CASES[n][1])
-LU_SEED = {"lu13": 129, "lu17": 131}                                     # (sn_cases: 29, 31)
+LU_SEED = {"lu13": 129, "lu17": 131, "lx13": 137, "lx17": 141, "lx21": 143}   # (sn_cases: 29, 31; 37, 41, 43)
 HANDOVER_SCALE = 1e-11                                                  # pivoting_like(HANDOVER_SCALE): see test_gpu_sn_refresh.py, test 5
 
 
