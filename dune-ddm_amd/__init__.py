@@ -104,6 +104,8 @@ SYMBOLS = {
     "ddm_ilu0_num_levels": (_I64, [_P, _I32]),
     "ddm_ilu0_wait": (_I32, [_P, _P]),
     "ddm_ilu0_box_check": (_I32, [_P, _P]),
+    "ddm_ilu0_box_info": (_I32, [_P, _P, ctypes.c_int64, _P]),
+    "ddm_ilu0_solve_tail": (_I32, [_P, _P, _P, _P, _P, _P]),
     "ddm_ilu0_engine": (_I32, [_P]),
     "ddm_chol_create": (_I32, [_P, _P, _I64, _P, _D, _PP]),
     "ddm_ilu0_is_direct": (_I32, [_P]),
@@ -594,6 +596,24 @@ class Ilu0:
         out = np.zeros(1024, dtype=np.uint64)
         self.ctx.lib.ddm_ilu0_box_check(self.h, _hp(out))
         return out.reshape(2, 128, 4)
+
+    def box_info(self):
+        """what the box engine's builder made of the matrix (ddm_ilu0_box_info, for tests): dict with `blocks` = [(nx, ny, nz, steps
+        per plane, rows behind the box)], `grid` = workgroups of a sweep launch, `nested` = settled engine of the factor that solves
+        the rows behind the boxes (None without such rows); no blocks for a factor that is not on the box engine"""
+        cnt = ctypes.c_int64()
+        rc = self.ctx.lib.ddm_ilu0_box_info(self.h, None, 0, ctypes.byref(cnt))
+        out = np.zeros(cnt.value, dtype=np.int64)
+        rc = rc or self.ctx.lib.ddm_ilu0_box_info(self.h, _hp(out), cnt.value, ctypes.byref(cnt))
+        if rc != DDM_OK:
+            raise DdmError(rc, "ddm_ilu0_box_info failed")
+        return {"blocks": [tuple(int(v) for v in out[3 + 5 * b:8 + 5 * b]) for b in range(int(out[0]))], "grid": int(out[1]),
+                "nested": SchwarzPreconditioner.ENGINES[int(out[2])] if out[2] >= 0 else None}
+
+    def solve_tail(self, d, x, scale=None, add=None):
+        """x = ((LU)^-1 d) * scale + add entry by entry; scale / add: device vectors or None (ddm_ilu0_solve_tail)"""
+        self.ctx.check(self.ctx.lib.ddm_ilu0_solve_tail(self.ctx.h, self.h, _ptr(d), _ptr(x), _ptr(scale) if scale is not None else None,
+                                                       _ptr(add) if add is not None else None))
 
     def wait(self):
         """joins the part of the setup that runs in the background (ddm_ilu0_wait)"""

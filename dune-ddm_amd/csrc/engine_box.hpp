@@ -21,6 +21,7 @@ static int build_box_engine(ddm_ctx *ctx, ddm_ilu0 *F)
   X->nshell = (int64_t)S.srow.size();
   X->nprod = (int64_t)S.ext_val.size();
   X->stats = S.stats;
+  X->h_blocks = S.blocks;
   int rc = upload(ctx, S.blocks.data(), (int64_t)S.blocks.size(), X->blocks);
   if (!rc) rc = upload(ctx, S.steps.data(), (int64_t)S.steps.size(), X->steps);
   if (!rc) rc = upload(ctx, S.stream.data(), (int64_t)S.stream.size(), X->stream);
@@ -144,5 +145,29 @@ extern "C" int ddm_ilu0_box_check(const ddm_ilu0 *F, unsigned long long *out1024
 {
   if (!F || !out1024) return DDM_EINVAL;
   for (int k = 0; k < 1024; ++k) out1024[k] = (F->box && F->box->dbg) ? F->box->dbg[k] : 0ull;
+  return DDM_OK;
+}
+
+// read-only (tests): what the builder made of the matrix and how the solve is launched.  out = {blocks, workgroups of a sweep launch,
+// engine code of the nested factor once settled (ddm_ilu0_engine; -1: no rows behind the boxes)}, then per block {nx, ny, nz, steps
+// per plane, rows behind the box}.  *count = 3 + 5 blocks; out may be null to ask for it.  A factor that is not on the box engine
+// reports 0 blocks.
+extern "C" int ddm_ilu0_box_info(const ddm_ilu0 *F, int64_t *out, int64_t capacity, int64_t *count)
+{
+  if (!F || !count) return DDM_EINVAL;
+  ilu0_join_builder(const_cast<ddm_ilu0 *>(F));
+  const BoxEngine *X = F->engine == Engine::Box ? F->box.get() : nullptr;
+  const int64_t nb = X ? (int64_t)X->h_blocks.size() : 0;
+  *count = 3 + 5 * nb;
+  if (!out) return DDM_OK;
+  if (capacity < *count) return DDM_EINVAL;
+  out[0] = nb;
+  out[1] = X ? X->grid : 0;
+  out[2] = X && X->shell ? ddm_ilu0_engine(X->shell) : -1;
+  for (int64_t b = 0; b < nb; ++b) {
+    const box::Block &B = X->h_blocks[(size_t)b];
+    const int64_t v[5] = {B.nx, B.ny, B.nz, B.nsteps, B.nloc - B.nb};
+    std::copy(v, v + 5, out + 3 + 5 * b);
+  }
   return DDM_OK;
 }

@@ -109,6 +109,7 @@ struct BoxEngine { // box (trsv_box_host.hpp): structured leading box of every b
   ddm_ilu0 *shell = nullptr;
   int grid = 0;
   box::Stats stats;
+  std::vector<box::Block> h_blocks;     // host copy of `blocks` (ddm_ilu0_box_info)
   ~BoxEngine() // the body runs before the members go: the nested factor (it reads shell_csr), then its matrix, then the arrays above
   {
     ddm_ilu0_destroy(shell);

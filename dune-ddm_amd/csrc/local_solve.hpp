@@ -200,6 +200,12 @@ static int ilu0_solve_epilogue(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, doubl
 }
 
 extern "C" int ddm_ilu0_solve(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x) { return ilu0_solve_epilogue(ctx, F, d, x, nullptr, nullptr); }
+// the solve with the tail of a Schwarz level, x = (LU)^-1 d * scale + add entry by entry (either may be null), on whatever engine the
+// factor has: what the Schwarz applies enqueue, reachable at row level (tests)
+extern "C" int ddm_ilu0_solve_tail(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, const double *scale, const double *add)
+{
+  return ilu0_solve_epilogue(ctx, F, d, x, scale, add);
+}
 
 // Multi-RHS solve X = (LU)^-1 D for row-major n x nrhs block vectors with leading dimensions ldd / ldx (GenEO setup path).
 // One launch per level (wide levels of direct factors: one workgroup per row); the launches of one (D, X, nrhs) combination are

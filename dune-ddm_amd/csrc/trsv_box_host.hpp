@@ -109,7 +109,10 @@ inline int jlo_of(int l, int nx) { return l < nx ? 0 : (l - nx + 2) / 2; }      
 inline int jhi_of(int l, int ny) { return std::min(ny - 1, l / 2); }
 
 // Finds the box of one block: rows [r0, r0 + nb) with the exact 27-point pattern.  Returns false when there is none worth the engine.
-inline bool detect(const int64_t *rp, const int32_t *ci, const int64_t *diag, int64_t r0, int64_t r1, int &nx, int &ny, int &nz, std::string &why)
+// given_back (optional): planes that conform on their own but leave the box again, because a row of theirs, or with them behind it a row
+// of the plane in front, has more than MAX_EXT entries outside the box.
+inline bool detect(const int64_t *rp, const int32_t *ci, const int64_t *diag, int64_t r0, int64_t r1, int &nx, int &ny, int &nz, std::string &why,
+                   int *given_back = nullptr)
 {
   const int64_t nloc = r1 - r0;
   if (nloc < 64) { why = "block too small"; return false; }
@@ -159,6 +162,7 @@ inline bool detect(const int64_t *rp, const int32_t *ci, const int64_t *diag, in
     }
     if (!ok) break;
   }
+  const int kconf = k;
   // rows of the last accepted plane must not point into a plane that was rejected; rows of earlier planes must have exactly the nine
   // neighbours of the next plane
   for (;;) {
@@ -186,6 +190,7 @@ inline bool detect(const int64_t *rp, const int32_t *ci, const int64_t *diag, in
     --k;
   }
   nz = k;
+  if (given_back) *given_back = kconf - k;
   if ((int64_t)nz * cxy * 2 < nloc) { why = "the box covers less than half of the block"; return false; }
   return true;
 }

@@ -172,6 +172,10 @@ int ddm_ilu0_refresh(ddm_ctx *ctx, ddm_ilu0 *F);
 int ddm_ilu0_refresh_count(const ddm_ilu0 *F);
 /* x = (LU)^-1 d ; d and x must not alias */
 int ddm_ilu0_solve(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x);
+/* x = ((LU)^-1 d) * scale + add, entry by entry with two roundings; scale and add are device vectors of n doubles, either may be
+ * NULL.  The tail of a Schwarz level (partition of unity, coarse correction) as the applies enqueue it: folded into the output pass
+ * by the pipe and box engines, two more kernels on the others.  d and x must not alias. */
+int ddm_ilu0_solve_tail(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, const double *scale, const double *add);
 /* X = (LU)^-1 D for row-major n x nrhs block vectors (cf. the reference's multi-RHS triangular
  * solve eigensolvers/umfpack.hh:131-197); D and X must not alias */
 int ddm_ilu0_solve_multi(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double *D, double *X);
@@ -205,6 +209,11 @@ int ddm_ilu0_wait(ddm_ctx *ctx, ddm_ilu0 *F);
  * kernels stamp every plane of block 0; out1024 = [2 sweeps][128 planes][4] = {start, end (100 MHz clock), polls of the previous plane's
  * progress word, XCC id} of the last solve (zeros without the switch). */
 int ddm_ilu0_box_check(const ddm_ilu0 *F, unsigned long long *out1024);
+/* Read-only, for tests: what the box engine's builder made of the matrix.  out = {blocks, workgroups of a sweep launch, engine of the
+ * nested factor that solves the rows behind the boxes (the codes of ddm_ilu0_engine, settled; -1 when there are no such rows)}, then
+ * per block {nx, ny, nz, steps per plane, rows behind the box}.  *count = 3 + 5 blocks is always set; out may be NULL to ask for it,
+ * otherwise capacity >= *count.  A factor that is not on the box engine reports 0 blocks.  Waits for the background builder. */
+int ddm_ilu0_box_info(const ddm_ilu0 *F, int64_t *out, int64_t capacity, int64_t *count);
 /* diagnostic: one solve with in-kernel cycle stamps of one compute wave */
 int ddm_ilu0_debug_stamps(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned long long *out6_host);
 /* diagnostic: one solve with the stamped build of the pipe engine's kernel (DDM_TRSV_MODE=pipe, the default); per task 272
