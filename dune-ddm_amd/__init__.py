@@ -166,6 +166,10 @@ SYMBOLS = {
     "ddm_harmonic_create": (_I32, [_P, _P, _I64, _P, _I64, _P, _I64, _P, _PP]),
     "ddm_harmonic_destroy": (None, [_P]),
     "ddm_harmonic_extend": (_I32, [_P, _P, _I32, _P, _I64]),
+    "ddm_harmonic_create_classes": (_I32, [_P, _P, _I64, _P, _P, _I32, _PP]),
+    "ddm_harmonic_debug_apply": (_I32, [_P, _P, _I32, _I32, _P, _I64, _P, _P, _I64]),
+    "ddm_harmonic_info": (_I32, [_P, _P]),
+    "ddm_harmonic_get_host": (_I32, [_P, _I32, _P, _P, _P]),
     "ddm_blockvec_gram": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, _I32, _P]),
     "ddm_blockvec_gram2_sym": (_I32, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "ddm_blockvec_rotate": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64]),
@@ -1225,6 +1229,44 @@ class HarmonicExtension:
         h = ctypes.c_void_p()
         ctx.check(ctx.lib.ddm_harmonic_create(ctx.h, A.h, len(bp) - 1, _hp(bp), len(ii), _hp(ii), len(bb), _hp(bb), ctypes.byref(h)))
         self.h = h
+
+    @classmethod
+    def from_classes(cls, ctx: Context, A: "CsrMatrix", classes, block_ptr=None, transpose=True):
+        """ddm_harmonic_create_classes: classes[n] = 0 interior, 1 boundary, anything else neither; transpose: with G_bi (tests)"""
+        self = cls.__new__(cls)
+        self.ctx, self.h = ctx, None
+        c = _np(classes, np.uint8)
+        assert c.shape == (A.shape[0],)
+        bp = _np(block_ptr if block_ptr is not None else [0, A.shape[0]], np.int64)
+        h = ctypes.c_void_p()
+        ctx.check(ctx.lib.ddm_harmonic_create_classes(ctx.h, A.h, len(bp) - 1, _hp(bp), _hp(c), int(bool(transpose)), ctypes.byref(h)))
+        self.h = h
+        return self
+
+    def debug_apply(self, op, X, pou_int=None, Y=None):
+        """ddm_harmonic_debug_apply on row-major device views (n, nrhs) with any row stride: op 0 extension, 1 P, 2 P^T (in place),
+        3 Y = T T^T X with the host vector pou_int (tests)"""
+        assert X.dim() == 2 and X.stride(1) == 1 and (Y is None or (Y.shape == X.shape and Y.stride(1) == 1))
+        d = _np(pou_int, np.float64) if pou_int is not None else None
+        self.ctx.check(self.ctx.lib.ddm_harmonic_debug_apply(self.ctx.h, self.h, int(op), X.shape[1], _ptr(X), X.stride(0), _hp(d),
+                                                             _ptr(Y) if Y is not None else None, Y.stride(0) if Y is not None else 0))
+
+    def info(self):
+        """ddm_harmonic_info as a dict (tests)"""
+        o = np.zeros(8, dtype=np.int64)
+        assert self.ctx.lib.ddm_harmonic_info(self.h, _hp(o)) == DDM_OK
+        keys = ("n", "symmetric", "nnz_gib", "nnz_gbi", "supernodal", "factor_nnz", "refine_steps", "work_cols")
+        return {k: int(v) for k, v in zip(keys, o)}
+
+    def host_matrix(self, which):
+        """G_ib (which = 0) or G_bi (1) as the library holds it: (rowptr, col, val) (tests)"""
+        i = self.info()
+        nnz = i["nnz_gbi"] if which else i["nnz_gib"]
+        if nnz < 0:
+            raise ValueError("the object has no G_bi")
+        rp, ci, va = np.empty(i["n"] + 1, dtype=np.int64), np.empty(nnz, dtype=np.int32), np.empty(nnz, dtype=np.float64)
+        assert self.ctx.lib.ddm_harmonic_get_host(self.h, int(which), _hp(rp), _hp(ci), _hp(va)) == DDM_OK
+        return rp, ci, va
 
     def extend(self, X):
         """in place on a row-major device tensor (n, nrhs) holding the boundary values: interior rows are overwritten"""

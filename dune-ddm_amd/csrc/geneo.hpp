@@ -292,14 +292,15 @@ static void launch_geneo_start_block(ddm_ctx *ctx, int64_t n, int m, int mk, int
   hipLaunchKernelGGL(k_geneo_start_block, dim3(geneo_grid(n * 3 * (int64_t)m)), dim3(256), 0, ctx->stream, n, m, mk, ldk, seed, mask, kept, S);
 }
 
-// X = keep .* X - Y  (rows: keep = 0 / 1): tail of the harmonic projection / extension
+// X = (keep ? X : 0) - Y  (rows: keep = 0 / 1): tail of the harmonic projection / extension.  Rows with keep = 0 are OUTPUTS: what
+// they held does not enter (a product 0 * X would carry a NaN or Inf left there into the result).
 __global__ void k_geneo_project(int64_t n, int m, const double *__restrict__ keep, const double *__restrict__ Y, int64_t ldy, double *__restrict__ X, int64_t ldx)
 {
   const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= n * m) return;
   const int64_t i = t / m;
   const int j = (int)(t - i * m);
-  X[i * ldx + j] = keep[i] * X[i * ldx + j] - Y[i * ldy + j];
+  X[i * ldx + j] = (keep[i] != 0.0 ? X[i * ldx + j] : 0.0) - Y[i * ldy + j];
 }
 // Y = w .* X
 __global__ void k_geneo_rowscale_to(int64_t n, int m, const double *__restrict__ w, const double *__restrict__ X, int64_t ldx, double *__restrict__ Y, int64_t ldy)
@@ -909,6 +910,22 @@ extern "C" int ddm_msgfem_basis(ddm_ctx *ctx, const ddm_csr *A_neu, const ddm_cs
   return geneo_basis_impl(ctx, Q, params, kmax, basis_host, nconv, eigenvalues_host, info);
 }
 
+// Y = T T^T X = D A^^-1 G_ib G_bi A^^-T D X for the symmetric interior block of H (d: DEVICE vector D, zero outside the interior)
+static int harmonic_apply_ttt(ddm_ctx *ctx, ddm_harmonic *H, const double *d, int m, const double *X, int64_t ldx, double *Y, int64_t ldy)
+{
+  const int64_t n = H->n;
+  HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
+  const unsigned gr = (unsigned)((n * (int64_t)m + 255) / 256);
+  hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, d, X, ldx, H->t1, (int64_t)m); // D x
+  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t1, m, H->t2, m));                                           // A_ii^-T
+  DDMCHECK(csr_mm_ld(ctx, H->Gbi.get(), m, H->t2, m, H->t1, m));                                                   // A_{i,Gamma}^T
+  DDMCHECK(csr_mm_ld(ctx, H->Gib.get(), m, H->t1, m, H->t2, m));                                                   // A_{i,Gamma}
+  DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t2, m, H->t1, m));                                           // A_ii^-1
+  hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, d, (const double *)H->t1, (int64_t)m, Y, ldy); // D
+  HIPCHECK(ctx, hipGetLastError());
+  return DDM_OK;
+}
+
 // SVDCoarseSpace (coarse_spaces.hh:1268-1407): the leading left singular vectors of T = D A_ii^-1 A_{i,Gamma} (interior x subdomain
 // boundary; the reference forms T densely column by column and calls Eigen's bdcSvd).  Here: the leading eigenvectors of
 //     T T^T = D A_ii^-1 (A_{i,Gamma} A_{i,Gamma}^T) A_ii^-T D
@@ -938,18 +955,7 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   dbuf<double> d;
   DDMCHECK(ddm_csr_create(ctx, n, n, rp.data(), ci.data(), ones.data(), out_ptr(I)));
   DDMCHECK(upload(ctx, pou_int.data(), n, d));
-  const BlockOp op = [&](int m, const double *X, int64_t ldx, double *Y, int64_t ldy) -> int {
-    HIPCHECK(ctx, reserve_cols<double>(H->tcols, m, {{H->t1, H->n}, {H->t2, H->n}}));
-    const unsigned gr = (unsigned)((n * (int64_t)m + 255) / 256);
-    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)d, X, ldx, H->t1, (int64_t)m); // D x
-    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t1, m, H->t2, m));                                                          // A_ii^-T
-    DDMCHECK(csr_mm_ld(ctx, H->Gbi.get(), m, H->t2, m, H->t1, m));                                                                  // A_{i,Gamma}^T
-    DDMCHECK(csr_mm_ld(ctx, H->Gib.get(), m, H->t1, m, H->t2, m));                                                                  // A_{i,Gamma}
-    DDMCHECK(ilu0_solve_multi_ld(ctx, H->F.get(), m, H->t2, m, H->t1, m));                                                          // A_ii^-1
-    hipLaunchKernelGGL(k_geneo_rowscale_to, dim3(gr), dim3(256), 0, ctx->stream, n, m, (const double *)d, (const double *)H->t1, (int64_t)m, Y, ldy); // D
-    HIPCHECK(ctx, hipGetLastError());
-    return DDM_OK;
-  };
+  const BlockOp op = [&](int m, const double *X, int64_t ldx, double *Y, int64_t ldy) -> int { return harmonic_apply_ttt(ctx, H, d, m, X, ldx, Y, ldy); };
   ddm_geneo_params P;
   ddm_geneo_params_default(&P);
   P.nev = n_vectors;
@@ -964,6 +970,59 @@ extern "C" int ddm_svd_basis(ddm_ctx *ctx, const ddm_csr *A_dir, int64_t nsub, c
   const GeneoProblem Q{"ddm_svd_basis", I.get(), I.get(), nsub, sub_ptr, pou_host, notint.data(), nullptr, ones.data(), &op};
   DDMCHECK(geneo_basis_impl(ctx, Q, &P, n_vectors, basis_host, nconv.data(), eig.data(), info));
   for (size_t k = 0; k < eig.size(); ++k) singular_values_host[k] = 1.0 / std::sqrt(std::max(eig[k], 1e-300)); // mu = sigma^2 = 1 / lambda
+  return DDM_OK;
+}
+
+// ---- ddm_harmonic read-only and step by step (for tests: tests/test_gpu_harmonic_shapes.py) -----------------------------------------
+// Each export forwards to the function the builders call -- harmonic_create_impl, harmonic_apply, harmonic_apply_transposed,
+// harmonic_apply_ttt -- with the caller's classes, DEVICE pointers, widths and leading dimensions; none chunks, dispatches or sizes a grid.
+extern "C" int ddm_harmonic_create_classes(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, const uint8_t *cls_host, int want_transpose,
+                                           ddm_harmonic **out)
+{
+  if (!ctx || !A || !out || nblocks < 1 || !block_ptr || !cls_host) return fail(ctx, DDM_EINVAL, "ddm_harmonic_create_classes: bad arguments");
+  if (A->nrows != A->ncols) return fail(ctx, DDM_EINVAL, "ddm_harmonic_create_classes: square matrix expected");
+  return harmonic_create_impl(ctx, A, nblocks, block_ptr, cls_host, want_transpose != 0, out);
+}
+// op 0: X <- extension (harmonic_apply, keep); 1: X <- P X (keep_b); 2: X <- P^T X; 3: Y = T T^T X with D = pou_int (HOST, n entries;
+// synchronous).  Ops 0 .. 2 work in place and ignore pou_int, Y and ldy.
+extern "C" int ddm_harmonic_debug_apply(ddm_ctx *ctx, ddm_harmonic *H, int op, int nrhs, double *X, int64_t ldx, const double *pou_int, double *Y, int64_t ldy)
+{
+  if (!ctx || !H || !X || op < 0 || op > 3 || nrhs < 1 || ldx < nrhs) return fail(ctx, DDM_EINVAL, "ddm_harmonic_debug_apply: bad arguments");
+  if (op <= 1) return harmonic_apply(ctx, H, nrhs, X, ldx, op == 1);
+  if (!H->symmetric) return fail(ctx, DDM_ENOTIMPL, "ddm_harmonic_debug_apply: the interior block is not symmetric");
+  if (!H->Gbi) return fail(ctx, DDM_EINVAL, "ddm_harmonic_debug_apply: the object was created without G_bi");
+  if (op == 2) return harmonic_apply_transposed(ctx, H, nrhs, X, ldx);
+  if (!pou_int || !Y || Y == X || ldy < nrhs) return fail(ctx, DDM_EINVAL, "ddm_harmonic_debug_apply: bad arguments");
+  dbuf<double> d;
+  DDMCHECK(upload(ctx, pou_int, H->n, d));
+  DDMCHECK(harmonic_apply_ttt(ctx, H, d, nrhs, X, ldx, Y, ldy));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream)); // (d goes out of scope)
+  return DDM_OK;
+}
+// out: n, symmetric, nnz(G_ib), nnz(G_bi) (-1: absent), 1 = device supernodal factor, the factor's nnz, its refinement steps, columns
+// the work blocks hold
+extern "C" int ddm_harmonic_info(const ddm_harmonic *H, int64_t *out)
+{
+  if (!H || !out) return DDM_EINVAL;
+  out[0] = H->n;
+  out[1] = H->symmetric ? 1 : 0;
+  out[2] = H->Gib ? H->Gib->nnz : -1;
+  out[3] = H->Gbi ? H->Gbi->nnz : -1;
+  out[4] = H->F && H->F->sn ? 1 : 0;
+  out[5] = ddm_ilu0_nnz(H->F.get());
+  out[6] = ddm_ilu0_refinement(H->F.get(), nullptr);
+  out[7] = H->tcols;
+  return DDM_OK;
+}
+// the host arrays of G_ib (which = 0) or G_bi (1): rowptr[n + 1], col[nnz], val[nnz], each copied where not NULL
+extern "C" int ddm_harmonic_get_host(const ddm_harmonic *H, int which, int64_t *rowptr, int32_t *col, double *val)
+{
+  if (!H || which < 0 || which > 1) return DDM_EINVAL;
+  const ddm_csr *G = which ? H->Gbi.get() : H->Gib.get();
+  if (!G) return DDM_EINVAL;
+  if (rowptr) std::copy(G->h_rp.begin(), G->h_rp.end(), rowptr);
+  if (col) std::copy(G->h_ci.begin(), G->h_ci.end(), col);
+  if (val) std::copy(G->h_va.begin(), G->h_va.end(), val);
   return DDM_OK;
 }
 

@@ -516,6 +516,27 @@ int ddm_harmonic_create(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const i
                         int64_t n_boundary, const int64_t *boundary_host, ddm_harmonic **out);
 void ddm_harmonic_destroy(ddm_harmonic *H);
 int ddm_harmonic_extend(ddm_ctx *ctx, ddm_harmonic *H, int nrhs, double *X, int64_t ldx);
+/* The same object read-only and step by step (for tests): each forwards to the function ddm_harmonic_extend, ddm_msgfem_basis and
+ * ddm_svd_basis call, with the caller's DEVICE pointers, widths and leading dimensions; nothing is chunked.
+ *   ddm_harmonic_create_classes  the object from row classes cls_host[n] (0 = interior, 1 = boundary, anything else = neither), as
+ *                            ddm_msgfem_basis and ddm_svd_basis make it; want_transpose != 0: with G_bi = G_ib^T.  DDM_ENUMERIC for an
+ *                            interior row without interior entries.
+ *   ddm_harmonic_debug_apply op 0: X <- the extension of at most 48 columns (interior rows overwritten, every other row kept);
+ *                            op 1: X <- P X (interior rows overwritten, boundary rows kept, every other row zero);
+ *                            op 2: X <- P^T X (boundary rows R_b - G_bi A_ii^-T R_i, every other row zero);
+ *                            op 3: Y = T T^T X, T = D A_ii^-1 A_{i,Gamma} with D = pou_int (HOST, n entries, zero outside the
+ *                                  interior); synchronous.
+ *                            Ops 0 .. 2 work in place and ignore pou_int, Y, ldy.  Ops 2 and 3: DDM_ENOTIMPL when the interior block
+ *                            is not symmetric, DDM_EINVAL when the object has no G_bi.
+ *   ddm_harmonic_info        out[8] = n, symmetric (0 / 1), nnz(G_ib), nnz(G_bi) (-1: absent), 1 when the factor is the device
+ *                            supernodal one, the factor's stored entries, its refinement steps, columns the work blocks hold
+ *   ddm_harmonic_get_host    the host arrays of G_ib (which = 0) or G_bi (which = 1): rowptr[n + 1], col[nnz], val[nnz], each where
+ *                            not NULL */
+int ddm_harmonic_create_classes(ddm_ctx *ctx, const ddm_csr *A, int64_t nblocks, const int64_t *block_ptr, const uint8_t *cls_host, int want_transpose,
+                                ddm_harmonic **out);
+int ddm_harmonic_debug_apply(ddm_ctx *ctx, ddm_harmonic *H, int op, int nrhs, double *X, int64_t ldx, const double *pou_int, double *Y, int64_t ldy);
+int ddm_harmonic_info(const ddm_harmonic *H, int64_t *out);
+int ddm_harmonic_get_host(const ddm_harmonic *H, int which, int64_t *rowptr, int32_t *col, double *val);
 /* The two dense contractions of the block eigensolver on their own (FP64 MFMA, csrc/geneo_kernels.hpp), for row-major DEVICE
  * blocks split into subdomain row ranges sub_ptr[nsub+1]:
  *   gram  : G_host[s] = U[rows of s]^T V[rows of s]   (nsub matrices pu x pv, row-major; split-K over 2048-row chunks, summed in
