@@ -55,7 +55,13 @@ using namespace ddm;
 #include "halo.hpp"             // ddm_halo: single-vector and m-column exchange over one RCCL wire function.  Needs context.hpp.
 #include "krylov_work.hpp"      // KrylovWork: the block Krylov drivers' work blocks, one pool per ddm_combined.  Needs device_buffer.hpp, multi_kernels.hpp.
 #include "preconditioners.hpp"  // dot products, ddm_op, ddm_schwarz, ddm_galerkin, ddm_combined: single and m-column applies side by side.  Needs halo.hpp, local_solver.hpp, krylov_work.hpp.
-#include "krylov.hpp"           // CG (begin / steps / defect / solve), GMRES, BiCGSTAB, flexible CG, block CG, block GMRES, block flexible CG.  Needs preconditioners.hpp.
+#include "krylov_frame.hpp"     // what the drivers share: StreamDrain, the frame around a loop, MultiFrame, launch_check, defect_norm_multi, gmres_memory_check.  Needs preconditioners.hpp.
+#include "krylov_cg.hpp"        // CG: begin / steps / defect / solve, m columns at once, queued (ddm_cg_solve_queue).  Needs krylov_frame.hpp.
+#include "krylov_bicgstab.hpp"  // BiCGSTAB: single, queued (ddm_bicgstab_solve_queue).  Needs krylov_frame.hpp.
+#include "krylov_gmres.hpp"     // restarted GMRES, left and flexible: GmresColumn, gmres_loop, gmres_loop_multi and their four exports.  Needs krylov_frame.hpp.
+#include "krylov_fcg.hpp"       // flexible CG, restarted and complete: fcg_loop, fcg_loop_multi, ddm_fcg_orth_multi.  Needs krylov_frame.hpp.
+#include "krylov_bcg.hpp"       // block CG (ddm_bcg_solve_multi) and its three pass exports.  Needs krylov_frame.hpp.
+#include "krylov_bgmres.hpp"    // block GMRES (ddm_bgmres_solve_multi) and its three pass exports.  Needs krylov_frame.hpp.
 
 // ---- dense host helpers exposed for the CPU tests (host logic of the GenEO Rayleigh-Ritz step) -------------------------
 extern "C" int ddm_dense_sym_eig_host(int n, double *V, double *w) { return dense::sym_eig(n, V, w) ? DDM_OK : DDM_ENUMERIC; }

@@ -1506,7 +1506,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_fin(int64_t n, double *sc
 }
 
 // ---------------------------------------------------------------------------------------------
-// Flexible CG (ddm_fcg_solve, csrc/krylov.hpp): the orthogonalisation of a fresh direction d against stored slots.
+// Flexible CG (ddm_fcg_solve, csrc/krylov_fcg.hpp): the orthogonalisation of a fresh direction d against stored slots.
 // The stored vectors of a launch, passed by value: vector j of the set is base + buf[j] * stride.
 constexpr int FCG_SET_MAX = 16;  // entries of one FcgSet (k_fcg_coef, k_fcg_orth and their block forms take that many per launch)
 constexpr int FCG_SG1 = 8;       // slots one pass of k_fcg_project takes (one accumulator each)

@@ -1,4 +1,4 @@
-// KrylovWork: the n x width work blocks that the block Krylov drivers (krylov.hpp) keep between calls, one pool per preconditioner
+// KrylovWork: the n x width work blocks that the block Krylov drivers (krylov_*.hpp) keep between calls, one pool per preconditioner
 // object (ddm_combined::work).  A driver opens with ONE reserve call and names its blocks by local pointers; what a block holds on
 // entry is whatever the last driver left there.  Needs device_buffer.hpp and MULTI_MAX (multi_kernels.hpp).
 #pragma once

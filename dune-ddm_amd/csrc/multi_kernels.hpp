@@ -1,4 +1,4 @@
-// Device kernels of the multi-right-hand-side path (ddm_*_multi: the block applies of csrc/halo.hpp and csrc/preconditioners.hpp, the block drivers of csrc/krylov.hpp): m independent columns stored as a row-major
+// Device kernels of the multi-right-hand-side path (ddm_*_multi: the block applies of csrc/halo.hpp and csrc/preconditioners.hpp, the block drivers of csrc/krylov_*.hpp): m independent columns stored as a row-major
 // n x m block (entry (i, c) at i * m + c, the layout of ddm_csr_mm and ddm_ilu0_solve_multi), 1 <= m <= MULTI_MAX.
 // Element-wise kernels run one thread per block entry (consecutive threads = consecutive addresses).  Reductions keep the tree of
 // the single-vector kernels where that costs nothing: the owner-masked dots and the fused CG update use the grid, the thread-to-row
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(WG) void k_cg_update_norm_multi(int64_t n, int m, i
   }
 }
 
-// ---- queued CG (ddm_cg_solve_queue, csrc/krylov.hpp): columns of the caller's n x ncols blocks enter and leave the slots of the n x m work blocks ----
+// ---- queued CG (ddm_cg_solve_queue, csrc/krylov_cg.hpp): columns of the caller's n x ncols blocks enter and leave the slots of the n x m work blocks ----
 // tab: nload (slot, column) pairs, tab[2k] = slot < m and tab[2k + 1] = column < ncols.  One thread per (row, pair) entry, the pair
 // index running fastest (consecutive lanes = consecutive table entries of one row).
 // Load: x_slot = X[:, column], b_slot = B[:, column], p_slot = 0 and rholast_slot = 1 (scal as in k_cg_beta_multi): the slot's next
@@ -302,7 +302,7 @@ __global__ void k_column_store_multi(int64_t n, int m, int nstore, const int64_t
   }
 }
 
-// ---- queued BiCGSTAB (ddm_bicgstab_solve_queue, csrc/krylov.hpp) -----------------------------------------------------------------------
+// ---- queued BiCGSTAB (ddm_bicgstab_solve_queue, csrc/krylov_bicgstab.hpp) -----------------------------------------------------------------------
 // Per-column scalars in ctx->mscal, M = MULTI_MAX: [0..M) rho, [M..2M) alpha, [2M..3M) omega, [3M..4M) beta.  The sums the host
 // reads are packed at stride m (the block width), so that one copy takes a group of them:
 //   first half step   [4M..): <r, r>, then h = <rt, v>, then the rho and the omega that the direction update used (4 m doubles)
@@ -394,7 +394,7 @@ __global__ void k_scal_dev_multi(int64_t n, int m, const int32_t *__restrict__ a
   }
 }
 
-// ---- restarted GMRES vector work (ddm_gmres_solve_multi, csrc/krylov.hpp) -----------------------------------------------------------------------------
+// ---- restarted GMRES vector work (ddm_gmres_solve_multi, csrc/krylov_gmres.hpp) -----------------------------------------------------------------------------
 // per-column host scalars of one launch, passed by value (no upload, no synchronisation)
 struct MultiCoef {
   double a[MULTI_MAX];
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(WG) void k_gmres_update_multi(int64_t n, int m, con
   }
 }
 
-// ---- flexible restarted GMRES (ddm_fgmres_solve_multi, csrc/krylov.hpp) -------------------------------------------------------------
+// ---- flexible restarted GMRES (ddm_fgmres_solve_multi, csrc/krylov_gmres.hpp) -------------------------------------------------------------
 // Restart of the flexible driver for columns [c0, c0 + CB): b -= t (t = A W, the operator applied to the cycle's solution update) in
 // the active columns and, in the same pass, the owner-masked partial sums of <b, b> -- the true defect norms the next cycle starts
 // from.  The grid, the rows per thread and block_sum are those of k_dot_partial_multi, so b and the sums are bit-identical to
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(WG) void k_defect_norm_multi(int64_t n, int m, int 
   }
 }
 
-// ---- flexible CG (ddm_fcg_solve_multi, csrc/krylov.hpp): the orthogonalisation of a fresh direction block against stored slots ---------
+// ---- flexible CG (ddm_fcg_solve_multi, csrc/krylov_fcg.hpp): the orthogonalisation of a fresh direction block against stored slots ---------
 constexpr int FCG_SG = 4; // slots one pass of k_fcg_project_multi takes: FCG_SG x CB accumulators
 // Projection for columns [c0, c0 + CB): the owner-masked partial sums of <Ad_j, d> for the set.n <= FCG_SG stored image blocks of the
 // set (block j at AD + set.buf[j] * stride) in ONE pass over the block d.  The grid, the rows per thread and block_sum are those of
@@ -612,7 +612,7 @@ __global__ void k_fcg_alpha_multi(int m, const int32_t *__restrict__ active, con
   }
 }
 
-// ---- block CG (ddm_bcg_solve_multi, csrc/krylov.hpp): the m x m coupling of the columns ------------------------------------------------
+// ---- block CG (ddm_bcg_solve_multi, csrc/krylov_bcg.hpp): the m x m coupling of the columns ------------------------------------------------
 // All three kernels walk the block in tiles of whole rows that one workgroup stages in LDS with contiguous loads (a tile of rows IS a
 // contiguous piece of a row-major block), tile tb = blockIdx.x, blockIdx.x + gridDim.x, ...  No atomics: every sum has one owner and a
 // fixed order, so the results do not change from call to call.  Plain FP64 multiplies and adds (the build does not contract them); the
@@ -774,7 +774,7 @@ __global__ __launch_bounds__(WG) void k_bcg_direction(int64_t n, int m, const do
   }
 }
 
-// ---- block GMRES (ddm_bgmres_solve_multi, csrc/krylov.hpp): block classical Gram-Schmidt against the stored basis blocks ----------------
+// ---- block GMRES (ddm_bgmres_solve_multi, csrc/krylov_bgmres.hpp): block classical Gram-Schmidt against the stored basis blocks ----------------
 // Blocks are n x p row-major, 1 <= p <= MULTI_MAX; stored block k starts at V + k * vstride.  As for block CG: LDS-staged tiles of whole
 // rows, tile tb = blockIdx.x, blockIdx.x + gridDim.x, ..., no atomics, plain FP64 multiplies and adds in a fixed order.
 constexpr int BGM_SG = 4; // stored blocks of one group of k_bgmres_project: BGM_SG x 4 accumulators per thread

@@ -1,4 +1,4 @@
-"""Plain numpy restatement of the queue protocol of ddm_bicgstab_solve_queue (csrc/krylov.hpp) beside the single loop it must reproduce
+"""Plain numpy restatement of the queue protocol of ddm_bicgstab_solve_queue (csrc/krylov_bicgstab.hpp) beside the single loop it must reproduce
 (the evaluation order of oracle/apply_oracle.py::bicgstab_solve), on a small dense system A with a fixed right preconditioner W^-1
 given as a matrix.  tests/test_bicgstab_queue_cpu.py asserts on it what the device driver relies on:
 

@@ -14,7 +14,7 @@ from tests.oracle_bridge import oracle_objects
 
 
 def generate_rotation(dx, dy):
-    """the Givens rotation of dune-istl's GMRES (generatePlaneRotation), as gmres_generate_rotation in csrc/krylov.hpp"""
+    """the Givens rotation of dune-istl's GMRES (generatePlaneRotation), as gmres_generate_rotation in csrc/krylov_gmres.hpp"""
     ndx, ndy = abs(dx), abs(dy)
     if ndy < 1e-15:
         return 1.0, 0.0
