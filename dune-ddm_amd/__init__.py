@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libddm_hip.so")
 GENEO_AVAILABLE = True   # dune-ddm_amd/geneo.py: device GenEO coarse-basis builder
 
 DDM_OK, DDM_EINVAL, DDM_EHIP, DDM_ENOTIMPL, DDM_ENUMERIC, DDM_ECOMM = 0, -1, -2, -3, -4, -5
+MULTI_ENGINES = ("levels", "xcd", "xcd1")   # modes of ddm_ilu0_set_multi_engine: one launch per level; one persistent launch; that with one team
 
 
 class DdmError(RuntimeError):
@@ -215,6 +216,11 @@ SYMBOLS = {
     "ddm_bgmres_combine_gram_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "ddm_dense_bgmres_factor_host": (_I32, [_I32, _P, _P, _D, _P, _P, _P]),
     "ddm_schwarz_set_multi_precision": (_I32, [_P, _I32]),
+    "ddm_schwarz_set_multi_engine": (_I32, [_P, _I32]),
+    "ddm_ilu0_set_multi_engine": (_I32, [_P, _P, _I32]),
+    "ddm_ilu0_multi_info": (_I32, [_P, _P, _I64, _P]),
+    "ddm_trsv_multi_plan_host": (_I32, [_I64, _P, _P, _I64, _P, _I32, _P, _I64, _P, _P]),
+    "ddm_trsv_multi_team_host": (_I32, [_P, _I32, _I32, _I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P]),
     "ddm_local_maps_host": (_I32, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ddm_schwarz_debug_local": (_I32, [_P, _P, ctypes.POINTER(ctypes.c_int), _PP, _PP]),
     "ddm_ctx_scalars": (_P, [_P]),
@@ -591,6 +597,27 @@ class Ilu0:
         m, (ldd, ldx) = _block_ld(D, X)
         self.ctx.check(self.ctx.lib.ddm_ilu0_solve_multi_ld(self.ctx.h, self.h, m, _ptr(D), ldd, _ptr(X), ldx, int(bool(single_precision))))
 
+    def set_multi_engine(self, name):
+        """engine of the block solves (ddm_ilu0_set_multi_engine): 'levels' (one launch per level, the default), 'xcd' (one persistent
+        launch, same bits) or 'xcd1' (xcd with all workgroups in one team, for tests); no effect on a direct factor"""
+        if name not in MULTI_ENGINES:
+            raise ValueError("unknown multi engine '" + str(name) + "' (levels, xcd, xcd1)")
+        self.ctx.check(self.ctx.lib.ddm_ilu0_set_multi_engine(self.ctx.h, self.h, MULTI_ENGINES.index(name)))
+
+    def multi_info(self):
+        """what the block solves run on (ddm_ilu0_multi_info, after a synchronisation): dict with `requested` and `engine` ('levels' /
+        'xcd' / 'xcd1'; engine None before the first block solve), `declined` (None, 'not requested', 'direct factor', 'wide level')
+        and of the last xcd launch `grid`, `teams`, `one_team`, `tickets` (workgroups per XCD)"""
+        self.ctx.sync()
+        out = np.zeros(14, dtype=np.int64)
+        cnt = ctypes.c_int64()
+        rc = self.ctx.lib.ddm_ilu0_multi_info(self.h, _hp(out), 14, ctypes.byref(cnt))
+        if rc != DDM_OK or cnt.value != 14:
+            raise DdmError(rc, "ddm_ilu0_multi_info failed")
+        return {"requested": MULTI_ENGINES[int(out[0])], "engine": None if out[1] < 0 else MULTI_ENGINES[int(out[1])],
+                "declined": (None, "not requested", "direct factor", "wide level")[int(out[2])], "grid": int(out[3]), "teams": int(out[4]),
+                "one_team": bool(out[5]), "tickets": [int(v) for v in out[6:14]]}
+
     def num_levels(self, upper=False):
         return int(self.ctx.lib.ddm_ilu0_num_levels(self.h, int(upper)))
 
@@ -777,6 +804,13 @@ class SchwarzPreconditioner:
         """f32 true: the block applies run their local solve with single-precision sweeps (ddm_schwarz_set_multi_precision; meant for
         the flexible drivers only); false (the default): double"""
         self.ctx.check(self.ctx.lib.ddm_schwarz_set_multi_precision(self.h, 1 if f32 else 0))
+
+    def set_multi_engine(self, name):
+        """engine of the local solves of the block applies (ddm_schwarz_set_multi_engine): 'levels' (the default), 'xcd' (one persistent
+        launch for both sweeps of all subdomains; the same bits) or 'xcd1' (xcd with one team, for tests)"""
+        if name not in MULTI_ENGINES:
+            raise ValueError("unknown multi engine '" + str(name) + "' (levels, xcd, xcd1)")
+        self.ctx.check(self.ctx.lib.ddm_schwarz_set_multi_engine(self.h, MULTI_ENGINES.index(name)))
 
     def local_solver(self):
         """the local solver object (ddm_ilu0 *, borrowed) as a raw pointer"""
@@ -1311,6 +1345,37 @@ def dia_build_and_apply_host(A, x):
     if rc != DDM_OK:
         raise ValueError("ddm_dia_build_and_apply_host: bad arguments")
     return y, kinds[:counts[0]], dict(zip(("blocks", "dia", "csr", "rows_dia", "slots", "segments", "symmetric_segments"), counts.tolist()))
+
+
+def trsv_multi_plan_host(A, block_ptr, upper):
+    """(off, blk_nlev): the plan of the single-launch block solve for one triangle of the pattern of A (ddm_trsv_multi_plan_host) --
+    off[l, b] = first position of diagonal block b among the rows of level l (off[l, nblocks] = rows of the level), blk_nlev[b] = levels
+    of block b.  Host only."""
+    lib = load_library()
+    n = A.shape[0]
+    rp, ci, bp = _np(A.indptr, np.int64), _np(A.indices, np.int32), _np(block_ptr, np.int64)
+    nb = len(bp) - 1
+    nlev = ctypes.c_int64()
+    rc = lib.ddm_trsv_multi_plan_host(n, _hp(rp), _hp(ci), nb, _hp(bp), int(bool(upper)), None, 0, None, ctypes.byref(nlev))
+    off = np.zeros((max(nlev.value, 1), nb + 1), dtype=np.int32)
+    bn = np.zeros(nb, dtype=np.int32)
+    rc = rc or lib.ddm_trsv_multi_plan_host(n, _hp(rp), _hp(ci), nb, _hp(bp), int(bool(upper)), _hp(off), off.size, _hp(bn), ctypes.byref(nlev))
+    if rc != DDM_OK:
+        raise ValueError("ddm_trsv_multi_plan_host: bad arguments")
+    return off[:nlev.value], bn
+
+
+def trsv_multi_team_host(tickets, nblocks, xcc, xcd_ticket, global_ticket, force_one=False):
+    """dict(teams, team, rank, size, one_team) of one workgroup of the single-launch block solve (ddm_trsv_multi_team_host); tickets:
+    workgroups per XCD (8 values), the grid is their sum.  Host only."""
+    lib = load_library()
+    tk = _np(tickets, np.uint32)
+    assert len(tk) == 8
+    out = np.zeros(5, dtype=np.int32)
+    rc = lib.ddm_trsv_multi_team_host(_hp(tk), int(nblocks), int(bool(force_one)), int(xcc), int(xcd_ticket), int(global_ticket), int(tk.sum()), _hp(out))
+    if rc != DDM_OK:
+        raise ValueError("ddm_trsv_multi_team_host: bad arguments")
+    return dict(teams=int(out[0]), team=int(out[1]), rank=int(out[2]), size=int(out[3]), one_team=bool(out[4]))
 
 
 def local_maps_host(n, n_novlp, ext_map, plan_copy, plan_add):

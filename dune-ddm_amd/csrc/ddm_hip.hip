@@ -26,6 +26,7 @@
 // ---- building blocks without a context ------------------------------------------------------------
 #include "host_vec.hpp"         // hvec<T>: host arrays without value initialisation.  Needs nothing.
 #include "device_buffer.hpp"    // dbuf<T>, reserve_cols: the one owner of a device allocation.  Needs nothing.
+#include "trsv_multi_plan.hpp" // namespace multi_xcd: levels, per-block plan tables and team arithmetic of the single-launch block solve (host; team_of also device).  Needs nothing.
 #include "kernels.hpp"          // namespace ddm: single-vector kernels, WG, RED_MAX_BLOCKS, RowChunk, level descriptors.  Needs nothing.
 #include "multi_kernels.hpp"    // kernels of the m-column paths, MULTI_MAX, MultiCoef.  Needs kernels.hpp.
 #include "trsv_pipe.hpp"        // pipe engine of the ILU(0) solve: kernels and host schedule.  Needs host_vec.hpp.
@@ -46,6 +47,7 @@ using namespace ddm;
 #include "tri_csr.hpp"          // CSR level schedules of the host direct factor: supernodes, build_csr_schedule, enqueue_tri_csr, enqueue_multi_levels_csr.  Needs local_factor.hpp.
 #include "engine_xcd2.hpp"      // xcd2 engine: build_xcd_schedule, enqueue_xcd2.  Needs local_factor.hpp.
 #include "engine_pipe.hpp"      // pipe engine: build_pipe_schedule, enqueue_pipe.  Needs local_factor.hpp, trsv_pipe.hpp.
+#include "engine_multi_xcd.hpp" // engine `xcd` of the block solve: build_multi_xcd, enqueue_multi_xcd, ddm_ilu0_set_multi_engine / _multi_info, ddm_trsv_multi_*_host.  Needs local_factor.hpp.
 #include "ilu0_refactor.hpp"    // value refresh of an ILU(0) factor: device factorisation, scatter into the engines, ddm_ilu0_refresh.  Needs tri_levels.hpp, engine_xcd2.hpp, engine_pipe.hpp.
 #include "engine_box.hpp"       // box engine: build_box_engine, enqueue_box, ddm_ilu0_box_check.  Needs local_factor.hpp, trsv_box.hpp.
 #include "local_solve.hpp"      // the solves: ilu0_enqueue, graph capture, ilu0_solve_epilogue, ilu0_solve_multi_ld, ddm_ilu0_solve*.  Needs tri_*.hpp, engine_*.hpp.

@@ -828,6 +828,228 @@ __global__ void k_trsv_xcd_prologue(XcdState *st)
 __device__ __forceinline__ unsigned hw_xcc_id() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u; } // HW_REG_XCC_ID[3:0]
 
 // ---------------------------------------------------------------------------------------------
+// Block solve of a plain ILU(0) factor in ONE launch (engine `xcd` of the multi-RHS path; host side: engine_multi_xcd.hpp, plan and
+// team arithmetic: trsv_multi_plan.hpp).  The kernel walks the level engine's own arrays (TriSchedule: rows, cols, vals, dinv and
+// their float copies) with the strides, widths and padding of k_trsv_level_multi4 / k_trsv_level_multi / k_trsv_level_multi4_f32, and
+// sums every row over the same entries in the same order: its results are the bits of the level launches.  Teams of workgroups
+// (team_of) take the diagonal blocks in turn; inside a team the (row, column quad) items of a level are dealt as those kernels deal
+// them to their grids, and the levels are separated by the all-to-all flag barrier of k_sn_top1 in place of a kernel boundary.
+// Visibility: X (f32: the work block xf) is written by one workgroup and read by others inside the launch, so EVERY load of it is
+// an sc1 load (also the upper sweep's own row) and every store is written through and drained before the flag; D, the factor
+// arrays and the plan are constant during the launch (plain loads); xout is only written (plain stores).
+constexpr int MULTI_XCD_TEAMS = 8;
+constexpr int MULTI_XCD_FLAG_STRIDE = 16; // unsigned long long words between two flags (128 bytes)
+constexpr unsigned MULTI_XCD_SPINS = 1u << 22;
+constexpr unsigned MULTI_XCD_ERR_RESIDENCY = 12, MULTI_XCD_ERR_BARRIER = 13, MULTI_XCD_ERR_SLOTS = 14; // codes left in the status word
+template <class T>
+struct MultiXcdTri { // views of one TriSchedule
+  const LevelDesc *desc;
+  const int32_t *rows, *cols;
+  const T *vals, *dinv;
+  const int32_t *blk_off, *blk_nlev;
+};
+template <class T>
+struct MultiXcdArgs {
+  int nb, nrhs, force_one, slots; // diagonal blocks; columns; one team forced (tests); flag slots per team (= the grid)
+  MultiXcdTri<T> tri[2];          // L, U
+  const double *D;
+  int64_t ldd;
+  T *X;                           // double: the result block; float: the work block xf
+  int64_t ldx;
+  double *xout;                   // float only: the result block, written in the upper sweep
+  int64_t ldo;
+  XcdState *st;
+  unsigned long long *flags;
+  unsigned *err, *report;
+};
+typedef double mx_d4 __attribute__((ext_vector_type(4)));
+typedef double mx_d2 __attribute__((ext_vector_type(2)));
+typedef float mx_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned mx_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ mx_d4 mx_ld_sc1(const double *p, mx_d4) { return mx_d4{ld_sc1(p), ld_sc1(p + 1), ld_sc1(p + 2), ld_sc1(p + 3)}; }
+__device__ __forceinline__ mx_f4 mx_ld_sc1(const float *p, mx_f4)
+{
+  const unsigned long long a = __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long b = __hip_atomic_load((const unsigned long long *)(p + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return mx_f4{__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b), __uint_as_float((unsigned)(b >> 32))};
+}
+// 16-byte write-through store (p 16-byte aligned); the two idle cycles keep the data registers untouched while the store reads them
+__device__ __forceinline__ void mx_st16_sc1(void *p, mx_u4 v)
+{
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void mx_st_sc1(double *p, mx_d4 s)
+{
+  mx_st16_sc1(p, __builtin_bit_cast(mx_u4, mx_d2{s[0], s[1]}));
+  mx_st16_sc1(p + 2, __builtin_bit_cast(mx_u4, mx_d2{s[2], s[3]}));
+}
+__device__ __forceinline__ void mx_st_sc1(float *p, mx_f4 s) { mx_st16_sc1(p, __builtin_bit_cast(mx_u4, s)); }
+
+// one (row, column quad) item of a level: k_trsv_level_multi4 (T = double) / k_trsv_level_multi4_f32 (T = float) with coherent accesses
+template <class T, bool UPPER>
+__device__ __forceinline__ void mx_item_quad(int m, int w, int r, int j, const int32_t *__restrict__ rows, const int32_t *__restrict__ cols, const T *__restrict__ vals,
+                                             const T *__restrict__ dinv, const double *__restrict__ d, int64_t ldd, T *x, int64_t ldx, double *__restrict__ xout, int64_t ldo)
+{
+  typedef T V4 __attribute__((ext_vector_type(4)));
+  const int64_t row = rows[r], o = row * ldx + j;
+  V4 s;
+  if (UPPER) s = mx_ld_sc1(x + o, V4{});
+  else {
+    const mx_d4 dv = *reinterpret_cast<const mx_d4 *>(d + row * ldd + j);
+    s = V4{(T)dv[0], (T)dv[1], (T)dv[2], (T)dv[3]};
+  }
+  for (int k0 = 0; k0 < w; k0 += TRSV_UNROLL) {
+    int32_t c[TRSV_UNROLL];
+    T v[TRSV_UNROLL];
+    V4 xv[TRSV_UNROLL];
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) {
+      const bool ok = k0 + u < w;
+      c[u] = ok ? cols[(int64_t)(k0 + u) * m + r] : -1;
+      v[u] = ok ? vals[(int64_t)(k0 + u) * m + r] : (T)0;
+    }
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) { // (k0 + u < w is uniform: a scalar branch around the coherent loads; c[u] >= 0 says the same)
+      if (k0 + u < w) xv[u] = mx_ld_sc1(x + (int64_t)c[u] * ldx + j, V4{});
+      else xv[u] = V4{(T)0, (T)0, (T)0, (T)0};
+    }
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) s -= v[u] * xv[u];
+  }
+  if (UPPER) {
+    s *= dinv[r];
+    if (sizeof(T) == 4) *reinterpret_cast<mx_d4 *>(xout + row * ldo + j) = mx_d4{(double)s[0], (double)s[1], (double)s[2], (double)s[3]};
+  }
+  mx_st_sc1(x + o, s);
+}
+// one (row, column) item: k_trsv_level_multi over trsv_row_sum_multi
+template <bool UPPER>
+__device__ __forceinline__ void mx_item_scalar(int m, int w, int r, int j, const int32_t *__restrict__ rows, const int32_t *__restrict__ cols, const double *__restrict__ vals,
+                                               const double *__restrict__ dinv, const double *__restrict__ d, int64_t ldd, double *x, int64_t ldx)
+{
+  const int64_t o = (int64_t)rows[r] * ldx + j;
+  double s = UPPER ? ld_sc1(x + o) : d[(int64_t)rows[r] * ldd + j];
+  for (int k0 = 0; k0 < w; k0 += TRSV_UNROLL) {
+    int32_t c[TRSV_UNROLL];
+    double v[TRSV_UNROLL], xv[TRSV_UNROLL];
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) {
+      const bool ok = k0 + u < w;
+      c[u] = ok ? cols[(int64_t)(k0 + u) * m + r] : -1;
+      v[u] = ok ? vals[(int64_t)(k0 + u) * m + r] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) xv[u] = k0 + u < w ? ld_sc1(x + (int64_t)c[u] * ldx + j) : 0.0;
+#pragma unroll
+    for (int u = 0; u < TRSV_UNROLL; ++u) s -= v[u] * xv[u];
+  }
+  st_sc1(x + o, UPPER ? s * dinv[r] : s);
+}
+
+template <class T, bool QUAD>
+__global__ __launch_bounds__(WG) void k_trsv_multi_xcd(MultiXcdArgs<T> A)
+{
+  static_assert(QUAD || sizeof(T) == 8, "the single-precision sweeps exist in the quad form only");
+  __shared__ unsigned sh_xcc, sh_xt, sh_gt, sh_fail;
+  const int tid = threadIdx.x, lane = tid & 63;
+  XcdState *st = A.st;
+  // ---- placement: ticket on the own XCD, then a bounded grid barrier (k_sn_top1) ----
+  if (tid == 0) {
+    const unsigned xcc = hw_xcc_id();
+    sh_xcc = xcc;
+    sh_xt = __hip_atomic_fetch_add(&st->tickets[xcc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sh_gt = __hip_atomic_fetch_add(&st->global_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&st->arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned fail_ = 0;
+    for (unsigned spins = 0; __hip_atomic_load(&st->arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x; ++spins) {
+      if (spins > MULTI_XCD_SPINS) { // the workgroups are not co-resident (another process on the GPU?)
+        __hip_atomic_store(A.err, MULTI_XCD_ERR_RESIDENCY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        fail_ = 1;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    sh_fail = fail_;
+  }
+  __syncthreads();
+  if (sh_fail) return;
+  const unsigned epoch = __hip_atomic_load(&st->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  unsigned tks[8];
+#pragma unroll
+  for (int x = 0; x < 8; ++x) tks[x] = __hip_atomic_load(&st->tickets[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const multi_xcd::Team tm = multi_xcd::team_of(tks, A.nb, A.force_one, sh_xcc, sh_xt, sh_gt, gridDim.x);
+  if (sh_gt == 0 && tid == 0) { // the report of ddm_ilu0_multi_info
+#pragma unroll
+    for (int x = 0; x < 8; ++x) __hip_atomic_store(A.report + x, tks[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(A.report + 8, (unsigned)tm.nteams, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(A.report + 9, (unsigned)tm.one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (tm.size > A.slots || tm.rank >= tm.size) { // (cannot happen with slots = the grid; the same verdict in every workgroup of a team)
+    if (tid == 0) __hip_atomic_store(A.err, MULTI_XCD_ERR_SLOTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return;
+  }
+  unsigned long long *gflags = A.flags + (size_t)tm.team * (size_t)A.slots * MULTI_XCD_FLAG_STRIDE;
+  const unsigned W = (unsigned)tm.size;
+  unsigned count = 0;
+  bool failed = false;
+  // all-to-all flag barrier among the W workgroups of the team: every storing wave drains, one lane publishes, wave 0 polls all flags
+  auto team_barrier = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    ++count;
+    if (tid == 0) __hip_atomic_store(gflags + (size_t)tm.rank * MULTI_XCD_FLAG_STRIDE, ((unsigned long long)epoch << 32) | count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < 64) {
+      for (unsigned spins = 0;; ++spins) {
+        bool ok = true;
+        for (unsigned j = (unsigned)lane; j < W; j += 64u) {
+          const unsigned long long v = __hip_atomic_load(gflags + (size_t)j * MULTI_XCD_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ok = ok && (unsigned)(v >> 32) == epoch && (unsigned)v >= count;
+        }
+        if (__all(ok)) break;
+        if (spins > MULTI_XCD_SPINS) {
+          if (lane == 0) {
+            __hip_atomic_store(A.err, MULTI_XCD_ERR_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            sh_fail = 1;
+          }
+          break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+      }
+    }
+    __syncthreads();
+    if (sh_fail) failed = true;
+  };
+  // (Measured and not kept, tools/multi_trsv_bench.py, DESIGN.md section 9: plain stores and a plain flag where a team is one XCD,
+  //  together with the barrier split into arrive / wait and the next level's plan loaded and its first factor entries touched in
+  //  between -- 38.8 against 29.6 ms at 216^3, m = 8.)
+  const int nq = QUAD ? A.nrhs / 4 : A.nrhs;
+  for (int b = tm.team; b < A.nb && !failed; b += tm.nteams)
+    for (int pass = 0; pass < 2 && !failed; ++pass) {
+      const MultiXcdTri<T> &S = A.tri[pass];
+      const int nl = S.blk_nlev[b];
+      for (int l = 0; l < nl && !failed; ++l) {
+        const LevelDesc Ld = S.desc[l];
+        const int p0 = S.blk_off[(int64_t)l * (A.nb + 1) + b], p1 = S.blk_off[(int64_t)l * (A.nb + 1) + b + 1];
+        const int64_t nitem = (int64_t)(p1 - p0) * nq;
+        const int32_t *rows = S.rows + Ld.row_off, *cols = S.cols + Ld.ent_off;
+        const T *vals = S.vals + Ld.ent_off, *dinv = pass ? S.dinv + Ld.row_off : nullptr;
+        for (int64_t it = (int64_t)tm.rank * WG + tid; it < nitem; it += (int64_t)W * WG) {
+          const int r = p0 + (int)(it / nq);
+          const int jq = (int)(it - (int64_t)(r - p0) * nq);
+          if constexpr (QUAD) {
+            if (pass) mx_item_quad<T, true>(Ld.m, Ld.w, r, 4 * jq, rows, cols, vals, dinv, A.D, A.ldd, A.X, A.ldx, A.xout, A.ldo);
+            else mx_item_quad<T, false>(Ld.m, Ld.w, r, 4 * jq, rows, cols, vals, dinv, A.D, A.ldd, A.X, A.ldx, A.xout, A.ldo);
+          } else {
+            if (pass) mx_item_scalar<true>(Ld.m, Ld.w, r, jq, rows, cols, vals, dinv, A.D, A.ldd, A.X, A.ldx);
+            else mx_item_scalar<false>(Ld.m, Ld.w, r, jq, rows, cols, vals, dinv, A.D, A.ldd, A.X, A.ldx);
+          }
+        }
+        team_barrier();
+      }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // XCD-local solve with a dedicated LOADER wave per workgroup ("xcd2" engine).
 // vmcnt retires in order, so a wave that both streams factor entries from HBM and polls flags pays
 // the HBM latency on every level.  Here each workgroup has two waves: wave 1 streams the tiles of

@@ -24,6 +24,9 @@ struct TriSchedule { // one triangular factor, level by level in sliced ELL
   };
   std::vector<Launch> plan;
   int64_t ell_entries = 0;
+  // single-launch block solve (trsv_multi_plan.hpp): blk_off[l (nb + 1) + b] = first position of block b inside level l, blk_nlev[b]
+  dbuf<int32_t> blk_off, blk_nlev;
+  std::vector<int32_t> h_blk_nlev;
 };
 
 struct TriCsr { // one triangular factor of the sparse direct solver: rows in level order, CSR entries (kernels.hpp: CsrLevel)
@@ -53,10 +56,17 @@ struct TriCsr { // one triangular factor of the sparse direct solver: rows in le
 // Engine of the single-vector solve; the values are the codes ddm_ilu0_engine reports.
 enum class Engine : int { Levels = 0, Xcd2 = 4, Pipe = 8, Supernodal = 16, Box = 32 };
 
+struct MultiXcdSync { // what the single-launch block solve (engine_multi_xcd.hpp) adds to the level engine: flags and a report, no factor memory
+  dbuf<unsigned long long> flags; // MULTI_XCD_TEAMS x grid flag slots, MULTI_XCD_FLAG_STRIDE words apart (zero-initialised; epochs separate launches)
+  unsigned *report = nullptr;     // pinned, device-mapped host words the kernel's first workgroup writes: tickets[8], teams, one-team flag
+  int grid = 0;
+  ~MultiXcdSync() { if (report) (void)hipHostFree(report); }
+};
 struct LevelEngine { // one launch per level (runs of small levels in one workgroup); also the multi-RHS solves of every ILU(0) factor
   TriSchedule L, U;
   dbuf<float> xf; // n x xf_nrhs work block of the single-precision multi-RHS sweeps
   int xf_nrhs = 0;
+  std::unique_ptr<MultiXcdSync> mx; // built by the first block solve on engine `xcd`
 };
 
 struct XcdEngine { // xcd2 (XCD-local + loader waves): per-block (subdomain) level schedules, built on first use (build_xcd_schedule)
@@ -157,7 +167,11 @@ struct SolveKey { // the arguments a captured solve is bound to; the single-vect
   double *x = nullptr;
   int64_t nrhs = 1, ldd = 1, ldx = 1;
   bool f32 = false; // the graph runs the single-precision sweeps
-  bool operator==(const SolveKey &o) const { return d == o.d && x == o.x && scale == o.scale && add == o.add && nrhs == o.nrhs && ldd == o.ldd && ldx == o.ldx && f32 == o.f32; }
+  int engine = 0;   // block solves: MULTI_LEVELS, MULTI_XCD or MULTI_XCD_ONE_TEAM, whichever the graph runs
+  bool operator==(const SolveKey &o) const
+  {
+    return d == o.d && x == o.x && scale == o.scale && add == o.add && nrhs == o.nrhs && ldd == o.ldd && ldx == o.ldx && f32 == o.f32 && engine == o.engine;
+  }
 };
 struct GraphCache { // one captured, instantiated solve and the key it was captured for (capture_and_launch sets both)
   hipGraphExec_t exec = nullptr;
@@ -167,9 +181,16 @@ struct GraphCache { // one captured, instantiated solve and the key it was captu
   ~GraphCache() { reset(); }
 };
 
+// Engine of the block solve of a plain ILU(0) factor (ddm_ilu0_set_multi_engine; DDM_TRSV_MULTI_MODE at creation) and why a request
+// for `xcd` was not followed (ddm_ilu0_multi_info)
+enum { MULTI_LEVELS = 0, MULTI_XCD = 1, MULTI_XCD_ONE_TEAM = 2 };
+enum { MULTI_RAN_REQUESTED = 0, MULTI_NOT_REQUESTED = 1, MULTI_DIRECT_FACTOR = 2, MULTI_WIDE_LEVEL = 3 };
+
 struct ddm_ilu0 {
   int64_t n = 0, nnz = 0;
   Engine engine = Engine::Levels;
+  int multi_mode = MULTI_LEVELS;                                  // requested engine of the block solves
+  int multi_last = -1, multi_decline = MULTI_NOT_REQUESTED;       // engine of the last block solve (-1: none yet), decline reason
   hvec<double> h_lu; // factor values in the pattern of A
   std::vector<int64_t> h_diag, h_block_ptr;
   const ddm_csr *A = nullptr;

@@ -220,8 +220,12 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
   if (f32)
     for (const TriSchedule *S : {&F->lev->L, &F->lev->U})
       for (const LevelDesc &L : S->desc) f32 = f32 && L.w < 96;
+  // engine `xcd` (engine_multi_xcd.hpp) where it was requested and applies; otherwise what ran before it existed
+  int why;
+  const int engine = multi_xcd_applies(F, &why) ? F->multi_mode : MULTI_LEVELS;
+  F->multi_last = engine != MULTI_LEVELS ? MULTI_XCD : MULTI_LEVELS, F->multi_decline = why;
   SolveKey key;
-  key.d = D, key.x = X, key.nrhs = nrhs, key.ldd = ldd, key.ldx = ldx, key.f32 = f32;
+  key.d = D, key.x = X, key.nrhs = nrhs, key.ldd = ldd, key.ldx = ldx, key.f32 = f32, key.engine = engine;
   if (F->mgraph.hit(key)) {
     HIPCHECK(ctx, hipGraphLaunch(F->mgraph.exec, ctx->stream));
     return DDM_OK;
@@ -242,6 +246,7 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
     HIPCHECK(ctx, hipGetLastError());
   }
   F->mgraph.reset();
+  if (engine != MULTI_LEVELS) DDMCHECK(build_multi_xcd(ctx, F));
   if (F->sn) {
     SnDirect &S = *F->sn;
     const int w = std::min(nrhs, 48); // the panel kernels take up to 48 columns: wider blocks are solved in column panels
@@ -260,6 +265,8 @@ static int ilu0_solve_multi_ld(ddm_ctx *ctx, ddm_ilu0 *F, int nrhs, const double
       for (int c0 = 0; c0 < nrhs; c0 += 48) enqueue_sn_panel(ctx, F, std::min(48, nrhs - c0), D + c0, ldd, X + c0, ldx, F->pD, nullptr, nullptr);
     } else if (F->csr) {
       return enqueue_csr_direct(ctx, F, /*block=*/true, nrhs, D, ldd, X, ldx);
+    } else if (engine != MULTI_LEVELS) {
+      enqueue_multi_xcd(ctx, F, engine, f32, nrhs, D, ldd, X, ldx);
     } else if (f32) {
       // (Splitting the columns into two halves that run as two parallel chains of the captured graph -- a second stream joining the
       //  capture -- was measured and is slower: 6.8 against 5.6 s for the 109 block iterations of the headline GenEO run; every level

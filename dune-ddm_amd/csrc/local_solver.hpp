@@ -42,6 +42,7 @@ static int ilu0_build_engines(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, const
                               bool multi_rhs_only, bool box_allowed)
 {
   F->engine = requested_engine(multi_rhs_only, box_allowed);
+  F->multi_mode = requested_multi_mode();
   F->A = A;
   F->h_diag = diag;
   F->h_block_ptr.assign(block_ptr, block_ptr + nblocks + 1);
@@ -53,7 +54,7 @@ static int ilu0_build_engines(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, const
   std::thread tu([&]() {
     (void)hipSetDevice(ctx->device);
     BackgroundTransfers own_stream;   // (this create may itself run on a background thread: the box engine's nested factor)
-    rcU = build_schedule(ctx, A, F->h_lu, diag, true, F->lev->U);
+    rcU = build_schedule(ctx, A, F->h_lu, diag, true, F->h_block_ptr, F->lev->U);
   });
   if ((F->engine == Engine::Pipe || F->engine == Engine::Box) && F->n > 0) {
     F->builder = std::thread([ctx, F]() {
@@ -65,7 +66,7 @@ static int ilu0_build_engines(ddm_ctx *ctx, ddm_ilu0 *F, const ddm_csr *A, const
       if (rc) F->builder_err = last_error_of_this_thread();
     });
   }
-  int rc = build_schedule(ctx, A, F->h_lu, diag, false, F->lev->L);
+  int rc = build_schedule(ctx, A, F->h_lu, diag, false, F->h_block_ptr, F->lev->L);
   tu.join();
   if (!rc) rc = rcU;
   static const bool background = !std::getenv("DDM_PIPE_ASYNC") || std::atoi(std::getenv("DDM_PIPE_ASYNC")) != 0;

@@ -453,6 +453,12 @@ extern "C" int ddm_schwarz_set_multi_precision(ddm_schwarz *S, int f32)
   S->multi_f32 = f32 != 0;
   return DDM_OK;
 }
+// the engine of the local solver's block solves (ddm_ilu0_set_multi_engine); the single-vector apply is not affected
+extern "C" int ddm_schwarz_set_multi_engine(ddm_schwarz *S, int mode)
+{
+  if (!S) return DDM_EINVAL;
+  return ilu0_set_multi_mode(S->solver, mode);
+}
 // diagnostic: overwrite the status word of a local solver (0 clears it) -- lets a caller exercise the fail-fast path of the applies
 extern "C" int ddm_ilu0_set_status(ddm_ilu0 *F, int status)
 {

@@ -6,28 +6,13 @@ static constexpr int SMALL_LEVELS_PER_LAUNCH = 256;
 
 // Builds the level schedule of the lower (upper=false) or upper factor.
 static int build_schedule(ddm_ctx *ctx, const ddm_csr *A, const hvec<double> &lu, const std::vector<int64_t> &diag,
-                          bool upper, TriSchedule &S)
+                          bool upper, const std::vector<int64_t> &block_ptr, TriSchedule &S)
 {
   const int64_t n = A->nrows;
   const int64_t *rp = A->h_rp.data();
   const int32_t *ci = A->h_ci.data();
   std::vector<int32_t> level(n, 0);
-  int32_t maxlev = -1;
-  if (!upper) {
-    for (int64_t i = 0; i < n; ++i) {
-      int32_t l = 0;
-      for (int64_t k = rp[i]; k < diag[i]; ++k) l = std::max(l, level[ci[k]] + 1);
-      level[i] = l;
-      maxlev = std::max(maxlev, l);
-    }
-  } else {
-    for (int64_t i = n - 1; i >= 0; --i) {
-      int32_t l = 0;
-      for (int64_t k = diag[i] + 1; k < rp[i + 1]; ++k) l = std::max(l, level[ci[k]] + 1);
-      level[i] = l;
-      maxlev = std::max(maxlev, l);
-    }
-  }
+  const int32_t maxlev = multi_xcd::tri_levels(n, rp, ci, diag.data(), upper, level.data());
   const int64_t nlev = (int64_t)maxlev + 1;
   S.nlev = nlev;
   std::vector<int64_t> lptr(nlev + 1, 0);
@@ -109,6 +94,13 @@ static int build_schedule(ddm_ctx *ctx, const ddm_csr *A, const hvec<double> &lu
   DDMCHECK(upload(ctx, vals.data(), ent, S.vals));
   if (upper) DDMCHECK(upload(ctx, dinv.data(), n, S.dinv));
   DDMCHECK(upload(ctx, S.desc.data(), nlev, S.d_desc));
+  // per-block sub-ranges of the levels (trsv_multi_plan.hpp): what the single-launch block solve walks; depends on the pattern only
+  {
+    std::vector<int32_t> off;
+    multi_xcd::plan_tables(nlev, (int64_t)block_ptr.size() - 1, block_ptr.data(), level.data(), off, S.h_blk_nlev);
+    DDMCHECK(upload(ctx, off.data(), (int64_t)off.size(), S.blk_off));
+    DDMCHECK(upload(ctx, S.h_blk_nlev.data(), (int64_t)S.h_blk_nlev.size(), S.blk_nlev));
+  }
   return DDM_OK;
 }
 

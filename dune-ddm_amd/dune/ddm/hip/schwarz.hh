@@ -80,6 +80,12 @@ public:
     // library's sparse direct solvers (host factorisation, device triangular solves) -- ddm_schwarz_create_ex validates the name
     solver = solver_subtree.get("type", std::string(""));
     if (solver == "hip_ilu0") solver = "ilu0";
+    // engine of the local solves of the block applies (ddm_schwarz_set_multi_engine): one launch per level, or one persistent launch
+    // with the same bits; not a key of the reference
+    const auto multi_engine_string = subtree.get("multi_engine", std::string("levels"));
+    if (multi_engine_string == "levels") multi_engine = 0;
+    else if (multi_engine_string == "xcd") multi_engine = 1;
+    else DUNE_THROW(Dune::NotImplemented, "Unknown multi_engine '" + multi_engine_string + "' (levels, xcd)");
     ctx->require(this->comm->communicator());
     // size checks of init() (:186-193)
     if (this->comm->indexSet().size() != this->Aovlp->N())
@@ -173,6 +179,7 @@ private:
                    ddm_schwarz_create_ex(ctx->handle(), dA->handle(), 1, bp, (int64_t)n_novlp, ext.data(), pou ? w.data() : nullptr,
                                          type == SchwarzType::Restricted ? 1 : 0, solver.c_str(), h_copy->handle(), h_add->handle(), &S),
                    "ddm_schwarz_create");
+    ddm_hip::check(ctx->handle(), ddm_schwarz_set_multi_engine(S, multi_engine), "ddm_schwarz_set_multi_engine");
     dd = std::make_unique<ddm_hip::DeviceVector>(ctx, n_novlp);
     dx = std::make_unique<ddm_hip::DeviceVector>(ctx, n_novlp);
   }
@@ -183,6 +190,7 @@ private:
   std::shared_ptr<ddm_hip::Context> ctx;
   SchwarzType type;
   std::string solver;
+  int multi_engine = 0;   // [schwarz] multi_engine = levels | xcd (ddm_schwarz_set_multi_engine)
   std::unique_ptr<ddm_hip::DeviceCsr> dA;
   std::unique_ptr<ddm_hip::Halo> h_copy, h_add;
   std::unique_ptr<ddm_hip::DeviceVector> dd, dx;

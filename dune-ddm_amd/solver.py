@@ -103,7 +103,7 @@ def pou_basis(rl: RankLocal, template_vecs=None):
 
 class TwoLevelSchwarz:
     def __init__(self, dec: Decomposition, rank=0, nranks=1, device=0, comm: TorchComm | None = None,
-                 schwarz_type="standard", mode="additive", coarse="pou", use_pou_in_schwarz=True, subdomain_solver="ilu0"):
+                 schwarz_type="standard", mode="additive", coarse="pou", use_pou_in_schwarz=True, subdomain_solver="ilu0", multi_engine="levels"):
         import torch
         self.torch = torch
         torch.cuda.set_device(device)
@@ -144,6 +144,8 @@ class TwoLevelSchwarz:
             # gloo rehearsal: several ranks share one GPU.  The single-launch triangular solves need all
             # their workgroups co-resident (one process per GPU); fall back to one launch per level.
             os.environ["DDM_TRSV_MODE"] = "levels"
+            os.environ["DDM_TRSV_MULTI_MODE"] = "levels"
+            multi_engine = "levels"
         self.A = CsrMatrix(ctx, rl.A)
         self.A_dir = CsrMatrix(ctx, rl.A_dir)
         lap("matrix upload (A, A_dir)")
@@ -159,6 +161,9 @@ class TwoLevelSchwarz:
                                              subdomain_solver=subdomain_solver)   # [schwarz.subdomain_solver] type (schwarz.hh:85-92)
         self._schwarz_args = (rl.pou if use_pou_in_schwarz else None, schwarz_type, subdomain_solver)   # (update_values may build the level anew)
         self._mode = mode
+        self.multi_engine = multi_engine          # engine of the local solves of the block applies: 'levels' | 'xcd' (same bits)
+        if multi_engine != "levels":
+            self.schwarz.set_multi_engine(multi_engine)
         lap("halo plans, operator, local solver (factorisation, schedules)")
         self.galerkin = None
         self.a0 = None
@@ -269,6 +274,8 @@ class TwoLevelSchwarz:
                 raise
             self.schwarz = SchwarzPreconditioner(self.ctx, self.A_dir, self.rl.block_ptr, self.rl.n_o, self.rl.ext_map, self._schwarz_args[0],
                                                  self._schwarz_args[1], self.h_copy, self.h_add, subdomain_solver=self._schwarz_args[2])
+            if self.multi_engine != "levels":
+                self.schwarz.set_multi_engine(self.multi_engine)
             lap("local solver (created anew)")
             recreated = True
         if coarse == "refresh":

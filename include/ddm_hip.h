@@ -197,6 +197,30 @@ int ddm_ilu0_status(ddm_ctx *ctx, const ddm_ilu0 *F, int *status);
 int ddm_ilu0_peek_status(const ddm_ilu0 *F);
 /* diagnostic: overwrite that status word (0 clears it), so that a caller can exercise the fail-fast path of the applies */
 int ddm_ilu0_set_status(ddm_ilu0 *F, int status);
+/* Engine of the BLOCK solves (ddm_ilu0_solve_multi*, and with them every block apply and the GenEO / harmonic-extension setup) of a plain
+ * ILU(0) factor: mode 0 = levels (one launch per dependency level and sweep; the default), 1 = xcd (both sweeps of all diagonal blocks
+ * in ONE persistent launch: teams of XCDs take the blocks in turn, a flag barrier separates the levels; the results are the bits of
+ * mode 0), 2 = xcd with all workgroups in one team (the path taken when an XCD received no workgroup; for tests).  Other values:
+ * DDM_EINVAL.  A direct factor: DDM_OK, no effect.  A factor with a level of 96 or more entries per row keeps the level launches
+ * (ddm_ilu0_multi_info says so).  DDM_TRSV_MULTI_MODE=levels|xcd, read when a factor is created, sets the initial mode -- also of the
+ * factors the GenEO and harmonic-extension setups create internally.  The co-residency rule of ddm_ilu0_peek_status holds for mode
+ * 1 and 2 (one workgroup per CU); a time-out leaves 12 (grid barrier), 13 (level barrier) or 14 in the status word. */
+int ddm_ilu0_set_multi_engine(ddm_ctx *ctx, ddm_ilu0 *F, int mode);
+/* What the block solves of F run on.  *count = 14 values; out (capacity cap >= 14, or NULL to query the count): [0] requested mode,
+ * [1] engine of the last block solve (-1 none yet, 0 levels, 1 xcd), [2] why xcd did not run (0 it ran, 1 not requested, 2 direct
+ * factor, 3 a level of w >= 96), and of the last xcd launch [3] workgroups, [4] teams, [5] 1 if all workgroups formed one team,
+ * [6..13] workgroups per XCD.  [4..13] are written by the kernel: synchronise first. */
+int ddm_ilu0_multi_info(const ddm_ilu0 *F, int64_t *out, int64_t cap, int64_t *count);
+/* Host only (tests): the plan of mode xcd for one triangle (upper = 0 / 1) of a CSR pattern with sorted rows and a full diagonal, as the
+ * factor computes it: *nlev dependency levels; off[l (nblocks + 1) + b] = first position of diagonal block b among the ascending rows
+ * of level l (off[l (nblocks + 1) + nblocks] = rows of the level); blk_nlev[b] = levels of block b.  off == NULL: only *nlev; otherwise
+ * cap >= *nlev (nblocks + 1).  DDM_EINVAL for a malformed pattern. */
+int ddm_trsv_multi_plan_host(int64_t n, const int64_t *rp, const int32_t *ci, int64_t nblocks, const int64_t *block_ptr, int upper, int32_t *off, int64_t cap,
+                             int32_t *blk_nlev, int64_t *nlev);
+/* Host only (tests): the team arithmetic of mode xcd for the workgroup that drew xcd_ticket on XCD xcc and global_ticket overall, from
+ * the workgroups per XCD tickets8: out5 = {teams T = min(nblocks, 8), team = xcc % T, rank within the team, workgroups of the team,
+ * 0}, or {1, 0, global_ticket, grid, 1} when a team would be empty or force_one is set. */
+int ddm_trsv_multi_team_host(const uint32_t *tickets8, int nblocks, int force_one, int xcc, uint32_t xcd_ticket, uint32_t global_ticket, uint32_t grid, int32_t *out5);
 /* engine the next ddm_ilu0_solve uses: 8 = pipe, 4 = xcd2 (also when pipe declined the matrix), 0 = one launch per level (also the
  * host sparse direct factor), 16 = device supernodal factor, 32 = box (DDM_TRSV_MODE=box; pipe when box declined the matrix) */
 int ddm_ilu0_engine(const ddm_ilu0 *F);
@@ -682,6 +706,9 @@ int ddm_schwarz_apply_multi(ddm_ctx *ctx, ddm_schwarz *S, int nrhs, double *X, c
  * are meant to be combined with it: they keep M^-1 v and test the true defect; CG and left-preconditioned GMRES assume a fixed M^-1 and
  * would report the defect of a system preconditioned in single precision.  The single-vector apply never changes.  DDM_EINVAL for S == NULL. */
 int ddm_schwarz_set_multi_precision(ddm_schwarz *S, int f32);
+/* ddm_ilu0_set_multi_engine on the local solver of S: the engine of the local solves of the block applies (0 levels, 1 xcd, 2 xcd with
+ * one team); same results, bit for bit.  DDM_EINVAL for another mode or a null S. */
+int ddm_schwarz_set_multi_engine(ddm_schwarz *S, int mode);
 int ddm_galerkin_apply_multi(ddm_ctx *ctx, ddm_galerkin *G, int nrhs, double *X, const double *D); /* galerkin_preconditioner.hh:151-194 */
 int ddm_combined_apply_multi(ddm_ctx *ctx, ddm_combined *C, int nrhs, double *X, const double *D); /* combined_preconditioner.hh:127-163 */
 /* nrhs INDEPENDENT dune-istl CGSolver::apply recurrences (the loop of ddm_cg_solve per column; not a block-Krylov method).  X: initial

@@ -7,7 +7,7 @@ ddm_cg_solve (each column is solved once; the sequential time of m columns is th
 RHS-iterations per second of both, their ratio, ms per block iteration, the iteration counts, and the per-block breakdown of a
 --profile-iters run with the library's event timers (ddm_timing_*).
 
-    python tools/multi_rhs_bench.py [--grid 216] [--m 1,4,8,16] [--coarse geneo|pou]
+    python tools/multi_rhs_bench.py [--grid 216] [--m 1,4,8,16] [--coarse geneo|pou] [--multi-engine levels|xcd]
 """
 from __future__ import annotations
 
@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--maxit", type=int, default=1000)
     ap.add_argument("--profile-iters", type=int, default=20, help="iterations of the timer run per block width (0 = none)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--multi-engine", default="levels", choices=["levels", "xcd"], help="engine of the local solves of the block applies")
     args = ap.parse_args()
     ms_ = sorted({int(v) for v in args.m.split(",")})
     assert all(1 <= m <= 32 for m in ms_)
@@ -63,6 +64,7 @@ def main():
         tl.rebuild_combined("additive")
     else:
         tl = TwoLevelSchwarz(dec, schwarz_type="standard", mode="additive", coarse="pou")
+    tl.schwarz.set_multi_engine(args.multi_engine)
     tl.schwarz.wait_setup()
     tl.ctx.sync()
     log(f"setup {time.perf_counter() - t0:.1f} s, n_o = {tl.rl.n_o}, local engine {tl.schwarz.engine()}")
@@ -117,7 +119,7 @@ def main():
             f"{row['rhs_iterations_per_s']:.0f} RHS-it/s against {row['sequential_rhs_iterations_per_s']:.0f} sequential: x{row['ratio']:.2f}")
         del X
     out = {"workload": f"{G}^3 Q1 Poisson, {P ** 3} subdomains, overlap {args.overlap}, ILU(0) Schwarz + {args.coarse} coarse space, additive, CG to {args.reduction:g}",
-           "n_o": int(tl.rl.n_o), "device": torch.cuda.get_device_name(0), "single_ms_per_iteration_by_timer": single_prof, "rows": rows,
+           "n_o": int(tl.rl.n_o), "multi_engine": args.multi_engine, "device": torch.cuda.get_device_name(0), "single_ms_per_iteration_by_timer": single_prof, "rows": rows,
            "what": "rhs_iterations_per_s = sum of the columns' CG iterations / wall time of the solve; sequential = the same columns solved one by one with "
                    "ddm_cg_solve; *_by_timer: ms per (block) iteration of a fixed-length run with the library's event timers on"}
     print(json.dumps(out))
