@@ -102,6 +102,7 @@ SYMBOLS = {
     "ddm_halo_exchange_to": (_I32, [_P, _P, _P, _P]),
     "ddm_schwarz_local_solver": (_P, [_P]),
     "ddm_ilu0_pipe_trace": (_I32, [_P, _P, _P, _P, _P, _P, _I64, ctypes.POINTER(ctypes.c_int64)]),
+    "ddm_ilu0_pipe_info": (_I32, [_P, _P, _P, _I64, ctypes.POINTER(ctypes.c_int64)]),
     "ddm_ilu0_num_levels": (_I64, [_P, _I32]),
     "ddm_ilu0_wait": (_I32, [_P, _P]),
     "ddm_ilu0_box_check": (_I32, [_P, _P]),
@@ -663,6 +664,18 @@ class Ilu0:
         meta = np.zeros((nt.value, 2), dtype=np.int32)
         self.ctx.check(self.ctx.lib.ddm_ilu0_pipe_trace(self.ctx.h, self.h, _ptr(d), _ptr(x), _hp(out), _hp(meta), nt.value, ctypes.byref(nt)))
         return out, meta
+
+    def pipe_info(self):
+        """diagnostic: the pipe engine's queue order: a dict of the launch's workgroups, spread mode, the bound and the gap of the
+        moved tasks, how many were moved per sweep and at most in one queue, and per task start level and moved flag"""
+        cnt = ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.ddm_ilu0_pipe_info(self.ctx.h, self.h, None, 0, ctypes.byref(cnt)))
+        out = np.zeros(cnt.value, dtype=np.int64)
+        self.ctx.check(self.ctx.lib.ddm_ilu0_pipe_info(self.ctx.h, self.h, _hp(out), cnt.value, ctypes.byref(cnt)))
+        names = ("grid", "spread", "move_max", "moved_forward", "moved_backward", "max_moved", "move_gap", "ntasks")
+        info = dict(zip(names, out[:8].tolist()))
+        info["start_level"], info["moved"] = out[8::2].copy(), out[9::2].copy()
+        return info
 
     def engine(self):
         return SchwarzPreconditioner.ENGINES[int(self.ctx.lib.ddm_ilu0_engine(self.h))]

@@ -15,6 +15,26 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   if (const char *e = std::getenv("DDM_PIPE_SPREAD")) spread_env = std::atoi(e);
   pipe::Schedule S;
   const int nb = (int)F->h_block_ptr.size() - 1;
+  // the grid first: it bounds how many tasks the builder may queue in front of producers
+  HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
+  HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
+  int per_cu = 0;
+  HIPCHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_trsv_pipe<false>, 64 * PIPE_WAVES, PIPE_LDS_BYTES));
+  per_cu = std::max(1, std::min(per_cu, 2));
+  if (const char *e = std::getenv("DDM_PIPE_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));
+  const int grid = per_cu * (ctx->num_cu / 8 * 8);
+  // All workgroups of the grid are resident (the kernel starts with a barrier over them) and go round-robin over the XCDs.  A queue
+  // is first served by the workgroups that start on its subdomain: in XCD-local mode the XCD's share of the grid over the
+  // subdomains the XCD owns, in spread mode the grid over all subdomains (the kernel falls back to it by itself when an XCD hosts no
+  // workgroup).  Half the smaller of the two may be moved, at most 32 -- "fewer than the queue has workgroups" with room to
+  // spare (trsv_pipe_host.hpp, 5.) -- and none where that leaves a queue fewer than 8 slots for its other tasks.
+  {
+    const int per_queue = std::min((grid / 8) / ((nb + 7) / 8), grid / std::max(nb, 1));
+    opt.move_max = std::min(per_queue / 2, 32);
+    if (per_queue - opt.move_max < 8) opt.move_max = 0;
+    if (const char *e = std::getenv("DDM_PIPE_MOVE")) opt.move_max = std::max(0, std::min(opt.move_max, std::atoi(e)));
+    if (const char *e = std::getenv("DDM_PIPE_MOVE_GAP")) opt.move_gap = std::atoi(e);
+  }
   if (!pipe::build(A->nrows, A->h_rp.data(), A->h_ci.data(), F->h_lu.data(), F->h_diag.data(), nb, F->h_block_ptr.data(), opt, S)) {
     if (std::getenv("DDM_PIPE_VERBOSE")) std::fprintf(stderr, "[ddm] pipe engine not applicable: %s\n", S.error.c_str());
     return DDM_OK;
@@ -51,23 +71,21 @@ static int build_pipe_schedule(ddm_ctx *ctx, ddm_ilu0 *F)
   HIPCHECK(ctx, E->queue.alloc(32 * 4 * (int64_t)nb));
   HIPCHECK(ctx, dev_memset(E->queue, 0, sizeof(unsigned) * 32 * 4 * (size_t)nb));
   DDMCHECK(ilu0_alloc_xstate(ctx, F));
-  HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
-  HIPCHECK(ctx, hipFuncSetAttribute((const void *)k_trsv_pipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES));
-  int per_cu = 0;
-  HIPCHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_trsv_pipe<false>, 64 * PIPE_WAVES, PIPE_LDS_BYTES));
-  per_cu = std::max(1, std::min(per_cu, 2));
-  if (const char *e = std::getenv("DDM_PIPE_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));
-  E->grid = per_cu * (ctx->num_cu / 8 * 8);
+  E->grid = grid;
+  E->move_max = opt.move_max;
+  E->move_gap = opt.move_gap;
   if (std::getenv("DDM_PIPE_VERBOSE")) {
     const pipe::Stats &st = S.stats;
     std::fprintf(stderr,
                  "[ddm] pipe schedule: %lld rows, tasks %lld+%lld, steps %lld+%lld (lane occupancy %.3f / %.3f), entries %lld: local %.3f self-global %.3f remote %.3f, "
-                 "stream %.1f MB (%.2fx of 12 B/entry), max producers %lld, max steps %lld, regrouped %lld, levels <= %lld, rows/level <= %.0f, spread %d, grid %d\n",
+                 "stream %.1f MB (%.2fx of 12 B/entry), max producers %lld, max steps %lld, regrouped %lld, levels <= %lld, rows/level <= %.0f, spread %d, grid %d, "
+                 "moved in the queues %lld+%lld (most in one %lld; at most %d, gap %d)\n",
                  (long long)st.rows, (long long)st.ntasks[0], (long long)st.ntasks[1], (long long)st.nsteps[0], (long long)st.nsteps[1],
                  (double)st.rows / (64.0 * std::max<int64_t>(st.nsteps[0], 1)), (double)st.rows / (64.0 * std::max<int64_t>(st.nsteps[1], 1)), (long long)st.entries,
                  (double)st.entries_local / std::max<int64_t>(st.entries, 1), (double)st.entries_self_global / std::max<int64_t>(st.entries, 1),
                  (double)st.entries_remote / std::max<int64_t>(st.entries, 1), S.stream.size() / 1e6, S.stream.size() / (12.0 * std::max<int64_t>(st.entries, 1)),
-                 (long long)st.max_prod, (long long)st.max_steps, (long long)st.regrouped, (long long)st.max_levels, st.max_rows_per_level, E->spread, E->grid);
+                 (long long)st.max_prod, (long long)st.max_steps, (long long)st.regrouped, (long long)st.max_levels, st.max_rows_per_level, E->spread, E->grid,
+                 (long long)st.moved[0], (long long)st.moved[1], (long long)st.max_moved, opt.move_max, opt.move_gap);
   }
   F->pipe = std::move(E);
   return DDM_OK;

@@ -94,6 +94,7 @@ struct PipeEngine { // pipe: chains x tasks, see trsv_pipe_host.hpp
   int64_t nposU = 0;
   int spread = 0; // placement-independent mode (set when a subdomain has more work per level than one XCD's workgroups take)
   int grid = 0;
+  int move_max = 0, move_gap = 0; // queue order the schedule was built with (pipe::Options)
   pipe::Stats stats;
 };
 

@@ -143,6 +143,29 @@ extern "C" int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, d
   return rc;
 }
 
+// Diagnostic: what the builder did to the queue order (layout: ddm_hip.h).
+extern "C" int ddm_ilu0_pipe_info(ddm_ctx *ctx, ddm_ilu0 *F, int64_t *out, int64_t capacity, int64_t *count)
+{
+  if (!F || !count) return fail(ctx, DDM_EINVAL, "ddm_ilu0_pipe_info: bad arguments");
+  DDMCHECK(ilu0_join(ctx, F));
+  PipeEngine *E = F->pipe.get();
+  const int64_t nt = E ? E->stats.ntasks[0] + E->stats.ntasks[1] : 0;
+  *count = 8 + 2 * nt;
+  if (!out) return DDM_OK;
+  if (capacity < *count) return fail(ctx, DDM_EINVAL, "ddm_ilu0_pipe_info: capacity too small");
+  const int64_t v[8] = {E ? E->grid : 0, E ? E->spread : 0, E ? E->move_max : 0, E ? E->stats.moved[0] : 0, E ? E->stats.moved[1] : 0, E ? E->stats.max_moved : 0,
+                        E ? E->move_gap : 0, nt};
+  std::copy(v, v + 8, out);
+  if (!nt) return DDM_OK;
+  std::vector<pipe::Task> tasks((size_t)nt);
+  DDMCHECK(ddm_memcpy_d2h(ctx, tasks.data(), E->tasks, (int64_t)sizeof(pipe::Task) * nt));
+  for (int64_t t = 0; t < nt; ++t) {
+    out[8 + 2 * t] = tasks[(size_t)t].start_level;
+    out[9 + 2 * t] = tasks[(size_t)t].moved;
+  }
+  return DDM_OK;
+}
+
 // whether the settled engine of the factor is pipe (waits for the background builder)
 static int ilu0_is_pipe(ddm_ctx *ctx, ddm_ilu0 *F, bool *yes)
 {

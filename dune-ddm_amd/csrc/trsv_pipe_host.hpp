@@ -8,7 +8,8 @@
 // level by level (lane = chain, step = level), so that
 //   * a dependency inside the task is read from a small LDS ring of the wave's own recent results,
 //   * a dependency on another task is read from global memory; the producer task only has to be AHEAD,
-//     not in lock-step: tasks form a DAG, are queued in topological order and publish a monotone
+//     not in lock-step: tasks form a DAG, are queued in topological order (but for a bounded number of tasks that are
+//     queued by their start level, in front of producers: build_block_sweep, 5.) and publish a monotone
 //     "steps stored" word, so the L2 latency hides behind the natural lag of the consumer,
 //   * everything static a step needs (factor entries, operand addresses, inverse pivots, progress
 //     requirements) is one fixed-size TILE; the tiles of a task are contiguous in memory in processing
@@ -60,7 +61,7 @@ struct Task { // device-visible descriptor, 512 bytes
   int64_t koff_base; // index of the task's nsteps + 1 cumulative tile offsets (KiB, relative to tile_off) in Schedule::koff
   int32_t nsteps, nprod, group, sweep;
   int32_t W, first_kib, pad0;       // widest row of the task; size of its first tile in KiB
-  int32_t start_level, pad[2];      // dependency level of the task's first step (diagnostics)
+  int32_t start_level, moved, pad;  // dependency level of the task's first step; 1: queued in front of some of its producers (both diagnostics)
   int32_t prod[MAXPROD]; // global task ids of the producers
 };
 static_assert(sizeof(Task) == 512, "Task layout");
@@ -95,12 +96,19 @@ struct Options {
   int vote = 1;     // 1: lanes are re-used by later chains; 0: one chain per lane
   int pack_steps = 64; // steps of a task of dependency-free rows
   int max_span = 256;  // longest task (steps); measured at 216^3: delta 16/32/48 -> 4.59/4.47/4.41 ms per solve, stream 1.78x/1.89x/1.98x
+  // Queue order ("Queue order" below): tasks that sit more than move_gap levels behind their start level are queued where
+  // their start level puts them, at most move_max of them per (block, sweep).  move_max must stay BELOW the number of
+  // workgroups that serve one queue (the device sets it: engine_pipe.hpp); 0: creation order, every producer in front.
+  int move_gap = 24;
+  int move_max = 32;
 };
 
 struct Stats {
   int64_t ntasks[2] = {0, 0}, nsteps[2] = {0, 0};
   int64_t rows = 0, entries = 0, entries_local = 0, entries_self_global = 0, entries_remote = 0;
   int64_t max_prod = 0, max_steps = 0, regrouped = 0, nchains[2] = {0, 0};
+  int64_t moved[2] = {0, 0};        // tasks queued in front of their creation place, per sweep (all blocks)
+  int64_t max_moved = 0;            // most of them in one queue: a queue needs more workgroups than that
   int64_t max_levels = 0;           // deepest sweep of any subdomain
   double max_rows_per_level = 0.0;  // largest average parallelism of a sweep (rows / levels)
 };
@@ -126,13 +134,15 @@ namespace detail {
 struct BlockSweep { // tasks of one block and one sweep, block-local numbering
   struct TaskRec {
     int32_t start0 = 0, nsteps = 0, W = 1;
+    bool moved = false;          // queued in front of its creation place: producers may stand behind it
     std::vector<int32_t> stepW;  // widest row per step
     std::vector<int32_t> rows; // nsteps * LANES block-local rows or -1
     std::vector<int32_t> prod; // producer tasks (local ids, final queue numbering)
   };
-  std::vector<TaskRec> tasks;      // in queue (topological) order
+  std::vector<TaskRec> tasks;      // in queue order (topological but for the moved tasks)
   std::vector<int32_t> task_of, step_of, lane_of; // per block-local row
   int64_t nchains = 0;
+  int32_t nmoved = 0;
   bool cyclic = false, too_many_prod = false;
   int dissolve_rounds = 0;
   int32_t nlev = 0; // dependency levels of the sweep
@@ -147,6 +157,23 @@ struct BlockSweep { // tasks of one block and one sweep, block-local numbering
 //    order of the components, smallest (start level / delta, head row) first.
 // 4. tasks = consecutive components of that order (=> the task graph is acyclic and the creation order is a valid
 //    queue order); lanes are re-used by later chains of the task once a chain has ended.
+// 5. Queue order.  The creation order (the BASE order) emits a task behind all its producers.  The long chains of the overlap
+//    shell start early but read, in their last steps, tasks that start some 200 levels later: such a task is created behind
+//    those producers, and as workgroups dequeue strictly in order it waits for a slot behind tasks that hold theirs and poll.
+//    So: walk the base order with the running maximum of start0; a task more than move_gap levels below that maximum is a
+//    candidate; the at most move_max candidates with the largest gaps are MOVED, each in front of the first unmoved task with a
+//    larger start0 (moved tasks among themselves by (start0, base place)); all other tasks keep their relative order.  A moved
+//    task only moves towards the head (the task that set the maximum is no candidate), and it may now stand in front of
+//    producers: the kernel finds a producer's progress word by task id and does not care where the producer is queued.
+//
+//    No deadlock with S workgroups on the queue, each holding its task until it is done, when at most S - 1 tasks are moved.
+//    Suppose nothing advances and tasks remain.  Let X be the unfinished task that is first in the BASE order: its producers all
+//    precede it there, so they are finished, and X, if dequeued, is not blocked.  So X is not dequeued, every workgroup holds a
+//    blocked task, and as fewer than S tasks are moved one of them, R, is unmoved.  The dequeued tasks are a prefix of the queue:
+//    R stands in front of X.  If X is unmoved, R precedes X in the base order too (unmoved tasks keep their order); if X is moved,
+//    the unmoved tasks in front of it in the queue are those in front of the task it was placed before, which preceded X in the
+//    base order.  Either way R is unfinished and precedes X in the base order: contradiction.  (emulate() below runs every
+//    schedule with exactly moved + 1 slots.)
 template <class Deps>
 static void build_block_sweep(int64_t nb, bool upper, const Deps &deps, const Options &opt, BlockSweep &B)
 {
@@ -399,7 +426,44 @@ static void build_block_sweep(int64_t nb, bool upper, const Deps &deps, const Op
     B.cyclic = true;
     return;
   }
-  // numbering: packs 0..npack-1, then protos in creation order
+  // queue order of the protos (5.)
+  std::vector<uint8_t> moved(protos.size(), 0);
+  if (opt.move_max > 0 && protos.size() > 1) {
+    std::vector<std::pair<int32_t, int32_t>> cand; // (-gap, base place)
+    int32_t runmax = protos[0].start0;
+    for (int32_t p = 1; p < (int32_t)protos.size(); ++p) {
+      if (runmax - protos[p].start0 > opt.move_gap) cand.push_back({protos[p].start0 - runmax, p});
+      runmax = std::max(runmax, protos[p].start0);
+    }
+    std::sort(cand.begin(), cand.end());
+    if ((int)cand.size() > opt.move_max) cand.resize((size_t)opt.move_max);
+    if (!cand.empty()) {
+      for (auto &c : cand) {
+        moved[c.second] = 1;
+        c.first = protos[c.second].start0; // now (start0, base place)
+      }
+      std::sort(cand.begin(), cand.end());
+      std::vector<int32_t> order;
+      order.reserve(protos.size());
+      size_t m = 0;
+      for (int32_t p = 0; p < (int32_t)protos.size(); ++p) {
+        if (moved[p]) continue;
+        while (m < cand.size() && cand[m].first < protos[p].start0) order.push_back(cand[m++].second);
+        order.push_back(p);
+      }
+      while (m < cand.size()) order.push_back(cand[m++].second); // (cannot happen: the task that set the maximum is unmoved)
+      std::vector<Proto> queued(protos.size());
+      std::vector<uint8_t> qmoved(protos.size());
+      for (size_t q = 0; q < order.size(); ++q) {
+        queued[q] = std::move(protos[order[q]]);
+        qmoved[q] = moved[order[q]];
+      }
+      protos.swap(queued);
+      moved.swap(qmoved);
+      B.nmoved = (int32_t)cand.size();
+    }
+  }
+  // numbering: packs 0..npack-1, then protos in queue order
   const int64_t per_pack = (int64_t)opt.pack_steps * LANES;
   const int64_t npack = ((int64_t)freerows.size() + per_pack - 1) / per_pack;
   const int64_t ntask = npack + (int64_t)protos.size();
@@ -432,6 +496,7 @@ static void build_block_sweep(int64_t nb, bool upper, const Deps &deps, const Op
     } else {
       T.start0 = protos[t - npack].start0;
       T.nsteps = protos[t - npack].end - protos[t - npack].start0;
+      T.moved = moved[t - npack] != 0;
     }
     T.rows.assign((size_t)T.nsteps * LANES, -1);
     T.stepW.assign((size_t)T.nsteps, 1);
@@ -443,7 +508,7 @@ static void build_block_sweep(int64_t nb, bool upper, const Deps &deps, const Op
     B.tasks[t].stepW[B.step_of[i]] = std::max(B.tasks[t].stepW[B.step_of[i]], ndep[i]);
     deps(i, [&](int64_t j) {
       const int32_t tj = B.task_of[j];
-      if (tj > t) B.cyclic = true; // cannot happen (see 4.)
+      if (tj > t && !B.tasks[t].moved) B.cyclic = true; // cannot happen (see 4.): only a moved task stands in front of a producer
       if (tj != t) B.tasks[t].prod.push_back(tj);
     });
   }
@@ -520,6 +585,8 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
       }
       S.stats.regrouped += regrouped[(size_t)b * 2 + sweep];
       S.stats.nchains[sweep] += B.nchains;
+      S.stats.moved[sweep] += B.nmoved;
+      S.stats.max_moved = std::max<int64_t>(S.stats.max_moved, B.nmoved);
       S.stats.max_levels = std::max<int64_t>(S.stats.max_levels, B.nlev);
       if (B.nlev > 0) S.stats.max_rows_per_level = std::max(S.stats.max_rows_per_level, (double)(block_ptr[b + 1] - block_ptr[b]) / B.nlev);
     }
@@ -575,6 +642,7 @@ inline bool build(int64_t n, const int64_t *rp, const int32_t *ci, const double 
           T.tile_off = off;
           T.W = B.tasks[q].W;
           T.start_level = B.tasks[q].start0;
+          T.moved = B.tasks[q].moved ? 1 : 0;
           T.koff_base = kb;
           int32_t k = 0;
           for (int32_t t = 0; t < B.tasks[q].nsteps; ++t) {
@@ -699,9 +767,12 @@ inline void refresh_values(unsigned char *stream, const int64_t *slotL, const in
 }
 
 // CPU emulation of the device kernel's data flow on the tile stream (test infrastructure for the builder):
-// tasks in queue order, steps in order, operands from the emulated LDS ring or the position arrays.  Checks the
-// progress requirements on the way.  Returns an empty string or a description of the first violation.
-inline std::string emulate(const Schedule &S, int64_t n, const double *d, double *x)
+// `slots` workgroups per queue dequeue tasks in queue order and hold them until they are done; the held tasks advance round-robin,
+// one step at a time, a step only when the producers have stored what its tile requires; operands from the emulated LDS ring or
+// the position arrays.  Checks the progress requirements on the way.  slots <= 0: the queue's moved tasks + 1, the fewest the
+// builder's argument allows (one slot, task after task, when nothing is moved).  Returns an empty string or a description of the
+// first violation; a state in which no held task can advance is "queue order deadlocks with N slots".
+inline std::string emulate(const Schedule &S, int64_t n, const double *d, double *x, int slots = 0)
 {
   std::vector<double> ypos((size_t)S.nposL, 0.0), xpos((size_t)S.nposU, 0.0);
   std::vector<int32_t> done(S.tasks.size(), 0);
@@ -718,15 +789,48 @@ inline std::string emulate(const Schedule &S, int64_t n, const double *d, double
       const bool upper = sweep == 1;
       const std::vector<double> &src = upper ? xpos : ypos;
       std::vector<double> &dst = upper ? xpos : ypos;
-      for (int32_t q = 0; q < S.groups[g].ntask[sweep]; ++q) {
-        const int32_t tid = S.groups[g].task0[sweep] + q;
+      const int32_t task0 = S.groups[g].task0[sweep], ntask = S.groups[g].ntask[sweep];
+      struct Held { // a workgroup's task
+        int32_t tid = -1, t = 0;
+        std::vector<double> ring;
+        std::vector<int32_t> prev_req;
+      };
+      int nslots = slots;
+      if (nslots <= 0) {
+        nslots = 1;
+        for (int32_t q = 0; q < ntask; ++q) nslots += S.tasks[(size_t)(task0 + q)].moved ? 1 : 0;
+      }
+      std::vector<Held> held((size_t)std::min<int64_t>(nslots, ntask));
+      int32_t next = 0, finished = 0;
+      auto dequeue = [&](Held &H) -> std::string { // the next task of the queue with steps (H.tid = -1: the queue is empty)
+        H.tid = -1;
+        while (next < ntask && H.tid < 0) {
+          const int32_t tid = task0 + next++;
+          const Task &T = S.tasks[(size_t)tid];
+          if (T.W > S.geo.W) return "tile geometry mismatch";
+          for (int p = 0; p < T.nprod; ++p) {
+            if (T.prod[p] == tid || T.prod[p] < task0 || T.prod[p] >= task0 + ntask) return "producer is not another task of the queue of its sweep";
+            if (T.prod[p] > tid && !T.moved) return "producer is not earlier in the queue of its sweep";
+          }
+          if (T.nsteps <= 0) {
+            ++finished;
+            continue;
+          }
+          H.tid = tid;
+          H.t = 0;
+          H.ring.assign((size_t)RING_BYTES / 8, 0.0);
+          H.prev_req.assign(MAXPROD, 0);
+        }
+        return "";
+      };
+      // the next step of a held task; ran = false: its producers are not far enough
+      auto advance = [&](Held &H, bool &ran) -> std::string {
+        const int32_t tid = H.tid, t = H.t;
         const Task &T = S.tasks[(size_t)tid];
-        if (T.W > S.geo.W) return "tile geometry mismatch";
-        std::vector<double> ring((size_t)RING_BYTES / 8, 0.0);
-        std::vector<int32_t> prev_req(MAXPROD, 0);
-        for (int p = 0; p < T.nprod; ++p)
-          if (T.prod[p] >= tid || T.prod[p] < S.groups[g].task0[sweep]) return "producer is not earlier in the queue of its sweep";
-        for (int32_t t = 0; t < T.nsteps; ++t) {
+        std::vector<double> &ring = H.ring;
+        std::vector<int32_t> &prev_req = H.prev_req;
+        ran = false;
+        {
           const unsigned char *tile = S.stream.data() + T.tile_off + (int64_t)S.koff[(size_t)T.koff_base + t] * 1024;
           const int32_t *hdr = reinterpret_cast<const int32_t *>(tile);
           const Geometry G(hdr[2]);
@@ -740,8 +844,11 @@ inline std::string emulate(const Schedule &S, int64_t n, const double *d, double
             const int32_t rq = (int32_t)(((uint32_t)hdr[HDR_REQ0 + p / 2] >> (16 * (p & 1))) & 0xffffu);
             if (rq < prev_req[p]) return "progress requirement decreases";
             if (rq > S.tasks[(size_t)T.prod[p]].nsteps) return "progress requirement beyond the producer's steps";
-            prev_req[p] = rq;
           }
+          for (int p = 0; p < T.nprod; ++p)
+            if ((int32_t)(((uint32_t)hdr[HDR_REQ0 + p / 2] >> (16 * (p & 1))) & 0xffffu) > done[(size_t)T.prod[p]]) return ""; // the kernel polls here
+          for (int p = 0; p < T.nprod; ++p) prev_req[p] = (int32_t)(((uint32_t)hdr[HDR_REQ0 + p / 2] >> (16 * (p & 1))) & 0xffffu);
+          ran = true;
           double out[LANES];
           for (int l = 0; l < LANES; ++l) {
             const int64_t pos = T.pos_base + (int64_t)t * LANES + l;
@@ -788,6 +895,29 @@ inline std::string emulate(const Schedule &S, int64_t n, const double *d, double
           }
           done[(size_t)tid] = t + 1;
         }
+        H.t = t + 1;
+        return "";
+      };
+      for (Held &H : held) {
+        const std::string e = dequeue(H);
+        if (!e.empty()) return e;
+      }
+      while (finished < ntask) {
+        bool any = false;
+        for (Held &H : held) {
+          if (H.tid < 0) continue;
+          bool ran = false;
+          std::string e = advance(H, ran);
+          if (!e.empty()) return e;
+          if (!ran) continue;
+          any = true;
+          if (H.t == S.tasks[(size_t)H.tid].nsteps) { // done: the workgroup takes the next task
+            ++finished;
+            e = dequeue(H);
+            if (!e.empty()) return e;
+          }
+        }
+        if (!any && finished < ntask) return "queue order deadlocks with " + std::to_string(nslots) + " slots";
       }
     }
   for (int64_t i = 0; i < n; ++i) x[i] = xpos[(size_t)S.posU[(size_t)i]];

@@ -247,6 +247,11 @@ int ddm_ilu0_debug_stamps(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x,
  * sweep per task.  out_host == NULL queries *ntasks. */
 int ddm_ilu0_pipe_trace(ddm_ctx *ctx, ddm_ilu0 *F, const double *d, double *x, unsigned long long *out_host, int32_t *meta_host,
                         int64_t capacity_tasks, int64_t *ntasks);
+/* diagnostic of the pipe engine's queue order (csrc/trsv_pipe_host.hpp, "Queue order"): out = {workgroups of the launch, spread mode,
+ * most tasks a queue may hold in front of producers (0: creation order), tasks moved in the forward sweeps, in the backward sweeps,
+ * most in one queue, gap in levels, tasks}, then per task {start level, moved}.  *count = 8 + 2 tasks is always set; out may be NULL to
+ * ask for it, otherwise capacity >= *count.  A factor that is not on the pipe engine reports 0 tasks.  Waits for the background builder. */
+int ddm_ilu0_pipe_info(ddm_ctx *ctx, ddm_ilu0 *F, int64_t *out, int64_t capacity, int64_t *count);
 /* factor values in the pattern of A (inverse pivots on the diagonal), for parity tests */
 int ddm_ilu0_get_factors_host(ddm_ctx *ctx, const ddm_ilu0 *F, double *lu_host);
 

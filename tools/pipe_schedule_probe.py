@@ -1,6 +1,9 @@
 """CPU-side probe of the pipe schedule (diagnostic): builds the schedule of selected subdomains of an N^3 / 2x2x2 problem with the
 test harness and dumps per task: group sweep W nsteps active-rows nprod wide-steps start-level (+ producers and, in
 gpurun_out/pipe_needs.bin, the steps required of each producer at every step).  usage: python tools/pipe_schedule_probe.py N SUBDOMAINS(e.g. 0,7)"""
+# With the queue order's options, python tools/pipe_schedule_probe.py N SUBDOMAINS MOVE_MAX[,MOVE_MAX...] GAP[,GAP...]: one schedule per
+# subdomain, bound and gap (one for the bound 0) through tests/cpp/pipe_queue_test.cpp (no emulation), dumped as
+# <PIPE_PROBE_OUT>_s<subdomain>_m<move_max>_g<gap>_{tasks.txt,needs.bin} for tools/pipe_sim.py (PIPE_PROBE_OUT: a path prefix, default pipe_probe).
 import os, sys, ctypes, numpy as np, scipy.sparse as sp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,6 +18,24 @@ lib = ctypes.CDLL(os.path.join(tps.CPP, "libpipe_host_test.so")); lib.pipe_test_
 N = int(sys.argv[1])
 dec = build_structured(synth.StructuredPoisson((N, N, N), (2, 2, 2)), overlap=2, pou_type="distance", shrink=0)
 which = [int(a) for a in sys.argv[2].split(",")]
+if len(sys.argv) > 3:
+    import test_pipe_queue_order as tq
+    from tests import pipe_cases as pc
+    qlib = tq.harness(); qlib.pipe_queue_dump.restype = ctypes.c_int
+    OUT = os.environ.get("PIPE_PROBE_OUT", "pipe_probe")
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    for k in which:
+        M = sp.csr_matrix(dec.subs[k].A_dir); M.sort_indices()
+        _, lu, diag = pc.oracle_factor(M)
+        lu, diag = np.ascontiguousarray(lu, dtype=np.float64), np.ascontiguousarray(diag, dtype=np.int64)
+        rp, ci, bp = np.asarray(M.indptr, dtype=np.int64), np.asarray(M.indices, dtype=np.int32), np.array([0, M.shape[0]], dtype=np.int64)
+        for mv, gap in ((int(m), int(a)) for m in sys.argv[3].split(",") for a in (sys.argv[4].split(",") if int(m) else ["0"])):
+            out = np.zeros(3, dtype=np.int64)
+            pre = f"{OUT}_s{k}_m{mv}_g{gap}"
+            rc = qlib.pipe_queue_dump(ctypes.c_int64(M.shape[0]), p(rp), p(ci), p(lu), p(diag), ctypes.c_int(1), p(bp), ctypes.c_int(int(os.environ.get("PIPE_TEST_DELTA", "24"))),
+                                      ctypes.c_int(gap), ctypes.c_int(mv), (pre + "_tasks.txt").encode(), (pre + "_needs.bin").encode(), p(out))
+            print(f"subdomain {k} move_max {mv} gap {gap}: rc {rc} moved {out[0]}+{out[1]} of {out[2]} tasks -> {pre}_*", flush=True)
+    sys.exit(0)
 mats = [dec.subs[k].A_dir.tocsr() for k in which]
 M = sp.block_diag(mats, format="csr"); M.sort_indices()
 bp = np.concatenate([[0], np.cumsum([m.shape[0] for m in mats])]).astype(np.int64)

@@ -38,11 +38,12 @@ ap.add_argument("--slots", type=int, default=64)
 ap.add_argument("--spec", action="store_true")
 ap.add_argument("--pair", action="store_true", help="adjacent queue tasks share a workgroup: hand-overs between them through LDS")
 ap.add_argument("--quiet", action="store_true")
+ap.add_argument("--moved", action="store_true", help="list the moved tasks: dequeued, first step, end")
 args = ap.parse_args()
 
 data = open(args.prefix, "rb").read()
 tasks_txt = args.tasks or args.prefix.replace("needs_", "tasks_").replace(".bin", ".txt")
-meta = np.array([[int(v) for v in ln.split()[:9]] for ln in open(tasks_txt)], dtype=np.int64)
+meta = np.array([[int(v) for v in ln.split()[:9]] + [int(ln.split()[9]) if len(ln.split()) == 10 else 0] for ln in open(tasks_txt)], dtype=np.int64)  # (10th column: moved flag, dumps of the queue-order probe only)
 nt = len(meta)
 off = 0
 prods, needs, stepw = [], [], []
@@ -66,7 +67,53 @@ def step_cost(w):
 
 
 def simulate(sw, t_start):
+    """Queue order = task order of the dump.  When every producer stands earlier in the queue, one pass: a task is dequeued when a slot
+    is free and its step times follow from those of its producers.  Otherwise (tasks moved in front of producers: trsv_pipe_host.hpp,
+    "Queue order") a fixed point: step times in dependency order from assumed dequeue times, dequeue times from the queue order and the
+    slot releases those step times give, until no dequeue time moves by more than 0.2 us."""
     ids = [i for i in range(nt) if sweep[i] == sw]
+    if all(int(p) < i for i in ids for p in prods[i]):
+        r = one_pass(ids, t_start, None)
+        return r[:6] + (r[6], 0)
+    inq = set(ids)
+    indeg = {i: sum(1 for p in set(int(x) for x in prods[i]) if p in inq) for i in ids}
+    cons = {i: [] for i in ids}
+    for i in ids:
+        for p in set(int(x) for x in prods[i]):
+            if p in inq:
+                cons[p].append(i)
+    ready = [i for i in ids if indeg[i] == 0]
+    heapq.heapify(ready)
+    dep = []
+    while ready:
+        i = heapq.heappop(ready)
+        dep.append(i)
+        for c in cons[i]:
+            indeg[c] -= 1
+            if indeg[c] == 0:
+                heapq.heappush(ready, c)
+    assert len(dep) == len(ids), "the task graph has a cycle"
+    deq = {i: t_start for i in ids}
+    for it in range(100):
+        r = one_pass(dep, t_start, deq)
+        end = r[4]
+        free = [t_start] * args.slots
+        heapq.heapify(free)
+        new = {}
+        for i in ids:
+            new[i] = heapq.heappop(free)
+            heapq.heappush(free, max(end[i][-1], new[i]) + 0.3)
+        diff = max(abs(new[i] - deq[i]) for i in ids)
+        deq = new
+        if diff <= 0.2:
+            break
+    else:
+        print(f"sweep {sw}: dequeue times still move by {diff:.1f} us after {it + 1} rounds", file=sys.stderr)
+    return r[:6] + (deq, it + 1)
+
+
+def one_pass(order, t_start, deq):
+    """step times of the tasks in `order` (producers first); deq = None: dequeued in that order as slots come free, else at deq[i]"""
     end = {}          # task -> array of step end times
     first = {}
     free = [t_start] * args.slots
@@ -74,8 +121,10 @@ def simulate(sw, t_start):
     nblocked = 0
     ntot = 0
     tblocked = 0.0
-    for i in ids:     # queue order
-        t0 = heapq.heappop(free)
+    dequeued = {}
+    for i in order:
+        t0 = heapq.heappop(free) if deq is None else deq[i]
+        dequeued[i] = t0
         ns = int(nsteps[i])
         E = np.zeros(ns)
         pr, nd, W = prods[i], needs[i], stepw[i]
@@ -133,13 +182,20 @@ def simulate(sw, t_start):
             tblocked += e - E[t - 1] - c
             E[t] = e
         end[i] = E
-        heapq.heappush(free, E[-1] + 0.3)
-    span_end = max(end[i][-1] for i in ids)
-    return span_end, nblocked, ntot, tblocked, end, first
+        if deq is None:
+            heapq.heappush(free, E[-1] + 0.3)
+    span_end = max(end[i][-1] for i in order)
+    return span_end, nblocked, ntot, tblocked, end, first, dequeued
 
 
-t_fwd, nb0, n0, tb0, endF, _ = simulate(0, 0.0)
-t_bwd, nb1, n1, tb1, endB, _ = simulate(1, t_fwd + 1.0)
-nlev_note = ""
+t_fwd, nb0, n0, tb0, endF, firstF, deqF, itF = simulate(0, 0.0)
+t_bwd, nb1, n1, tb1, endB, firstB, deqB, itB = simulate(1, t_fwd + 1.0)
+nlev_note = f"   (fixed point: {itF} / {itB} rounds)" if itF or itB else ""
+if args.moved and meta.shape[1] > 9:
+    for name, endX, firstX, deqX, t0 in (("forward", endF, firstF, deqF, 0.0), ("backward", endB, firstB, deqB, t_fwd + 1.0)):
+        for i in sorted(deqX):
+            if meta[i, 9]:
+                print(f"  {name} task {i - min(deqX):4d} (moved): start level {meta[i, 7]:4d} steps {nsteps[i]:4d} dequeued {deqX[i] - t0:8.1f} first step done {firstX[i] - t0:8.1f} "
+                      f"(waited {firstX[i] - deqX[i]:6.1f}) end {endX[i][-1] - t0:8.1f} us")
 print(f"forward {t_fwd:8.1f} us  (blocked steps {nb0 / max(n0, 1):.1%}, extra {tb0 / max(nb0, 1):.2f} us each)   backward {t_bwd - t_fwd:8.1f} us  "
       f"(blocked {nb1 / max(n1, 1):.1%}, extra {tb1 / max(nb1, 1):.2f} us each)   total {t_bwd:8.1f} us{nlev_note}")

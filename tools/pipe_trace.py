@@ -54,5 +54,34 @@ for g in sorted(set(meta[:, 0]))[:2]:
         for i in sel:
             print(f"    task {i - idx[0]:4d}: dequeued {start[i]:8.1f} first {first[i]:8.1f} end {end[i]:8.1f} steps {int(steps[i]):4d} "
                   f"us/step {(end[i] - first[i]) / steps[i]:.3f} tile {st[i, 3] / steps[i]:.0f} prod {st[i, 4] / steps[i]:.0f} | a {st[i, 8] / steps[i]:.0f} b {st[i, 9] / steps[i]:.0f} d {st[i, 11] / steps[i]:.0f} cyc/step xcc {int(st[i, 7])}")
+# queue order (csrc/trsv_pipe_host.hpp, "Queue order"): span of every sweep, and the moved tasks' wait in their slot.  With nothing
+# moved (MOVE=0) the tasks the builder WOULD move are listed instead: same rule, from the start levels in queue order.
+info = F.pipe_info()
+lvl, moved = info["start_level"], info["moved"].astype(bool)
+would = not moved.any()
+print(f"queue order: bound {info['move_max']} gap {info['move_gap']} moved {info['moved_forward']}+{info['moved_backward']} (most in one queue {info['max_moved']})")
+gap, bound = int(os.environ.get("DDM_PIPE_MOVE_GAP", "24")), 32
+for g in sorted(set(meta[:, 0])):
+    line = f"group {g}:"
+    for sw in (0, 1):
+        idx = np.where((meta[:, 0] == g) & (meta[:, 1] == sw))[0]
+        line += f"  {'backward' if sw else 'forward'} [{start[idx].min():7.1f}, {end[idx].max():7.1f}] = {end[idx].max() - start[idx].min():7.1f} us"
+        if would:
+            runmax = np.maximum.accumulate(np.concatenate([[0], lvl[idx][:-1]]))
+            cand = np.where(runmax - lvl[idx] > gap)[0]
+            cand = cand[np.argsort(-(runmax - lvl[idx])[cand], kind="stable")][:bound]
+            moved[idx[cand]] = True
+    print(line)
+for g in sorted(set(meta[:, 0])):
+    for sw in (0, 1):
+        idx = np.where((meta[:, 0] == g) & (meta[:, 1] == sw))[0]
+        m = idx[moved[idx]]
+        if not len(m):
+            continue
+        w, wall = first[m] - start[m], first[idx] - start[idx]
+        print(f"group {g} sweep {sw}: {len(m)} tasks {'that would be moved' if would else 'moved'}: first - dequeued median {np.median(w):.1f} max {w.max():.1f} us "
+              f"(all {len(idx)} tasks of the queue: median {np.median(wall):.1f} us); those of more than 150 steps:")
+        for i in m[steps[m] > 150]:
+            print(f"    task {i - idx[0]:4d}: start level {lvl[i]:4d} steps {int(steps[i]):4d} dequeued {start[i]:8.1f} first {first[i]:8.1f} (waited {first[i] - start[i]:6.1f}) end {end[i]:8.1f}")
 np.savez(os.path.join(ROOT, 'gpurun_out', f'pipe_trace{N}.npz'), st=st, meta=meta)
 ctx.close()
